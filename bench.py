@@ -2,16 +2,23 @@
 """bench.py — throughput of the MI355X MSM hot path (BASELINE.json metric: BN254 G1 MSM points/s) and, in the same JSON line,
 the other workloads SURVEY 8(d) names.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20] [--blocks all|none|hyrax,sweep,sumcheck]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20] [--dump-outputs DIR]
+    python bench.py --full [--blocks all|none|hyrax,sweep,sumcheck,prove_stages] [--group-devices 0,0] ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     (python bench.py --gpus N without a launcher starts the N ranks itself, before anything touches the GPU)
 
-Headline (`value`, `ms_per_step`, `roofline`, `cpu_baseline`; BASELINE configs[1] / SURVEY 8d config 2): one MSM of 2^log_n points
-per GPU per step — uniform full-width scalars (SplitMix64, reduced mod r), distinct bases with known discrete logs, inputs
-resident in HBM.  With N > 1 the MSM of N*2^log_n points is sharded by base-point range; each rank's 64-byte partial sum goes
-through ONE all-gather over RCCL and a local fold (weak scaling: per-GPU work fixed).
+Headline (`value`, `ms_per_step`; BASELINE configs[1] / SURVEY 8d config 2): one MSM of 2^log_n points per GPU per step —
+uniform full-width scalars (SplitMix64, reduced mod r), distinct bases with known discrete logs, inputs resident in HBM.  With
+N > 1 the MSM of N*2^log_n points is sharded by base-point range; each rank's 64-byte partial sum goes through ONE all-gather
+over RCCL and a local fold (weak scaling: per-GPU work fixed).
 
-Further blocks on the same line, each parity-gated before it is timed, one step in flight:
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs (--dump-outputs) and the line.
+--dump-outputs DIR writes the result of the last timed step, as a caller of the timed path receives it, to DIR/*.npy: every
+affine point (64 B: x, y little-endian) as float32 16-bit limbs of shape (..., 2, 16), exact, and its infinity flag.
+
+--full adds everything else, as before: the parity gate of the headline (discrete-log identity / CPU oracle, checked before
+timing), the one-step-in-flight pass behind `serial_reference` and `roofline`, `cpu_baseline` (16 threads and 1 thread), and
+the blocks below (--blocks, default all; --group-devices).  Each block is parity-gated before it is timed, one step in flight:
   hyrax      config 3: the derefs commitment shape, 4096 x 8192 uniform Fr scalars (rows 3072.. zero, hyrax.rs:245) against the
              reference's own generator set MultiCommitGens::new(8192, "gens_r1cs_eval"); fixed-base lookup table and bucket method;
              sampled rows checked against the CPU oracle; roofline with 32.02 B / pair.  With N > 1: ONE matrix, interleaved rows
@@ -104,6 +111,23 @@ def self_launch(ngpus):
 
 def kernel_avgs(prof):
     return {k: round(ms / max(cnt, 1), 4) for k, (ms, cnt) in prof.items()}
+
+
+def g1_limbs(xy):
+    """affine points as the C ABI returns them (64 B each: x, y little-endian) -> float32 array (points, 2, 16) of their
+    16-bit limbs: exact in float32, so two builds compare bit for bit"""
+    import numpy as np
+    return np.frombuffer(bytes(xy), dtype="<u2").reshape(-1, 2, 16).astype(np.float32)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: DIR/<name>.npy per array (float32 / float64 only, 64 MB at most in all)"""
+    import numpy as np
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def hbm_roofline(alg_bytes, kernel, kernel_ms, traffic=None, extra=None):
@@ -203,7 +227,10 @@ def main():
     ap.add_argument("--rows", type=int, default=4096, help="hyrax: matrix rows")
     ap.add_argument("--cols", type=int, default=8192, help="hyrax: matrix columns")
     ap.add_argument("--inflight", type=int, default=6, help="headline: independent steps kept in flight on separate HIP streams (contexts); 1 = strictly serial")
-    ap.add_argument("--blocks", default="all", help="extra blocks: all | none | comma list of hyrax,sweep,sumcheck,prove_stages")
+    ap.add_argument("--full", action="store_true", help="also run the parity gates, the one-step-in-flight pass (serial_reference, roofline), the CPU "
+                    "baseline and the extra blocks; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's result to DIR/<name>.npy (float32)")
+    ap.add_argument("--blocks", default=None, help="with --full: extra blocks, all (default) | none | comma list of hyrax,sweep,sumcheck,prove_stages")
     ap.add_argument("--sweep", default="22,24,26", help="msm_sweep sizes (log2) on one GPU")
     ap.add_argument("--strong-log-n", type=int, default=26, help="N > 1: log2 of the FIXED total size of the strong-scaling MSM (config 4)")
     ap.add_argument("--sc-log-n", type=int, default=21, help="sumcheck block: log2 of the table length")
@@ -218,6 +245,13 @@ def main():
                     "partial sum / row commitment through the same all-gathers the N > 1 run uses (sharding.allgather_fold / gather_rows on device uint8 tensors) — "
                     "the collective code path exercised on a one-GPU box")
     args = ap.parse_args()
+    if not args.full:
+        if args.blocks not in (None, "none"):
+            ap.error("--blocks needs --full")
+        if args.group_devices:
+            ap.error("--group-devices needs --full")
+    if args.blocks is None:
+        args.blocks = "all" if args.full else "none"
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -289,11 +323,12 @@ def main():
         return [sbn.g1_sum(b"".join(a[64 * j:64 * j + 64] for a in allb)) for j in range(len(parts))]
 
     # ------------------------------------------------------------------------------------------------ one MSM problem
-    def msm_problem(n, first):
-        """bases P_i = (S0 + (first+i) DSTEP) G, scalars from the SplitMix64 stream at offset `first`, the expected partial sum"""
+    def msm_problem(n, first, expect=True):
+        """bases P_i = (S0 + (first+i) DSTEP) G, scalars from the SplitMix64 stream at offset `first`, the expected partial sum
+        (None unless `expect`)"""
         d_scal = synth_scalars(n, first)
         bases = ctx.bases_synthetic(n, first, S0.to_bytes(32, "little"), DSTEP.to_bytes(32, "little"))
-        want = ol.g1_mul(G_XY, dlog_expect(d_scal, first, n))
+        want = ol.g1_mul(G_XY, dlog_expect(d_scal, first, n)) if expect else None
         return d_scal, bases, want
 
     def check_sharded(total, want):
@@ -305,7 +340,8 @@ def main():
         return total == sbn.g1_sum(b"".join(wants))[0]
 
     def timed_msm(cx_list, d_scal, bases, n, steps, warm):
-        """`steps` MSMs, one in flight on cx_list[0] when len == 1, else shared out over the streams; returns (seconds, profile)"""
+        """`steps` MSMs, one in flight on cx_list[0] when len == 1, else shared out over the streams; returns (seconds, profile,
+        the result of the last step as the caller receives it: the folded sum when the partials travel through the collective)"""
         from concurrent.futures import ThreadPoolExecutor
         Mx = len(cx_list)
         pool = ThreadPoolExecutor(max_workers=Mx) if Mx > 1 else None
@@ -314,23 +350,25 @@ def main():
             return cx.msm_bases_dev(bases, d_scal.data_ptr(), n)
 
         def run(count):
+            last = None
             if Mx == 1:
                 for _ in range(count):
-                    fold_partials([local(cx_list[0])])
-                return
+                    last = fold_partials([local(cx_list[0])])[-1]
+                return last
             if not use_coll:
                 shares = [count // Mx + (1 if j < count % Mx else 0) for j in range(Mx)]
                 futs = [pool.submit(lambda cx=cx, k=k: [local(cx) for _ in range(k)]) for cx, k in zip(cx_list, shares)]
                 for f in futs:
-                    f.result()
-                return
+                    last = (f.result() or [last])[-1]
+                return last
             done = 0
             while done < count:                   # rounds of up to 4 steps per stream, then ONE all-gather carrying all their partials
                 g = min(4 * Mx, count - done)
                 shares = [g // Mx + (1 if j < g % Mx else 0) for j in range(Mx)]
                 futs = [pool.submit(lambda cx=cx, k=k: [local(cx) for _ in range(k)]) for cx, k in zip(cx_list, shares) if k]
-                fold_partials([p for f in futs for p in f.result()])
+                last = fold_partials([p for f in futs for p in f.result()])[-1]
                 done += g
+            return last
 
         for cx in cx_list:                        # every stream's workspace is sized before the timed region
             local(cx)
@@ -338,7 +376,7 @@ def main():
         for cx in cx_list:
             cx.prof_enable(True); cx.prof_reset()
         barrier(); t0 = time.perf_counter()
-        run(steps)
+        last = run(steps)
         barrier(); dt = time.perf_counter() - t0
         prof = {}
         for cx in cx_list:
@@ -347,7 +385,7 @@ def main():
             cx.prof_enable(False)
         if pool:
             pool.shutdown()
-        return max_over_ranks(dt), prof
+        return max_over_ranks(dt), prof, last
 
     def msm_alu(job, kernel_ms):
         madds = job["slots"]                      # uniform scalars: a digit is zero with probability 2^-c
@@ -379,36 +417,41 @@ def main():
 
     line_extra = {}
     cpu_baseline = None
+    serial = roofline = None
+    outputs = {}                                                   # --dump-outputs: name -> array, what the last timed step returned
     # ================================================================================================ headline
     if args.workload == "msm":
         n = 1 << args.log_n
         first = rank * n                                           # this rank's base-point range of the N*n-point MSM
-        d_scal, bases, want = msm_problem(n, first)
-        part, _ = ctx.msm_bases_dev(bases, d_scal.data_ptr(), n)   # parity gate: partial == (sum k_i s_i) G, exact
-        if part != want:
-            raise SystemExit(f"rank {rank}: GPU MSM result differs from the discrete-log oracle")
-        total = fold_partials([(part, False)])[0][0]
-        if not check_sharded(total, want):
-            raise SystemExit("sharded MSM result differs from the folded oracle partials")
-        dt, prof = timed_msm(ctxs, d_scal, bases, n, args.steps, args.warmup)
-        serial = None
-        ns_ser = max(2, min(16, args.steps))
-        ts, sp = timed_msm([ctx], d_scal, bases, n, ns_ser, 1)
-        serial = {"steps": ns_ser, "ms_per_step": round(ts / ns_ser * 1e3, 4), "kernels_avg_ms": kernel_avgs(sp)}
+        d_scal, bases, want = msm_problem(n, first, expect=args.full)
+        if args.full:
+            part, _ = ctx.msm_bases_dev(bases, d_scal.data_ptr(), n)   # parity gate: partial == (sum k_i s_i) G, exact
+            if part != want:
+                raise SystemExit(f"rank {rank}: GPU MSM result differs from the discrete-log oracle")
+            total = fold_partials([(part, False)])[0][0]
+            if not check_sharded(total, want):
+                raise SystemExit("sharded MSM result differs from the folded oracle partials")
+        dt, prof, last = timed_msm(ctxs, d_scal, bases, n, args.steps, args.warmup)
+        if last is not None:
+            outputs = {"msm_point": g1_limbs(last[0]), "msm_infinity": np.array([float(last[1])], dtype=np.float32)}
         units_per_step = n
         dominant = "k_acc_first"
-        dom_ms = serial["kernels_avg_ms"].get(dominant, 0.0)
-        roofline = hbm_roofline(96.0 * n, dominant, dom_ms, stored_traffic("msm", f"2^{args.log_n}", dominant),
-                                {"note": "kernel time from the one-step-in-flight pass (with several streams a launch shares the chip and its event-to-event time "
-                                         "stretches); MSM is integer-ALU bound (~170 modular products per point vs 96 B): see roofline.alu and DESIGN.md"})
-        if M > 1:
-            pm, pc = prof.get(dominant, (0.0, 0))
-            roofline["inflight_pass_kernel_avg_ms"] = round(pm / max(pc, 1), 4)
-        if dom_ms:
-            roofline["alu"] = msm_alu(ctx.prof_last_job(), dom_ms)
+        if args.full:
+            ns_ser = max(2, min(16, args.steps))
+            ts, sp, _ = timed_msm([ctx], d_scal, bases, n, ns_ser, 1)
+            serial = {"steps": ns_ser, "ms_per_step": round(ts / ns_ser * 1e3, 4), "kernels_avg_ms": kernel_avgs(sp)}
+            dom_ms = serial["kernels_avg_ms"].get(dominant, 0.0)
+            roofline = hbm_roofline(96.0 * n, dominant, dom_ms, stored_traffic("msm", f"2^{args.log_n}", dominant),
+                                    {"note": "kernel time from the one-step-in-flight pass (with several streams a launch shares the chip and its event-to-event time "
+                                             "stretches); MSM is integer-ALU bound (~170 modular products per point vs 96 B): see roofline.alu and DESIGN.md"})
+            if M > 1:
+                pm, pc = prof.get(dominant, (0.0, 0))
+                roofline["inflight_pass_kernel_avg_ms"] = round(pm / max(pc, 1), 4)
+            if dom_ms:
+                roofline["alu"] = msm_alu(ctx.prof_last_job(), dom_ms)
         workload = f"synthetic BN254 G1 MSM, 2^{args.log_n} uniform Fr scalars x distinct bases per GPU, inputs resident in HBM"
         sharding_desc = "base-point ranges + one RCCL all-gather of 64-B partial sums"
-        if rank == 0 and not args.no_cpu_baseline:          # rank 0 only, at every N (the other ranks wait at the next barrier, outside any timed region)
+        if args.full and rank == 0 and not args.no_cpu_baseline:   # rank 0 only, at every N (the other ranks wait at the next barrier, outside any timed region)
             cores = min(len(os.sched_getaffinity(0)), 16)
             ns = min(n, 1 << 20); n1 = min(n, 1 << 18)
             pts = ctx.bases_download(bases, 0, ns)
@@ -436,20 +479,27 @@ def main():
         Zl = Z.view(L, Rc * 32)[rank::world].contiguous() if world > 1 else Z
         nl = len(my_rows)
 
+        last_rows = [None]
+
         def hy_step():
             out, _ = ctx.commit_rows_dev(bases, Zl.data_ptr(), 0, nl, Rc)
-            return sharding.gather_rows(out, L, rank, world, device=coll_dev) if use_coll else out
+            last_rows[0] = sharding.gather_rows(out, L, rank, world, device=coll_dev) if use_coll else out
+            return last_rows[0]
 
         out = hy_step()
-        gxy, _ = ol.gens_new(Rc, b"gens_r1cs_eval")
-        bad = hyrax_check(Z, out, L, Rc, (0, 1, L // 2, 3 * L // 4 - 1, L - 1), gxy) if rank == 0 else None
-        if bad is not None:
-            raise SystemExit(f"Hyrax row {bad} differs from the oracle")
+        if args.full:
+            gxy, _ = ol.gens_new(Rc, b"gens_r1cs_eval")
+            bad = hyrax_check(Z, out, L, Rc, (0, 1, L // 2, 3 * L // 4 - 1, L - 1), gxy) if rank == 0 else None
+            if bad is not None:
+                raise SystemExit(f"Hyrax row {bad} differs from the oracle")
         for _ in range(args.warmup):
             hy_step()
         ctx.prof_enable(True); ctx.prof_reset()
+        last_rows[0] = None
         dt = max_over_ranks(timer.run(hy_step, args.steps))
         prof = ctx.prof_get(); ctx.prof_enable(False)
+        if last_rows[0] is not None:
+            outputs = {"hyrax_row_commitments": g1_limbs(last_rows[0])}
         serial = {"steps": args.steps, "ms_per_step": round(dt / args.steps * 1e3, 4), "kernels_avg_ms": kernel_avgs(prof)}
         units_per_step = L * Rc / world
         dominant = "k_comb_rows" if comb_c else "k_acc_first"
@@ -462,8 +512,12 @@ def main():
         bases.free(); del Z, Zl
 
     value = units_per_step * world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        if not outputs:
+            raise SystemExit("--dump-outputs: the timed path returned nothing (--steps 0?)")
+        dump_outputs(args.dump_outputs, outputs)
 
-    # ================================================================================================ extra blocks
+    # ================================================================================================ extra blocks (--full)
     torch.cuda.empty_cache()
     if "hyrax" in blocks and args.workload == "msm":
         L, Rc = args.rows, args.cols
@@ -606,7 +660,7 @@ def main():
                     if got != wt:
                         raise SystemExit(f"msm_sweep 2^{ln}: GPU result differs from the discrete-log oracle")
                     ksteps = 12 if ln <= 22 else 6 if ln <= 24 else 3
-                    sdt, sp = timed_msm([ctx], ds, bs, nn, ksteps, 1)
+                    sdt, sp, _ = timed_msm([ctx], ds, bs, nn, ksteps, 1)
                     ka = kernel_avgs(sp)
                     e = {"ms_per_step": round(sdt / ksteps * 1e3, 4), "points_per_s": round(nn * ksteps / sdt, 1), "steps": ksteps, "steps_in_flight": 1,
                          "parity": "bit-exact vs the discrete-log identity", "kernels_avg_ms": ka,
@@ -631,7 +685,7 @@ def main():
             if not check_sharded(total, wt):
                 raise SystemExit("strong-scaling MSM: folded result differs from the folded oracle partials")
             ksteps = 4
-            sdt, sp = timed_msm([ctx], ds, bs, nn, ksteps, 1)
+            sdt, sp, _ = timed_msm([ctx], ds, bs, nn, ksteps, 1)
             ka = kernel_avgs(sp)
             size_key = f"2^{nn.bit_length() - 1}" if nn & (nn - 1) == 0 else str(nn)
             strong_roof = hbm_roofline(96.0 * nn, "k_acc_first", ka.get("k_acc_first", 0.0), stored_traffic("msm", size_key, "k_acc_first"),
@@ -669,9 +723,10 @@ def main():
     if rank == 0:
         line = {"metric": "msm_points_per_s", "value": round(value, 1), "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                 "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                "dtype": "u32", "data": "synthetic",
+                "dtype": "u32", "data": "synthetic", "full": bool(args.full),
                 "config": {"workload": workload, "units_per_step_per_gpu": int(units_per_step), "steps_in_flight": M, "collective_backend": backend if use_coll else None,
-                           "sharding": sharding_desc, "parity": "bit-exact vs the discrete-log identity / CPU oracle, checked before timing"},
+                           "sharding": sharding_desc, "parity": "bit-exact vs the discrete-log identity / CPU oracle, checked before timing" if args.full
+                           else "not checked by a plain run (--full checks it before timing; --dump-outputs writes the result)"},
                 "roofline": roofline, "cpu_baseline": cpu_baseline, "kernels_avg_ms": kernel_avgs(prof), "serial_reference": serial}
         line.update(line_extra)
         if use_coll:

@@ -45,6 +45,7 @@ ol.sc_eval_cubic(A, B, C); ol.sc_eval_r1cs(A, B, C, A); ol.sc_eval_quad(A, B); o
 ol.unipoly_from_evals(sc[:128]); ol.g1_decompress(ol.g1_compress(pts[:64])); ol.shake256(b"x" * 300, 500)
 print("ORACLE SANITIZE OK")
 """
-    env = dict(os.environ, LD_PRELOAD=libasan, ASAN_OPTIONS="detect_leaks=0")
+    preload = os.environ.get("LD_PRELOAD")              # the ASan runtime must come first; anything already preloaded stays
+    env = dict(os.environ, LD_PRELOAD=libasan + (":" + preload if preload else ""), ASAN_OPTIONS="detect_leaks=0")
     r = _run([sys.executable, "-c", code], env=env)
     assert r.returncode == 0 and "ORACLE SANITIZE OK" in r.stdout, r.stdout + r.stderr[-3000:]

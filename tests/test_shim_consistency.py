@@ -1,14 +1,14 @@
 """CPU: the Rust shim (shim/src/hip.rs + shim/patches/*.diff) against the C header.  No Rust toolchain exists in this image, so what can
 be checked mechanically is checked here: every `extern "C"` declaration of the shim has the name, arity, argument order, pointer depth,
 constness and base type of its twin in include/sbn254.h (and vice versa), every ABI function the shim's bodies call is declared, every
-`crate::hip::` item the patches use exists, nothing is left as a placeholder, and the committed patches are exactly what the recorded
-edits produce on the reference's files (checked where the reference lies; skipped on the GPU box)."""
+`crate::hip::` item the patches use exists, nothing is left as a placeholder, and the committed patches are what the recorded edits
+produce on the reference text they quote (on the reference's whole files too, where SBN_REFERENCE names a checkout of it)."""
+import importlib.util
 import os
 import re
 import subprocess
 import sys
 
-import pytest
 from conftest import ROOT
 
 HIP_RS = os.path.join(ROOT, "shim", "src", "hip.rs")
@@ -149,8 +149,66 @@ def test_patches_only_use_what_the_shim_defines():
     assert "+#[repr(transparent)]" in sc
 
 
+def _patch_tool():
+    spec = importlib.util.spec_from_file_location("make_shim_patches", os.path.join(ROOT, "tools", "make_shim_patches.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _hunks(diff):
+    """(old path, new path, [(old start, old count, new start, new count, pre-image lines, post-image lines)]) of a one-file unified diff"""
+    lines = diff.splitlines(keepends=True)
+    assert lines[0].startswith("--- ") and lines[1].startswith("+++ ")
+    hunks = []
+    for ln in lines[2:]:
+        m = re.match(r"^@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", ln)
+        if m:
+            hunks.append((int(m.group(1)), int(m.group(2) or 1), int(m.group(3)), int(m.group(4) or 1), [], []))
+            continue
+        assert hunks and ln[:1] in " -+", f"not a hunk line: {ln!r}"
+        if ln[0] in " -":
+            hunks[-1][4].append(ln[1:])
+        if ln[0] in " +":
+            hunks[-1][5].append(ln[1:])
+    return lines[0][4:].strip(), lines[1][4:].strip(), hunks
+
+
 def test_patches_are_what_the_edits_produce_on_the_reference():
-    if not os.path.isdir("/root/reference/src"):
-        pytest.skip("the reference is not on this machine (GPU box)")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "make_shim_patches.py"), "--check"], capture_output=True, text=True)
-    assert out.returncode == 0, out.stdout + out.stderr
+    """The committed patches against the recorded (anchor, replacement) edits of tools/make_shim_patches.py, from this repository alone:
+    each patch is a well-formed unified diff of the file its edit names; every line it adds or removes is a line of its edit's text;
+    and where every anchor of an edit lies inside the reference text the patch quotes (its hunks' pre-images), the edit applied to
+    that text gives exactly the hunks' post-images.  With SBN_REFERENCE naming a checkout of the reference, the patches are also
+    regenerated from its files and compared byte for byte."""
+    tool = _patch_tool()
+    sep = "\x00 hunk \x00\n"
+    replayed = []
+    for name, rel, fn in tool.EDITS:
+        diff = open(os.path.join(PATCHES, name + ".diff")).read()
+        a, b, hunks = _hunks(diff)
+        assert (a, b) == ("a/" + rel, "b/" + rel), name
+        assert hunks, name
+        prev_end = 0
+        for o0, on, n0, nn, pre, post in hunks:
+            assert (len(pre), len(post)) == (on, nn), f"{name}: hunk @@ -{o0},{on} +{n0},{nn} @@ has {len(pre)} / {len(post)} lines"
+            assert o0 > prev_end, f"{name}: hunks overlap or are out of order"
+            prev_end = o0 + on - 1
+        literal = {s.strip() for c in fn.__code__.co_consts if isinstance(c, str) for s in c.split("\n")}
+        changed = [ln[1:].rstrip("\n") for ln in diff.splitlines(keepends=True)[2:] if ln[:1] in "+-"]
+        stray = [ln for ln in changed if ln.strip() and ln.strip() not in literal]
+        assert not stray, f"{name}: lines the edit does not write: {stray[:3]}"
+        pre_text = sep.join("".join(h[4]) for h in hunks)
+        post_text = sep.join("".join(h[5]) for h in hunks)
+        try:
+            got = fn(pre_text)
+        except SystemExit as e:          # an anchor reaches past the quoted context: only the reference's whole file can replay it
+            assert "anchor occurs 0 times" in str(e) or "literals found" in str(e), f"{name}: {e}"
+            continue
+        assert got == post_text, f"{name}: the edit on the quoted reference text differs from the patch"
+        replayed.append(name)
+    assert len(replayed) >= 5, replayed
+    ref = os.environ.get("SBN_REFERENCE")
+    if ref:
+        assert os.path.isdir(os.path.join(ref, "src")), f"SBN_REFERENCE={ref} is not a checkout of the reference"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "make_shim_patches.py"), "--check"], capture_output=True, text=True)
+        assert out.returncode == 0, out.stdout + out.stderr

@@ -18,7 +18,7 @@ prof() {   # tag workload size pmc? -- program args...
 want() { [ $# -eq 0 ] && return 0; }
 TAGS="$*"
 has() { [ -z "$TAGS" ] || [[ " $TAGS " == *" $1 "* ]]; }
-B="python3 bench.py --no-cpu-baseline --blocks none"
+B="python3 bench.py --full --no-cpu-baseline --blocks none"
 has msm20 && prof msm20 msm 2^20 0 -- $B --steps 40 --warmup 4
 has msm20_serial && prof msm20_serial msm 2^20 1 -- $B --steps 20 --warmup 2 --inflight 1
 has msm22 && prof msm22 msm 2^22 1 -- $B --log-n 22 --steps 6 --warmup 1 --inflight 1
@@ -29,5 +29,5 @@ has hyrax_bucket && prof hyrax_bucket hyrax-bucket 4096x8192 1 -- $B --workload 
 has sumcheck && prof sumcheck sumcheck 18x2^21 1 -- python3 tools/bench_sumcheck.py 21 2
 has bullet && prof bullet bullet 8192 1 -- python3 tools/bench_bullet.py
 # round 3: the driver's own command (every block of the bench line) and the compiled prove-stages harness (kernel stats only)
-has bench && prof bench bench default 0 -- python3 bench.py
+has bench && prof bench bench default 0 -- python3 bench.py --full
 has prove && prof prove prove keyless 0 -- python3 tools/trace_harness.py 2

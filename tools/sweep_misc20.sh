@@ -1,6 +1,6 @@
 #!/bin/bash
 # 2^20 headline (6 in flight) and one MSM alone under the accumulate kernel's block size / segment length and the sort's split / tile overrides
-run() { python bench.py --steps 16 --warmup 4 --blocks none --no-cpu-baseline 2>/dev/null | python -c "
+run() { python bench.py --full --steps 16 --warmup 4 --blocks none --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys,os
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['serial_reference']; k=s['kernels_avg_ms']
 print(os.environ.get('TAG'), 'pipelined', d['ms_per_step'], 'alone', s['ms_per_step'], 'acc', k['k_acc_first'], 'sort', round(sum(v for n,v in k.items() if n.startswith('k_s2')),4))"; }

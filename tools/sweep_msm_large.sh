@@ -1,6 +1,6 @@
 # large single MSMs, one step in flight: window bits around the automatic choice (round 3: after the single-reduction Y3)
 # usage (GPU box): bash tools/sweep_msm_large.sh > gpurun_out/sweep_msm_large.log
-run() { python bench.py --log-n $LOGN --inflight 1 --steps $STEPS --warmup 1 --no-cpu-baseline --blocks none 2>/dev/null | python -c "
+run() { python bench.py --full --log-n $LOGN --inflight 1 --steps $STEPS --warmup 1 --no-cpu-baseline --blocks none 2>/dev/null | python -c "
 import json,sys,os
 d=json.loads(sys.stdin.readline()); k=d['serial_reference']['kernels_avg_ms']; a=d['roofline'].get('alu',{})
 sort=sum(v for n,v in k.items() if n.startswith(('k_s2','k_digits','k_hist','k_scatter','k_block_prefix','k_scan')))

@@ -6,7 +6,7 @@ for L in 3 5 7; do
 done
 for cfg in "1 -" "1 3" "1 4" "1 5" "1 6" "1 8" "0 5"; do set -- $cfg
   if [ "$2" = "-" ]; then unset SBN_RED_L; else export SBN_RED_L=$2; fi
-  SBN_RED_QUAD=$1 python bench.py --steps 12 --warmup 3 --blocks none --no-cpu-baseline --inflight 1 2>/dev/null | python -c "
+  SBN_RED_QUAD=$1 python bench.py --full --steps 12 --warmup 3 --blocks none --no-cpu-baseline --inflight 1 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['serial_reference']['kernels_avg_ms']
 print('quad=$1 L=$2 ms_per_step', d['ms_per_step'], 'l1', k['k_reduce_l1'], 'combine', k['k_reduce_combine'], 'acc', k['k_acc_first'])"

@@ -1,6 +1,6 @@
 # large single MSMs (one step in flight): the two-level sort against the one-level sort, and the window width it unlocks
 # usage (GPU box): bash tools/sweep_sort2.sh [quick] > gpurun_out/sweep_sort2.log
-run() { python bench.py --log-n $LOGN --inflight 1 --steps $STEPS --warmup 1 --no-cpu-baseline --blocks none 2>gpurun_out/sweep_sort2.err | python -c "
+run() { python bench.py --full --log-n $LOGN --inflight 1 --steps $STEPS --warmup 1 --no-cpu-baseline --blocks none 2>>"${ERR_LOG:-/dev/null}" | python -c "
 import json,sys,os
 d=json.loads(sys.stdin.readline()); k=d['kernels_avg_ms']
 a=d['roofline']['alu']
