@@ -543,6 +543,73 @@ void orc_sc_prove_cubic_batched(const uint8_t* const* A_par, const uint8_t* cons
   for (size_t t = 0; t < ntab; t++) free(T[t]);
   free(T); free(co);
 }
+/* prove_cubic_with_additive_term (sumcheck.rs:502-555, r1csproof.rs:280-300: comb = tau * (Az * Bz - Cz)) and prove_quad
+ * (sumcheck.rs:691-716, r1csproof.rs:389-397: comb = Z * ABC), challenges supplied by the caller as above.  Per round, in the
+ * reference's expression order: (e0, e2, e3) for R1CS, (e0, e2) for quad, then every table bound to r_j (:547-550, :715-716).
+ * Outputs: evals = rounds x (e0, e2, e3) / rounds x (e0, e2); finals = tau[0], Az[0], Bz[0], Cz[0] / Z[0], ABC[0]. */
+static void r1cs_sums(fe out[3], const fe* T, const fe* A, const fe* B, const fe* C, size_t h, int threads) {
+  fe s0 = {{0}}, s2 = {{0}}, s3 = {{0}};
+#pragma omp parallel num_threads(threads > 0 ? threads : 1)
+  {
+    fe e0 = {{0}}, e2 = {{0}}, e3 = {{0}};
+#pragma omp for schedule(static) nowait
+    for (size_t i = 0; i < h; i++) {
+      fe t2, t3, a2, a3, b2, b3, c2, c3, x;
+      comb_r1cs(&x, &T[i], &A[i], &B[i], &C[i]); fe_add(&FR, &e0, &e0, &x);
+      pts(&t2, &t3, &T[i], &T[i + h]); pts(&a2, &a3, &A[i], &A[i + h]); pts(&b2, &b3, &B[i], &B[i + h]); pts(&c2, &c3, &C[i], &C[i + h]);
+      comb_r1cs(&x, &t2, &a2, &b2, &c2); fe_add(&FR, &e2, &e2, &x);
+      comb_r1cs(&x, &t3, &a3, &b3, &c3); fe_add(&FR, &e3, &e3, &x);
+    }
+#pragma omp critical
+    { fe_add(&FR, &s0, &s0, &e0); fe_add(&FR, &s2, &s2, &e2); fe_add(&FR, &s3, &s3, &e3); }
+  }
+  out[0] = s0; out[1] = s2; out[2] = s3;
+}
+static void quad_sums(fe out[2], const fe* Z, const fe* ABC, size_t h, int threads) {
+  fe s0 = {{0}}, s2 = {{0}};
+#pragma omp parallel num_threads(threads > 0 ? threads : 1)
+  {
+    fe e0 = {{0}}, e2 = {{0}};
+#pragma omp for schedule(static) nowait
+    for (size_t i = 0; i < h; i++) {
+      fe z2, a2, t;
+      fe_mul(&FR, &t, &Z[i], &ABC[i]); fe_add(&FR, &e0, &e0, &t);
+      fe_add(&FR, &z2, &Z[i + h], &Z[i + h]); fe_sub(&FR, &z2, &z2, &Z[i]);
+      fe_add(&FR, &a2, &ABC[i + h], &ABC[i + h]); fe_sub(&FR, &a2, &a2, &ABC[i]);
+      fe_mul(&FR, &t, &z2, &a2); fe_add(&FR, &e2, &e2, &t);
+    }
+#pragma omp critical
+    { fe_add(&FR, &s0, &s0, &e0); fe_add(&FR, &s2, &s2, &e2); }
+  }
+  out[0] = s0; out[1] = s2;
+}
+/* the loop shared by both: ntab tables, npts values per round */
+static void sc_prove_tables(const uint8_t* const* tabs, size_t ntab, size_t npts, size_t len, size_t num_rounds, const uint8_t* challenges,
+                            uint8_t* evals, uint8_t* finals, int threads) {
+  fe* T[4];
+  for (size_t t = 0; t < ntab; t++) { T[t] = (fe*)malloc(sizeof(fe) * len); tab_to_fe(T[t], tabs[t], len, threads); }
+  size_t cur = len;
+  for (size_t j = 0; j < num_rounds && cur >= 2; j++) {
+    const size_t h = cur / 2;
+    fe e[3];
+    if (ntab == 4) r1cs_sums(e, T[0], T[1], T[2], T[3], h, threads); else quad_sums(e, T[0], T[1], h, threads);
+    if (evals) for (size_t k = 0; k < npts; k++) fe_to_bytes(&FR, evals + 32 * (npts * j + k), &e[k]);
+    fe rj; fe_from_bytes(&FR, &rj, challenges + 32 * j);
+    for (size_t t = 0; t < ntab; t++) bind_fe(T[t], h, &rj, threads);
+    cur = h;
+  }
+  if (finals) for (size_t t = 0; t < ntab; t++) fe_to_bytes(&FR, finals + 32 * t, &T[t][0]);
+  for (size_t t = 0; t < ntab; t++) free(T[t]);
+}
+void orc_sc_prove_r1cs(const uint8_t* T, const uint8_t* A, const uint8_t* B, const uint8_t* C, size_t len, size_t num_rounds, const uint8_t* challenges,
+                       uint8_t* evals, uint8_t* finals, int threads) {
+  const uint8_t* tabs[4] = {T, A, B, C};
+  sc_prove_tables(tabs, 4, 3, len, num_rounds, challenges, evals, finals, threads);
+}
+void orc_sc_prove_quad(const uint8_t* Z, const uint8_t* ABC, size_t len, size_t num_rounds, const uint8_t* challenges, uint8_t* evals, uint8_t* finals, int threads) {
+  const uint8_t* tabs[2] = {Z, ABC};
+  sc_prove_tables(tabs, 2, 2, len, num_rounds, challenges, evals, finals, threads);
+}
 /* unipoly.rs:28-59 — same expression order as the reference */
 void orc_unipoly_from_evals(const uint8_t* evals, size_t n, uint8_t* coeffs) {
   fe e[4], two, six, two_inv, six_inv; for (size_t i = 0; i < n; i++) fe_from_bytes(&FR, &e[i], evals + 32 * i);

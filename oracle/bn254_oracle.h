@@ -79,6 +79,11 @@ void orc_sc_prove_cubic_batched(const uint8_t* const* A_par, const uint8_t* cons
                                 const uint8_t* const* A_seq, const uint8_t* const* B_seq, const uint8_t* const* C_seq, size_t n_seq,
                                 size_t len, size_t num_rounds, const uint8_t* coeffs, const uint8_t* challenges,
                                 uint8_t* evals, uint8_t* combined, uint8_t* finals, int threads);
+/* prove_cubic_with_additive_term (sumcheck.rs:502-555), comb = tau*(Az*Bz-Cz): evals = rounds x (e0,e2,e3), finals = tau,Az,Bz,Cz [0] */
+void orc_sc_prove_r1cs(const uint8_t* T, const uint8_t* A, const uint8_t* B, const uint8_t* C, size_t len, size_t num_rounds, const uint8_t* challenges,
+                       uint8_t* evals, uint8_t* finals, int threads);
+/* prove_quad (sumcheck.rs:691-716), comb = Z*ABC: evals = rounds x (e0,e2), finals = Z[0], ABC[0]; challenges supplied by the caller */
+void orc_sc_prove_quad(const uint8_t* Z, const uint8_t* ABC, size_t len, size_t num_rounds, const uint8_t* challenges, uint8_t* evals, uint8_t* finals, int threads);
 /* unipoly.rs:28-59: evals at 0,1,2[,3] -> coefficients low..high; n = 3 or 4 */
 void orc_unipoly_from_evals(const uint8_t* evals, size_t n, uint8_t* coeffs);
 void orc_unipoly_eval(const uint8_t* coeffs, size_t n, const uint8_t r[32], uint8_t out[32]);

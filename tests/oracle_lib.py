@@ -174,6 +174,36 @@ def sc_prove_cubic_batched(A_par, B_par, C_par, A_seq, B_seq, C_seq, coeffs, cha
     return evals, [cb[96 * j:96 * j + 96] for j in range(rounds)], [fin[32 * t:32 * t + 32] for t in range(ntab)]
 
 
+def _np_ptr(x, keep):
+    import numpy as np
+    a = np.frombuffer(x, dtype=np.uint8) if not isinstance(x, np.ndarray) else x
+    keep.append(a)
+    return a.ctypes.data_as(C.c_void_p), a.nbytes // 32
+
+
+def _sc_prove_tables(fn, tabs, npts, challenges, threads):
+    keep = []
+    ptrs = [_np_ptr(x, keep) for x in tabs]
+    ln = ptrs[0][1]
+    assert all(n == ln for _, n in ptrs), "tables differ in length"
+    rounds = len(challenges) // 32
+    ev, fin = _buf(32 * npts * rounds), _buf(32 * len(tabs))
+    fn(*[p for p, _ in ptrs], C.c_size_t(ln), C.c_size_t(rounds), bytes(challenges), ev, fin, threads)
+    ev, fin = _b(ev), _b(fin)
+    return [ev[32 * npts * j:32 * npts * (j + 1)] for j in range(rounds)], [fin[32 * t:32 * t + 32] for t in range(len(tabs))]
+
+
+def sc_prove_r1cs(T, A, B, Cc, challenges, threads=8):
+    """prove_cubic_with_additive_term (sumcheck.rs:502-555, comb tau*(Az*Bz-Cz)) with caller-supplied challenges.  Tables: bytes-like
+    (numpy uint8 arrays are taken without a copy).  -> (evals[round] = e0||e2||e3, 96 B; finals = [tau, Az, Bz, Cz][0])"""
+    return _sc_prove_tables(lib().orc_sc_prove_r1cs, (T, A, B, Cc), 3, challenges, threads)
+
+
+def sc_prove_quad(Z, ABC, challenges, threads=8):
+    """prove_quad (sumcheck.rs:691-716, comb Z*ABC) with caller-supplied challenges -> (evals[round] = e0||e2, 64 B; finals = [Z, ABC][0])"""
+    return _sc_prove_tables(lib().orc_sc_prove_quad, (Z, ABC), 2, challenges, threads)
+
+
 def unipoly_from_evals(ev):
     n = len(ev) // 32; out = _buf(32 * n); lib().orc_unipoly_from_evals(ev, C.c_size_t(n), out); return _b(out)
 

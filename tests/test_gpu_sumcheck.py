@@ -802,3 +802,215 @@ def test_stateful_sumcheck_keyless_layer0(ctx, ol):
     """the ops product-circuit layer-0 sumcheck at keyless size (12 par + 6 seq, tables of 2^21 uniform Fr): all 21 combined round
     values and the 43 final claims against the oracle"""
     _run_stateful_sumcheck(ctx, ol, 1 << 21, 12, 6, 9900)
+
+
+# ---- prove_cubic_with_additive_term (R1CS: tau * (Az * Bz - Cz)) and prove_quad (Z * ABC) driven as the shim's R1csRounds /
+# QuadRounds and the compiled harness drive them: one eval call, one fused bind + eval per round while the tables hold >= 4 entries,
+# bind_top_many for the last round, the finals in one read.  Every round and the finals against the oracle's loops
+# (orc_sc_prove_r1cs / orc_sc_prove_quad), byte for byte.
+
+def _ints(b):
+    b = bytes(b)
+    return [int.from_bytes(b[k:k + 32], "little") for k in range(0, len(b), 32)]
+
+
+def _comb(kind, vals):
+    return vals[0] * (vals[1] * vals[2] - vals[3]) if kind == "r1cs" else vals[0] * vals[1]
+
+
+def _device_loop(cx, kind, dev, ch):
+    """-> (the round values (96 B for r1cs, 64 B for quad), the finals); `dev` is bound to every challenge in `ch`"""
+    rounds = len(ch) // 32
+    assert len(dev[0]) == 1 << rounds
+    got = [cx.sc_eval_r1cs(*dev) if kind == "r1cs" else cx.sc_eval_quad(*dev)]
+    for j in range(rounds):
+        r = ch[32 * j:32 * j + 32]
+        if len(dev[0]) >= 4:
+            got.append(cx.sc_bind_eval_r1cs(*dev, r) if kind == "r1cs" else cx.sc_bind_eval_quad(*dev, r))
+        else:
+            cx.bind_top_many(dev, r)                  # last round: nothing left to evaluate
+    assert len(got) == rounds and all(len(t) == 1 for t in dev)
+    return got, cx.table_read0_many(dev)
+
+
+def _check_loop(ol, pr, kind, host, got, finals, ch, what, relation=True):
+    """device rounds + finals == the oracle loop; with `relation`, also the sumcheck relation on the device values in big integers:
+    claim_0 = sum of the comb function over the cube, p through (e0, claim - e0, e2[, e3]), next claim = p(r_j), last claim = comb(finals)"""
+    want, want_fin = (ol.sc_prove_r1cs(*host, ch, 16) if kind == "r1cs" else ol.sc_prove_quad(*host, ch, 16))
+    assert len(got) == len(want)
+    for j, (g, w) in enumerate(zip(got, want)):
+        assert g == w, f"{what}: {kind} round {j} of {len(want)}"
+    assert finals == want_fin, f"{what}: {kind} finals"
+    if not relation:
+        return
+    from conftest import fr_bytes
+    claim = sum(_comb(kind, v) for v in zip(*(_ints(t) for t in host))) % pr.R
+    for j, g in enumerate(got):
+        e = _ints(g)
+        poly = ol.unipoly_from_evals(fr_bytes([e[0], (claim - e[0]) % pr.R] + e[1:]))
+        claim = int.from_bytes(ol.unipoly_eval(poly, ch[32 * j:32 * j + 32]), "little")
+    assert _comb(kind, _ints(b"".join(finals))) % pr.R == claim, f"{what}: {kind} final claim"
+
+
+def test_keyless_r1cs_sumcheck_every_round(ctx, ol, pr):
+    """The R1CS sat proof's first sumcheck at keyless size (r1csproof.rs:280-300: 4 tables of 2^20 uniform full-width Fr values,
+    20 rounds): the streaming kernel, the single-launch rounds with the ticketed fold, the four-lane tail and the last bind in one run"""
+    n = 1 << 20
+    dev, host = _uniform_tables(ctx, 4, n, 9200)
+    ch = rand_scalars(20, 9210)
+    got, finals = _device_loop(ctx, "r1cs", dev, ch)
+    for t in dev:
+        t.free()
+    _check_loop(ol, pr, "r1cs", host, got, finals, ch, "keyless")
+
+
+def test_keyless_quad_sumcheck_every_round(ctx, ol, pr):
+    """The R1CS sat proof's second sumcheck at keyless size (r1csproof.rs:389-397: Z and ABC of 2^21, 21 rounds); the first round
+    where the streaming kernel runs two indices per thread"""
+    n = 1 << 21
+    dev, host = _uniform_tables(ctx, 2, n, 9300)
+    ch = rand_scalars(21, 9310)
+    got, finals = _device_loop(ctx, "quad", dev, ch)
+    for t in dev:
+        t.free()
+    _check_loop(ol, pr, "quad", host, got, finals, ch, "keyless")
+
+
+def _context_with(sbn, env):
+    """a fresh context created with `env` set (the SBN_SC_* overrides are read once, at creation); the environment is restored"""
+    import os
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return sbn.Context(0)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+
+
+def _cubic_shared_c_loop(cx, ol, dev, host, ch, what):
+    """prove_cubic_batched with two "par" instances sharing C (sumcheck.rs:201-235) on the fused path: dev / host = A1, B1, A2, B2, C.
+    From 2^16 entries the shared C arrives pre-bound in the streaming kernel (its PREMASK = 4 form)."""
+    As, Bs, Cs = [dev[0], dev[2]], [dev[1], dev[3]], [dev[4], dev[4]]
+    rounds = len(ch) // 32
+    got = [cx.sc_eval_cubic_batched(As, Bs, Cs)]
+    for j in range(rounds):
+        r = ch[32 * j:32 * j + 32]
+        if len(dev[0]) >= 4:
+            got.append(cx.sc_bind_eval_cubic_batched(As, Bs, Cs, r))
+        else:
+            cx.bind_top_many(dev, r)
+    finals = cx.table_read0_many(dev)
+    want, _, want_fin = ol.sc_prove_cubic_batched([host[0], host[2]], [host[1], host[3]], host[4], [], [], [], bytes(64), ch, 16)
+    for j in range(rounds):
+        assert got[j] == b"".join(want[j]), f"{what}: cubic round {j} of {rounds}"
+    # finals order of the oracle: A_par.., B_par.., C_par
+    assert [finals[0], finals[2], finals[1], finals[3], finals[4]] == want_fin, f"{what}: cubic finals"
+
+
+_KNOBS = [
+    {"SBN_SC_GRID": "1"},                 # one block: 2^16 / 256 indices per thread at 2^18
+    {"SBN_SC_GRID": "3"},                 # a stride that does not divide q: threads with unequal trip counts
+    {"SBN_SC_GRID": "61"},
+    {"SBN_SC_BLOCK_ROUNDS": "1"},
+    {"SBN_SC_WAVES": "3"},                # k_sc_bind_eval<KIND, 3> + k_sc_finish
+    {"SBN_SC_WAVES": "4"},
+    {"SBN_SC_NO_STREAM_MBOX": "1"},       # k_sc_finish after the eval and the streaming rounds
+    {"SBN_SC_NO_TINY": "1"},              # the lane-per-index kernel on the last rounds
+    {"SBN_SC_SINGLE_MAX": "256"},         # the single-launch edge moved down: streaming from 512-entry tables on
+]
+
+
+@pytest.mark.parametrize("knobs", _KNOBS, ids=lambda k: ",".join(f"{a}={b}" for a, b in k.items()))
+def test_r1cs_quad_loops_paths(sbn, ol, pr, knobs):
+    """the full R1CS and quad loops at 2^17 and 2^18 on the non-default paths of the eval and fused rounds, against the oracle loops"""
+    cx = _context_with(sbn, knobs)
+    try:
+        for logn in (17, 18):
+            for kind, ntab in (("r1cs", 4), ("quad", 2)):
+                seed = 9400 + 10 * logn + ntab
+                dev, host = _uniform_tables(cx, ntab, 1 << logn, seed)
+                ch = rand_scalars(logn, seed + 5)
+                got, finals = _device_loop(cx, kind, dev, ch)
+                for t in dev:
+                    t.free()
+                _check_loop(ol, pr, kind, host, got, finals, ch, f"{knobs} 2^{logn}", relation=logn == 17)
+            if knobs.get("SBN_SC_GRID") == "3":
+                dev, host = _uniform_tables(cx, 5, 1 << logn, 9480 + logn)
+                _cubic_shared_c_loop(cx, ol, dev, host, rand_scalars(logn, 9490 + logn), f"{knobs} 2^{logn}")
+                for t in dev:
+                    t.free()
+    finally:
+        cx.close()
+
+
+def _edge_values(pr):
+    """extreme scalars: 0, 1, 2, r - 1, r - 2, (r - 1) / 2, 2^252, 2^253, 2^253 - 1, 2^29 - 1, 2^29, 2^58 - 1 and the values with
+    every 29-bit limb at its maximum below r (limbs 0..7 all ones, top limb 0 or r's top limb - 1).  The tables hold Montgomery forms
+    (R = 2^261), so each value also enters as its Montgomery preimage: the device then computes on a representative of the value itself."""
+    R = pr.R
+    top = R >> 232
+    plain = [0, 1, 2, R - 1, R - 2, (R - 1) // 2, 1 << 252, 1 << 253, (1 << 253) - 1, (1 << 29) - 1, 1 << 29, (1 << 58) - 1,
+             (1 << 232) - 1, (top << 232) - 1]
+    assert all(v < R for v in plain)
+    rinv = pow(1 << 261, -1, R)
+    out = []
+    for v in plain + [v * rinv % R for v in plain]:
+        if v not in out:
+            out.append(v)
+    return out
+
+
+def _edge_tables(E, mtop, n, run):
+    """five index arrays into E (one per table) for layout `run` on tables of n entries; E[mtop] = the Montgomery preimage of r - 1"""
+    import numpy as np
+    m, h, ar = len(E), n // 2, np.arange(n)
+    i0, itop = E.index(0), 3                                  # E[3] = r - 1
+    if run == "pairs":                        # every ordered pair of E at the (lo, hi) positions of some index
+        out = []
+        for k in range(5):
+            p = (k * h + np.arange(h)) % (m * m)
+            out.append(np.concatenate([p // m, p % m]))
+        return out
+    if run.startswith("const"):               # the same value everywhere
+        c = int(run[5:])
+        return [np.full(n, (5 * c + k) % m) for k in range(5)]
+    halves = lambda a, b: np.concatenate([np.full(h, a), np.full(h, b)])
+    if run == "halves":                       # lo 0 / hi r - 1 and the reverse: the largest and the most negative 2 hi - lo
+        return [halves(i0, itop), halves(itop, i0), halves(i0, mtop), halves(mtop, i0), halves(itop, i0)]
+    if run == "alternating":                  # neighbouring indices alternate between two extremes, and cycles through E
+        alt = np.where(ar % 2 == 0, i0, itop)
+        return [alt, (ar + 1) % m, np.where(ar % 2 == 0, mtop, i0), (ar * 7 + 3) % m, np.where(ar % 2 == 0, itop, mtop)]
+    raise ValueError(run)
+
+
+@pytest.mark.parametrize("logn", [9, 15, 17])      # 2^9: the four-lane kernel from the first fused round; 2^15: single launch; 2^17: streaming
+def test_sumcheck_loops_edge_values(ctx, ol, pr, logn):
+    """the full R1CS, quad and cubic (shared C) loops on tables built from extreme scalars, with extreme challenges, against the oracle
+    loops.  Every kernel computes on the unsigned lazy-reduction path (stored representatives in [0, 2.5 r), points below 8 r and 13.5 r,
+    biased differences): the rounds after the first run on the non-canonical representatives the binds store, so the whole loop is the test."""
+    import numpy as np
+    E = _edge_values(pr)
+    R = pr.R
+    rinv = pow(1 << 261, -1, R)
+    mtop = E.index((R - 1) * rinv % R)
+    vals = np.frombuffer(b"".join(v.to_bytes(32, "little") for v in E), dtype=np.uint8).reshape(-1, 32)
+    chs = [0, 1, R - 1, R - 2, 1 << 253, int.from_bytes(rand_scalars(1, 9600), "little"), (R - 1) * rinv % R, rinv]
+    n = 1 << logn
+    runs = ["pairs", "halves", "alternating"] + [f"const{c}" for c in range((len(E) + 4) // 5)]
+    for ri, run in enumerate(runs):
+        host = [np.ascontiguousarray(vals[idx].reshape(-1)) for idx in _edge_tables(E, mtop, n, run)]
+        ch = b"".join(chs[(ri + j) % len(chs)].to_bytes(32, "little") for j in range(logn))   # every challenge, in a different order per run
+        for kind, sel in (("r1cs", (0, 1, 2, 3)), ("quad", (0, 1)), ("quad", (2, 4))):
+            dev = [ctx.table_upload(host[k]) for k in sel]
+            got, finals = _device_loop(ctx, kind, dev, ch)
+            for t in dev:
+                t.free()
+            _check_loop(ol, pr, kind, [host[k] for k in sel], got, finals, ch, f"{run} 2^{logn}", relation=logn == 9)
+        dev = [ctx.table_upload(x) for x in host]
+        _cubic_shared_c_loop(ctx, ol, dev, host, ch, f"{run} 2^{logn}")
+        for t in dev:
+            t.free()

@@ -267,3 +267,41 @@ def test_prove_cubic_batched_loop_vs_round_functions(ol, pr):
     assert ev2[0] == [ol.sc_eval_cubic(As[i], Bs[i], Cs[i]) for i in range(n_seq)] and len(fin2) == 6
     ev3, cb3, fin3 = ol.sc_prove_cubic_batched(Ap, Bp, Cp, [], [], [], co[:96], ch[:32], 2)
     assert ev3[0] == [ol.sc_eval_cubic(Ap[i], Bp[i], Cp) for i in range(n_par)] and len(fin3) == 7
+
+
+@pytest.mark.parametrize("kind", ["r1cs", "quad"])
+def test_prove_r1cs_quad_loops_vs_round_functions(ol, pr, kind):
+    """orc_sc_prove_r1cs / orc_sc_prove_quad (sumcheck.rs:502-555, 691-716, threaded) against the per-round oracle functions that the
+    golden vectors pin (sc_eval_r1cs / sc_eval_quad, bind_top), and the verifier's relations in big integers: claim_0 = sum of the comb
+    function over the cube, p(0) + p(1) == claim with p through (e0, claim - e0, e2[, e3]), next claim = p(r_j), and the final claim
+    = the comb function of the finals"""
+    from conftest import fr_bytes, rand_scalars
+    n, rounds = 64, 6
+    ntab = 4 if kind == "r1cs" else 2
+    tabs = [rand_scalars(n, 110 + k) for k in range(ntab)]
+    ch = rand_scalars(rounds, 120)
+    ints = lambda b: [int.from_bytes(b[32 * i:32 * i + 32], "little") for i in range(len(b) // 32)]
+    comb = (lambda t, a, b, c: t * (a * b - c)) if kind == "r1cs" else (lambda z, abc: z * abc)
+    for threads in (1, 3):
+        if kind == "r1cs":
+            evals, fin = ol.sc_prove_r1cs(*tabs, ch, threads)
+        else:
+            evals, fin = ol.sc_prove_quad(*tabs, ch, threads)
+        assert len(evals) == rounds and len(fin) == ntab
+        host = list(tabs)
+        claim = sum(comb(*v) for v in zip(*(ints(t) for t in host))) % pr.R
+        for j in range(rounds):
+            want = ol.sc_eval_r1cs(*host) if kind == "r1cs" else ol.sc_eval_quad(*host)
+            assert evals[j] == want, j
+            e = ints(evals[j])
+            poly = ol.unipoly_from_evals(fr_bytes([e[0], (claim - e[0]) % pr.R] + e[1:]))
+            pc = ints(poly)
+            assert (pc[0] + sum(pc)) % pr.R == claim, j
+            r = ch[32 * j:32 * j + 32]
+            claim = int.from_bytes(ol.unipoly_eval(poly, r), "little")
+            host = [ol.bind_top(t, r) for t in host]
+        assert fin == [t[:32] for t in host]
+        assert comb(*ints(b"".join(fin))) % pr.R == claim
+    # fewer rounds than variables: the finals are entry 0 of the partly bound tables
+    ev2, fin2 = ol.sc_prove_r1cs(*tabs, ch[:64], 2) if kind == "r1cs" else ol.sc_prove_quad(*tabs, ch[:64], 2)
+    assert ev2 == evals[:2] and fin2 == [ol.bind_top(ol.bind_top(t, ch[:32]), ch[32:64])[:32] for t in tabs]
