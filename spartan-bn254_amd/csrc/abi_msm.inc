@@ -30,6 +30,7 @@ int sbn_ctx_create(int device, sbn_ctx** out) {
   else (void)hipGetLastError();
   c->sort2_ok = sort2_set_lds();
   if (const char* e2 = getenv("SBN_SORT2_MIN")) c->sort2_min = (size_t)strtoull(e2, nullptr, 0);
+  if (const char* eg = getenv("SBN_MSM_GLV")) { const int v = atoi(eg); if (v == 0 || v == 1) c->msm_glv = v; }
   *out = c;
   return SBN_OK;
 }
@@ -39,7 +40,7 @@ void sbn_ctx_destroy(sbn_ctx* c) {
   hipStreamSynchronize(c->stream);
   prof_drain(c);
   DevBuf* bufs[] = {&c->scal_canon, &c->hist, &c->offs, &c->sorted, &c->buckets, &c->red_a, &c->red_b, &c->wsum, &c->stage_scal, &c->stage_pts, &c->out_small,
-                    &c->sc_args, &c->sc_partial, &c->sc_out, &c->sc_r, &c->sc_tabs, &c->sc_tickets, &c->gen_tmp, &c->acc_ctr, &c->extra_list, &c->extra_out, &c->big_list, &c->digits, &c->blockhist, &c->perm, &c->merged, &c->zstage[0], &c->zstage[1], &c->out_rows, &c->comb_partial, &c->s2_cnt, &c->s2_part, &c->s2_idx, &c->s2_lo};
+                    &c->sc_args, &c->sc_partial, &c->sc_out, &c->sc_r, &c->sc_tabs, &c->sc_tickets, &c->gen_tmp, &c->acc_ctr, &c->extra_list, &c->extra_out, &c->big_list, &c->digits, &c->blockhist, &c->perm, &c->merged, &c->zstage[0], &c->zstage[1], &c->out_rows, &c->comb_partial, &c->s2_cnt, &c->s2_part, &c->s2_idx, &c->s2_lo, &c->glv_scal};
   for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
   for (auto& b : c->pool) hipFree(b.first);
   if (c->pin) hipHostFree(c->pin);
@@ -93,7 +94,7 @@ void sbn_bases_free(sbn_ctx* c, sbn_bases* b) {
   if (b->uniq) { sbn_bases_free(c, b->uniq); b->uniq = nullptr; }
   for (auto& kv : b->bullet_ext) sbn_bases_free(c, kv.second);
   b->bullet_ext.clear();
-  for (void* p : {b->d_comb, b->d_csr_off, b->d_csr_cols, b->d_big, b->d_pts}) if (p) hipFree(p);
+  for (void* p : {b->d_comb, b->d_csr_off, b->d_csr_cols, b->d_big, b->d_glv, b->d_pts}) if (p) hipFree(p);
   for (auto& kv : b->tables) hipFree(kv.second);
   delete b;
 }
@@ -116,7 +117,7 @@ int sbn_msm_bases_dev(sbn_ctx* c, const sbn_bases* b, const void* d_scalars, siz
   if (n == 0) { memset(out_xy, 0, 64); if (out_is_inf) *out_is_inf = 1; return SBN_OK; }      // before any launch: a zero-size grid is an error
   const uint32_t* ds; int rc;
   if ((rc = canon_scalars_dev(c, d_scalars, n, flags, &ds))) return rc;
-  return msm_device(c, ds, (const uint32_t*)b->d_pts, n, out_xy, out_is_inf);
+  return msm_device(c, ds, (const uint32_t*)b->d_pts, n, out_xy, out_is_inf, b);
 }
 int sbn_msm_bases(sbn_ctx* c, const sbn_bases* b, const uint8_t* scalars, size_t n, uint32_t flags, uint8_t out_xy[64], int* out_is_inf) {
   if (!c || !b || !out_xy || (!scalars && n)) return SBN_EINVAL;
@@ -126,7 +127,7 @@ int sbn_msm_bases(sbn_ctx* c, const sbn_bases* b, const uint8_t* scalars, size_t
   if (n == 0) { memset(out_xy, 0, 64); if (out_is_inf) *out_is_inf = 1; return SBN_OK; }
   const uint32_t* ds; int rc;
   if ((rc = stage_scalars(c, scalars, n, flags, &ds))) return rc;
-  return msm_device(c, ds, (const uint32_t*)b->d_pts, n, out_xy, out_is_inf);
+  return msm_device(c, ds, (const uint32_t*)b->d_pts, n, out_xy, out_is_inf, b);
 }
 int sbn_msm(sbn_ctx* c, const uint8_t* scalars, const uint8_t* points, size_t n, uint32_t flags, uint8_t out_xy[64], int* out_is_inf) {
   if (!c || !out_xy || ((!scalars || !points) && n)) return SBN_EINVAL;

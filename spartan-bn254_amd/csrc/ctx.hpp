@@ -46,6 +46,8 @@ struct sbn_ctx {
   hipEvent_t z_consumed = nullptr;            // set while a chunked commit is running: recorded when a chunk's scalars have been read
   DevBuf zstage[2], out_rows, comb_partial;
   DevBuf s2_cnt, s2_part, s2_idx, s2_lo;     // two-level sort of a large single MSM (sort2_kernels.cuh)
+  DevBuf glv_scal;                           // GLV half-scalars of a single MSM (glv_kernels.cuh): 2n x 16 B
+  int msm_glv = -1;                          // single MSMs over the GLV endomorphism: -1 automatic (msm_host.hpp: glv_applies), 0 never, 1 wherever it can run (SBN_MSM_GLV)
   bool sort2_ok = false;      // dynamic LDS of its level-1 scatter granted
   size_t sort2_min = (size_t)1 << 20;   // terms from which a single MSM takes the two-level sort (SBN_SORT2_MIN; 0 = never)
   int sc_waves = 2;           // streaming sumcheck rounds: 2 = software-pipelined loads, 2 waves per SIMD (default); 3 / 4 = the plain kernel at that occupancy (SBN_SC_WAVES)
@@ -77,6 +79,9 @@ struct sbn_bases {
   void* d_comb = nullptr; int comb_c = 0; size_t comb_bytes = 0;
   // bullet reduction (abi_bullet.inc): derived sets G ‖ Q (+ h), one per distinct Q, built on first use and owned by this handle
   mutable std::vector<std::pair<std::string, sbn_bases*>> bullet_ext;
+  // GLV table (glv_kernels.cuh): the n + has_h points, then their images phi(P) = (beta x, y); built by the first single MSM that takes the
+  // GLV path and owned by this handle (a derived handle never shares it)
+  mutable void* d_glv = nullptr;
 };
 static const uint32_t MERGE_BIG = 64;
 extern "C" void sbn_bases_free(sbn_ctx* c, sbn_bases* b);

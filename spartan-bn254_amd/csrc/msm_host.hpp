@@ -5,11 +5,12 @@
 // ------------------------------------------------------------------------------------------------
 static int ilog2_ceil(size_t n) { int l = 0; while (((size_t)1 << l) < n) l++; return l; }
 
-// Signed radix-2^c digits: W windows cover 254 bits, the top digit (+ carry) must stay <= 2^(c-1).
-static MsmShape make_shape(int c) {
+// Signed radix-2^c digits: W windows cover `bits` bits (254: canonical scalars; 127: GLV half-scalars), the top digit (+ carry)
+// must stay <= 2^(c-1).
+static MsmShape make_shape(int c, int bits = 254) {
   MsmShape s; s.c = c; s.nb = 1 << (c - 1);
-  int W = (254 + c - 1) / c;
-  int tb = 254 - (W - 1) * c;          // bits in the top window
+  int W = (bits + c - 1) / c;
+  int tb = bits - (W - 1) * c;         // bits in the top window
   if (tb > c - 1) W += 1;
   s.W = W;
   return s;
@@ -68,6 +69,7 @@ static MsmShape choose_shape(size_t terms, bool shared_bucket_set, int cmax, siz
 
 // ---- two-level sort of a large single MSM (sort2_kernels.cuh) ----
 #define S2_FOR_EACH_C(X) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) X(22)
+#define S2_GLV_FOR_EACH_C(X) X(13) X(14) X(15) X(16) X(17)        // window bits the GLV half-scalars (16-byte records) are instantiated for
 static bool sort2_set_lds() {
   bool ok = true;
   const int bytes = (int)s2_scatter_lds_bytes(S2_P_MAX);
@@ -83,14 +85,22 @@ static bool sort2_set_lds() {
              if (hipFuncSetAttribute((const void*)k_s2_count<C, S2_SPT_SMALL>, hipFuncAttributeMaxDynamicSharedMemorySize, cnt_bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; }
   S2_FOR_EACH_C(X)
 #undef X
+#define X(C) if (hipFuncSetAttribute((const void*)k_s2_count<C, S2_SPT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, cnt_bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } \
+             if (hipFuncSetAttribute((const void*)k_s2_count<C, S2_SPT_SMALL, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, cnt_bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } \
+             if (hipFuncSetAttribute((const void*)k_s2_scatter<C, S2_SPT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } \
+             if (hipFuncSetAttribute((const void*)k_s2_scatter<C, S2_SPT_SMALL, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; }
+  S2_GLV_FOR_EACH_C(X)
+#undef X
   return ok;
 }
 static bool sort2_applies(const sbn_ctx* c, int mode, size_t n, int cbits) {
   return mode == MODE_SINGLE && c->sort2_ok && c->sort2_min && n >= c->sort2_min && cbits >= S2_C_MIN && cbits <= S2_C_MAX;
 }
 // scalars -> hist / offs / sorted of all W windows (the arrays the one-level sort leaves behind)
-static int sort2_run(sbn_ctx* c, const uint32_t* scalars, size_t n, const MsmShape& s, size_t estride, uint32_t* hist, uint32_t* offs, uint32_t* sorted) {
-  S2Geom g; g.n = n; g.c = s.c; g.W = s.W;
+// glv: the n records are GLV half-scalars (16 B each, glv_kernels.cuh); record t >= n/2 indexes point t + glv_gap
+static int sort2_run(sbn_ctx* c, const uint32_t* scalars, size_t n, const MsmShape& s, size_t estride, uint32_t* hist, uint32_t* offs, uint32_t* sorted, bool glv = false, size_t glv_gap = 0) {
+  S2Geom g; g.n = n; g.c = s.c; g.W = s.W; g.half = n / 2; g.gap = glv ? glv_gap : 0;
+  if (glv && (s.c < 13 || s.c > 17)) return fail(c, SBN_EINVAL, "two-level sort: no GLV instantiation for windows of %d bits", s.c);
   // bucket index = hi (level 1, <= 1024 partitions) | lo (level 2, <= 2048 LDS counters): runs of 8192 / P entries leave level 1,
   // runs of tile / 2^lo_log leave level 2
   g.lo_log = std::max(s.c - 1 - 8, 8); if (g.lo_log > S2_LO_LOG_MAX) g.lo_log = S2_LO_LOG_MAX;
@@ -121,7 +131,12 @@ static int sort2_run(sbn_ctx* c, const uint32_t* scalars, size_t n, const MsmSha
   if (lds_a > (size_t)24 * S2_P_MAX * 4) return fail(c, SBN_EINVAL, "two-level sort: %zu level-1 counters do not fit the LDS granted to k_s2_count", WP);
   {
     ProfScope _ps(c, "k_s2_count");
-    switch (s.c) {
+    if (glv) switch (s.c) {
+#define X(C) case C: if (spt == S2_SPT) hipLaunchKernelGGL((k_s2_count<C, S2_SPT, 4>), dim3(g.K), dim3(1024), lds_a, c->stream, scalars, g, cntA, c->d_bad); \
+                     else hipLaunchKernelGGL((k_s2_count<C, S2_SPT_SMALL, 4>), dim3(g.K), dim3(1024), lds_a, c->stream, scalars, g, cntA, c->d_bad); break;
+      S2_GLV_FOR_EACH_C(X)
+#undef X
+    } else switch (s.c) {
 #define X(C) case C: if (spt == S2_SPT) hipLaunchKernelGGL((k_s2_count<C, S2_SPT>), dim3(g.K), dim3(1024), lds_a, c->stream, scalars, g, cntA, c->d_bad); \
                      else hipLaunchKernelGGL((k_s2_count<C, S2_SPT_SMALL>), dim3(g.K), dim3(1024), lds_a, c->stream, scalars, g, cntA, c->d_bad); break;
       S2_FOR_EACH_C(X)
@@ -132,7 +147,12 @@ static int sort2_run(sbn_ctx* c, const uint32_t* scalars, size_t n, const MsmSha
   LAUNCH(c, "k_s2_prefix", k_s2_prefix_hi, 1, 1024, (const uint32_t*)part_cnt, g.W, g.P, part_off, sc_off);
   {
     ProfScope _ps(c, "k_s2_scatter");
-    switch (s.c) {
+    if (glv) switch (s.c) {
+#define X(C) case C: if (spt == S2_SPT) hipLaunchKernelGGL((k_s2_scatter<C, S2_SPT, 4>), dim3(g.K), dim3(1024), lds_c, c->stream, scalars, g, (const uint32_t*)cntA, (const uint32_t*)part_off, tmp_idx, tmp_lo); \
+                     else hipLaunchKernelGGL((k_s2_scatter<C, S2_SPT_SMALL, 4>), dim3(g.K), dim3(1024), lds_c, c->stream, scalars, g, (const uint32_t*)cntA, (const uint32_t*)part_off, tmp_idx, tmp_lo); break;
+      S2_GLV_FOR_EACH_C(X)
+#undef X
+    } else switch (s.c) {
 #define X(C) case C: if (spt == S2_SPT) hipLaunchKernelGGL((k_s2_scatter<C, S2_SPT>), dim3(g.K), dim3(1024), lds_c, c->stream, scalars, g, (const uint32_t*)cntA, (const uint32_t*)part_off, tmp_idx, tmp_lo); \
                      else hipLaunchKernelGGL((k_s2_scatter<C, S2_SPT_SMALL>), dim3(g.K), dim3(1024), lds_c, c->stream, scalars, g, (const uint32_t*)cntA, (const uint32_t*)part_off, tmp_idx, tmp_lo); break;
       S2_FOR_EACH_C(X)
@@ -160,6 +180,8 @@ struct BucketJob {
   size_t threads;         // digit-kernel threads
   const uint32_t* points; // Montgomery affine points the entries index
   const uint8_t* skip;    // ROWS: per-row flags, 2 = all-zero row whose stages can be skipped (or null)
+  bool glv;               // SINGLE over GLV half-scalars (da.n = 2 x bases, 16-byte records): points = the GLV table, record t >= n/2
+  size_t glv_gap;         // indexes point t + glv_gap
 };
 
 // digits -> counting sort -> segmented bucket accumulation -> per-problem weighted sums in c->wsum (P x XYZZ)
@@ -232,8 +254,9 @@ static int run_bucket_job(sbn_ctx* c, const BucketJob& J) {
   const uint8_t* skip = nullptr;
   const bool two_level = sort2_applies(c, J.mode, J.da.n, s.c) && !J.skip;
   if (s.c > MSM_C_MAX && !two_level) return fail(c, SBN_EINVAL, "window of %d bits needs the two-level sort", s.c);
+  if (J.glv && !two_level) return fail(c, SBN_EINVAL, "GLV half-scalars need the two-level sort");
   if (two_level) {
-    if ((rc = sort2_run(c, J.da.scalars, J.da.n, s, estride, hist, offs, sorted))) return rc;
+    if ((rc = sort2_run(c, J.da.scalars, J.da.n, s, estride, hist, offs, sorted, J.glv, J.glv_gap))) return rc;
   } else {
   if (J.P > 65535 || g.R > 65535) return fail(c, SBN_EINVAL, "sort grid too large (P=%zu R=%d)", J.P, g.R);
   if ((rc = ensure(c, c->digits, J.P * estride * sizeof(dig_t)))) return rc;
@@ -298,8 +321,60 @@ static int run_bucket_job(sbn_ctx* c, const BucketJob& J) {
   return SBN_OK;
 }
 
+// A generator set may be shared by several contexts (one per host thread / stream); its lazily built tables (window, GLV) are guarded by
+// one process-wide mutex (taken after the context's own, never the other way round).
+static std::mutex g_bases_tables_mu;
+
+// ---- GLV (glv_kernels.cuh): one MSM of n full-width scalars as an MSM of 2n half-width ones over P_i and phi(P_i) ----
+// Products of the window model above for one MSM in the two-level sort regime (40 per bucket): `terms` x W mixed additions, W x 2^(c-1)
+// buckets, and the half window's worth of additions a short top window costs.
+static double single_msm_cost(size_t terms, const MsmShape& s, int bits) {
+  double cost = (double)terms * s.W * 10.0 + (double)s.W * s.nb * 40.0;
+  if (bits - (s.W - 1) * s.c < s.c - 1) cost += (double)terms * 5.0;
+  return cost;
+}
+// GLV shape for n bases (2n half-scalars of 127 bits): SBN_MSM_C when it is one of the instantiated widths, else the model's best of 13..17
+// (c = 16: 8 windows of 16 bits fill all 2^15 buckets of the top window, 127 = 7 x 16 + 15)
+static MsmShape glv_shape(size_t n) {
+  if (const char* env = getenv("SBN_MSM_C")) { const int v = atoi(env); if (v >= 13 && v <= 17) return make_shape(v, 127); }
+  MsmShape best = make_shape(16, 127);
+  for (int cc = 13; cc <= 17; cc++) { const MsmShape s = make_shape(cc, 127); if (single_msm_cost(2 * n, s, 127) < single_msm_cost(2 * n, best, 127)) best = s; }
+  return best;
+}
+// Whether a single MSM of n terms over the generator set b takes the GLV path.  It needs the two-level sort for its 2n records and a
+// handle (the table of images phi(P) is kept with it).  Automatic rule: the window model's products at least 4 % below the plain shape's
+// (a margin for the split pass and for gathering from a table twice the size) — 2^19 .. 2^20 bases (c = 16 against c = 15: 8 x 2n
+// against 17 x n mixed additions, -5.9 %); at 2^21 the model gains 2 %, at 2^22 and above the plain windows (c = 17, 15 x n) win.
+// SBN_MSM_GLV=0 / 1 (read when the context is created) switches it off / on wherever it can run; with it unset, an SBN_MSM_C experiment
+// keeps the plain windows it asks for.
+static bool glv_applies(const sbn_ctx* c, const sbn_bases* b, size_t n, const MsmShape& plain) {
+  if (!b || c->msm_glv == 0 || (c->msm_glv < 0 && getenv("SBN_MSM_C"))) return false;
+  const size_t npts = b->n + (b->has_h ? 1 : 0);
+  if (2 * npts > 0x7fffffffull || !sort2_applies(c, MODE_SINGLE, 2 * n, S2_C_MIN)) return false;
+  if (c->msm_glv == 1) return true;
+  return single_msm_cost(2 * n, glv_shape(n), 127) * 1.04 < single_msm_cost(n, plain, 254);
+}
+// the GLV table of a generator set: its npts points, then phi of each (2 x npts x 64 B), built on the first GLV MSM and kept with the
+// handle (the contexts that share a handle share one table; derived handles build their own)
+static int bases_glv_table(sbn_ctx* c, const sbn_bases* b, const uint32_t** out) {
+  std::lock_guard<std::mutex> tg(g_bases_tables_mu);
+  if (b->d_glv) { *out = (const uint32_t*)b->d_glv; return SBN_OK; }
+  const size_t npts = b->n + (b->has_h ? 1 : 0);
+  void* tab = nullptr;
+  hipError_t e = hipMalloc(&tab, 2 * npts * 64);
+  if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, SBN_ENOMEM, "hipMalloc GLV table (%zu B): %s", 2 * npts * 64, hipGetErrorString(e)); }
+  LAUNCH(c, "k_glv_table", k_glv_table, (unsigned)((npts + 255) / 256), 256, (const uint32_t*)b->d_pts, npts, (uint32_t*)tab);
+  hipError_t le = hipGetLastError();
+  hipError_t se = hipStreamSynchronize(c->stream);
+  if (le != hipSuccess || se != hipSuccess) { hipFree(tab); return fail(c, SBN_EHIP, "GLV table build: %s", hipGetErrorString(le != hipSuccess ? le : se)); }
+  b->d_glv = tab;
+  *out = (const uint32_t*)tab;
+  return SBN_OK;
+}
+
 // MSM over device-resident canonical scalars and Montgomery affine bases -> canonical affine bytes on the host
-static int msm_device(sbn_ctx* c, const uint32_t* d_scal, const uint32_t* d_bases, size_t n, uint8_t out_xy[64], int* out_is_inf) {
+// (b: the generator set d_bases belongs to, or null for points staged by the call — only a set keeps a GLV table)
+static int msm_device(sbn_ctx* c, const uint32_t* d_scal, const uint32_t* d_bases, size_t n, uint8_t out_xy[64], int* out_is_inf, const sbn_bases* b = nullptr) {
   if (n == 0) { memset(out_xy, 0, 64); if (out_is_inf) *out_is_inf = 1; return SBN_OK; }
   if (n > 0x7fffffffull) return fail(c, SBN_EINVAL, "msm: n=%zu exceeds 2^31-1", n);
   BucketJob J; memset(&J, 0, sizeof J);
@@ -311,9 +386,19 @@ static int msm_device(sbn_ctx* c, const uint32_t* d_scal, const uint32_t* d_base
   }
   J.P = (size_t)J.s.W; J.threads = n; J.points = d_bases;
   J.da.scalars = d_scal; J.da.n = n; J.da.estride = n; J.da.bad = c->d_bad;
+  const bool glv = glv_applies(c, b, n, J.s);
   int rc;
+  if (glv) {
+    const uint32_t* tab;
+    if ((rc = bases_glv_table(c, b, &tab))) return rc;
+    if ((rc = ensure(c, c->glv_scal, 2 * n * 16))) return rc;
+    J.s = glv_shape(n); J.P = (size_t)J.s.W; J.threads = 2 * n; J.points = tab;
+    J.da.scalars = (const uint32_t*)c->glv_scal.p; J.da.n = 2 * n; J.da.estride = 2 * n;
+    J.glv = true; J.glv_gap = b->n + (b->has_h ? 1 : 0) - n;
+  }
   if ((rc = ensure_pin(c, std::max<size_t>(4096, J.P * 128)))) return rc;
   if ((rc = input_check_begin(c))) return rc;
+  if (glv) LAUNCH(c, "k_glv_split", k_glv_split, (unsigned)((n + 255) / 256), 256, d_scal, n, (uint32_t*)c->glv_scal.p, c->d_bad);
   if ((rc = run_bucket_job(c, J))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->pin, c->wsum.p, J.P * 128, hipMemcpyDeviceToHost, c->stream));
   if ((rc = input_check_fetch(c))) return rc;
@@ -329,9 +414,6 @@ static int msm_device(sbn_ctx* c, const uint32_t* d_scal, const uint32_t* d_base
 }
 
 // window table 2^(c w) * P_j of a generator set, built on first use for a given c and kept with the handle
-// A generator set may be shared by several contexts (one per host thread / stream); its lazily built tables are guarded by
-// one process-wide mutex (taken after the context's own, never the other way round).
-static std::mutex g_bases_tables_mu;
 static int bases_window_table(sbn_ctx* c, const sbn_bases* b, const MsmShape& s, const uint32_t** out) {
   std::lock_guard<std::mutex> tg(g_bases_tables_mu);
   auto it = b->tables.find(s.c);

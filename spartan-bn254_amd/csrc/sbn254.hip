@@ -10,6 +10,7 @@
 #include "host_field.hpp"
 #include "msm_kernels.cuh"
 #include "sort2_kernels.cuh"
+#include "glv_kernels.cuh"
 #include "comb_kernels.cuh"
 #include "sumcheck_kernels.cuh"
 #include "sumcheck_comb_kernels.cuh"

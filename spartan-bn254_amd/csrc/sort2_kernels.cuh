@@ -28,14 +28,18 @@ struct S2Geom {
   int c, W, P;     // window bits, windows, partitions per window
   int lo_log;      // log2 of the buckets per partition: bucket b = hi << lo_log | lo
   int K;           // level-1 chunks (blocks)
+  size_t half, gap;  // GLV (16-byte records, glv_kernels.cuh): record t >= half is the second half-scalar of base t - half, whose point
+                     // sits at t + gap in the base table (gap = table points - scalars; 0 and unused on the plain path)
 };
 
 // Digits are taken from scalars held in REGISTERS: window bits C and window index w are compile-time (the kernels are
 // instantiated per C and unrolled over w), so limb and shift of every digit are constants and a scalar is read from memory once
 // per pass (two 16-byte loads per lane) instead of two or three words per window with a 32-byte lane stride.
-template <int C> struct S2Shape {
-  static constexpr int W0 = (254 + C - 1) / C;
-  static constexpr int W = W0 + ((254 - (W0 - 1) * C) > C - 1 ? 1 : 0);      // == make_shape(C).W
+// SW: 32-bit words per scalar record — 8 (canonical Fr scalars, 254 bits) or 4 (GLV half-scalars, 127 bits)
+template <int C, int SW = 8> struct S2Shape {
+  static constexpr int BITS = SW == 8 ? 254 : 127;
+  static constexpr int W0 = (BITS + C - 1) / C;
+  static constexpr int W = W0 + ((BITS - (W0 - 1) * C) > C - 1 ? 1 : 0);      // == make_shape(C, BITS).W
 };
 // (the scalar is a VALUE of vector type, not an array: an array gets its two-word reads merged into overlapping 64-bit loads,
 //  which keeps it in scratch memory)
@@ -51,8 +55,9 @@ template <int C, int w> __device__ __forceinline__ int s2_digit(const s2_u32x8 k
   carry = 0;
   return (int)v;
 }
-__device__ __forceinline__ s2_u32x8 s2_load_scalar(const uint32_t* __restrict__ p) {
-  const uint4 a = reinterpret_cast<const uint4*>(p)[0], b = reinterpret_cast<const uint4*>(p)[1];
+template <int SW = 8> __device__ __forceinline__ s2_u32x8 s2_load_scalar(const uint32_t* __restrict__ scalars, size_t t) {
+  const uint4* p = reinterpret_cast<const uint4*>(scalars + (size_t)SW * t);
+  const uint4 a = p[0], b = SW == 8 ? p[1] : make_uint4(0u, 0u, 0u, 0u);
   s2_u32x8 k; k[0] = a.x; k[1] = a.y; k[2] = a.z; k[3] = a.w; k[4] = b.x; k[5] = b.y; k[6] = b.z; k[7] = b.w;
   return k;
 }
@@ -71,17 +76,17 @@ __device__ __forceinline__ void s2_count_scalar(const s2_u32x8 kk, int P, int lo
   };
   (one(std::integral_constant<int, Ws>{}), ...);
 }
-template <int C, int SPT>
+template <int C, int SPT, int SW = 8>
 __global__ void __launch_bounds__(1024) k_s2_count(const uint32_t* __restrict__ scalars, S2Geom g, uint32_t* __restrict__ cntA, uint32_t* __restrict__ bad) {
-  constexpr int W = S2Shape<C>::W; constexpr int CH = 1024 * SPT;
+  constexpr int W = S2Shape<C, SW>::W; constexpr int CH = 1024 * SPT;
   const int k = blockIdx.x, P = g.P;
   for (int j = threadIdx.x; j < W * P; j += 1024) s2_lds[j] = 0;
   __syncthreads();
   for (int i = 0; i < SPT; i++) {
     const size_t t = (size_t)k * CH + (size_t)i * 1024 + threadIdx.x;
     if (t >= g.n) break;
-    const s2_u32x8 kk = s2_load_scalar(scalars + 8 * t);
-    if (!s2_is_canonical(kk)) atomicAdd(bad, 1u);       // reported as SBN_EINVAL by the entry point (scalar.rs:87-95)
+    const s2_u32x8 kk = s2_load_scalar<SW>(scalars, t);
+    if (SW == 8 && !s2_is_canonical(kk)) atomicAdd(bad, 1u);       // reported as SBN_EINVAL by the entry point (scalar.rs:87-95); GLV: checked by k_glv_split
     s2_count_scalar<C>(kk, P, g.lo_log, std::make_integer_sequence<int, W>{});
   }
   __syncthreads();
@@ -143,7 +148,7 @@ __global__ void __launch_bounds__(1024) k_s2_prefix_hi(const uint32_t* __restric
 __host__ __device__ inline size_t s2_scatter_lds_bytes(int P, int spt = S2_SPT) { return ((size_t)3 * P + 32) * 4 + (size_t)1024 * spt * 8; }
 struct S2ScatterArgs {
   const uint32_t* cntA; const uint32_t* part_off; uint32_t* tmp_idx; uint16_t* tmp_lo;
-  size_t n; int P, K, k, lo_log;
+  size_t n, half, gap; int P, K, k, lo_log;
 };
 template <int C, int w, int SPT>
 __device__ __forceinline__ void s2_scatter_window(const s2_u32x8 (&kk)[SPT], uint32_t (&carry)[SPT], const S2ScatterArgs& a) {
@@ -175,7 +180,9 @@ __device__ __forceinline__ void s2_scatter_window(const s2_u32x8 (&kk)[SPT], uin
     if (d[i] == 0) continue;
     const uint32_t b = (uint32_t)((d[i] < 0 ? -d[i] : d[i]) - 1), hi = b >> a.lo_log;
     const uint32_t pos = base[hi] + rank[i];
-    stage_idx[pos] = (uint32_t)(t0 + (size_t)i * 1024) | (d[i] < 0 ? 0x80000000u : 0u);
+    size_t e = t0 + (size_t)i * 1024;
+    if (a.gap && e >= a.half) e += a.gap;                // GLV: the second half-scalar of a base indexes its image phi(P)
+    stage_idx[pos] = (uint32_t)e | (d[i] < 0 ? 0x80000000u : 0u);
     stage_lo[pos] = (uint16_t)(b & ((1u << a.lo_log) - 1u)); stage_hi[pos] = (uint16_t)hi;
   }
   __syncthreads();
@@ -190,18 +197,19 @@ template <int C, int SPT, int... Ws>
 __device__ __forceinline__ void s2_scatter_windows(const s2_u32x8 (&kk)[SPT], uint32_t (&carry)[SPT], const S2ScatterArgs& a, std::integer_sequence<int, Ws...>) {
   (s2_scatter_window<C, Ws, SPT>(kk, carry, a), ...);
 }
-template <int C, int SPT>
+template <int C, int SPT, int SW = 8>
 __global__ void __launch_bounds__(1024) k_s2_scatter(const uint32_t* __restrict__ scalars, S2Geom g, const uint32_t* __restrict__ cntA /* prefixed over k */,
                                                      const uint32_t* __restrict__ part_off, uint32_t* __restrict__ tmp_idx, uint16_t* __restrict__ tmp_lo) {
   S2ScatterArgs a; a.cntA = cntA; a.part_off = part_off; a.tmp_idx = tmp_idx; a.tmp_lo = tmp_lo; a.n = g.n; a.P = g.P; a.K = g.K; a.k = blockIdx.x; a.lo_log = g.lo_log;
+  a.half = g.half; a.gap = SW == 8 ? 0 : g.gap;
   s2_u32x8 kk[SPT]; uint32_t carry[SPT];
 #pragma unroll
   for (int i = 0; i < SPT; i++) {
     const size_t t = (size_t)blockIdx.x * (1024 * SPT) + (size_t)i * 1024 + threadIdx.x;
     carry[i] = 0;
-    kk[i] = t < g.n ? s2_load_scalar(scalars + 8 * t) : (s2_u32x8)(0u);      // zero scalar: every digit 0, no entries
+    kk[i] = t < g.n ? s2_load_scalar<SW>(scalars, t) : (s2_u32x8)(0u);      // zero scalar: every digit 0, no entries
   }
-  s2_scatter_windows<C, SPT>(kk, carry, a, std::make_integer_sequence<int, S2Shape<C>::W>{});
+  s2_scatter_windows<C, SPT>(kk, carry, a, std::make_integer_sequence<int, S2Shape<C, SW>::W>{});
 }
 
 // level 2: a block = one sub-chunk (S2_SUB entries of one partition).  Consecutive workgroup ids go round-robin over the 8 XCDs,
