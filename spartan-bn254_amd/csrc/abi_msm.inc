@@ -21,7 +21,6 @@ int sbn_ctx_create(int device, sbn_ctx** out) {
   }
   *c->h_bad = 0;
   c->sck = sc_knobs_read();
-  if (const char* ew = getenv("SBN_SC_WAVES")) { const int v = atoi(ew); if (v >= 2 && v <= 4) c->sc_waves = v; }
   // 128 KiB of dynamic LDS per sort block (32768 counters); gfx950 has 160 KiB per CU
   if (hipFuncSetAttribute((const void*)k_hist_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * 4) == hipSuccess &&
       hipFuncSetAttribute((const void*)k_scatter_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * 4) == hipSuccess) c->sort_rs_max = 32768;

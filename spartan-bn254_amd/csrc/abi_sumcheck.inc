@@ -9,7 +9,7 @@
 //           while a round has >= 2^14 index pairs (SC_COMB_MIN_Q), the "seq" instances on the per-instance kernels; smaller rounds: everything on the
 //           per-instance single-launch kernels (A' is already scaled: the host only adds the "par" triples);
 //   SCALED  (smaller tables): the "par" A tables are copied scaled when the sumcheck begins (one launch), then the per-instance kernels;
-//   PLAIN   (a zero coefficient among the "par" instances, or SBN_SC_NO_COMB set): nothing is scaled, the host combines with coeffs.
+//   PLAIN   (a zero coefficient among the "par" instances): nothing is scaled, the host combines with coeffs.
 // In every mode the "seq" instances' triples are weighted on the host (18 products per round at most).
 // Final claims (:302-318): A_i[0] = A'_i[0] / c_i — one host inversion per sumcheck (batched), the same field elements bit for bit.
 
@@ -28,7 +28,6 @@ struct sbn_sumcheck {
   ScCombGroup* d_groups = nullptr;          // device: the groups of the round-0 sums and of every combined round, written once when the sumcheck begins
   size_t eval_groups = 0;                   // groups [0, eval_groups): round-0 sums
   std::vector<size_t> grp_off, grp_cnt;     // combined round j (= binds so far): groups [grp_off[j], + grp_cnt[j])
-  bool fuse_c = false;                      // COMB mode: the combined rounds bind the shared C inside the round kernel
   sbn_table* owned_c = nullptr;             // sbn_sumcheck_begin_eq: the eq table built for this sumcheck (poly_C_par), released with the state
   std::vector<uint8_t> finals_host;         // the final claims as the last round delivered them (canonical, before the division by c_i)
   uint32_t* d_finals = nullptr;             // ntab x 32 B: where the LAST bind puts every table's single entry (sbn_sumcheck_finish reads it in one go)
@@ -119,20 +118,20 @@ static int sc_launch_inst_fused(sbn_ctx* c, ScFusedPack& pack, size_t count, siz
   unsigned gx;
   {
     const size_t br = 4;
-    size_t want = std::max<size_t>(1, br * 256 * (size_t)c->sc_waves / count), cap = (q + 255) / 256;
+    size_t want = std::max<size_t>(1, br * 256 * 2 / count), cap = (q + 255) / 256;
     gx = (unsigned)std::max<size_t>(1, std::min(std::min(want, cap), SC_PART_INST_BLOCKS));
   }
   if ((rc = ensure(c, c->sc_partial, SC_PARTIAL_BYTES))) return rc;
   const ScFusedArgs* dargs = nullptr;
   if (single) {
-    if (q <= 128 && !c->sck.no_tiny) {
+    if (q <= 128) {
       const unsigned bt = (unsigned)std::max<size_t>(64, (4 * q + 63) / 64 * 64);
       LAUNCH(c, "k_sc_bind_eval_cubic", (k_sc_bind_eval_tiny<KIND_CUBIC>), dim3(1, (unsigned)count), bt, dargs, pack, q, rs, c->mbox, seq);
     } else
       LAUNCH(c, "k_sc_bind_eval_cubic", (k_sc_bind_eval<KIND_CUBIC, 2>), dim3(gx, (unsigned)count), 256, dargs, pack, q, rs, (uint32_t*)c->sc_partial.p, (uint32_t*)c->sc_tickets.p, c->mbox, seq);
   } else {
     // streaming: every table needs its writer in the launch or must arrive bound (the caller pre-binds shared tables)
-    bool pf_ok = c->sc_waves == 2;
+    bool pf_ok = true;
     for (size_t i = 0; i < count && pf_ok; i++) {
       unsigned mask = 0;
       for (int t = 0; t < 3; t++) { if (pack.a[i].pre[t]) mask |= 1u << t; else if (!pack.a[i].dst[t]) pf_ok = false; }
@@ -238,7 +237,7 @@ static int sumcheck_begin_locked(sbn_ctx* c, const sbn_table* const* A_par, cons
   for (size_t i = 0; i < n_seq; i++) st->cur.push_back((const uint32_t*)C_seq[i]->d);
   bool zero_coeff = false;
   for (size_t i = 0; i < ninst; i++) { st->co.push_back(el_from(coeffs + 32 * i)); st->co_m.push_back(sbn_host::fr::to_m(st->co[i])); if (i < n_par && sbn_host::fr::is_zero(st->co[i])) zero_coeff = true; }
-  st->mode = (zero_coeff || n_par == 0 || c->sck.no_comb) ? 0 : (len >= SC_COMB_MIN_LEN && len / 4 >= sc_comb_min_q() && n_par >= 2 && c->sc_waves == 2 && !c->sck.no_comb_kernel) ? 2 : 1;   // (the first bind, len / 4 index pairs, is where COMB mode scales A: it must be a combined round)
+  st->mode = (zero_coeff || n_par == 0) ? 0 : (len >= SC_COMB_MIN_LEN && len / 4 >= sc_comb_min_q() && n_par >= 2) ? 2 : 1;   // (the first bind, len / 4 index pairs, is where COMB mode scales A: it must be a combined round)
   // one slab: per table len/2 + len/4 entries, the groups, and (SCALED mode) full-length copies of the "par" A tables
   const size_t half = len / 2, quarter = std::max<size_t>(len / 4, 1);
   const size_t per_tab = (half + quarter) * 32;
@@ -286,17 +285,16 @@ static int sumcheck_begin_locked(sbn_ctx* c, const sbn_table* const* A_par, cons
       // u, v depend on the challenge: a one-wave kernel derives them on the device when it arrives (k_sc_first_uv)
       if ((rc = ensure_pin(c, 4096 + (ngroups_total + 1) * sizeof(ScCombGroup)))) return rc;
       ScCombGroup* hg = (ScCombGroup*)((uint8_t*)c->pin + 4096);
-      const bool fuse_c = st->fuse_c = !c->sck.no_fuse_c;      // the combined rounds bind the shared C themselves (no k_bind_oop launch per round)
       size_t per = 0; n_comb = sc_comb_group_count(c, st.get(), half, SC_PACK_MAX - n_seq, &per);
       sc_comb_groups_fill(st.get(), hg, n_comb, per, st->cur.data(), nullptr, st->cur[2 * n_par], true, u.data(), nullptr);
       if (!plan_q.empty()) {     // the first bind (reads the caller's tables, writes buf[0], scales A): u = c_i for now, k_sc_first_uv finishes u, v once r_0 is known
         sc_comb_group_count(c, st.get(), plan_q[0], SC_PACK_MAX - n_seq, &per);
         sc_comb_groups_fill(st.get(), hg + st->grp_off[0], st->grp_cnt[0], per, st->cur.data(), st->buf[0].data(), st->buf[0][2 * n_par], true, u.data(), nullptr);      // (the scaling first bind reads a pre-bound C: its kernel has no register to spare)
       }
-      for (size_t j = 1; j < plan_q.size(); j++) {
+      for (size_t j = 1; j < plan_q.size(); j++) {     // the later binds bind the shared C themselves (no k_bind_oop launch per round)
         sc_comb_group_count(c, st.get(), plan_q[j], SC_PACK_MAX - n_seq, &per);
         sc_comb_groups_fill(st.get(), hg + st->grp_off[j], st->grp_cnt[j], per, (const uint32_t* const*)st->buf[(j - 1) & 1].data(), st->buf[j & 1].data(), st->buf[j & 1][2 * n_par], false, nullptr, nullptr,
-                            fuse_c ? st->buf[(j - 1) & 1][2 * n_par] : nullptr);
+                            st->buf[(j - 1) & 1][2 * n_par]);
       }
       HIPCHK(c, hipMemcpyAsync(st->d_groups, hg, ngroups_total * sizeof(ScCombGroup), hipMemcpyHostToDevice, c->stream));
     }
@@ -306,8 +304,7 @@ static int sumcheck_begin_locked(sbn_ctx* c, const sbn_table* const* A_par, cons
       for (size_t j = 0; j < n_seq; j++) { pack.a[j].t[0] = st->cur[o + j]; pack.a[j].t[1] = st->cur[o + n_seq + j]; pack.a[j].t[2] = st->cur[o + 2 * n_seq + j]; inst_ids.push_back(n_par + j); }
     }
     uint32_t* part2 = (uint32_t*)c->sc_partial.p + (size_t)SC_PACK_MAX * 1024 * 24;         // the second half of the partial-sum area
-    const bool mixed_ok = !c->sck.no_mixed && !c->sck.no_mixed_eval;
-    if (n_seq && mixed_ok && half >= ((size_t)1 << 16)) {
+    if (n_seq && half >= ((size_t)1 << 16)) {
       // both kinds in ONE launch: 0.78-0.83 ms against 0.835-0.875 for the two launches on the 2^21 tables (tools/sc_blocks_sweep.sh MODE=begin);
       // 2.9 GB at 3.6 TB/s: round 0 is VALU-bound (6 products per "seq" index, two scalings per "par" instance)
       const size_t mc = c->sck.comb_eval_blocks_mixed, ms = c->sck.eval_blocks_mixed;
@@ -413,8 +410,8 @@ int sbn_sumcheck_round(sbn_ctx* c, sbn_sumcheck* st, const uint8_t r[32], uint8_
   const bool comb = st->mode == 2 && q >= sc_comb_min_q();
   if (st->mode == 2 && !comb && !st->scaled) return fail(c, SBN_EINVAL, "sumcheck: internal: unscaled tables below the combined kernels' range");
   if (comb) {
-    // shared C: bound inside the round kernel (every group binds its entries, group 0 stores them), or — SBN_SC_NO_FUSE_C — once ahead of it
-    if (!st->fuse_c || !st->scaled) LAUNCH(c, "k_bind_oop", k_bind_oop, stream_grid(len / 2), 256, st->cur[oC], dst[oC], len / 2, rs);
+    // shared C: bound inside the round kernel (every group binds its entries, group 0 stores them), except by the scaling first bind: once ahead of it
+    if (!st->scaled) LAUNCH(c, "k_bind_oop", k_bind_oop, stream_grid(len / 2), 256, st->cur[oC], dst[oC], len / 2, rs);
     const bool scale_now = !st->scaled;
     if ((rc = ensure(c, c->sc_partial, SC_PARTIAL_BYTES))) return rc;
     const size_t jr = (size_t)st->binds;
@@ -433,13 +430,13 @@ int sbn_sumcheck_round(sbn_ctx* c, sbn_sumcheck* st, const uint8_t r[32], uint8_
       inst_ids.push_back(n_par + j);
     }
     // streaming rounds with both kinds of instance: ONE grid, the VALU-bound "seq" blocks interleaved with the memory-bound "par" blocks
-    const bool mixed = n_seq > 0 && q > SC_SINGLE_LAUNCH_MAX / 2 && c->sc_waves == 2 && !c->sck.no_mixed;
+    const bool mixed = n_seq > 0 && q > SC_SINGLE_LAUNCH_MAX / 2;
     if (n_seq && !mixed) { if ((rc = sc_launch_inst_fused(c, seqpack, n_seq, q, rs, seq))) return rc; }
     // grid: 512 blocks for the "par" groups + 512 for the "seq" instances = two block rounds of the 512 resident blocks.  Every block
     // ends in a ~7 us epilogue (three wave sums, write-through stores, the ticket), so the 3070 blocks of the first version cost ~40 us
     // per launch whatever the table size (t = 40 us + bytes / 4.4 TB/s over the six streaming rounds); and EQUAL counts do best
     // (tools/sc_blocks_sweep.sh: 512:512 3.77-3.95 ms per sumcheck, 1024:2048 3.99-4.02, 512:768 4.01, 512:256 4.26).  Both kinds end up
-    // evenly spread over the 8 XCDs and finish within 2 % of each other (tools/sc_blocks_timeline.py: 930 / 912 us on the 2^21 tables);
+    // evenly spread over the 8 XCDs and finish within 2 % of each other (per-block clocks: 930 / 912 us on the 2^21 tables);
     // forcing one long + one short block per slot, or one kind per XCD, changes nothing (4.04 against 4.01 ms)
     const size_t comb_blocks = c->sck.comb_blocks, seq_blocks = c->sck.seq_blocks;
     size_t want = std::max<size_t>(1, comb_blocks / n_comb), cap = (q + 255) / 256;
@@ -450,21 +447,8 @@ int sbn_sumcheck_round(sbn_ctx* c, sbn_sumcheck* st, const uint8_t r[32], uint8_
       const size_t capq = (q + 255) / 256;
       const unsigned gx_seq = (unsigned)std::max<size_t>(1, std::min(std::min<size_t>(seq_blocks / n_seq, capq), SC_PART_INST_BLOCKS));
       const unsigned total = (unsigned)(n_comb * gx + n_seq * gx_seq);
-      // diagnostic: SBN_SC_DEBUG_BLOCKS=<file> appends one line per block of every such launch (kind, XCD, start / end on the 100 MHz clock)
-      const char* dbg_path = c->sck.debug_blocks.empty() ? nullptr : c->sck.debug_blocks.c_str();
-      unsigned long long* d_dbg = nullptr;
-      if (dbg_path) HIPCHK(c, hipMalloc((void**)&d_dbg, (size_t)total * 32));
-      if (scale_now) LAUNCH(c, "k_sc_round_mixed_first", k_sc_round_mixed<true>, total, 256, d_grp, (uint32_t)n_comb, gx, seqpack, (uint32_t)n_seq, gx_seq, q, rs, (uint32_t*)c->sc_partial.p, part2, (uint32_t*)c->sc_tickets.p, c->mbox, seq, d_dbg);
-      else LAUNCH(c, "k_sc_round_mixed", k_sc_round_mixed<false>, total, 256, d_grp, (uint32_t)n_comb, gx, seqpack, (uint32_t)n_seq, gx_seq, q, rs, (uint32_t*)c->sc_partial.p, part2, (uint32_t*)c->sc_tickets.p, c->mbox, seq, d_dbg);
-      if (d_dbg) {
-        std::vector<unsigned long long> h((size_t)total * 4);
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(h.data(), d_dbg, h.size() * 8, hipMemcpyDeviceToHost)); hipFree(d_dbg);
-        if (FILE* f = fopen(dbg_path, "a")) {
-          for (unsigned b = 0; b < total; b++) fprintf(f, "%u,%zu,%u,%llu,%llu,%llu,%llu\n", seq, q, b, h[4 * b], h[4 * b + 1], h[4 * b + 2], h[4 * b + 3]);
-          fclose(f);
-        }
-      }
+      if (scale_now) LAUNCH(c, "k_sc_round_mixed_first", k_sc_round_mixed<true>, total, 256, d_grp, (uint32_t)n_comb, gx, seqpack, (uint32_t)n_seq, gx_seq, q, rs, (uint32_t*)c->sc_partial.p, part2, (uint32_t*)c->sc_tickets.p, c->mbox, seq);
+      else LAUNCH(c, "k_sc_round_mixed", k_sc_round_mixed<false>, total, 256, d_grp, (uint32_t)n_comb, gx, seqpack, (uint32_t)n_seq, gx_seq, q, rs, (uint32_t*)c->sc_partial.p, part2, (uint32_t*)c->sc_tickets.p, c->mbox, seq);
     } else
     if (scale_now) LAUNCH(c, "k_sc_comb_bind_eval_first", k_sc_comb_bind_eval<true>, dim3(gx, (unsigned)n_comb), 256, d_grp, q, rs, part2, (uint32_t*)c->sc_tickets.p, c->mbox, (uint32_t)n_seq, seq);
     else LAUNCH(c, "k_sc_comb_bind_eval", k_sc_comb_bind_eval<false>, dim3(gx, (unsigned)n_comb), 256, d_grp, q, rs, part2, (uint32_t*)c->sc_tickets.p, c->mbox, (uint32_t)n_seq, seq);

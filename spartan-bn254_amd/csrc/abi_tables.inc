@@ -133,7 +133,7 @@ static int sc_eval_common(sbn_ctx* c, const sbn_table* const* const* cols, int n
   // One launch whatever the size: the last block of an instance (ticket) folds the blocks' partial sums into the polled host
   // mailbox.  The partial sums are written through the caches (fr_store_coherent), so the hand-over needs no device-scope release
   // fence — the fence is what made this 3.5x slower on large tables in round 1 (it writes back the XCD's whole L2).
-  const bool single = packed && (half <= SC_SINGLE_LAUNCH_MAX || !c->sck.no_stream_mbox);
+  // (more than SC_PACK_MAX instances: k_sc_finish folds them, and the result is copied back)
   ScArgsPack pack; memset(&pack, 0, sizeof pack);
   if (packed) { for (size_t i = 0; i < count; i++) for (int j = 0; j < ncols; j++) pack.a[i].t[j] = (const uint32_t*)cols[j][i]->d; }
   else {
@@ -144,7 +144,7 @@ static int sc_eval_common(sbn_ctx* c, const sbn_table* const* const* cols, int n
     HIPCHK(c, hipMemcpyAsync(c->sc_args.p, ha, count * sizeof(ScArgs), hipMemcpyHostToDevice, c->stream));
   }
   const ScArgs* dargs = packed ? nullptr : (const ScArgs*)c->sc_args.p;
-  if (single) {
+  if (packed) {
     if ((rc = sc_tickets(c))) return rc;
     hres = (uint8_t*)c->mbox;
     const uint32_t seq = ++c->mbox_seq;
@@ -225,7 +225,7 @@ static int sc_bind_eval_common(sbn_ctx* c, sbn_table* const* const* cols, int nc
     }
   }
   std::vector<char> prebound(distinct.size(), 0);
-  if (!single && !c->sck.no_prebind)
+  if (!single)
     for (size_t k = 0; k < distinct.size(); k++) if (uses[k] >= 2) {
       prebound[k] = 1;
       LAUNCH(c, "k_bind_oop", k_bind_oop, stream_grid(len / 2), 256, (const uint32_t*)distinct[k]->d, (uint32_t*)distinct[k]->d2, len / 2, rs);
@@ -251,7 +251,7 @@ static int sc_bind_eval_common(sbn_ctx* c, sbn_table* const* const* cols, int nc
     // Four block rounds (interleaved sweep on one box, all six streaming rounds of a 2^21 sumcheck, SBN_SC_BLOCK_ROUNDS = 1 / 2 / 3 /
     // 4 / 6: 2.60-2.63 / 2.50-2.56 / 2.46-2.53 / 2.43-2.44 / 2.56-2.63 ms)
     const size_t br = single ? 4 : c->sck.block_rounds;
-    size_t want = std::max<size_t>(1, br * 256 * (size_t)c->sc_waves / count), cap = (q + 255) / 256;
+    size_t want = std::max<size_t>(1, br * 256 * 2 / count), cap = (q + 255) / 256;
     if (c->sck.grid) want = c->sck.grid;
     gx = (unsigned)std::max<size_t>(1, std::min(std::min(want, cap), (size_t)1024));
   }
@@ -267,7 +267,7 @@ static int sc_bind_eval_common(sbn_ctx* c, sbn_table* const* const* cols, int nc
     if ((rc = sc_tickets(c))) return rc;
     hres = (uint8_t*)c->mbox;
     const uint32_t seq = ++c->mbox_seq;
-    if (q <= 128 && !c->sck.no_tiny) {
+    if (q <= 128) {
       // the last rounds of a sumcheck: four lanes per index (k_sc_bind_eval_tiny), one block of up to 512 lanes per instance
       // (measured per round at 18 instances: 64 / 128 / 256 indices 10.5 / 13.8 / 21.8 us against 16 us for the lane-per-index kernel)
       const unsigned bt = (unsigned)std::max<size_t>(64, (4 * q + 63) / 64 * 64);
@@ -279,7 +279,7 @@ static int sc_bind_eval_common(sbn_ctx* c, sbn_table* const* const* cols, int nc
     if ((rc = sc_mbox_wait(c, count, seq))) return rc;
   } else {
     if ((rc = ensure(c, c->sc_out, std::max<size_t>(4096, count * 96)))) return rc;
-    bool pf_ok = c->sc_waves == 2;              // the software-pipelined kernel is built for the usual patterns only
+    bool pf_ok = true;                          // the software-pipelined kernel is built for the usual patterns only
     for (size_t i = 0; i < count && pf_ok; i++) {
       unsigned mask = 0;
       const int order[4] = {KIND == KIND_R1CS ? 1 : 0, KIND == KIND_R1CS ? 2 : 1, KIND == KIND_R1CS ? 3 : 2, 0};
@@ -287,7 +287,7 @@ static int sc_bind_eval_common(sbn_ctx* c, sbn_table* const* const* cols, int nc
       if (!sc_pf_mask_supported(KIND, mask)) pf_ok = false;
     }
     const char* nms = KIND == KIND_CUBIC ? "k_sc_bind_eval_cubic_stream" : KIND == KIND_R1CS ? "k_sc_bind_eval_r1cs_stream" : "k_sc_bind_eval_quad_stream";   // profiled apart from the single-launch rounds
-    if (pf_ok && packed && !c->sck.no_stream_mbox) {
+    if (pf_ok && packed) {
       // the streaming round finishes in the kernel too (ticketed fold into the host mailbox): no finishing launch, no copy, no stream wait
       if ((rc = sc_tickets(c))) return rc;
       const uint32_t seq = ++c->mbox_seq;
@@ -297,7 +297,6 @@ static int sc_bind_eval_common(sbn_ctx* c, sbn_table* const* const* cols, int nc
       hres = (uint8_t*)c->mbox;
     } else {
     if (pf_ok) LAUNCH(c, nms, (k_sc_bind_eval_pf<KIND>), dim3(gx, (unsigned)count), 256, dargs, pack, q, rs, (uint32_t*)c->sc_partial.p, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u);
-    else if (c->sc_waves >= 4) LAUNCH(c, nm, (k_sc_bind_eval<KIND, 4>), dim3(gx, (unsigned)count), 256, dargs, pack, q, rs, (uint32_t*)c->sc_partial.p, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u);
     else LAUNCH(c, nm, (k_sc_bind_eval<KIND, 3>), dim3(gx, (unsigned)count), 256, dargs, pack, q, rs, (uint32_t*)c->sc_partial.p, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u);
     LAUNCH(c, "k_sc_finish", k_sc_finish, (unsigned)count, 64, (const uint32_t*)c->sc_partial.p, (int)gx, (uint32_t*)c->sc_out.p);
     LAUNCHCHK(c);

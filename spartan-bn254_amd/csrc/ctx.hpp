@@ -9,27 +9,21 @@ struct DevBuf {
   void* p = nullptr; size_t cap = 0;
 };
 
-// Experiment overrides of the sumcheck paths (SBN_SC_*: tools/README.md), read ONCE when the context is created — never on a round's path
+// Numeric overrides of the sumcheck thresholds and grids (SBN_SC_*: tools/README.md), read ONCE when the context is created — never on a round's path
 // (441 rounds per prove; getenv is not safe against a concurrent setenv).  A test or sweep that wants another setting creates a context.
 struct ScKnobs {
-  bool no_tiny = false, no_mixed = false, no_mixed_eval = false, no_comb = false, no_comb_kernel = false, no_prebind = false, no_stream_mbox = false, no_fuse_c = false;
   size_t comb_grid = 0;              // 0: automatic
   size_t comb_blocks = 512, seq_blocks = 512, comb_eval_blocks_mixed = 768, eval_blocks_mixed = 768, comb_eval_blocks = 1024, eval_blocks = 2048;
   size_t comb_min_q = (size_t)1 << 14, comb_lanes = 262144, single_max = (size_t)1 << 14, grid = 0, block_rounds = 4;
-  std::string debug_blocks;          // SBN_SC_DEBUG_BLOCKS=<file>
 };
 static ScKnobs sc_knobs_read() {
   ScKnobs k;
-  auto flag = [](const char* n) { return getenv(n) != nullptr; };
   auto num = [](const char* n, long long lo, size_t* out) { const char* e = getenv(n); if (!e) return false; const long long x = atoll(e); if (x < lo) return false; *out = (size_t)x; return true; };
-  k.no_tiny = flag("SBN_SC_NO_TINY"); k.no_mixed = flag("SBN_SC_NO_MIXED"); k.no_mixed_eval = flag("SBN_SC_NO_MIXED_EVAL"); k.no_comb = flag("SBN_SC_NO_COMB");
-  k.no_comb_kernel = flag("SBN_SC_NO_COMB_KERNEL"); k.no_prebind = flag("SBN_SC_NO_PREBIND"); k.no_stream_mbox = flag("SBN_SC_NO_STREAM_MBOX"); k.no_fuse_c = flag("SBN_SC_NO_FUSE_C");
   num("SBN_SC_COMB_GRID", 1, &k.comb_grid); num("SBN_SC_COMB_BLOCKS", 1, &k.comb_blocks); num("SBN_SC_SEQ_BLOCKS", 1, &k.seq_blocks);
   if (num("SBN_SC_COMB_EVAL_BLOCKS", 1, &k.comb_eval_blocks)) k.comb_eval_blocks_mixed = k.comb_eval_blocks;
   if (num("SBN_SC_EVAL_BLOCKS", 1, &k.eval_blocks)) k.eval_blocks_mixed = k.eval_blocks;
   num("SBN_SC_COMB_MIN_Q", 1, &k.comb_min_q); num("SBN_SC_COMB_LANES", 1, &k.comb_lanes); num("SBN_SC_SINGLE_MAX", 2, &k.single_max); num("SBN_SC_GRID", 1, &k.grid);
   { size_t v = 0; if (num("SBN_SC_BLOCK_ROUNDS", 1, &v) && v <= 16) k.block_rounds = v; }
-  if (const char* e = getenv("SBN_SC_DEBUG_BLOCKS")) k.debug_blocks = e;
   return k;
 }
 
@@ -50,7 +44,6 @@ struct sbn_ctx {
   int msm_glv = -1;                          // single MSMs over the GLV endomorphism: -1 automatic (msm_host.hpp: glv_applies), 0 never, 1 wherever it can run (SBN_MSM_GLV)
   bool sort2_ok = false;      // dynamic LDS of its level-1 scatter granted
   size_t sort2_min = (size_t)1 << 20;   // terms from which a single MSM takes the two-level sort (SBN_SORT2_MIN; 0 = never)
-  int sc_waves = 2;           // streaming sumcheck rounds: 2 = software-pipelined loads, 2 waves per SIMD (default); 3 / 4 = the plain kernel at that occupancy (SBN_SC_WAVES)
   bool sort_rows_ok = false;  // 160 KiB dynamic LDS granted to k_sort_rows
   int sort_rs_max = 16384;   // LDS counters per sort block (raised to 32768 when 128 KiB of dynamic LDS is granted)
   void* pin = nullptr; size_t pin_cap = 0;   // pinned host staging for small D2H results

@@ -73,8 +73,7 @@ static MsmShape choose_shape(size_t terms, bool shared_bucket_set, int cmax, siz
 static bool sort2_set_lds() {
   bool ok = true;
   const int bytes = (int)s2_scatter_lds_bytes(S2_P_MAX);
-  if (hipFuncSetAttribute((const void*)k_s2_place<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2_place_lds_bytes<8>(S2_LO_LOG_MAX)) != hipSuccess) { (void)hipGetLastError(); ok = false; }
-  if (hipFuncSetAttribute((const void*)k_s2_place<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2_place_lds_bytes<16>(S2_LO_LOG_MAX)) != hipSuccess) { (void)hipGetLastError(); ok = false; }
+  if (hipFuncSetAttribute((const void*)k_s2_place, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2_place_lds_bytes(S2_LO_LOG_MAX)) != hipSuccess) { (void)hipGetLastError(); ok = false; }
 #define X(C) if (hipFuncSetAttribute((const void*)k_s2_scatter<C, S2_SPT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } \
              if (hipFuncSetAttribute((const void*)k_s2_scatter<C, S2_SPT_SMALL>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; }
   S2_FOR_EACH_C(X)
@@ -164,11 +163,8 @@ static int sort2_run(sbn_ctx* c, const uint32_t* scalars, size_t n, const MsmSha
   LAUNCH(c, "k_s2_prefix", k_s2_prefix2, (unsigned)WP, 1024, bh, g, (const uint32_t*)part_off, (const uint32_t*)sc_off, hist, offs);
   {
     ProfScope _ps(c, "k_s2_place");
-    int ept = 8; if (const char* e = getenv("SBN_SORT2_EPT")) { if (atoi(e) == 16) ept = 16; }
-#define S2_PLACE_ARGS (const uint16_t*)tmp_lo, (const uint32_t*)tmp_idx, g, (const uint32_t*)part_off, (const uint32_t*)part_cnt, (const uint32_t*)sc_off, (const uint32_t*)bh, (const uint32_t*)offs, sorted, estride
-    if (ept == 16) hipLaunchKernelGGL(k_s2_place<16>, dim3(l2), dim3(1024), s2_place_lds_bytes<16>(g.lo_log), c->stream, S2_PLACE_ARGS);
-    else hipLaunchKernelGGL(k_s2_place<8>, dim3(l2), dim3(1024), s2_place_lds_bytes<8>(g.lo_log), c->stream, S2_PLACE_ARGS);
-#undef S2_PLACE_ARGS
+    hipLaunchKernelGGL(k_s2_place, dim3(l2), dim3(1024), s2_place_lds_bytes(g.lo_log), c->stream,
+                       (const uint16_t*)tmp_lo, (const uint32_t*)tmp_idx, g, (const uint32_t*)part_off, (const uint32_t*)part_cnt, (const uint32_t*)sc_off, (const uint32_t*)bh, (const uint32_t*)offs, sorted, estride);
   }
   LAUNCHCHK(c);            // a refused launch (LDS, grid) is reported here, by the sort, not by whatever runs next
   return SBN_OK;
@@ -200,9 +196,8 @@ static int run_bucket_job(sbn_ctx* c, const BucketJob& J) {
   if (const char* es = getenv("SBN_MSM_SEG")) { int v = atoi(es); if (v >= 8 && v <= (int)ACC_SEG_MAX) SEG = (uint32_t)v; }
   // lanes per bucket (k_acc_first<G>): chains of ~32 mixed additions when the buckets are loaded enough to be split
   // (only while one lane per bucket would leave the chip short of lanes: at 2^22, c = 17 — 983 k buckets of 64 points — two lanes per bucket accumulate no
-  //  faster (4.74 against 4.77 ms) and make the reduction read two slots per bucket: k_reduce_l1 0.53 against 0.37 ms; tools/sweep_acc_g.sh)
+  //  faster (4.74 against 4.77 ms) and make the reduction read two slots per bucket: k_reduce_l1 0.53 against 0.37 ms)
   int LPB = 1; if (J.mode == MODE_SINGLE && mean >= 48 && NB <= ((size_t)1 << 19)) LPB = 2;
-  if (const char* eg = getenv("SBN_ACC_G")) { int v = atoi(eg); if (v == 1 || v == 2 || v == 4) LPB = v; }
   const size_t max_extra = J.P * estride / SEG + 1;
   const size_t max_big = std::min(NB, max_extra);
   int rc;
@@ -264,7 +259,7 @@ static int run_bucket_job(sbn_ctx* c, const BucketJob& J) {
   dig_t* dig = (dig_t*)c->digits.p; uint32_t* bh = (uint32_t*)c->blockhist.p;
   const unsigned gd = (unsigned)((J.threads + 255) / 256);
   const size_t rows_lds = sort_rows_lds_bytes(s.nb);
-  const bool fused_rows = J.mode == MODE_ROWS && c->sort_rows_ok && rows_lds <= 160 * 1024 && estride <= 8 * (size_t)SORT_SL && !getenv("SBN_NO_FUSED_SORT");
+  const bool fused_rows = J.mode == MODE_ROWS && c->sort_rows_ok && rows_lds <= 160 * 1024 && estride <= 8 * (size_t)SORT_SL;
   skip = fused_rows ? J.skip : nullptr;    // the generic sort reads every digit, so nothing may be left unwritten there
   if (J.mode == MODE_SINGLE) LAUNCH(c, "k_digits_store", (k_digits_store<MODE_SINGLE>), gd, 256, J.da, s, dig, (const uint8_t*)nullptr);
   else LAUNCH(c, "k_digits_store", (k_digits_store<MODE_ROWS>), gd, 256, J.da, s, dig, skip);
@@ -291,12 +286,10 @@ static int run_bucket_job(sbn_ctx* c, const BucketJob& J) {
   LAUNCH(c, "k_size_sort", k_size_hist, (unsigned)((NB + 1023) / 1024), 1024, hist, NB, SEG, size_bins);
   LAUNCH(c, "k_size_sort", k_size_scan, 1, 64, size_bins, SEG);
   LAUNCH(c, "k_size_sort", k_size_scatter, (unsigned)((NB + 1023) / 1024), 1024, hist, NB, SEG, size_bins, (uint32_t*)c->perm.p);
-  unsigned ab = 256; if (const char* eb = getenv("SBN_ACC_BLOCK")) { int v = atoi(eb); if (v == 64 || v == 128 || v == 256) ab = (unsigned)v; }
-  const unsigned agrid = (unsigned)((NB * (size_t)LPB + ab - 1) / ab);
+  const unsigned agrid = (unsigned)((NB * (size_t)LPB + 255) / 256);
 #define ACC_FIRST_ARGS J.points, NB, s.nb, estride, SEG, hist, offs, sorted, (const uint32_t*)c->perm.p, buckets, ctr, (ExtraItem*)c->extra_list.p, (BigItem*)c->big_list.p
-  if (LPB == 1) LAUNCH(c, "k_acc_first", k_acc_first<1>, agrid, ab, ACC_FIRST_ARGS);
-  else if (LPB == 2) LAUNCH(c, "k_acc_first", k_acc_first<2>, agrid, ab, ACC_FIRST_ARGS);
-  else LAUNCH(c, "k_acc_first", k_acc_first<4>, agrid, ab, ACC_FIRST_ARGS);
+  if (LPB == 1) LAUNCH(c, "k_acc_first", k_acc_first<1>, agrid, 256, ACC_FIRST_ARGS);
+  else LAUNCH(c, "k_acc_first", k_acc_first<2>, agrid, 256, ACC_FIRST_ARGS);
 #undef ACC_FIRST_ARGS
   LAUNCH(c, "k_acc_extra", k_acc_extra, 2048, 256, J.points, s.nb, estride, SEG, hist, offs, sorted, ctr, (const ExtraItem*)c->extra_list.p, (uint32_t*)c->extra_out.p);
   LAUNCH(c, "k_acc_merge", k_acc_merge, 4096, 64, ctr, (const BigItem*)c->big_list.p, (const uint32_t*)c->extra_out.p, buckets, LPB);
@@ -304,8 +297,7 @@ static int run_bucket_job(sbn_ctx* c, const BucketJob& J) {
   // quad-cooperative kernel (256 threads per group of 64 chunks, 3.5 instead of 7.6 us per dependent addition) runs it in 0.115 instead of
   // 0.141 ms at 2^20.  Level 1 stays one wave per chunk: measured with quads 0.35 - 0.38 ms against 0.277 at L = 4 / 8 / 16 (level 1 is SIMD-issue
   // bound, not a latency chain: four times the waves at 2.3x the instructions only make the queues longer; profiles/r04_reduce_quad_sweep.txt).
-  static const int red_quad_env = [] { const char* e = getenv("SBN_RED_QUAD"); return e ? atoi(e) : -1; }();
-  const bool red_quad = red_quad_env >= 0 ? red_quad_env != 0 : (J.P * (size_t)chunks <= 2048);
+  const bool red_quad = J.P * (size_t)chunks <= 2048;
   LAUNCH(c, "k_reduce_l1", k_reduce_l1, (unsigned)(J.P * chunks), 64, buckets, L, s.nb, (uint32_t*)c->red_a.p, skip, chunks, LPB);
   uint32_t* in = (uint32_t*)c->red_a.p; uint32_t* outb = (uint32_t*)c->red_b.p;
   int G = chunks, k64 = 1;
@@ -636,7 +628,7 @@ static int bases_build_dedupe(sbn_ctx* c, sbn_bases* b, const std::vector<std::s
     else umap[j] = it->second;
   }
   const size_t U = first_col.size();
-  if (getenv("SBN_NO_DEDUPE") || U * 10 > tot * 9) return SBN_OK;         // < 10 % repeats: not worth the extra pass
+  if (U * 10 > tot * 9) return SBN_OK;         // < 10 % repeats: not worth the extra pass
   std::vector<uint32_t> off(U + 1, 0), cols(tot), big;
   for (size_t j = 0; j < tot; j++) off[umap[j] + 1]++;
   for (size_t u = 0; u < U; u++) off[u + 1] += off[u];

@@ -264,17 +264,17 @@ __global__ void __launch_bounds__(1024) k_s2_prefix2(uint32_t* __restrict__ bloc
     offs[b] = part_off[q] + r; offs[b + 1] = part_off[q] + r + r0;
   }
 }
-// Final placement, staged: the sub-chunk is taken in tiles of 1024 * EPT entries; a tile is sorted by lo inside LDS and leaves
+// Final placement, staged: the sub-chunk is taken in tiles of 1024 * S2_EPT entries; a tile is sorted by lo inside LDS and leaves
 // as runs (the entries of one bucket are consecutive in the stage AND at their destination), so a wave's 64 stores fall into a
 // few contiguous pieces instead of 64 separate 4-byte L2 transactions (scattered dword stores run at ~5.6e10/s chip-wide, which
 // is what bounded the unstaged form: 13.5 ms for the 8.7e8 entries of a 2^26 MSM).
 // LDS: cnt[LO] | base[LO] | cur[LO] | scan tmp[32] | stage_idx[T] | stage_lo[T] (u16)
-template <int EPT> __host__ __device__ inline size_t s2_place_lds_bytes(int lo_log) { return ((size_t)3 * ((size_t)1 << lo_log) + 32) * 4 + (size_t)1024 * EPT * 6; }
-template <int EPT>
+constexpr int S2_EPT = 8;          // entries per thread of a tile
+__host__ __device__ inline size_t s2_place_lds_bytes(int lo_log) { return ((size_t)3 * ((size_t)1 << lo_log) + 32) * 4 + (size_t)1024 * S2_EPT * 6; }
 __global__ void __launch_bounds__(1024) k_s2_place(const uint16_t* __restrict__ tmp_lo, const uint32_t* __restrict__ tmp_idx, S2Geom g, const uint32_t* __restrict__ part_off, const uint32_t* __restrict__ part_cnt,
                                                    const uint32_t* __restrict__ sc_off, const uint32_t* __restrict__ blockhist /* prefixed over the partition's sub-chunks */,
                                                    const uint32_t* __restrict__ offs, uint32_t* __restrict__ sorted, size_t estride) {
-  constexpr uint32_t T = 1024 * EPT;
+  constexpr uint32_t T = 1024 * S2_EPT;
   int q; uint32_t sidx, k2; if (!s2_decode(g, sc_off, q, sidx, k2)) return;
   const int LO = 1 << g.lo_log, tid = threadIdx.x;
   uint32_t* cnt = s2_lds; uint32_t* base = cnt + LO; uint32_t* cur = base + LO; uint32_t* tmp = cur + LO;
@@ -288,9 +288,9 @@ __global__ void __launch_bounds__(1024) k_s2_place(const uint16_t* __restrict__ 
   size_t e0, e1; s2_range(g, part_off, part_cnt, q, k2, e0, e1);
   uint32_t* out = sorted + (size_t)w * estride;
   for (size_t tile = e0; tile < e1; tile += T) {          // (uniform trip count per block)
-    uint32_t lo[EPT], idx[EPT], rank[EPT];
+    uint32_t lo[S2_EPT], idx[S2_EPT], rank[S2_EPT];
 #pragma unroll
-    for (int i = 0; i < EPT; i++) {
+    for (int i = 0; i < S2_EPT; i++) {
       const size_t e = tile + (size_t)i * 1024 + tid;
       lo[i] = 0xffffffffu;
       if (e < e1) { lo[i] = tmp_lo[e]; idx[i] = tmp_idx[e]; rank[i] = atomicAdd(&cnt[lo[i]], 1u); }
@@ -307,7 +307,7 @@ __global__ void __launch_bounds__(1024) k_s2_place(const uint16_t* __restrict__ 
     }
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < EPT; i++) {
+    for (int i = 0; i < S2_EPT; i++) {
       if (lo[i] == 0xffffffffu) continue;
       const uint32_t pos = base[lo[i]] + rank[i];
       stage_idx[pos] = idx[i]; stage_lo[pos] = (uint16_t)lo[i];

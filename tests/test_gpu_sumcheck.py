@@ -543,17 +543,14 @@ def test_reference_product_tree_known_answers(ctx, pr):
 
 
 def test_fused_round_unspilled_build(sbn, ol):
-    """SBN_SC_WAVES=3 selects the 3-waves-per-SIMD build of the streaming fused round (no spills); same values"""
-    import os
+    """a streaming round whose every table is shared (A of one instance is B of the other, C of both): all three arrive pre-bound, a
+    pattern the software-pipelined kernel is not built for, so the 3-waves-per-SIMD build (no spills) + k_sc_finish run it; same values"""
     n = 1 << 16
     A, B, C = (rand_scalars(n, s + 77) for s in (1, 2, 3))
     r = rand_scalars(1, 78)
-    os.environ["SBN_SC_WAVES"] = "3"
+    cx = sbn.Context(0)
     try:
-        cx = sbn.Context(0)
-    finally:
-        del os.environ["SBN_SC_WAVES"]
-    try:
+        cx.prof_enable()
         tA, tB, tC = (cx.table_upload(x) for x in (A, B, C))
         got = cx.sc_bind_eval_cubic_batched([tA, tB], [tB, tA], [tC, tC], r)
         bA, bB, bC = (ol.bind_top(x, r) for x in (A, B, C))
@@ -561,6 +558,8 @@ def test_fused_round_unspilled_build(sbn, ol):
         assert cx.table_download(tC) == bC
         for t in (tA, tB, tC):
             t.free()
+        ran = cx.prof_get()
+        assert _launches(ran, "k_sc_bind_eval_cubic") == 1 and _launches(ran, "k_sc_finish") == 1 and "k_sc_bind_eval_cubic_stream" not in ran, ran
     finally:
         cx.close()
 
@@ -705,27 +704,48 @@ def test_stateful_sumcheck_combined_kernels(ctx, ol, logn, n_par, n_seq):
     _run_stateful_sumcheck(ctx, ol, 1 << logn, n_par, n_seq, 7500 + 10 * logn + n_par)
 
 
+def _launches(ran, name):
+    """launches of kernel `name` in a prof_get() result (0 if it never ran)"""
+    return ran.get(name, (0.0, 0))[1]
+
+
+def _stateful_kernels(sbn, ol, env, n, n_par, n_seq, seed, coeffs=None):
+    """_run_stateful_sumcheck on a fresh profiled context created with `env` -> the kernels that ran (prof_get)"""
+    cx = _context_with(sbn, env)
+    try:
+        cx.prof_enable()
+        _run_stateful_sumcheck(cx, ol, n, n_par, n_seq, seed, coeffs)
+        return cx.prof_get()
+    finally:
+        cx.close()
+
+
+_COMB_KERNELS = ("k_sc_comb_eval", "k_sc_eval_mixed", "k_sc_comb_bind_eval", "k_sc_comb_bind_eval_first", "k_sc_round_mixed", "k_sc_round_mixed_first")
+
+
 def test_stateful_sumcheck_modes_agree(ctx, sbn, ol, pr):
-    """a zero coefficient among the "par" instances (no inverse: nothing is scaled, the host weighs every triple), and SBN_SC_NO_COMB /
-    SBN_SC_NO_COMB_KERNEL forcing the other two modes onto a size the combined kernels would take, SBN_SC_NO_MIXED the separate launches of
-    the "par" groups and the "seq" instances, SBN_SC_NO_MIXED_EVAL the two-launch round 0 (k_sc_comb_eval + k_sc_eval with n_seq > 0 on
-    2^17-entry tables): all equal to the oracle.  The overrides are read when a context is created: a fresh context per variant."""
+    """a zero coefficient among the "par" instances (no inverse: nothing is scaled, the host weighs every triple), also on 2^16-entry
+    tables the combined kernels would otherwise take (PLAIN mode, the shared C pre-bound on the streaming rounds); one "par" instance
+    there (SCALED mode); SBN_SC_COMB_MIN_Q=64, under which the combined rounds of <= 8192 index pairs launch the "seq" instances apart;
+    2^16-entry tables with "seq" instances, whose round 0 (half < 2^16) runs as two launches, k_sc_eval_cubic + k_sc_comb_eval:
+    all equal to the oracle, and each path shown taken by the kernels that ran"""
     import os
     co = bytearray(rand_scalars(8, 4242)); co[32:64] = bytes(32)
     _run_stateful_sumcheck(ctx, ol, 1 << 15, 5, 3, 7900, bytes(co))
     _run_stateful_sumcheck(ctx, ol, 1 << 6, 5, 3, 7910, bytes(co))
     one = (1).to_bytes(32, "little"); top = (pr.R - 1).to_bytes(32, "little")
     _run_stateful_sumcheck(ctx, ol, 1 << 15, 3, 1, 7920, one + top + one + top)              # coefficients 1 and r - 1
-    for var, logn in (("SBN_SC_NO_COMB", 16), ("SBN_SC_NO_COMB_KERNEL", 16), ("SBN_SC_NO_MIXED", 17), ("SBN_SC_NO_MIXED_EVAL", 17)):
-        os.environ[var] = "1"
-        try:
-            cx = sbn.Context(0)
-        finally:
-            del os.environ[var]
-        try:
-            _run_stateful_sumcheck(cx, ol, 1 << logn, 4, 2, 7930 + logn)
-        finally:
-            cx.close()
+    co = bytearray(rand_scalars(6, 7946)); co[64:96] = bytes(32)
+    ran = _stateful_kernels(sbn, ol, {}, 1 << 16, 4, 2, 7946, bytes(co))                       # PLAIN
+    assert "k_sc_scale" not in ran and not any(k in ran for k in _COMB_KERNELS), ran
+    assert _launches(ran, "k_bind_oop") >= 1 and _launches(ran, "k_sc_bind_eval_cubic_stream") >= 1, ran
+    ran = _stateful_kernels(sbn, ol, {}, 1 << 16, 1, 2, 7956)                                  # SCALED: one "par" instance
+    assert _launches(ran, "k_sc_scale") == 1 and not any(k in ran for k in _COMB_KERNELS), ran
+    ran = _stateful_kernels(sbn, ol, {"SBN_SC_COMB_MIN_Q": "64"}, 1 << 17, 4, 2, 7947)         # COMB, "seq" launched apart below 8192 pairs
+    assert _launches(ran, "k_sc_round_mixed_first") == 1 and _launches(ran, "k_sc_round_mixed") == 1, ran   # q = 2^15, 2^14
+    assert _launches(ran, "k_sc_comb_bind_eval") == 8 and _launches(ran, "k_sc_bind_eval_cubic") >= 8, ran    # q = 2^13 .. 2^6
+    ran = _stateful_kernels(sbn, ol, {}, 1 << 16, 4, 2, 7948)                                  # COMB, two-launch round 0
+    assert _launches(ran, "k_sc_eval_cubic") == 1 and _launches(ran, "k_sc_comb_eval") == 1 and "k_sc_eval_mixed" not in ran, ran
     # grids asked for beyond the partial-sum area are clamped (ADVICE r3): 2^18-entry tables, 4096 blocks per group requested
     os.environ["SBN_SC_COMB_GRID"] = "4096"; os.environ["SBN_SC_COMB_EVAL_BLOCKS"] = "65536"
     try:
@@ -828,7 +848,7 @@ def _device_loop(cx, kind, dev, ch):
         if len(dev[0]) >= 4:
             got.append(cx.sc_bind_eval_r1cs(*dev, r) if kind == "r1cs" else cx.sc_bind_eval_quad(*dev, r))
         else:
-            cx.bind_top_many(dev, r)                  # last round: nothing left to evaluate
+            cx.bind_top_many([t for k, t in enumerate(dev) if t not in dev[:k]], r)     # last round: nothing left to evaluate; each table once
     assert len(got) == rounds and all(len(t) == 1 for t in dev)
     return got, cx.table_read0_many(dev)
 
@@ -916,10 +936,6 @@ _KNOBS = [
     {"SBN_SC_GRID": "3"},                 # a stride that does not divide q: threads with unequal trip counts
     {"SBN_SC_GRID": "61"},
     {"SBN_SC_BLOCK_ROUNDS": "1"},
-    {"SBN_SC_WAVES": "3"},                # k_sc_bind_eval<KIND, 3> + k_sc_finish
-    {"SBN_SC_WAVES": "4"},
-    {"SBN_SC_NO_STREAM_MBOX": "1"},       # k_sc_finish after the eval and the streaming rounds
-    {"SBN_SC_NO_TINY": "1"},              # the lane-per-index kernel on the last rounds
     {"SBN_SC_SINGLE_MAX": "256"},         # the single-launch edge moved down: streaming from 512-entry tables on
 ]
 
@@ -945,6 +961,54 @@ def test_r1cs_quad_loops_paths(sbn, ol, pr, knobs):
                     t.free()
     finally:
         cx.close()
+
+
+def test_r1cs_loop_shared_table_fallback(sbn, ol, pr):
+    """the full R1CS loop at 2^17 with Az and Bz the same table handle: the shared table is pre-bound in both slots of every streaming
+    round (mask 3), which the software-pipelined kernel is not built for, so those rounds run k_sc_bind_eval<R1CS, 3> + k_sc_finish"""
+    n, logn = 1 << 17, 17
+    cx = sbn.Context(0)
+    try:
+        cx.prof_enable()
+        dev, host = _uniform_tables(cx, 3, n, 9470)
+        ch = rand_scalars(logn, 9475)
+        got, finals = _device_loop(cx, "r1cs", [dev[0], dev[1], dev[1], dev[2]], ch)
+        ran = cx.prof_get()
+        for t in dev:
+            t.free()
+    finally:
+        cx.close()
+    _check_loop(ol, pr, "r1cs", [host[0], host[1], host[1], host[2]], got, finals, ch, "A = B 2^17")
+    assert "k_sc_bind_eval_r1cs_stream" not in ran, ran
+    assert _launches(ran, "k_sc_finish") == 2 and _launches(ran, "k_sc_bind_eval_r1cs") == logn - 1, ran    # q = 2^15, 2^14 streamed
+
+
+def test_streaming_round_finishing_kernel(sbn, ol):
+    """25 instances (more than travel as kernel arguments) with their own A and B and one shared C on 2^16-entry tables: the batched
+    eval and the streaming bind + eval run on the staged argument array, the latter on the software-pipelined kernel (the pre-bound
+    shared C: its mask-4 form), and k_sc_finish folds the blocks' partial sums; against the oracle, every bound table included"""
+    n, count = 1 << 16, 25
+    cx = sbn.Context(0)
+    try:
+        cx.prof_enable()
+        dev, host = _uniform_tables(cx, 2 * count + 1, n, 9600)
+        host = [h.tobytes() for h in host]
+        As, Bs, Cs = dev[:count], dev[count:2 * count], [dev[2 * count]] * count
+        hC = host[2 * count]
+        assert cx.sc_eval_cubic_batched(As, Bs, Cs) == b"".join(ol.sc_eval_cubic(host[i], host[count + i], hC) for i in range(count))
+        r = rand_scalars(1, 9610)
+        bound = [ol.bind_top(h, r) for h in host]
+        got = cx.sc_bind_eval_cubic_batched(As, Bs, Cs, r)
+        assert got == b"".join(ol.sc_eval_cubic(bound[i], bound[count + i], bound[2 * count]) for i in range(count))
+        for t, h in zip(dev, bound):
+            assert cx.table_download(t) == h
+        ran = cx.prof_get()
+        for t in dev:
+            t.free()
+    finally:
+        cx.close()
+    assert _launches(ran, "k_sc_bind_eval_cubic_stream") == 1 and "k_sc_bind_eval_cubic" not in ran, ran
+    assert _launches(ran, "k_sc_finish") == 2 and _launches(ran, "k_bind_oop") == 1, ran        # the eval and the bind + eval
 
 
 def _edge_values(pr):

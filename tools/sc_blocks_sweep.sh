@@ -1,6 +1,6 @@
 # stateful sumcheck (12 par + 6 seq x 2^21): blocks per launch.  Every block ends in a ~7 us epilogue (wave sums, write-through stores, ticket).
 #   MODE=round (default): the one-launch round kernel, PAIRS = SBN_SC_COMB_BLOCKS:SBN_SC_SEQ_BLOCKS ("par" groups : "seq" instances)
-#   MODE=begin: round 0's evaluation launch (one mixed launch; two with SBN_SC_NO_MIXED_EVAL=1), PAIRS = SBN_SC_COMB_EVAL_BLOCKS:SBN_SC_EVAL_BLOCKS
+#   MODE=begin: round 0's evaluation launch (one mixed launch), PAIRS = SBN_SC_COMB_EVAL_BLOCKS:SBN_SC_EVAL_BLOCKS
 if [ "${MODE:-round}" = begin ]; then A=SBN_SC_COMB_EVAL_BLOCKS; B=SBN_SC_EVAL_BLOCKS; PAIRS=${PAIRS:-2048:4096 1024:4096 512:4096 2048:2048 2048:1024 1024:1024 512:512 1024:2048}
 else A=SBN_SC_COMB_BLOCKS; B=SBN_SC_SEQ_BLOCKS; PAIRS=${PAIRS:-256:256 384:384 512:256 512:512 512:768 768:768 1024:1024 1024:2048}; fi
 for P in $PAIRS; do

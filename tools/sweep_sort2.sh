@@ -8,7 +8,7 @@ sort=sum(v for n,v in k.items() if n.startswith(('k_s2','k_digits','k_hist','k_s
 print(os.environ.get('TAG'), 'n=2^'+os.environ['LOGN'], 'c', a['window_bits'], 'W', a['windows'], 'ms/step', d['ms_per_step'], 'pts/s %.3e' % d['value'], 'sort %.3f' % sort, 'acc', k.get('k_acc_first'), 'extra', k.get('k_acc_extra'), 'l1', k.get('k_reduce_l1'), 'comb', k.get('k_reduce_combine'), {n: v for n, v in k.items() if n.startswith(('k_s2', 'k_block_prefix', 'k_scan'))})"; }
 export LOGN STEPS
 if [ "$1" = quick ]; then
-LOGN=26 STEPS=3; TAG="auto" run; TAG="ept16" SBN_SORT2_EPT=16 run; for LO in 9 10; do TAG="lo=$LO" SBN_SORT2_LO=$LO run; done
+LOGN=26 STEPS=3; TAG="auto" run; for LO in 9 10; do TAG="lo=$LO" SBN_SORT2_LO=$LO run; done
 LOGN=24 STEPS=5; TAG="auto" run; TAG="lo=10" SBN_SORT2_LO=10 run; TAG="c=19" SBN_MSM_C=19 run
 LOGN=23 STEPS=5; TAG="auto" run; TAG="c=18" SBN_MSM_C=18 run; TAG="c=20" SBN_MSM_C=20 run
 LOGN=22 STEPS=8; TAG="auto" run; TAG="lo=9" SBN_SORT2_LO=9 run; TAG="c=18" SBN_MSM_C=18 run
