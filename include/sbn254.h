@@ -324,6 +324,29 @@ int sbn_group_msm_bases(sbn_group* g, const sbn_group_bases* gb, const uint8_t* 
 /* scalars_dev[d]: device pointer ON device d to the (hi - lo) x 32 B of its range */
 int sbn_group_msm_bases_dev(sbn_group* g, const sbn_group_bases* gb, const void* const* scalars_dev, uint32_t flags, uint8_t out_xy[64], int* out_is_inf);
 
+/* ---- KZG mode (--features kzg): commitments and openings over a resident SRS (kzg.rs) ----
+ * The SRS is an sbn_bases handle (no h; sbn_bases_free / _len / _download work on it).  A polynomial is the first n entries of a
+ * table, coefficients low to high; n <= the table's length, entries from n on are never read.  z, gamma, tau: canonical (< r).
+ * Pairings, G2 and the transcript stay with the caller. */
+/* KZGSrs.powers_g1 (kzg.rs:25-31): n canonical affine points (SBN_POINTS_MONT: ark-ff limbs); no duplicate detection */
+int sbn_kzg_srs_upload(sbn_ctx* ctx, const uint8_t* powers_xy, size_t n, uint32_t flags, sbn_bases** out);
+/* [tau^i]G1 for i < n (kzg.rs:37-56 with tau supplied), built on the device; tau non-zero, n >= 1 */
+int sbn_kzg_srs_from_tau(sbn_ctx* ctx, const uint8_t tau[32], size_t n, sbn_bases** out);
+/* KZGPolyCommitment::commit (kzg.rs:386-395): MSM of the first min(n, srs len) coefficients; n = 0 gives the identity */
+int sbn_kzg_commit(sbn_ctx* ctx, const sbn_bases* srs, const sbn_table* t, size_t n, uint8_t out_xy[64], int* out_is_inf);
+/* evaluate_poly + compute_quotient (kzg.rs:220-260): eval = p(z), *q = (p - p(z)) / (X - z) as a new table of the n - 1 quotient
+ * coefficients zero-padded to a power of two (*q = NULL when n <= 1; n = 0 gives eval 0) */
+int sbn_poly_div_linear(sbn_ctx* ctx, const sbn_table* t, size_t n, const uint8_t z[32], uint8_t eval[32], sbn_table** q);
+/* KZGProof::prove (kzg.rs:174-192): eval = p(z), proof = MSM of the quotient over srs[0..n-1) (identity for n <= 1);
+ * n - 1 > srs len is SBN_EINVAL (the reference panics on the slice) */
+int sbn_kzg_open(sbn_ctx* ctx, const sbn_bases* srs, const sbn_table* t, size_t n, const uint8_t z[32],
+                 uint8_t eval[32], uint8_t proof_xy[64], int* proof_is_inf);
+/* KZGBatchedEvalProof::prove -> KZGBatchProof::batch_prove (kzg.rs:478-500, 268-312): evals[k] = p_k(z) (count x 32 B); the proof opens
+ * sum_k gamma^k p_k over max(ns) coefficients at z.  gamma comes from the caller's transcript (any canonical value, zero included);
+ * count = 0 gives the identity and no evals */
+int sbn_kzg_open_batched(sbn_ctx* ctx, const sbn_bases* srs, const sbn_table* const* ts, const size_t* ns, size_t count,
+                         const uint8_t z[32], const uint8_t gamma[32], uint8_t* evals, uint8_t proof_xy[64], int* proof_is_inf);
+
 /* ---- per-kernel timing (HIP events on the context's stream), for bench.py's roofline line ---- */
 int sbn_prof_enable(sbn_ctx* ctx, int on);
 int sbn_prof_reset(sbn_ctx* ctx);

@@ -148,6 +148,12 @@ extern "C" {
     pub fn sbn_group_range(gb: *const sbn_group_bases, device: usize, lo: *mut usize, hi: *mut usize);
     pub fn sbn_group_msm_bases(g: *mut sbn_group, gb: *const sbn_group_bases, scalars: *const u8, n: usize, flags: u32, out_xy: *mut u8, out_is_inf: *mut c_int) -> c_int;
     pub fn sbn_group_msm_bases_dev(g: *mut sbn_group, gb: *const sbn_group_bases, scalars_dev: *const *const c_void, flags: u32, out_xy: *mut u8, out_is_inf: *mut c_int) -> c_int;
+    pub fn sbn_kzg_srs_upload(ctx: *mut sbn_ctx, powers_xy: *const u8, n: usize, flags: u32, out: *mut *mut sbn_bases) -> c_int;
+    pub fn sbn_kzg_srs_from_tau(ctx: *mut sbn_ctx, tau: *const u8, n: usize, out: *mut *mut sbn_bases) -> c_int;
+    pub fn sbn_kzg_commit(ctx: *mut sbn_ctx, srs: *const sbn_bases, t: *const sbn_table, n: usize, out_xy: *mut u8, out_is_inf: *mut c_int) -> c_int;
+    pub fn sbn_poly_div_linear(ctx: *mut sbn_ctx, t: *const sbn_table, n: usize, z: *const u8, eval: *mut u8, q: *mut *mut sbn_table) -> c_int;
+    pub fn sbn_kzg_open(ctx: *mut sbn_ctx, srs: *const sbn_bases, t: *const sbn_table, n: usize, z: *const u8, eval: *mut u8, proof_xy: *mut u8, proof_is_inf: *mut c_int) -> c_int;
+    pub fn sbn_kzg_open_batched(ctx: *mut sbn_ctx, srs: *const sbn_bases, ts: *const *const sbn_table, ns: *const usize, count: usize, z: *const u8, gamma: *const u8, evals: *mut u8, proof_xy: *mut u8, proof_is_inf: *mut c_int) -> c_int;
     pub fn sbn_prof_enable(ctx: *mut sbn_ctx, on: c_int) -> c_int;
     pub fn sbn_prof_reset(ctx: *mut sbn_ctx) -> c_int;
     pub fn sbn_prof_count(ctx: *mut sbn_ctx) -> c_int;
@@ -661,4 +667,57 @@ mod tests {
         assert_eq!(commit_row(&s, &blind, &gens).unwrap(), want + blind * gens.h);
         assert_eq!(s.commit(&blind, &gens), want + blind * gens.h);
     }
+}
+
+// ---- KZG mode (--features hip,kzg; kzg.rs): the SRS stays resident, commitments and openings run over it ----------------------
+/// KZGSrs.powers_g1 on the device (kzg.rs:25-31)
+pub struct KzgSrs(pub *mut sbn_bases);
+unsafe impl Send for KzgSrs {}
+unsafe impl Sync for KzgSrs {}
+impl Drop for KzgSrs { fn drop(&mut self) { if !self.0.is_null() { unsafe { sbn_bases_free(ctx(), self.0) } } } }
+impl std::fmt::Debug for KzgSrs { fn fmt(&self, f: &mut std::fmt::Formatter<'_>) -> std::fmt::Result { write!(f, "KzgSrs({:p})", self.0) } }
+impl KzgSrs {
+    /// upload of the SRS points (no duplicate detection: an SRS has none)
+    pub fn upload(powers_g1: &[G1Affine]) -> KzgSrs {
+        let pts: Vec<u8> = powers_g1.iter().flat_map(point_xy_mont).collect();
+        let mut b = null_mut();
+        check(unsafe { sbn_kzg_srs_upload(ctx(), pts.as_ptr(), powers_g1.len(), SBN_POINTS_MONT, &mut b) });
+        KzgSrs(b)
+    }
+    /// [tau^i]G1 for i < n, built on the device (kzg.rs:37-56 with tau supplied)
+    pub fn from_tau(tau: &Scalar, n: usize) -> KzgSrs {
+        let mut b = null_mut();
+        check(unsafe { sbn_kzg_srs_from_tau(ctx(), tau.to_bytes().as_ptr(), n, &mut b) });
+        KzgSrs(b)
+    }
+    pub fn len(&self) -> usize { unsafe { sbn_bases_len(self.0) } }
+    pub fn is_empty(&self) -> bool { self.len() == 0 }
+}
+/// KZGPolyCommitment::commit (kzg.rs:386-395) and KZGCommitment::commit (kzg.rs:132-147): the first min(n, srs len) coefficients
+pub fn kzg_commit(coeffs: &Table, n: usize, srs: &KzgSrs) -> GroupElement {
+    let mut xy = [0u8; 64];
+    let mut inf: c_int = 0;
+    check(unsafe { sbn_kzg_commit(ctx(), srs.0, coeffs.0, n, xy.as_mut_ptr(), &mut inf) });
+    group_from_xy(&xy, inf != 0)
+}
+/// KZGProof::prove (kzg.rs:174-192) -> (proof, p(z))
+pub fn kzg_open(coeffs: &Table, n: usize, point: &Scalar, srs: &KzgSrs) -> (GroupElement, Scalar) {
+    let mut ev = [0u8; 32];
+    let mut xy = [0u8; 64];
+    let mut inf: c_int = 0;
+    check(unsafe { sbn_kzg_open(ctx(), srs.0, coeffs.0, n, point.to_bytes().as_ptr(), ev.as_mut_ptr(), xy.as_mut_ptr(), &mut inf) });
+    (group_from_xy(&xy, inf != 0), sc(&ev))
+}
+/// KZGBatchedEvalProof::prove -> KZGBatchProof::batch_prove (kzg.rs:478-500, 268-312) -> (proof, evals); gamma is what the caller drew
+/// from the transcript (`Scalar::from_bytes(..).unwrap_or(Scalar::one())`, kzg.rs:275-277)
+pub fn kzg_open_batched(polys: &[(&Table, usize)], point: &Scalar, gamma: &Scalar, srs: &KzgSrs) -> (GroupElement, Vec<Scalar>) {
+    let ts: Vec<*const sbn_table> = polys.iter().map(|(t, _)| t.0 as *const sbn_table).collect();
+    let ns: Vec<usize> = polys.iter().map(|(_, n)| *n).collect();
+    let mut ev = vec![0u8; 32 * polys.len()];
+    let mut xy = [0u8; 64];
+    let mut inf: c_int = 0;
+    check(unsafe {
+        sbn_kzg_open_batched(ctx(), srs.0, ts.as_ptr(), ns.as_ptr(), polys.len(), point.to_bytes().as_ptr(), gamma.to_bytes().as_ptr(), ev.as_mut_ptr(), xy.as_mut_ptr(), &mut inf)
+    });
+    (group_from_xy(&xy, inf != 0), ev.chunks(32).map(sc).collect())
 }

@@ -19,6 +19,7 @@ EXPORTED_SYMBOLS = [
     "sbn_group_create", "sbn_group_destroy", "sbn_group_size", "sbn_group_ctx", "sbn_group_last_error", "sbn_group_bases_upload", "sbn_group_gens_new", "sbn_group_bases_precompute",
     "sbn_group_bases_free", "sbn_group_commit_rows", "sbn_group_commit_rows_dev", "sbn_group_gather_commit", "sbn_group_msm", "sbn_group_bases_upload_ranges", "sbn_group_bases_synthetic_ranges", "sbn_group_range", "sbn_group_msm_bases", "sbn_group_msm_bases_dev",
     "sbn_eq_evals", "sbn_hash_layer", "sbn_hash_layer_pair", "sbn_product_layer", "sbn_product_circuit", "sbn_product_circuit_many", "sbn_table_halves", "sbn_table_slice", "sbn_table_dot", "sbn_table_evaluate", "sbn_table_evaluate_many", "sbn_table_bound", "sbn_gather_merge", "sbn_gather_merge_rows", "sbn_commit_table", "sbn_bullet_begin", "sbn_bullet_begin_scaled", "sbn_bullet_free", "sbn_bullet_len", "sbn_bullet_cross", "sbn_bullet_fold_cross", "sbn_bullet_fold", "sbn_bullet_finish", "sbn_prof_enable", "sbn_prof_reset", "sbn_prof_count", "sbn_prof_get", "sbn_prof_last_job",
+    "sbn_kzg_srs_upload", "sbn_kzg_srs_from_tau", "sbn_kzg_commit", "sbn_poly_div_linear", "sbn_kzg_open", "sbn_kzg_open_batched",
 ]
 
 
@@ -635,6 +636,43 @@ class Context:
         ah, bh, gh = (C.c_uint8 * 32)(), (C.c_uint8 * 32)(), (C.c_uint8 * 64)(); gi = C.c_int(0)
         self._chk(lib().sbn_bullet_finish(self.h, st.h, ah, bh, gh, C.byref(gi)), "sbn_bullet_finish")
         return bytes(ah), bytes(bh), bytes(gh)
+
+    # ---- KZG mode (kzg.rs): the SRS is a Bases handle, polynomials are the first n entries of a Table
+    def kzg_srs_upload(self, powers_xy, flags=0):
+        hb = C.c_void_p()
+        self._chk(lib().sbn_kzg_srs_upload(self.h, _ptr(powers_xy), C.c_size_t(len(powers_xy) // 64), C.c_uint32(flags), C.byref(hb)), "sbn_kzg_srs_upload")
+        return Bases(self, hb)
+
+    def kzg_srs_from_tau(self, tau, n):
+        """[tau^i]G1 for i < n, built on the device"""
+        hb = C.c_void_p()
+        self._chk(lib().sbn_kzg_srs_from_tau(self.h, _ptr(tau), C.c_size_t(n), C.byref(hb)), "sbn_kzg_srs_from_tau")
+        return Bases(self, hb)
+
+    def kzg_commit(self, srs, t, n=None):
+        out = (C.c_uint8 * 64)(); inf = C.c_int()
+        self._chk(lib().sbn_kzg_commit(self.h, srs.h, t.h, C.c_size_t(len(t) if n is None else n), out, C.byref(inf)), "sbn_kzg_commit")
+        return bytes(out), bool(inf.value)
+
+    def poly_div_linear(self, t, n, z):
+        """-> (p(z), quotient Table or None when n <= 1)"""
+        ev = (C.c_uint8 * 32)(); q = C.c_void_p()
+        self._chk(lib().sbn_poly_div_linear(self.h, t.h, C.c_size_t(n), _ptr(z), ev, C.byref(q)), "sbn_poly_div_linear")
+        return bytes(ev), (Table(self, q) if q.value else None)
+
+    def kzg_open(self, srs, t, n, z):
+        """-> (p(z), proof_xy, proof_is_inf)"""
+        ev = (C.c_uint8 * 32)(); out = (C.c_uint8 * 64)(); inf = C.c_int()
+        self._chk(lib().sbn_kzg_open(self.h, srs.h, t.h, C.c_size_t(n), _ptr(z), ev, out, C.byref(inf)), "sbn_kzg_open")
+        return bytes(ev), bytes(out), bool(inf.value)
+
+    def kzg_open_batched(self, srs, ts, ns, z, gamma):
+        """-> ([p_k(z)], proof_xy, proof_is_inf)"""
+        k = len(ts)
+        arr = (C.c_void_p * max(k, 1))(*[t.h for t in ts]); nn = (C.c_size_t * max(k, 1))(*ns)
+        ev = (C.c_uint8 * (32 * max(k, 1)))(); out = (C.c_uint8 * 64)(); inf = C.c_int()
+        self._chk(lib().sbn_kzg_open_batched(self.h, srs.h, arr, nn, C.c_size_t(k), _ptr(z), _ptr(gamma), ev, out, C.byref(inf)), "sbn_kzg_open_batched")
+        return [bytes(ev[32 * i:32 * i + 32]) for i in range(k)], bytes(out), bool(inf.value)
 
     # ---- profiling
     def prof_enable(self, on=True):

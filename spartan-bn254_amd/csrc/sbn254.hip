@@ -5,6 +5,7 @@
 //   MultiCommitGens                     src/commitments.rs:17-114   -> sbn_bases_upload / sbn_gens_new
 //   Commitments::commit, commit_inner   src/commitments.rs:144-154, src/hyrax.rs:253-308 -> sbn_commit_rows*
 //   sumcheck prover loops / bind        src/sumcheck.rs, src/hyrax.rs:195-203            -> sbn_sc_* / sbn_bind_top
+//   KZG commit / open (--features kzg)  src/kzg.rs                                       -> sbn_kzg_* / sbn_poly_div_linear
 // There is no CPU fallback in this file: every entry point needs the gfx950 device.
 #include "../../include/sbn254.h"
 #include "host_field.hpp"
@@ -14,6 +15,7 @@
 #include "comb_kernels.cuh"
 #include "sumcheck_kernels.cuh"
 #include "sumcheck_comb_kernels.cuh"
+#include "kzg_kernels.cuh"
 #include "host_keccak.hpp"
 
 #include <hip/hip_runtime.h>
@@ -42,6 +44,7 @@ using namespace sbn;
 #include "abi_sumcheck.inc"
 #include "abi_bullet.inc"
 #include "abi_group.inc"
+#include "abi_kzg.inc"
 
 extern "C" {
 
