@@ -15,6 +15,8 @@
  *     host pointers and stage through HBM themselves.
  *   - a context owns one HIP stream and a workspace; calls on one context are serialised by a mutex
  *     (hyrax.rs:259-261 may enter B1 from many rayon workers at once); use one context per thread for overlap.
+ *   - per-circuit data (generator sets, the SRS, the R1CS matrices) is uploaded once into a handle (sbn_bases, sbn_r1cs) that
+ *     later calls read; calls that produce vectors return new sbn_tables, which the sumcheck calls take as they are.
  *   - there is NO CPU fallback: without a gfx950 device sbn_ctx_create fails.
  */
 #ifndef SBN254_H
@@ -37,6 +39,7 @@ extern "C" {
 typedef struct sbn_ctx sbn_ctx;
 typedef struct sbn_bases sbn_bases;   /* device-resident generator table: MultiCommitGens.{G_affine,h_affine} (commitments.rs:17-27) */
 typedef struct sbn_table sbn_table;   /* device-resident Fr table: DensePolynomial.Z (hyrax.rs:155-160) */
+/* (sbn_r1cs, the device-resident R1CSShape, is declared with its calls below) */
 
 /* ---- context ---- */
 int sbn_ctx_create(int device, sbn_ctx** out);
@@ -346,6 +349,26 @@ int sbn_kzg_open(sbn_ctx* ctx, const sbn_bases* srs, const sbn_table* t, size_t 
  * count = 0 gives the identity and no evals */
 int sbn_kzg_open_batched(sbn_ctx* ctx, const sbn_bases* srs, const sbn_table* const* ts, const size_t* ns, size_t count,
                          const uint8_t z[32], const uint8_t gamma[32], uint8_t* evals, uint8_t proof_xy[64], int* proof_is_inf);
+
+/* ---- the R1CS matrices on the device: R1CSShape (r1cs.rs:22-82) uploaded once per circuit ----
+ * A, B, C as (row, col, val) triplets, mats[0..3) = A, B, C; num_cons and num_vars powers of two.  Columns index
+ * z = (vars, 1, inputs, 0 ...) of 2 * num_vars entries (r1csproof.rs:268-277).  Entries in any order, duplicates allowed (they add).
+ * row >= num_cons is SBN_EINVAL; col >= 2 * num_vars is dropped (all three reference loops skip it); a val >= r is SBN_EINVAL;
+ * SBN_SCALARS_MONT: vals are ark-ff limbs.  A matrix with nnz = 0 is valid (zero tables, zero evaluations); its arrays may be NULL.
+ * Outputs are ordinary tables that feed sbn_sc_eval_r1cs / sbn_sc_eval_quad and their bind variants directly. */
+typedef struct sbn_r1cs sbn_r1cs;
+int sbn_r1cs_upload(sbn_ctx* ctx, size_t num_cons, size_t num_vars, const uint32_t* const* rows, const uint32_t* const* cols,
+                    const uint8_t* const* vals, const size_t* nnz, uint32_t flags, sbn_r1cs** out);
+void sbn_r1cs_free(sbn_ctx* ctx, sbn_r1cs* m);
+/* R1CSShape::multiply_vec (r1cs.rs:132-146): z has 2 * num_vars entries; Az, Bz, Cz: three new tables of num_cons entries */
+int sbn_r1cs_multiply(sbn_ctx* ctx, const sbn_r1cs* m, const sbn_table* z, sbn_table** Az, sbn_table** Bz, sbn_table** Cz);
+/* evals_ABC of r1csproof.rs:376-387: r_A*evals_A + r_B*evals_B + r_C*evals_C with evals_M = compute_eval_table_sparse(eq(rx))
+ * (r1cs.rs:148-163); rx: ell_x = log2(num_cons) canonical scalars (the eq table is built inside the call); a new table of 2 * num_vars entries */
+int sbn_r1cs_eval_table(sbn_ctx* ctx, const sbn_r1cs* m, const uint8_t* rx, size_t ell_x, const uint8_t rA[32], const uint8_t rB[32],
+                        const uint8_t rC[32], sbn_table** out);
+/* R1CSShape::evaluate (r1cs.rs:126-129; snark.rs:465 "Instance evaluations"): out = A(rx,ry) || B(rx,ry) || C(rx,ry), canonical;
+ * ell_x = log2(num_cons), ell_y = log2(2 * num_vars) */
+int sbn_r1cs_evaluate(sbn_ctx* ctx, const sbn_r1cs* m, const uint8_t* rx, size_t ell_x, const uint8_t* ry, size_t ell_y, uint8_t out[96]);
 
 /* ---- per-kernel timing (HIP events on the context's stream), for bench.py's roofline line ---- */
 int sbn_prof_enable(sbn_ctx* ctx, int on);

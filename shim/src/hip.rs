@@ -30,6 +30,7 @@ use crate::commitments::MultiCommitGens;
 use crate::group::GroupElement;
 use crate::hyrax::DensePolynomial;
 use crate::scalar::Scalar;
+use crate::sparse_mlpoly::SparseMatPolynomial;
 use crate::sumcheck::SumcheckInstanceProof;
 use crate::transcript::{AppendToTranscript, ProofTranscript};
 use crate::unipoly::{CompressedUniPoly, UniPoly};
@@ -42,6 +43,7 @@ use crate::unipoly::{CompressedUniPoly, UniPoly};
 #[repr(C)] pub struct sbn_bullet { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_group { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_group_bases { _p: [u8; 0] }
+#[repr(C)] pub struct sbn_r1cs { _p: [u8; 0] }
 
 pub const SBN_OK: c_int = 0;
 pub const SBN_SCALARS_MONT: u32 = 1;
@@ -154,6 +156,11 @@ extern "C" {
     pub fn sbn_poly_div_linear(ctx: *mut sbn_ctx, t: *const sbn_table, n: usize, z: *const u8, eval: *mut u8, q: *mut *mut sbn_table) -> c_int;
     pub fn sbn_kzg_open(ctx: *mut sbn_ctx, srs: *const sbn_bases, t: *const sbn_table, n: usize, z: *const u8, eval: *mut u8, proof_xy: *mut u8, proof_is_inf: *mut c_int) -> c_int;
     pub fn sbn_kzg_open_batched(ctx: *mut sbn_ctx, srs: *const sbn_bases, ts: *const *const sbn_table, ns: *const usize, count: usize, z: *const u8, gamma: *const u8, evals: *mut u8, proof_xy: *mut u8, proof_is_inf: *mut c_int) -> c_int;
+    pub fn sbn_r1cs_upload(ctx: *mut sbn_ctx, num_cons: usize, num_vars: usize, rows: *const *const u32, cols: *const *const u32, vals: *const *const u8, nnz: *const usize, flags: u32, out: *mut *mut sbn_r1cs) -> c_int;
+    pub fn sbn_r1cs_free(ctx: *mut sbn_ctx, m: *mut sbn_r1cs);
+    pub fn sbn_r1cs_multiply(ctx: *mut sbn_ctx, m: *const sbn_r1cs, z: *const sbn_table, az: *mut *mut sbn_table, bz: *mut *mut sbn_table, cz: *mut *mut sbn_table) -> c_int;
+    pub fn sbn_r1cs_eval_table(ctx: *mut sbn_ctx, m: *const sbn_r1cs, rx: *const u8, ell_x: usize, ra: *const u8, rb: *const u8, rc: *const u8, out: *mut *mut sbn_table) -> c_int;
+    pub fn sbn_r1cs_evaluate(ctx: *mut sbn_ctx, m: *const sbn_r1cs, rx: *const u8, ell_x: usize, ry: *const u8, ell_y: usize, out: *mut u8) -> c_int;
     pub fn sbn_prof_enable(ctx: *mut sbn_ctx, on: c_int) -> c_int;
     pub fn sbn_prof_reset(ctx: *mut sbn_ctx) -> c_int;
     pub fn sbn_prof_count(ctx: *mut sbn_ctx) -> c_int;
@@ -720,4 +727,56 @@ pub fn kzg_open_batched(polys: &[(&Table, usize)], point: &Scalar, gamma: &Scala
         sbn_kzg_open_batched(ctx(), srs.0, ts.as_ptr(), ns.as_ptr(), polys.len(), point.to_bytes().as_ptr(), gamma.to_bytes().as_ptr(), ev.as_mut_ptr(), xy.as_mut_ptr(), &mut inf)
     });
     (group_from_xy(&xy, inf != 0), ev.chunks(32).map(sc).collect())
+}
+
+// ---- the R1CS matrices on the device (r1cs.rs): uploaded once per circuit, next to the instance --------------------------------
+/// R1CSShape (r1cs.rs:22-82) on the device: the field `dev` an R1CSInstance carries next to its shape, filled at encode time the way
+/// GensDev is filled for a generator set; shared by clones, rebuilt after deserialisation, dropped with the last clone
+pub struct R1csHandle(pub *mut sbn_r1cs);
+unsafe impl Send for R1csHandle {}
+unsafe impl Sync for R1csHandle {}
+impl Drop for R1csHandle { fn drop(&mut self) { if !self.0.is_null() { unsafe { sbn_r1cs_free(ctx(), self.0) } } } }
+impl std::fmt::Debug for R1csHandle { fn fmt(&self, f: &mut std::fmt::Formatter<'_>) -> std::fmt::Result { write!(f, "R1csHandle({:p})", self.0) } }
+#[derive(Clone, Debug, Default)]
+pub struct R1csDev {
+    one: Arc<OnceLock<R1csHandle>>,
+}
+impl R1csDev {
+    /// the triplets of A, B, C (SparseMatPolynomial.M, sparse_mlpoly.rs:36-40) as ark-ff limbs; columns >= 2 num_vars are dropped by the library
+    pub fn get(&self, num_cons: usize, num_vars: usize, mats: [&SparseMatPolynomial; 3]) -> *const sbn_r1cs {
+        self.one.get_or_init(|| {
+            let rows: Vec<Vec<u32>> = mats.iter().map(|m| m.M.iter().map(|e| e.row as u32).collect()).collect();
+            let cols: Vec<Vec<u32>> = mats.iter().map(|m| m.M.iter().map(|e| u32::try_from(e.col).unwrap_or(u32::MAX)).collect()).collect();
+            let vals: Vec<Vec<u8>> = mats.iter().map(|m| { let v: Vec<Scalar> = m.M.iter().map(|e| e.val).collect(); scalars_mont_bytes(&v).into_owned() }).collect();
+            let rp: Vec<*const u32> = rows.iter().map(|v| v.as_ptr()).collect();
+            let cp: Vec<*const u32> = cols.iter().map(|v| v.as_ptr()).collect();
+            let vp: Vec<*const u8> = vals.iter().map(|v| v.as_ptr()).collect();
+            let nnz: Vec<usize> = rows.iter().map(|v| v.len()).collect();
+            let mut h = null_mut();
+            check(unsafe { sbn_r1cs_upload(ctx(), num_cons, num_vars, rp.as_ptr(), cp.as_ptr(), vp.as_ptr(), nnz.as_ptr(), SBN_SCALARS_MONT, &mut h) });
+            R1csHandle(h)
+        })
+        .0
+    }
+}
+/// R1CSShape::multiply_vec (r1cs.rs:132-146) on the witness table z (2 num_vars entries, already on the device for its commitment):
+/// (Az, Bz, Cz) as tables, ready for R1csRounds without leaving the device
+pub fn r1cs_multiply(m: *const sbn_r1cs, z: &Table) -> (Table, Table, Table) {
+    let (mut a, mut b, mut c) = (null_mut(), null_mut(), null_mut());
+    check(unsafe { sbn_r1cs_multiply(ctx(), m, z.0, &mut a, &mut b, &mut c) });
+    (Table(a), Table(b), Table(c))
+}
+/// evals_ABC of r1csproof.rs:376-387: r_A evals_A + r_B evals_B + r_C evals_C with evals_M = compute_eval_table_sparse(eq(rx))
+pub fn r1cs_eval_table(m: *const sbn_r1cs, rx: &[Scalar], r_a: &Scalar, r_b: &Scalar, r_c: &Scalar) -> Table {
+    let rxb = scalars_canonical(rx);
+    let mut t = null_mut();
+    check(unsafe { sbn_r1cs_eval_table(ctx(), m, rxb.as_ptr(), rx.len(), r_a.to_bytes().as_ptr(), r_b.to_bytes().as_ptr(), r_c.to_bytes().as_ptr(), &mut t) });
+    Table(t)
+}
+/// R1CSShape::evaluate (r1cs.rs:126-129; snark.rs:465 "Instance evaluations") -> (A(rx, ry), B(rx, ry), C(rx, ry))
+pub fn r1cs_evaluate(m: *const sbn_r1cs, rx: &[Scalar], ry: &[Scalar]) -> (Scalar, Scalar, Scalar) {
+    let (rxb, ryb) = (scalars_canonical(rx), scalars_canonical(ry));
+    let mut out = [0u8; 96];
+    check(unsafe { sbn_r1cs_evaluate(ctx(), m, rxb.as_ptr(), rx.len(), ryb.as_ptr(), ry.len(), out.as_mut_ptr()) });
+    triple(&out)
 }

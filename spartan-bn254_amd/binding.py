@@ -20,6 +20,7 @@ EXPORTED_SYMBOLS = [
     "sbn_group_bases_free", "sbn_group_commit_rows", "sbn_group_commit_rows_dev", "sbn_group_gather_commit", "sbn_group_msm", "sbn_group_bases_upload_ranges", "sbn_group_bases_synthetic_ranges", "sbn_group_range", "sbn_group_msm_bases", "sbn_group_msm_bases_dev",
     "sbn_eq_evals", "sbn_hash_layer", "sbn_hash_layer_pair", "sbn_product_layer", "sbn_product_circuit", "sbn_product_circuit_many", "sbn_table_halves", "sbn_table_slice", "sbn_table_dot", "sbn_table_evaluate", "sbn_table_evaluate_many", "sbn_table_bound", "sbn_gather_merge", "sbn_gather_merge_rows", "sbn_commit_table", "sbn_bullet_begin", "sbn_bullet_begin_scaled", "sbn_bullet_free", "sbn_bullet_len", "sbn_bullet_cross", "sbn_bullet_fold_cross", "sbn_bullet_fold", "sbn_bullet_finish", "sbn_prof_enable", "sbn_prof_reset", "sbn_prof_count", "sbn_prof_get", "sbn_prof_last_job",
     "sbn_kzg_srs_upload", "sbn_kzg_srs_from_tau", "sbn_kzg_commit", "sbn_poly_div_linear", "sbn_kzg_open", "sbn_kzg_open_batched",
+    "sbn_r1cs_upload", "sbn_r1cs_free", "sbn_r1cs_multiply", "sbn_r1cs_eval_table", "sbn_r1cs_evaluate",
 ]
 
 
@@ -67,7 +68,7 @@ def lib():
         L.sbn_group_ctx.restype = C.c_void_p
         L.sbn_group_last_error.restype = C.c_char_p
         L.sbn_factored_lens.restype = None
-        for name in ("sbn_ctx_destroy", "sbn_bases_free", "sbn_table_free", "sbn_bullet_free", "sbn_sumcheck_free", "sbn_group_destroy", "sbn_group_bases_free", "sbn_group_range"):
+        for name in ("sbn_ctx_destroy", "sbn_bases_free", "sbn_table_free", "sbn_bullet_free", "sbn_sumcheck_free", "sbn_group_destroy", "sbn_group_bases_free", "sbn_group_range", "sbn_r1cs_free"):
             getattr(L, name).restype = None
         _LIB = L
     return _LIB
@@ -229,6 +230,18 @@ class Table:
     def free(self):
         if self.h:
             lib().sbn_table_free(self.ctx.h, self.h)
+            self.h = None
+
+
+class R1cs:
+    """R1CSShape (r1cs.rs:22-82) resident on the device (sbn_r1cs_upload)"""
+
+    def __init__(self, ctx, handle, num_cons, num_vars):
+        self.ctx, self.h, self.num_cons, self.num_vars = ctx, handle, num_cons, num_vars
+
+    def free(self):
+        if self.h:
+            lib().sbn_r1cs_free(self.ctx.h, self.h)
             self.h = None
 
 
@@ -673,6 +686,48 @@ class Context:
         ev = (C.c_uint8 * (32 * max(k, 1)))(); out = (C.c_uint8 * 64)(); inf = C.c_int()
         self._chk(lib().sbn_kzg_open_batched(self.h, srs.h, arr, nn, C.c_size_t(k), _ptr(z), _ptr(gamma), ev, out, C.byref(inf)), "sbn_kzg_open_batched")
         return [bytes(ev[32 * i:32 * i + 32]) for i in range(k)], bytes(out), bool(inf.value)
+
+    # ---- R1CS matrices on the device (r1cs.rs): multiply_vec, the phase-2 table, evaluate
+    def r1cs_upload(self, num_cons, num_vars, mats, flags=0):
+        """mats: three (rows, cols, vals) triplets for A, B, C; rows / cols: sequences or numpy arrays of uint32,
+        vals: 32 bytes per entry (bytes or a numpy uint8 array)"""
+        import numpy as np
+        if len(mats) != 3:
+            raise ValueError("r1cs_upload: mats must hold A, B and C")
+        keep, rows, cols, vals, nnz = [], (C.c_void_p * 3)(), (C.c_void_p * 3)(), (C.c_void_p * 3)(), (C.c_size_t * 3)()
+        for m, (r, c, v) in enumerate(mats):
+            r = np.ascontiguousarray(r, dtype=np.uint32); c = np.ascontiguousarray(c, dtype=np.uint32)
+            v = np.frombuffer(v, dtype=np.uint8) if isinstance(v, (bytes, bytearray)) else np.ascontiguousarray(v, dtype=np.uint8).reshape(-1)
+            n = len(r)
+            if len(c) != n or len(v) != 32 * n:
+                raise ValueError(f"r1cs_upload: matrix {m}: {n} rows, {len(c)} cols, {len(v)} value bytes")
+            keep += [r, c, v]
+            nnz[m] = n
+            rows[m] = r.ctypes.data if n else None; cols[m] = c.ctypes.data if n else None; vals[m] = v.ctypes.data if n else None
+        h = C.c_void_p()
+        self._chk(lib().sbn_r1cs_upload(self.h, C.c_size_t(num_cons), C.c_size_t(num_vars), rows, cols, vals, nnz, C.c_uint32(flags), C.byref(h)),
+                  "sbn_r1cs_upload")
+        return R1cs(self, h, num_cons, num_vars)
+
+    def r1cs_multiply(self, m, z):
+        """-> (Az, Bz, Cz) tables of num_cons entries"""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._chk(lib().sbn_r1cs_multiply(self.h, m.h, z.h, C.byref(a), C.byref(b), C.byref(c)), "sbn_r1cs_multiply")
+        return Table(self, a), Table(self, b), Table(self, c)
+
+    def r1cs_eval_table(self, m, rx, rA, rB, rC):
+        """r_A evals_A + r_B evals_B + r_C evals_C at eq(rx): a table of 2 num_vars entries"""
+        ht = C.c_void_p()
+        self._chk(lib().sbn_r1cs_eval_table(self.h, m.h, _ptr(rx), C.c_size_t(len(rx) // 32), _ptr(rA), _ptr(rB), _ptr(rC), C.byref(ht)),
+                  "sbn_r1cs_eval_table")
+        return Table(self, ht)
+
+    def r1cs_evaluate(self, m, rx, ry):
+        """-> (A(rx, ry), B(rx, ry), C(rx, ry)) as canonical 32-byte scalars"""
+        out = (C.c_uint8 * 96)()
+        self._chk(lib().sbn_r1cs_evaluate(self.h, m.h, _ptr(rx), C.c_size_t(len(rx) // 32), _ptr(ry), C.c_size_t(len(ry) // 32), out),
+                  "sbn_r1cs_evaluate")
+        return bytes(out[0:32]), bytes(out[32:64]), bytes(out[64:96])
 
     # ---- profiling
     def prof_enable(self, on=True):

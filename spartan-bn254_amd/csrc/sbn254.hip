@@ -6,6 +6,7 @@
 //   Commitments::commit, commit_inner   src/commitments.rs:144-154, src/hyrax.rs:253-308 -> sbn_commit_rows*
 //   sumcheck prover loops / bind        src/sumcheck.rs, src/hyrax.rs:195-203            -> sbn_sc_* / sbn_bind_top
 //   KZG commit / open (--features kzg)  src/kzg.rs                                       -> sbn_kzg_* / sbn_poly_div_linear
+//   R1CSShape multiply_vec / evaluate, compute_eval_table_sparse  src/r1cs.rs:126-163  -> sbn_r1cs_*
 // There is no CPU fallback in this file: every entry point needs the gfx950 device.
 #include "../../include/sbn254.h"
 #include "host_field.hpp"
@@ -16,6 +17,7 @@
 #include "sumcheck_kernels.cuh"
 #include "sumcheck_comb_kernels.cuh"
 #include "kzg_kernels.cuh"
+#include "r1cs_kernels.cuh"
 #include "host_keccak.hpp"
 
 #include <hip/hip_runtime.h>
@@ -45,6 +47,7 @@ using namespace sbn;
 #include "abi_bullet.inc"
 #include "abi_group.inc"
 #include "abi_kzg.inc"
+#include "abi_r1cs.inc"
 
 extern "C" {
 
