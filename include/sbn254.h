@@ -15,7 +15,7 @@
  *     host pointers and stage through HBM themselves.
  *   - a context owns one HIP stream and a workspace; calls on one context are serialised by a mutex
  *     (hyrax.rs:259-261 may enter B1 from many rayon workers at once); use one context per thread for overlap.
- *   - per-circuit data (generator sets, the SRS, the R1CS matrices) is uploaded once into a handle (sbn_bases, sbn_r1cs) that
+ *   - per-circuit data (generator sets, the SRS, the R1CS matrices and their dense representation) is uploaded once into a handle (sbn_bases, sbn_r1cs, sbn_dense) that
  *     later calls read; calls that produce vectors return new sbn_tables, which the sumcheck calls take as they are.
  *   - there is NO CPU fallback: without a gfx950 device sbn_ctx_create fails.
  */
@@ -369,6 +369,39 @@ int sbn_r1cs_eval_table(sbn_ctx* ctx, const sbn_r1cs* m, const uint8_t* rx, size
 /* R1CSShape::evaluate (r1cs.rs:126-129; snark.rs:465 "Instance evaluations"): out = A(rx,ry) || B(rx,ry) || C(rx,ry), canonical;
  * ell_x = log2(num_cons), ell_y = log2(2 * num_vars) */
 int sbn_r1cs_evaluate(sbn_ctx* ctx, const sbn_r1cs* m, const uint8_t* rx, size_t ell_x, const uint8_t* ry, size_t ell_y, uint8_t out[96]);
+
+/* ---- MultiSparseMatPolynomialAsDense on the device: what SNARK::encode -> R1CSShape::commit (r1cs.rs:375-400) builds once per circuit ----
+ * SparseMatPolynomial::multi_sparse_to_dense_rep -> AddrTimestamps::new (sparse_mlpoly_full.rs:89-101, 120-174, 211-243), from the same
+ * (row, col, val) triplets sbn_r1cs_upload takes, in the caller's entry order.  `batch` matrices (1 .. 8; the reference uses 3), nnz[k] entries each.
+ *   N     = max_k next_power_of_two(nnz[k]), with next_power_of_two(0) = 1;   cells = 2^max(num_vars_x, num_vars_y) (:145-149).
+ *   per matrix k (sparse_to_dense_vecs, :89-101): ops_row[k][i], ops_col[k][i], val[k][i] = entry i for i < nnz[k], zeros from nnz[k] to N.
+ *     Nothing is merged, dropped or reordered: duplicates, zero values and the padding are ops like any other (the padding reads cell 0).
+ *   per side (rows, then columns, independently; :211-243), ONE audit_ts running across the batch:
+ *     read_ts[k][i] = the number of ops (k', i') before (k, i) in (k, i) lexicographic order with the same address,
+ *     audit_ts[a]   = the number of ops on a over the whole batch.
+ *   comb_ops = merge(row addr[0..batch) || row read_ts[..] || col addr[..] || col read_ts[..] || val[..]) (:154-162): polynomial j of group g
+ *     (g = 0 .. 4 in this order) is the slice [(g * batch + j) * N, + N); the 5 * batch * N entries are zero-padded to the next power of two
+ *     (hyrax.rs:237-251); integers enter as Scalar::from_u64.
+ *   comb_mem = row audit_ts || col audit_ts (:163-164): 2 * cells entries, the column side from entry `cells`.
+ * Errors: an address >= cells (the reference asserts it, :226), a value >= r, batch outside 1 .. 8, a NULL array with nnz > 0, and
+ * batch * N > 2^31 (timestamps are 32-bit) are SBN_EINVAL; tables that do not fit are SBN_ENOMEM.  A matrix with nnz = 0 is valid.
+ * SBN_SCALARS_MONT: vals are ark-ff limbs.  The handle is independent of sbn_r1cs: encode calls both with the same arrays.
+ * Lifetime: every pointer and table below belongs to the handle and lives until sbn_dense_free.  The two tables are read-only: never pass
+ * them to a bind call or to sbn_table_free; views taken with sbn_table_slice / sbn_table_halves are freed before the handle. */
+typedef struct sbn_dense sbn_dense;
+int sbn_dense_build(sbn_ctx* ctx, size_t num_vars_x, size_t num_vars_y, const uint32_t* const* rows, const uint32_t* const* cols,
+                    const uint8_t* const* vals, const size_t* nnz, size_t batch, uint32_t flags, sbn_dense** out);
+void sbn_dense_free(sbn_ctx* ctx, sbn_dense* d);
+size_t sbn_dense_num_ops(const sbn_dense* d);      /* N */
+size_t sbn_dense_num_cells(const sbn_dense* d);
+size_t sbn_dense_batch(const sbn_dense* d);
+/* DEVICE arrays of uint32: what sbn_gather_merge / sbn_hash_layer[_pair] take.  side 0 = row, 1 = col; NULL for a bad side or k */
+const void* sbn_dense_addr_dev(const sbn_dense* d, int side, size_t k);      /* N entries (ops_addr_usize) */
+const void* sbn_dense_read_ts_dev(const sbn_dense* d, int side, size_t k);   /* N entries */
+const void* sbn_dense_audit_ts_dev(const sbn_dense* d, int side);            /* cells entries */
+/* the two merged polynomials as tables (for sbn_commit_table, sbn_table_slice, sbn_table_evaluate_many, sbn_table_bound, sbn_table_download) */
+const sbn_table* sbn_dense_comb_ops(const sbn_dense* d);
+const sbn_table* sbn_dense_comb_mem(const sbn_dense* d);
 
 /* ---- per-kernel timing (HIP events on the context's stream), for bench.py's roofline line ---- */
 int sbn_prof_enable(sbn_ctx* ctx, int on);

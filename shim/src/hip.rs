@@ -44,6 +44,7 @@ use crate::unipoly::{CompressedUniPoly, UniPoly};
 #[repr(C)] pub struct sbn_group { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_group_bases { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_r1cs { _p: [u8; 0] }
+#[repr(C)] pub struct sbn_dense { _p: [u8; 0] }
 
 pub const SBN_OK: c_int = 0;
 pub const SBN_SCALARS_MONT: u32 = 1;
@@ -161,6 +162,16 @@ extern "C" {
     pub fn sbn_r1cs_multiply(ctx: *mut sbn_ctx, m: *const sbn_r1cs, z: *const sbn_table, az: *mut *mut sbn_table, bz: *mut *mut sbn_table, cz: *mut *mut sbn_table) -> c_int;
     pub fn sbn_r1cs_eval_table(ctx: *mut sbn_ctx, m: *const sbn_r1cs, rx: *const u8, ell_x: usize, ra: *const u8, rb: *const u8, rc: *const u8, out: *mut *mut sbn_table) -> c_int;
     pub fn sbn_r1cs_evaluate(ctx: *mut sbn_ctx, m: *const sbn_r1cs, rx: *const u8, ell_x: usize, ry: *const u8, ell_y: usize, out: *mut u8) -> c_int;
+    pub fn sbn_dense_build(ctx: *mut sbn_ctx, num_vars_x: usize, num_vars_y: usize, rows: *const *const u32, cols: *const *const u32, vals: *const *const u8, nnz: *const usize, batch: usize, flags: u32, out: *mut *mut sbn_dense) -> c_int;
+    pub fn sbn_dense_free(ctx: *mut sbn_ctx, d: *mut sbn_dense);
+    pub fn sbn_dense_num_ops(d: *const sbn_dense) -> usize;
+    pub fn sbn_dense_num_cells(d: *const sbn_dense) -> usize;
+    pub fn sbn_dense_batch(d: *const sbn_dense) -> usize;
+    pub fn sbn_dense_addr_dev(d: *const sbn_dense, side: c_int, k: usize) -> *const c_void;
+    pub fn sbn_dense_read_ts_dev(d: *const sbn_dense, side: c_int, k: usize) -> *const c_void;
+    pub fn sbn_dense_audit_ts_dev(d: *const sbn_dense, side: c_int) -> *const c_void;
+    pub fn sbn_dense_comb_ops(d: *const sbn_dense) -> *const sbn_table;
+    pub fn sbn_dense_comb_mem(d: *const sbn_dense) -> *const sbn_table;
     pub fn sbn_prof_enable(ctx: *mut sbn_ctx, on: c_int) -> c_int;
     pub fn sbn_prof_reset(ctx: *mut sbn_ctx) -> c_int;
     pub fn sbn_prof_count(ctx: *mut sbn_ctx) -> c_int;
@@ -780,3 +791,43 @@ pub fn r1cs_evaluate(m: *const sbn_r1cs, rx: &[Scalar], ry: &[Scalar]) -> (Scala
     check(unsafe { sbn_r1cs_evaluate(ctx(), m, rxb.as_ptr(), rx.len(), ryb.as_ptr(), ry.len(), out.as_mut_ptr()) });
     triple(&out)
 }
+
+// ---- the dense representation on the device (sparse_mlpoly_full.rs:120-174): built once per circuit at encode, next to R1csDev -------
+/// MultiSparseMatPolynomialAsDense on the device: padded addresses, read / audit timestamps, comb_ops and comb_mem, from the same triplets
+/// R1csDev uploads.  Filled by R1CSShape::commit (r1cs.rs:375-400); shared by clones, dropped with the last clone.
+pub struct DenseHandle(pub *mut sbn_dense);
+unsafe impl Send for DenseHandle {}
+unsafe impl Sync for DenseHandle {}
+impl Drop for DenseHandle { fn drop(&mut self) { if !self.0.is_null() { unsafe { sbn_dense_free(ctx(), self.0) } } } }
+impl std::fmt::Debug for DenseHandle { fn fmt(&self, f: &mut std::fmt::Formatter<'_>) -> std::fmt::Result { write!(f, "DenseHandle({:p})", self.0) } }
+#[derive(Clone, Debug, Default)]
+pub struct DenseDev {
+    one: Arc<OnceLock<DenseHandle>>,
+}
+impl DenseDev {
+    /// the triplets of the batch (SparseMatPolynomial.M) in entry order, values as ark-ff limbs
+    pub fn get(&self, num_vars_x: usize, num_vars_y: usize, mats: &[&SparseMatPolynomial]) -> *const sbn_dense {
+        self.one.get_or_init(|| {
+            let rows: Vec<Vec<u32>> = mats.iter().map(|m| m.M.iter().map(|e| u32::try_from(e.row).unwrap_or(u32::MAX)).collect()).collect();
+            let cols: Vec<Vec<u32>> = mats.iter().map(|m| m.M.iter().map(|e| u32::try_from(e.col).unwrap_or(u32::MAX)).collect()).collect();
+            let vals: Vec<Vec<u8>> = mats.iter().map(|m| { let v: Vec<Scalar> = m.M.iter().map(|e| e.val).collect(); scalars_mont_bytes(&v).into_owned() }).collect();
+            let rp: Vec<*const u32> = rows.iter().map(|v| v.as_ptr()).collect();
+            let cp: Vec<*const u32> = cols.iter().map(|v| v.as_ptr()).collect();
+            let vp: Vec<*const u8> = vals.iter().map(|v| v.as_ptr()).collect();
+            let nnz: Vec<usize> = rows.iter().map(|v| v.len()).collect();
+            let mut h = null_mut();
+            check(unsafe { sbn_dense_build(ctx(), num_vars_x, num_vars_y, rp.as_ptr(), cp.as_ptr(), vp.as_ptr(), nnz.as_ptr(), mats.len(), SBN_SCALARS_MONT, &mut h) });
+            DenseHandle(h)
+        })
+        .0
+    }
+}
+/// (N, cells, batch) of the handle: SparseMatPolyCommitment's num_ops / num_mem_cells / batch_size (sparse_mlpoly_full.rs:186-193)
+pub fn dense_shape(d: *const sbn_dense) -> (usize, usize, usize) { unsafe { (sbn_dense_num_ops(d), sbn_dense_num_cells(d), sbn_dense_batch(d)) } }
+/// device arrays of one side (0 = row, 1 = col) for sbn_gather_merge / sbn_hash_layer_pair: (addr[k], read_ts[k]) per matrix, audit_ts
+pub fn dense_side(d: *const sbn_dense, side: c_int) -> (Vec<(*const c_void, *const c_void)>, *const c_void) {
+    let b = unsafe { sbn_dense_batch(d) };
+    ((0..b).map(|k| unsafe { (sbn_dense_addr_dev(d, side, k), sbn_dense_read_ts_dev(d, side, k)) }).collect(), unsafe { sbn_dense_audit_ts_dev(d, side) })
+}
+/// comb_ops and comb_mem: read-only tables that belong to the handle (never wrapped in `Table`, whose Drop frees)
+pub fn dense_tables(d: *const sbn_dense) -> (*const sbn_table, *const sbn_table) { unsafe { (sbn_dense_comb_ops(d), sbn_dense_comb_mem(d)) } }

@@ -21,6 +21,8 @@ EXPORTED_SYMBOLS = [
     "sbn_eq_evals", "sbn_hash_layer", "sbn_hash_layer_pair", "sbn_product_layer", "sbn_product_circuit", "sbn_product_circuit_many", "sbn_table_halves", "sbn_table_slice", "sbn_table_dot", "sbn_table_evaluate", "sbn_table_evaluate_many", "sbn_table_bound", "sbn_gather_merge", "sbn_gather_merge_rows", "sbn_commit_table", "sbn_bullet_begin", "sbn_bullet_begin_scaled", "sbn_bullet_free", "sbn_bullet_len", "sbn_bullet_cross", "sbn_bullet_fold_cross", "sbn_bullet_fold", "sbn_bullet_finish", "sbn_prof_enable", "sbn_prof_reset", "sbn_prof_count", "sbn_prof_get", "sbn_prof_last_job",
     "sbn_kzg_srs_upload", "sbn_kzg_srs_from_tau", "sbn_kzg_commit", "sbn_poly_div_linear", "sbn_kzg_open", "sbn_kzg_open_batched",
     "sbn_r1cs_upload", "sbn_r1cs_free", "sbn_r1cs_multiply", "sbn_r1cs_eval_table", "sbn_r1cs_evaluate",
+    "sbn_dense_build", "sbn_dense_free", "sbn_dense_num_ops", "sbn_dense_num_cells", "sbn_dense_batch", "sbn_dense_addr_dev", "sbn_dense_read_ts_dev",
+    "sbn_dense_audit_ts_dev", "sbn_dense_comb_ops", "sbn_dense_comb_mem",
 ]
 
 
@@ -68,8 +70,15 @@ def lib():
         L.sbn_group_ctx.restype = C.c_void_p
         L.sbn_group_last_error.restype = C.c_char_p
         L.sbn_factored_lens.restype = None
-        for name in ("sbn_ctx_destroy", "sbn_bases_free", "sbn_table_free", "sbn_bullet_free", "sbn_sumcheck_free", "sbn_group_destroy", "sbn_group_bases_free", "sbn_group_range", "sbn_r1cs_free"):
+        for name in ("sbn_ctx_destroy", "sbn_bases_free", "sbn_table_free", "sbn_bullet_free", "sbn_sumcheck_free", "sbn_group_destroy", "sbn_group_bases_free", "sbn_group_range", "sbn_r1cs_free", "sbn_dense_free"):
             getattr(L, name).restype = None
+        for name in ("sbn_dense_num_ops", "sbn_dense_num_cells", "sbn_dense_batch"):
+            getattr(L, name).restype = C.c_size_t; getattr(L, name).argtypes = [C.c_void_p]
+        for name in ("sbn_dense_addr_dev", "sbn_dense_read_ts_dev"):
+            getattr(L, name).restype = C.c_void_p; getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+        L.sbn_dense_audit_ts_dev.restype = C.c_void_p; L.sbn_dense_audit_ts_dev.argtypes = [C.c_void_p, C.c_int]
+        for name in ("sbn_dense_comb_ops", "sbn_dense_comb_mem"):
+            getattr(L, name).restype = C.c_void_p; getattr(L, name).argtypes = [C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -233,6 +242,13 @@ class Table:
             self.h = None
 
 
+class _BorrowedTable(Table):
+    """a table owned by another handle: never passed to sbn_table_free"""
+
+    def free(self):
+        self.h = None
+
+
 class R1cs:
     """R1CSShape (r1cs.rs:22-82) resident on the device (sbn_r1cs_upload)"""
 
@@ -242,6 +258,36 @@ class R1cs:
     def free(self):
         if self.h:
             lib().sbn_r1cs_free(self.ctx.h, self.h)
+            self.h = None
+
+
+class Dense:
+    """MultiSparseMatPolynomialAsDense (sparse_mlpoly_full.rs:120-174) resident on the device (sbn_dense_build).  Device pointers are ints;
+    comb_ops / comb_mem are Tables that belong to the handle: their free() does nothing, and free() of the handle ends them."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+        self.num_ops = lib().sbn_dense_num_ops(handle); self.num_cells = lib().sbn_dense_num_cells(handle); self.batch = lib().sbn_dense_batch(handle)
+        self.comb_ops = _BorrowedTable(ctx, C.c_void_p(lib().sbn_dense_comb_ops(handle)))
+        self.comb_mem = _BorrowedTable(ctx, C.c_void_p(lib().sbn_dense_comb_mem(handle)))
+
+    def addr_dev(self, side, k):
+        return lib().sbn_dense_addr_dev(self.h, side, k)
+
+    def read_ts_dev(self, side, k):
+        return lib().sbn_dense_read_ts_dev(self.h, side, k)
+
+    def audit_ts_dev(self, side):
+        return lib().sbn_dense_audit_ts_dev(self.h, side)
+
+    def ops_slice(self, group, j):
+        """polynomial j of group 0..4 (row addr, row read_ts, col addr, col read_ts, val) inside comb_ops, as a view to free before the handle"""
+        return self.ctx.table_slice(self.comb_ops, (group * self.batch + j) * self.num_ops, self.num_ops)
+
+    def free(self):
+        if self.h:
+            self.comb_ops.h = self.comb_mem.h = None
+            lib().sbn_dense_free(self.ctx.h, self.h)
             self.h = None
 
 
@@ -728,6 +774,26 @@ class Context:
         self._chk(lib().sbn_r1cs_evaluate(self.h, m.h, _ptr(rx), C.c_size_t(len(rx) // 32), _ptr(ry), C.c_size_t(len(ry) // 32), out),
                   "sbn_r1cs_evaluate")
         return bytes(out[0:32]), bytes(out[32:64]), bytes(out[64:96])
+
+    # ---- the dense representation of the R1CS matrices (sparse_mlpoly_full.rs:120-174): addresses, timestamps, comb_ops, comb_mem
+    def dense_build(self, num_vars_x, num_vars_y, mats, flags=0):
+        """mats: 1 .. 8 (rows, cols, vals) triplets as for r1cs_upload, in the caller's entry order"""
+        import numpy as np
+        b = len(mats); nb = max(b, 1)
+        keep, rows, cols, vals, nnz = [], (C.c_void_p * nb)(), (C.c_void_p * nb)(), (C.c_void_p * nb)(), (C.c_size_t * nb)()
+        for m, (r, c, v) in enumerate(mats):
+            r = np.ascontiguousarray(r, dtype=np.uint32); c = np.ascontiguousarray(c, dtype=np.uint32)
+            v = np.frombuffer(v, dtype=np.uint8) if isinstance(v, (bytes, bytearray)) else np.ascontiguousarray(v, dtype=np.uint8).reshape(-1)
+            n = len(r)
+            if len(c) != n or len(v) != 32 * n:
+                raise ValueError(f"dense_build: matrix {m}: {n} rows, {len(c)} cols, {len(v)} value bytes")
+            keep += [r, c, v]
+            nnz[m] = n
+            rows[m] = r.ctypes.data if n else None; cols[m] = c.ctypes.data if n else None; vals[m] = v.ctypes.data if n else None
+        h = C.c_void_p()
+        self._chk(lib().sbn_dense_build(self.h, C.c_size_t(num_vars_x), C.c_size_t(num_vars_y), rows, cols, vals, nnz, C.c_size_t(b), C.c_uint32(flags),
+                                        C.byref(h)), "sbn_dense_build")
+        return Dense(self, h)
 
     # ---- profiling
     def prof_enable(self, on=True):

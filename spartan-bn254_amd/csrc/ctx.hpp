@@ -43,6 +43,7 @@ struct sbn_ctx {
   DevBuf glv_scal;                           // GLV half-scalars of a single MSM (glv_kernels.cuh): 2n x 16 B
   DevBuf kzg_ws;                             // KZG division levels, evals and batched-opening arguments (abi_kzg.inc)
   DevBuf r1cs_ws;                            // R1CS SpMV carries and block sums (abi_r1cs.inc)
+  DevBuf dense_ws;                           // staged triplets and sort buffers of sbn_dense_build (abi_dense.inc)
   int msm_glv = -1;                          // single MSMs over the GLV endomorphism: -1 automatic (msm_host.hpp: glv_applies), 0 never, 1 wherever it can run (SBN_MSM_GLV)
   bool sort2_ok = false;      // dynamic LDS of its level-1 scatter granted
   size_t sort2_min = (size_t)1 << 20;   // terms from which a single MSM takes the two-level sort (SBN_SORT2_MIN; 0 = never)

@@ -7,6 +7,7 @@
 //   sumcheck prover loops / bind        src/sumcheck.rs, src/hyrax.rs:195-203            -> sbn_sc_* / sbn_bind_top
 //   KZG commit / open (--features kzg)  src/kzg.rs                                       -> sbn_kzg_* / sbn_poly_div_linear
 //   R1CSShape multiply_vec / evaluate, compute_eval_table_sparse  src/r1cs.rs:126-163  -> sbn_r1cs_*
+//   multi_sparse_to_dense_rep, AddrTimestamps::new      src/sparse_mlpoly_full.rs:120-174, 211-243  -> sbn_dense_*
 // There is no CPU fallback in this file: every entry point needs the gfx950 device.
 #include "../../include/sbn254.h"
 #include "host_field.hpp"
@@ -18,6 +19,7 @@
 #include "sumcheck_comb_kernels.cuh"
 #include "kzg_kernels.cuh"
 #include "r1cs_kernels.cuh"
+#include "dense_kernels.cuh"
 #include "host_keccak.hpp"
 
 #include <hip/hip_runtime.h>
@@ -48,6 +50,7 @@ using namespace sbn;
 #include "abi_group.inc"
 #include "abi_kzg.inc"
 #include "abi_r1cs.inc"
+#include "abi_dense.inc"
 
 extern "C" {
 
