@@ -184,6 +184,30 @@ size_t sbn_sumcheck_len(const sbn_sumcheck* st);                       /* curren
  * A_par[0..n_par), B_par[0..n_par), C_par, A_seq[..], B_seq[..], C_seq[..] */
 int sbn_sumcheck_finish(sbn_ctx* ctx, sbn_sumcheck* st, uint8_t* finals);
 void sbn_sumcheck_free(sbn_ctx* ctx, sbn_sumcheck* st);
+/* ---- transcript: Merlin v1.0 over STROBE-128 / Keccak-f[1600] (merlin::Transcript as src/transcript.rs uses it) ----
+ * Host only: no context, works without a device.  append_message / challenge_bytes are Merlin's; challenge_scalar is
+ * ProofTranscript::challenge_scalar (transcript.rs:56-67): 64 challenge bytes, little-endian, mod r, as 32 canonical bytes.
+ * The state record is 203 bytes: the 200 sponge bytes, then pos, pos_begin, cur_flags (from_state rejects pos >= 166,
+ * pos_begin > 166 and undefined flag bits).  A failed call (SBN_EINVAL) leaves the transcript as it was. */
+typedef struct sbn_transcript sbn_transcript;
+int sbn_transcript_new(const uint8_t* label, size_t label_len, sbn_transcript** out);
+int sbn_transcript_clone(const sbn_transcript* t, sbn_transcript** out);
+void sbn_transcript_free(sbn_transcript* t);
+int sbn_transcript_append_message(sbn_transcript* t, const uint8_t* label, size_t label_len, const uint8_t* msg, size_t msg_len);
+int sbn_transcript_challenge_bytes(sbn_transcript* t, const uint8_t* label, size_t label_len, uint8_t* out, size_t out_len);
+int sbn_transcript_challenge_scalar(sbn_transcript* t, const uint8_t* label, size_t label_len, uint8_t out[32]);
+int sbn_transcript_state(const sbn_transcript* t, uint8_t out[203]);
+int sbn_transcript_from_state(const uint8_t in[203], sbn_transcript** out);
+/* Fr::from_le_bytes_mod_order on 64 bytes: what challenge_scalar does with its challenge bytes.  Host only. */
+int sbn_fr_from_wide(const uint8_t in[64], uint8_t out[32]);
+/* SumcheckInstanceProof::prove_cubic_batched (sumcheck.rs:165-330) in ONE call: `st` fresh from sbn_sumcheck_begin /
+ * sbn_sumcheck_begin_eq, rounds = log2(sbn_sumcheck_len(st)).  Every round's kernels are queued at once; between them a one-wave
+ * kernel does the host's part on the device — the combination, e1 = e - e0, UniPoly::from_evals, the transcript's seven operations
+ * (unipoly.rs:117-122, challenge_scalar("challenge_nextround")), e = poly(r_j) — and leaves r_j in device memory for the launches
+ * behind it.  One wait, one copy back.  out_polys: rounds x 4 x 32 (c0..c3 of every round polynomial, canonical); out_r: rounds x 32;
+ * finals as sbn_sumcheck_finish.  `tr` moves on only if the whole call succeeded; a failure after the first launch leaves `st` dead
+ * (later calls return SBN_EINVAL).  Same values as the loop over sbn_sumcheck_round with the same transcript on the host, bit for bit. */
+int sbn_sumcheck_prove(sbn_ctx* ctx, sbn_sumcheck* st, sbn_transcript* tr, const uint8_t claim[32], uint8_t* out_polys, uint8_t* out_r, uint8_t* finals);
 /* EqPolynomial::evals (hyrax.rs:355-369) built on the device */
 int sbn_eq_evals(sbn_ctx* ctx, const uint8_t* r, size_t ell, sbn_table** out);
 

@@ -45,6 +45,7 @@ use crate::unipoly::{CompressedUniPoly, UniPoly};
 #[repr(C)] pub struct sbn_group_bases { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_r1cs { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_dense { _p: [u8; 0] }
+#[repr(C)] pub struct sbn_transcript { _p: [u8; 0] }
 
 pub const SBN_OK: c_int = 0;
 pub const SBN_SCALARS_MONT: u32 = 1;
@@ -110,6 +111,16 @@ extern "C" {
     pub fn sbn_sumcheck_len(st: *const sbn_sumcheck) -> usize;
     pub fn sbn_sumcheck_finish(ctx: *mut sbn_ctx, st: *mut sbn_sumcheck, finals: *mut u8) -> c_int;
     pub fn sbn_sumcheck_free(ctx: *mut sbn_ctx, st: *mut sbn_sumcheck);
+    pub fn sbn_transcript_new(label: *const u8, label_len: usize, out: *mut *mut sbn_transcript) -> c_int;
+    pub fn sbn_transcript_clone(t: *const sbn_transcript, out: *mut *mut sbn_transcript) -> c_int;
+    pub fn sbn_transcript_free(t: *mut sbn_transcript);
+    pub fn sbn_transcript_append_message(t: *mut sbn_transcript, label: *const u8, label_len: usize, msg: *const u8, msg_len: usize) -> c_int;
+    pub fn sbn_transcript_challenge_bytes(t: *mut sbn_transcript, label: *const u8, label_len: usize, out: *mut u8, out_len: usize) -> c_int;
+    pub fn sbn_transcript_challenge_scalar(t: *mut sbn_transcript, label: *const u8, label_len: usize, out: *mut u8) -> c_int;
+    pub fn sbn_transcript_state(t: *const sbn_transcript, out: *mut u8) -> c_int;
+    pub fn sbn_transcript_from_state(input: *const u8, out: *mut *mut sbn_transcript) -> c_int;
+    pub fn sbn_fr_from_wide(input: *const u8, out: *mut u8) -> c_int;
+    pub fn sbn_sumcheck_prove(ctx: *mut sbn_ctx, st: *mut sbn_sumcheck, tr: *mut sbn_transcript, claim: *const u8, out_polys: *mut u8, out_r: *mut u8, finals: *mut u8) -> c_int;
     pub fn sbn_eq_evals(ctx: *mut sbn_ctx, r: *const u8, ell: usize, out: *mut *mut sbn_table) -> c_int;
     pub fn sbn_table_dot(ctx: *mut sbn_ctx, a: *const sbn_table, b: *const sbn_table, out: *mut u8) -> c_int;
     pub fn sbn_table_evaluate(ctx: *mut sbn_ctx, z: *const sbn_table, r: *const u8, ell: usize, out: *mut u8) -> c_int;
@@ -474,6 +485,105 @@ pub fn prove_cubic_batched(
     let b_seq: Vec<Scalar> = (0..n_seq).map(|i| f(o + n_seq + i)).collect();
     let c_seq: Vec<Scalar> = (0..n_seq).map(|i| f(o + 2 * n_seq + i)).collect();
     // leave the host polynomials as the reference's loop leaves them: one entry, the final claim
+    for i in 0..n_par { poly_A_vec_par[i].set_final(a_par[i]); poly_B_vec_par[i].set_final(b_par[i]); }
+    if n_par > 0 { poly_C_par.set_final(c_par); }
+    for i in 0..n_seq { poly_A_vec_seq[i].set_final(a_seq[i]); poly_B_vec_seq[i].set_final(b_seq[i]); poly_C_vec_seq[i].set_final(c_seq[i]); }
+    (SumcheckInstanceProof::new(cubic_polys), r, (a_par, b_par, c_par), (a_seq, b_seq, c_seq))
+}
+
+/// A Merlin v1.0 transcript held by the library (`sbn_transcript`), with merlin::Transcript's method names.  The device can only
+/// continue a transcript whose state it can read, and the merlin crate does not expose its state: a prover that uses
+/// `prove_cubic_batched_dev` holds one of these in place of `merlin::Transcript` from `Transcript::new` on.
+pub struct DevTranscript(pub *mut sbn_transcript);
+unsafe impl Send for DevTranscript {}
+impl DevTranscript {
+    pub fn new(label: &'static [u8]) -> Self {
+        let mut t = null_mut();
+        check(unsafe { sbn_transcript_new(label.as_ptr(), label.len(), &mut t) });
+        DevTranscript(t)
+    }
+    pub fn append_message(&mut self, label: &'static [u8], message: &[u8]) {
+        check(unsafe { sbn_transcript_append_message(self.0, label.as_ptr(), label.len(), message.as_ptr(), message.len()) });
+    }
+    pub fn challenge_bytes(&mut self, label: &'static [u8], dest: &mut [u8]) {
+        check(unsafe { sbn_transcript_challenge_bytes(self.0, label.as_ptr(), label.len(), dest.as_mut_ptr(), dest.len()) });
+    }
+    /// ProofTranscript::append_scalar / challenge_scalar (transcript.rs:41-43, 56-67)
+    pub fn append_scalar(&mut self, label: &'static [u8], scalar: &Scalar) { self.append_message(label, &scalar.to_bytes()); }
+    pub fn challenge_scalar(&mut self, label: &'static [u8]) -> Scalar {
+        let mut out = [0u8; 32];
+        check(unsafe { sbn_transcript_challenge_scalar(self.0, label.as_ptr(), label.len(), out.as_mut_ptr()) });
+        sc(&out)
+    }
+    pub fn state(&self) -> [u8; 203] {
+        let mut out = [0u8; 203];
+        check(unsafe { sbn_transcript_state(self.0, out.as_mut_ptr()) });
+        out
+    }
+}
+impl Clone for DevTranscript {
+    fn clone(&self) -> Self {
+        let mut t = null_mut();
+        check(unsafe { sbn_transcript_clone(self.0, &mut t) });
+        DevTranscript(t)
+    }
+}
+impl Drop for DevTranscript {
+    fn drop(&mut self) { unsafe { sbn_transcript_free(self.0) } }
+}
+
+/// prove_cubic_batched with the transcript on the device: ONE foreign call for all rounds (sbn_sumcheck_prove) instead of one per round.
+/// Same proof, challenges and claims as `prove_cubic_batched` gives with a merlin::Transcript in the same state.
+pub fn prove_cubic_batched_dev(
+    claim: &Scalar,
+    num_rounds: usize,
+    poly_vec_par: (&mut Vec<&mut DensePolynomial>, &mut Vec<&mut DensePolynomial>, &mut DensePolynomial),
+    poly_vec_seq: (&mut Vec<&mut DensePolynomial>, &mut Vec<&mut DensePolynomial>, &mut Vec<&mut DensePolynomial>),
+    coeffs: &[Scalar],
+    transcript: &mut DevTranscript,
+) -> (SumcheckInstanceProof, Vec<Scalar>, (Vec<Scalar>, Vec<Scalar>, Scalar), (Vec<Scalar>, Vec<Scalar>, Vec<Scalar>)) {
+    let (poly_A_vec_par, poly_B_vec_par, poly_C_par) = poly_vec_par;
+    let (poly_A_vec_seq, poly_B_vec_seq, poly_C_vec_seq) = poly_vec_seq;
+    let (n_par, n_seq) = (poly_A_vec_par.len(), poly_A_vec_seq.len());
+    assert_eq!(coeffs.len(), n_par + n_seq);
+    let ta_par: Vec<Table> = poly_A_vec_par.iter().map(|p| Table::of(p)).collect();
+    let tb_par: Vec<Table> = poly_B_vec_par.iter().map(|p| Table::of(p)).collect();
+    let tc_par = if n_par > 0 { Some(Table::of(poly_C_par)) } else { None };
+    let ta_seq: Vec<Table> = poly_A_vec_seq.iter().map(|p| Table::of(p)).collect();
+    let tb_seq: Vec<Table> = poly_B_vec_seq.iter().map(|p| Table::of(p)).collect();
+    let tc_seq: Vec<Table> = poly_C_vec_seq.iter().map(|p| Table::of(p)).collect();
+    let ptrs = |v: &Vec<Table>| -> Vec<*const sbn_table> { v.iter().map(|t| t.0 as *const sbn_table).collect() };
+    let (pa, pb, sa, sb_, sc_) = (ptrs(&ta_par), ptrs(&tb_par), ptrs(&ta_seq), ptrs(&tb_seq), ptrs(&tc_seq));
+
+    let mut ev = [0u8; 96];
+    let mut st = null_mut();
+    check(unsafe {
+        sbn_sumcheck_begin(ctx(), pa.as_ptr(), pb.as_ptr(), tc_par.as_ref().map_or(null(), |t| t.0 as *const sbn_table), n_par,
+                           sa.as_ptr(), sb_.as_ptr(), sc_.as_ptr(), n_seq, scalars_canonical(coeffs).as_ptr(), ev.as_mut_ptr(), &mut st)
+    });
+    let st = SumcheckState(st);
+    assert_eq!(unsafe { sbn_sumcheck_len(st.0) }, 1usize << num_rounds);
+
+    let ntab = 2 * n_par + usize::from(n_par > 0) + 3 * n_seq;
+    let (mut polys, mut rs, mut fin) = (vec![0u8; 128 * num_rounds], vec![0u8; 32 * num_rounds], vec![0u8; 32 * ntab]);
+    check(unsafe { sbn_sumcheck_prove(ctx(), st.0, transcript.0, claim.to_bytes().as_ptr(), polys.as_mut_ptr(), rs.as_mut_ptr(), fin.as_mut_ptr()) });
+    let r: Vec<Scalar> = (0..num_rounds).map(|j| sc(&rs[32 * j..32 * j + 32])).collect();
+    let cubic_polys: Vec<CompressedUniPoly> = (0..num_rounds)
+        .map(|j| {
+            // UniPoly keeps its coefficients private: rebuild it from its values at 0, 1, 2, 3 (from_evals inverts exactly)
+            let c: Vec<Scalar> = (0..4).map(|k| sc(&polys[128 * j + 32 * k..128 * j + 32 * k + 32])).collect();
+            let at = |x: u64| { let x = Scalar::from_u64(x); c[0] + x * (c[1] + x * (c[2] + x * c[3])) };
+            UniPoly::from_evals(&[at(0), at(1), at(2), at(3)]).compress()
+        })
+        .collect();
+    let f = |i: usize| sc(&fin[32 * i..32 * i + 32]);
+    let a_par: Vec<Scalar> = (0..n_par).map(f).collect();
+    let b_par: Vec<Scalar> = (0..n_par).map(|i| f(n_par + i)).collect();
+    let c_par = if n_par > 0 { f(2 * n_par) } else { poly_C_par[0] };
+    let o = 2 * n_par + usize::from(n_par > 0);
+    let a_seq: Vec<Scalar> = (0..n_seq).map(|i| f(o + i)).collect();
+    let b_seq: Vec<Scalar> = (0..n_seq).map(|i| f(o + n_seq + i)).collect();
+    let c_seq: Vec<Scalar> = (0..n_seq).map(|i| f(o + 2 * n_seq + i)).collect();
     for i in 0..n_par { poly_A_vec_par[i].set_final(a_par[i]); poly_B_vec_par[i].set_final(b_par[i]); }
     if n_par > 0 { poly_C_par.set_final(c_par); }
     for i in 0..n_seq { poly_A_vec_seq[i].set_final(a_seq[i]); poly_B_vec_seq[i].set_final(b_seq[i]); poly_C_vec_seq[i].set_final(c_seq[i]); }

@@ -16,6 +16,8 @@ EXPORTED_SYMBOLS = [
     "sbn_bind_top", "sbn_bind_top_many", "sbn_sc_eval_cubic", "sbn_sc_eval_cubic_batched", "sbn_sc_eval_r1cs", "sbn_sc_eval_quad",
     "sbn_sc_bind_eval_cubic_batched", "sbn_sc_bind_eval_r1cs", "sbn_sc_bind_eval_quad",
     "sbn_sumcheck_begin", "sbn_sumcheck_begin_eq", "sbn_sumcheck_round", "sbn_sumcheck_len", "sbn_sumcheck_finish", "sbn_sumcheck_free",
+    "sbn_transcript_new", "sbn_transcript_clone", "sbn_transcript_free", "sbn_transcript_append_message", "sbn_transcript_challenge_bytes", "sbn_transcript_challenge_scalar",
+    "sbn_transcript_state", "sbn_transcript_from_state", "sbn_fr_from_wide", "sbn_sumcheck_prove",
     "sbn_group_create", "sbn_group_destroy", "sbn_group_size", "sbn_group_ctx", "sbn_group_last_error", "sbn_group_bases_upload", "sbn_group_gens_new", "sbn_group_bases_precompute",
     "sbn_group_bases_free", "sbn_group_commit_rows", "sbn_group_commit_rows_dev", "sbn_group_gather_commit", "sbn_group_msm", "sbn_group_bases_upload_ranges", "sbn_group_bases_synthetic_ranges", "sbn_group_range", "sbn_group_msm_bases", "sbn_group_msm_bases_dev",
     "sbn_eq_evals", "sbn_hash_layer", "sbn_hash_layer_pair", "sbn_product_layer", "sbn_product_circuit", "sbn_product_circuit_many", "sbn_table_halves", "sbn_table_slice", "sbn_table_dot", "sbn_table_evaluate", "sbn_table_evaluate_many", "sbn_table_bound", "sbn_gather_merge", "sbn_gather_merge_rows", "sbn_commit_table", "sbn_bullet_begin", "sbn_bullet_begin_scaled", "sbn_bullet_free", "sbn_bullet_len", "sbn_bullet_cross", "sbn_bullet_fold_cross", "sbn_bullet_fold", "sbn_bullet_finish", "sbn_prof_enable", "sbn_prof_reset", "sbn_prof_count", "sbn_prof_get", "sbn_prof_last_job",
@@ -70,12 +72,14 @@ def lib():
         L.sbn_group_ctx.restype = C.c_void_p
         L.sbn_group_last_error.restype = C.c_char_p
         L.sbn_factored_lens.restype = None
-        for name in ("sbn_ctx_destroy", "sbn_bases_free", "sbn_table_free", "sbn_bullet_free", "sbn_sumcheck_free", "sbn_group_destroy", "sbn_group_bases_free", "sbn_group_range", "sbn_r1cs_free", "sbn_dense_free"):
+        for name in ("sbn_ctx_destroy", "sbn_bases_free", "sbn_table_free", "sbn_bullet_free", "sbn_sumcheck_free", "sbn_group_destroy", "sbn_group_bases_free", "sbn_group_range", "sbn_r1cs_free", "sbn_dense_free", "sbn_transcript_free"):
             getattr(L, name).restype = None
         for name in ("sbn_dense_num_ops", "sbn_dense_num_cells", "sbn_dense_batch"):
             getattr(L, name).restype = C.c_size_t; getattr(L, name).argtypes = [C.c_void_p]
         for name in ("sbn_dense_addr_dev", "sbn_dense_read_ts_dev"):
             getattr(L, name).restype = C.c_void_p; getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+        L.sbn_transcript_free.argtypes = [C.c_void_p]
+        L.sbn_sumcheck_prove.argtypes = [C.c_void_p] * 7
         L.sbn_dense_audit_ts_dev.restype = C.c_void_p; L.sbn_dense_audit_ts_dev.argtypes = [C.c_void_p, C.c_int]
         for name in ("sbn_dense_comb_ops", "sbn_dense_comb_mem"):
             getattr(L, name).restype = C.c_void_p; getattr(L, name).argtypes = [C.c_void_p]
@@ -202,6 +206,77 @@ class Bullet:
         if self.h:
             lib().sbn_bullet_free(self.ctx.h, self.h)
             self.h = None
+
+
+def fr_from_wide(b64):
+    """Fr::from_le_bytes_mod_order on 64 bytes -> 32 canonical bytes (host side)"""
+    if len(b64) != 64:
+        raise ValueError("64 bytes are needed")
+    out = (C.c_uint8 * 32)()
+    rc = lib().sbn_fr_from_wide(_ptr(b64), out)
+    if rc:
+        raise SbnError(f"sbn_fr_from_wide rc={rc}")
+    return bytes(out)
+
+
+class Transcript:
+    """Merlin v1.0 transcript on the host (sbn_transcript_*), with Merlin's method names; no device needed"""
+
+    def __init__(self, label=None, _handle=None):
+        if _handle is None:
+            _handle = C.c_void_p()
+            self._chk(lib().sbn_transcript_new(_ptr(label), C.c_size_t(len(label)), C.byref(_handle)), "sbn_transcript_new")
+        self.h = _handle
+
+    @staticmethod
+    def _chk(rc, what):
+        if rc:
+            raise SbnError(f"{what} rc={rc}")
+
+    def append_message(self, label, msg):
+        self._chk(lib().sbn_transcript_append_message(self.h, _ptr(label), C.c_size_t(len(label)), _ptr(msg), C.c_size_t(len(msg))), "sbn_transcript_append_message")
+
+    def append_scalar(self, label, scalar32):
+        self.append_message(label, scalar32)
+
+    def challenge_bytes(self, label, n):
+        out = (C.c_uint8 * max(n, 1))()
+        self._chk(lib().sbn_transcript_challenge_bytes(self.h, _ptr(label), C.c_size_t(len(label)), out, C.c_size_t(n)), "sbn_transcript_challenge_bytes")
+        return bytes(out[:n])
+
+    def challenge_scalar(self, label):
+        out = (C.c_uint8 * 32)()
+        self._chk(lib().sbn_transcript_challenge_scalar(self.h, _ptr(label), C.c_size_t(len(label)), out), "sbn_transcript_challenge_scalar")
+        return bytes(out)
+
+    def state(self):
+        out = (C.c_uint8 * 203)()
+        self._chk(lib().sbn_transcript_state(self.h, out), "sbn_transcript_state")
+        return bytes(out)
+
+    @classmethod
+    def from_state(cls, rec):
+        if len(rec) != 203:
+            raise ValueError("a transcript state record has 203 bytes")
+        h = C.c_void_p()
+        cls._chk(lib().sbn_transcript_from_state(_ptr(rec), C.byref(h)), "sbn_transcript_from_state")
+        return cls(_handle=h)
+
+    def clone(self):
+        h = C.c_void_p()
+        self._chk(lib().sbn_transcript_clone(self.h, C.byref(h)), "sbn_transcript_clone")
+        return Transcript(_handle=h)
+
+    def free(self):
+        if self.h:
+            lib().sbn_transcript_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class Sumcheck:
@@ -585,6 +660,16 @@ class Context:
         self._chk(lib().sbn_sumcheck_begin_eq(self.h, mk(A_par), mk(B_par), C.c_size_t(len(A_par)), _ptr(rand), C.c_size_t(len(rand) // 32),
                                               mk(A_seq), mk(B_seq), mk(C_seq), C.c_size_t(len(A_seq)), _ptr(coeffs), out, C.byref(st)), "sbn_sumcheck_begin_eq")
         return Sumcheck(self, st, len(A_par), len(A_seq)), bytes(out)
+
+    def sumcheck_prove(self, st, tr, claim):
+        """the whole sumcheck in one call (sbn_sumcheck_prove): -> (polys: rounds x [c0..c3], challenges: rounds x 32 B, finals); `tr` (Transcript) moves on"""
+        n = len(st)
+        rounds = n.bit_length() - 1
+        polys = (C.c_uint8 * (128 * max(rounds, 1)))(); rs = (C.c_uint8 * (32 * max(rounds, 1)))(); fin = (C.c_uint8 * (32 * st.ntab))()
+        self._chk(lib().sbn_sumcheck_prove(self.h, st.h, tr.h, _ptr(claim), polys, rs, fin), "sbn_sumcheck_prove")
+        pb, rb = bytes(polys), bytes(rs)
+        return ([[pb[128 * j + 32 * k:128 * j + 32 * k + 32] for k in range(4)] for j in range(rounds)], [rb[32 * j:32 * j + 32] for j in range(rounds)],
+                [bytes(fin[32 * t:32 * t + 32]) for t in range(st.ntab)])
 
     def eq_evals(self, r):
         ell = len(r) // 32; ht = C.c_void_p()

@@ -39,7 +39,7 @@ void sbn_ctx_destroy(sbn_ctx* c) {
   hipStreamSynchronize(c->stream);
   prof_drain(c);
   DevBuf* bufs[] = {&c->scal_canon, &c->hist, &c->offs, &c->sorted, &c->buckets, &c->red_a, &c->red_b, &c->wsum, &c->stage_scal, &c->stage_pts, &c->out_small,
-                    &c->sc_args, &c->sc_partial, &c->sc_out, &c->sc_r, &c->sc_tabs, &c->sc_tickets, &c->gen_tmp, &c->acc_ctr, &c->extra_list, &c->extra_out, &c->big_list, &c->digits, &c->blockhist, &c->perm, &c->merged, &c->zstage[0], &c->zstage[1], &c->out_rows, &c->comb_partial, &c->s2_cnt, &c->s2_part, &c->s2_idx, &c->s2_lo, &c->glv_scal, &c->kzg_ws, &c->r1cs_ws, &c->dense_ws};
+                    &c->sc_args, &c->sc_partial, &c->sc_out, &c->sc_r, &c->sc_tabs, &c->sc_tickets, &c->sc_prove, &c->gen_tmp, &c->acc_ctr, &c->extra_list, &c->extra_out, &c->big_list, &c->digits, &c->blockhist, &c->perm, &c->merged, &c->zstage[0], &c->zstage[1], &c->out_rows, &c->comb_partial, &c->s2_cnt, &c->s2_part, &c->s2_idx, &c->s2_lo, &c->glv_scal, &c->kzg_ws, &c->r1cs_ws, &c->dense_ws};
   for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
   for (auto& b : c->pool) hipFree(b.first);
   if (c->pin) hipHostFree(c->pin);

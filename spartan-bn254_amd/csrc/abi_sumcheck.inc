@@ -12,6 +12,7 @@
 //   PLAIN   (a zero coefficient among the "par" instances): nothing is scaled, the host combines with coeffs.
 // In every mode the "seq" instances' triples are weighted on the host (18 products per round at most).
 // Final claims (:302-318): A_i[0] = A'_i[0] / c_i — one host inversion per sumcheck (batched), the same field elements bit for bit.
+// sbn_sumcheck_prove (end of this file) queues all rounds of such a state at once, with the transcript step on the device between them.
 
 struct sbn_sumcheck {
   size_t n_par = 0, n_seq = 0, ntab = 0;
@@ -29,6 +30,7 @@ struct sbn_sumcheck {
   size_t eval_groups = 0;                   // groups [0, eval_groups): round-0 sums
   std::vector<size_t> grp_off, grp_cnt;     // combined round j (= binds so far): groups [grp_off[j], + grp_cnt[j])
   sbn_table* owned_c = nullptr;             // sbn_sumcheck_begin_eq: the eq table built for this sumcheck (poly_C_par), released with the state
+  uint8_t evals0[96] = {0};                 // round 0's combined sums as sbn_sumcheck_begin returned them (sbn_sumcheck_prove starts from them)
   std::vector<uint8_t> finals_host;         // the final claims as the last round delivered them (canonical, before the division by c_i)
   uint32_t* d_finals = nullptr;             // ntab x 32 B: where the LAST bind puts every table's single entry (sbn_sumcheck_finish reads it in one go)
 };
@@ -61,7 +63,8 @@ __global__ void __launch_bounds__(256) k_sc_scale(ScScalePack<SC_PACK_MAX> pack,
 // with u = c_i; once the first challenge is known this kernel (one block per group, one lane per instance) replaces u, v by c_i (1 - r), c_i r
 // in place — canonical Montgomery words, the same field elements the host used to compute and copy up (a 1.5 KB copy per sumcheck, 13 us of
 // blit kernel in the prove's trace).
-__global__ void __launch_bounds__(64) k_sc_first_uv(ScCombGroup* __restrict__ groups, ScScalar rmont) {
+template <class RS>
+__global__ void __launch_bounds__(64) k_sc_first_uv(ScCombGroup* __restrict__ groups, RS rmont) {
   ScCombGroup* g = groups + blockIdx.x;
   const uint32_t k = threadIdx.x;
   if (k >= g->n) return;
@@ -86,7 +89,8 @@ __global__ void __launch_bounds__(256) k_bind_oop_many(BindOopPack pack, size_t 
 constexpr int SC_FINAL_MAX = 80;
 static_assert(SC_FINAL_MAX >= 3 * SC_PACK_MAX + 1, "one lane per table of the largest sumcheck");
 struct ScFinalPack { const uint32_t* src[SC_FINAL_MAX]; };
-__global__ void __launch_bounds__(128) k_sc_bind_finals(ScFinalPack pk, uint32_t count, ScScalar rmont, uint32_t* __restrict__ fin, uint32_t* __restrict__ host_out, uint32_t* __restrict__ flag, uint32_t seq) {
+template <class RS>
+__global__ void __launch_bounds__(128) k_sc_bind_finals(ScFinalPack pk, uint32_t count, RS rmont, uint32_t* __restrict__ fin, uint32_t* __restrict__ host_out, uint32_t* __restrict__ flag, uint32_t seq) {
   const uint32_t t = threadIdx.x;
   const uint32_t* z = nullptr;
 #pragma unroll
@@ -112,7 +116,10 @@ __global__ void __launch_bounds__(128) k_sc_finals_gather(ScRead0Pack pk, uint32
 
 // ---- the per-instance fused round on raw pointers (what sc_bind_eval_common does for table handles) -----------------------------
 // inst[i]: src / dst / pre of A, B, C (dst null: another instance writes that table).  Slots 0 .. count-1 of the mailbox.
-static int sc_launch_inst_fused(sbn_ctx* c, ScFusedPack& pack, size_t count, size_t q, const ScScalar& rs, uint32_t seq) {
+// RS: the challenge as a kernel argument (ScScalar) or in device memory (ScScalarDev); mbox: where the sums and their flags go (the host mailbox, or its
+// device twin when a transcript step kernel reads them: sbn_sumcheck_prove)
+template <class RS>
+static int sc_launch_inst_fused(sbn_ctx* c, ScFusedPack& pack, size_t count, size_t q, const RS& rs, uint32_t* mbox, uint32_t seq) {
   int rc;
   const bool single = q <= SC_SINGLE_LAUNCH_MAX / 2;
   unsigned gx;
@@ -126,9 +133,9 @@ static int sc_launch_inst_fused(sbn_ctx* c, ScFusedPack& pack, size_t count, siz
   if (single) {
     if (q <= 128) {
       const unsigned bt = (unsigned)std::max<size_t>(64, (4 * q + 63) / 64 * 64);
-      LAUNCH(c, "k_sc_bind_eval_cubic", (k_sc_bind_eval_tiny<KIND_CUBIC>), dim3(1, (unsigned)count), bt, dargs, pack, q, rs, c->mbox, seq);
+      LAUNCH(c, "k_sc_bind_eval_cubic", (k_sc_bind_eval_tiny<KIND_CUBIC, RS>), dim3(1, (unsigned)count), bt, dargs, pack, q, rs, mbox, seq);
     } else
-      LAUNCH(c, "k_sc_bind_eval_cubic", (k_sc_bind_eval<KIND_CUBIC, 2>), dim3(gx, (unsigned)count), 256, dargs, pack, q, rs, (uint32_t*)c->sc_partial.p, (uint32_t*)c->sc_tickets.p, c->mbox, seq);
+      LAUNCH(c, "k_sc_bind_eval_cubic", (k_sc_bind_eval<KIND_CUBIC, 2, RS>), dim3(gx, (unsigned)count), 256, dargs, pack, q, rs, (uint32_t*)c->sc_partial.p, (uint32_t*)c->sc_tickets.p, mbox, seq);
   } else {
     // streaming: every table needs its writer in the launch or must arrive bound (the caller pre-binds shared tables)
     bool pf_ok = true;
@@ -137,8 +144,8 @@ static int sc_launch_inst_fused(sbn_ctx* c, ScFusedPack& pack, size_t count, siz
       for (int t = 0; t < 3; t++) { if (pack.a[i].pre[t]) mask |= 1u << t; else if (!pack.a[i].dst[t]) pf_ok = false; }
       if (!sc_pf_mask_supported(KIND_CUBIC, mask)) pf_ok = false;
     }
-    if (pf_ok) LAUNCH(c, "k_sc_bind_eval_cubic_stream", (k_sc_bind_eval_pf<KIND_CUBIC>), dim3(gx, (unsigned)count), 256, dargs, pack, q, rs, (uint32_t*)c->sc_partial.p, (uint32_t*)c->sc_tickets.p, c->mbox, seq);
-    else LAUNCH(c, "k_sc_bind_eval_cubic", (k_sc_bind_eval<KIND_CUBIC, 2>), dim3(gx, (unsigned)count), 256, dargs, pack, q, rs, (uint32_t*)c->sc_partial.p, (uint32_t*)c->sc_tickets.p, c->mbox, seq);
+    if (pf_ok) LAUNCH(c, "k_sc_bind_eval_cubic_stream", (k_sc_bind_eval_pf<KIND_CUBIC, RS>), dim3(gx, (unsigned)count), 256, dargs, pack, q, rs, (uint32_t*)c->sc_partial.p, (uint32_t*)c->sc_tickets.p, mbox, seq);
+    else LAUNCH(c, "k_sc_bind_eval_cubic", (k_sc_bind_eval<KIND_CUBIC, 2, RS>), dim3(gx, (unsigned)count), 256, dargs, pack, q, rs, (uint32_t*)c->sc_partial.p, (uint32_t*)c->sc_tickets.p, mbox, seq);
   }
   LAUNCHCHK(c);
   return SBN_OK;
@@ -343,9 +350,122 @@ static int sumcheck_begin_locked(sbn_ctx* c, const sbn_table* const* A_par, cons
   }
   if ((rc = sc_mbox_wait(c, inst_ids.size() + n_comb, seq))) return rc;
   sc_combine_host(st.get(), (const uint8_t*)c->mbox, inst_ids, n_comb, out_evals);
+  memcpy(st->evals0, out_evals, 96);
   slab_guard.armed = false;
   st->owned_c = own.t; own.t = nullptr;
   *out = st.release();
+  return SBN_OK;
+}
+// ---- one round's launches, shared by sbn_sumcheck_round (challenge in the kernel arguments, sums to the host mailbox) and
+// sbn_sumcheck_prove (challenge in device memory, sums to the mailbox's device twin): the same kernels, grids and order ----
+struct ScRoundPlan { std::vector<size_t> inst_ids; size_t n_comb = 0; bool comb = false; };
+// the last bind + final claims (two entries per table left): one launch; fin_out / flag: host mailbox or device memory
+template <class RS>
+static int sc_final_enqueue(sbn_ctx* c, sbn_sumcheck* st, const RS& rs, uint32_t* fin_out, uint32_t* flag, uint32_t fseq) {
+  ScFinalPack fp; memset(&fp, 0, sizeof fp);
+  for (size_t t = 0; t < st->ntab; t++) fp.src[t] = st->cur[t];
+  LAUNCH(c, "k_bind_top", k_sc_bind_finals, 1, 128, fp, (uint32_t)st->ntab, rs, st->d_finals, fin_out, flag, fseq);
+  LAUNCHCHK(c);
+  return SBN_OK;
+}
+static void sc_final_advance(sbn_sumcheck* st) {
+  for (size_t t = 0; t < st->ntab; t++) st->cur[t] = st->d_finals + 8 * t;
+  st->len /= 2; st->binds++;
+}
+// a bind round with >= 4 entries per table: binds to rs and leaves the next round's sums in mbox slots [0, inst_ids.size() + n_comb)
+template <class RS>
+static int sc_round_enqueue(sbn_ctx* c, sbn_sumcheck* st, const RS& rs, uint32_t* mbox, uint32_t seq, ScRoundPlan& plan) {
+  const size_t n_par = st->n_par, n_seq = st->n_seq, ninst = n_par + n_seq, len = st->len;
+  std::vector<uint32_t*>& dst = st->buf[st->binds & 1];
+  std::vector<size_t>& inst_ids = plan.inst_ids;
+  size_t& n_comb = plan.n_comb;
+  int rc;
+  const size_t q = len / 4;
+  const size_t oC = 2 * n_par, o = 2 * n_par + (n_par ? 1 : 0);
+  const bool comb = st->mode == 2 && q >= sc_comb_min_q();
+  if (st->mode == 2 && !comb && !st->scaled) return fail(c, SBN_EINVAL, "sumcheck: internal: unscaled tables below the combined kernels' range");
+  if (comb) {
+    // shared C: bound inside the round kernel (every group binds its entries, group 0 stores them), except by the scaling first bind: once ahead of it
+    if (!st->scaled) LAUNCH(c, "k_bind_oop", k_bind_oop, stream_grid(len / 2), 256, st->cur[oC], dst[oC], len / 2, rs);
+    const bool scale_now = !st->scaled;
+    if ((rc = ensure(c, c->sc_partial, SC_PARTIAL_BYTES))) return rc;
+    const size_t jr = (size_t)st->binds;
+    if (jr >= st->grp_cnt.size()) return fail(c, SBN_EINVAL, "sumcheck: internal: no group plan for bind %zu", jr);
+    n_comb = st->grp_cnt[jr];
+    const ScCombGroup* d_grp = st->d_groups + st->grp_off[jr];
+    if (scale_now) {
+      // the first bind scales A: its groups (uploaded when the sumcheck began, u = c_i) get u = c (1 - r), v = c r on the device
+      if (jr != 0) return fail(c, SBN_EINVAL, "sumcheck: internal: unscaled tables after the first bind");
+      LAUNCH(c, "k_sc_first_uv", k_sc_first_uv, (unsigned)n_comb, 64, (ScCombGroup*)d_grp, rs);
+    }
+    ScFusedPack seqpack; memset(&seqpack, 0, sizeof seqpack);
+    for (size_t j = 0; j < n_seq; j++) {
+      const size_t ids[3] = {o + j, o + n_seq + j, o + 2 * n_seq + j};
+      for (int t = 0; t < 3; t++) { seqpack.a[j].src[t] = st->cur[ids[t]]; seqpack.a[j].dst[t] = dst[ids[t]]; }
+      inst_ids.push_back(n_par + j);
+    }
+    // streaming rounds with both kinds of instance: ONE grid, the VALU-bound "seq" blocks interleaved with the memory-bound "par" blocks
+    const bool mixed = n_seq > 0 && q > SC_SINGLE_LAUNCH_MAX / 2;
+    if (n_seq && !mixed) { if ((rc = sc_launch_inst_fused(c, seqpack, n_seq, q, rs, mbox, seq))) return rc; }
+    // grid: 512 blocks for the "par" groups + 512 for the "seq" instances = two block rounds of the 512 resident blocks.  Every block
+    // ends in a ~7 us epilogue (three wave sums, write-through stores, the ticket), so the 3070 blocks of the first version cost ~40 us
+    // per launch whatever the table size (t = 40 us + bytes / 4.4 TB/s over the six streaming rounds); and EQUAL counts do best
+    // (tools/sc_blocks_sweep.sh: 512:512 3.77-3.95 ms per sumcheck, 1024:2048 3.99-4.02, 512:768 4.01, 512:256 4.26).  Both kinds end up
+    // evenly spread over the 8 XCDs and finish within 2 % of each other (per-block clocks: 930 / 912 us on the 2^21 tables);
+    // forcing one long + one short block per slot, or one kind per XCD, changes nothing (4.04 against 4.01 ms)
+    const size_t comb_blocks = c->sck.comb_blocks, seq_blocks = c->sck.seq_blocks;
+    size_t want = std::max<size_t>(1, comb_blocks / n_comb), cap = (q + 255) / 256;
+    if (c->sck.comb_grid) want = c->sck.comb_grid;
+    const unsigned gx = (unsigned)std::max<size_t>(1, std::min(std::min(want, cap), SC_PART_COMB_BLOCKS));
+    uint32_t* part2 = (uint32_t*)c->sc_partial.p + (size_t)SC_PACK_MAX * 1024 * 24;
+    if (mixed) {
+      const size_t capq = (q + 255) / 256;
+      const unsigned gx_seq = (unsigned)std::max<size_t>(1, std::min(std::min<size_t>(seq_blocks / n_seq, capq), SC_PART_INST_BLOCKS));
+      const unsigned total = (unsigned)(n_comb * gx + n_seq * gx_seq);
+      if (scale_now) LAUNCH(c, "k_sc_round_mixed_first", (k_sc_round_mixed<true, RS>), total, 256, d_grp, (uint32_t)n_comb, gx, seqpack, (uint32_t)n_seq, gx_seq, q, rs, (uint32_t*)c->sc_partial.p, part2, (uint32_t*)c->sc_tickets.p, mbox, seq);
+      else LAUNCH(c, "k_sc_round_mixed", (k_sc_round_mixed<false, RS>), total, 256, d_grp, (uint32_t)n_comb, gx, seqpack, (uint32_t)n_seq, gx_seq, q, rs, (uint32_t*)c->sc_partial.p, part2, (uint32_t*)c->sc_tickets.p, mbox, seq);
+    } else
+    if (scale_now) LAUNCH(c, "k_sc_comb_bind_eval_first", (k_sc_comb_bind_eval<true, RS>), dim3(gx, (unsigned)n_comb), 256, d_grp, q, rs, part2, (uint32_t*)c->sc_tickets.p, mbox, (uint32_t)n_seq, seq);
+    else LAUNCH(c, "k_sc_comb_bind_eval", (k_sc_comb_bind_eval<false, RS>), dim3(gx, (unsigned)n_comb), 256, d_grp, q, rs, part2, (uint32_t*)c->sc_tickets.p, mbox, (uint32_t)n_seq, seq);
+    LAUNCHCHK(c);
+  } else {
+    // per-instance kernels for everything; a shared C of a streaming round is bound ahead (every table needs a writer there)
+    const bool single = q <= SC_SINGLE_LAUNCH_MAX / 2;
+    const bool prebind = n_par >= 2 && !single;
+    if (prebind) LAUNCH(c, "k_bind_oop", k_bind_oop, stream_grid(len / 2), 256, st->cur[oC], dst[oC], len / 2, rs);
+    ScFusedPack pack; memset(&pack, 0, sizeof pack);
+    for (size_t i = 0; i < n_par; i++) {
+      pack.a[i].src[0] = st->cur[i]; pack.a[i].dst[0] = dst[i];
+      pack.a[i].src[1] = st->cur[n_par + i]; pack.a[i].dst[1] = dst[n_par + i];
+      if (prebind) { pack.a[i].src[2] = dst[oC]; pack.a[i].pre[2] = 1; }
+      else { pack.a[i].src[2] = st->cur[oC]; pack.a[i].dst[2] = i == 0 ? dst[oC] : nullptr; }
+      inst_ids.push_back(i);
+    }
+    for (size_t j = 0; j < n_seq; j++) {
+      const size_t ids[3] = {o + j, o + n_seq + j, o + 2 * n_seq + j};
+      for (int t = 0; t < 3; t++) { pack.a[n_par + j].src[t] = st->cur[ids[t]]; pack.a[n_par + j].dst[t] = dst[ids[t]]; }
+      inst_ids.push_back(n_par + j);
+    }
+    if ((rc = sc_launch_inst_fused(c, pack, ninst, q, rs, mbox, seq))) return rc;
+  }
+  plan.comb = comb;
+  return SBN_OK;
+}
+// the state moves on all at once: tables, length, and (a combined round has folded c_i into A_i) the scaled flag
+static void sc_round_advance(sbn_sumcheck* st, const ScRoundPlan& plan) {
+  std::vector<uint32_t*>& dst = st->buf[st->binds & 1];
+  for (size_t t = 0; t < st->ntab; t++) st->cur[t] = dst[t];
+  st->len /= 2; st->binds++;
+  if (plan.comb) st->scaled = true;
+}
+// the final claims as the last round delivered them (k_sc_bind_finals), A_i[0] = A'_i[0] / c_i where the state scaled A
+static int sc_finals_deliver(sbn_ctx* c, const sbn_sumcheck* st, uint8_t* finals) {
+  memcpy(finals, st->finals_host.data(), st->ntab * 32);          // nothing to launch or wait for here
+  if (st->scaled) {
+    using namespace sbn_host::fr;
+    if (st->co_inv_m.size() != st->n_par) return fail(c, SBN_EINVAL, "sumcheck finish: internal: scaled tables without the inverse coefficients");
+    for (size_t i = 0; i < st->n_par; i++) { const El a = mmul(st->co_inv_m[i], el_from(finals + 32 * i)); memcpy(finals + 32 * i, a.v, 32); }
+  }
   return SBN_OK;
 }
 extern "C" {
@@ -379,106 +499,30 @@ int sbn_sumcheck_round(sbn_ctx* c, sbn_sumcheck* st, const uint8_t r[32], uint8_
   if (st->len < 2) return fail(c, SBN_EINVAL, "sumcheck round: no variable left");
   if (!fr_canonical(r)) return fail(c, SBN_EINVAL, "challenge scalar is not canonical (>= r)");
   using namespace sbn_host::fr;
-  const size_t n_par = st->n_par, n_seq = st->n_seq, ninst = n_par + n_seq, len = st->len;
+  const size_t len = st->len;
   const El rc_ = el_from(r);
   const ScScalar rs = scs_from(to_dev_mont(rc_));
-  std::vector<uint32_t*>& dst = st->buf[st->binds & 1];
   int rc;
   memset(out_evals, 0, 96);
   ScRoundGuard round_guard{st};         // from here on an error return leaves the state dead: the arguments were fine, something below failed
   if (len < 4) {
     // last round: bind (out of place: the tables may still be the caller's) and deliver the final claims — one launch, one wait
     if ((rc = sc_tickets(c))) return rc;
-    ScFinalPack fp; memset(&fp, 0, sizeof fp);
-    for (size_t t = 0; t < st->ntab; t++) fp.src[t] = st->cur[t];
     const uint32_t fseq = ++c->mbox_seq;
     uint32_t* hfin = c->mbox + SC_MBOX_FINALS;
-    LAUNCH(c, "k_bind_top", k_sc_bind_finals, 1, 128, fp, (uint32_t)st->ntab, rs, st->d_finals, hfin, c->mbox + SC_MBOX_FLAGS + SC_PACK_MAX, fseq);
-    LAUNCHCHK(c);
+    if ((rc = sc_final_enqueue(c, st, rs, hfin, c->mbox + SC_MBOX_FLAGS + SC_PACK_MAX, fseq))) return rc;
     if ((rc = sc_flag_wait(c, c->mbox + SC_MBOX_FLAGS + SC_PACK_MAX, fseq))) return rc;
     st->finals_host.assign((const uint8_t*)hfin, (const uint8_t*)hfin + st->ntab * 32);
-    for (size_t t = 0; t < st->ntab; t++) st->cur[t] = st->d_finals + 8 * t;
-    st->len = len / 2; st->binds++;
+    sc_final_advance(st);
     round_guard.ok = true;
     return SBN_OK;
   }
-  const size_t q = len / 4;
   const uint32_t seq = ++c->mbox_seq;
-  std::vector<size_t> inst_ids;
-  size_t n_comb = 0;
-  const size_t oC = 2 * n_par, o = 2 * n_par + (n_par ? 1 : 0);
-  const bool comb = st->mode == 2 && q >= sc_comb_min_q();
-  if (st->mode == 2 && !comb && !st->scaled) return fail(c, SBN_EINVAL, "sumcheck: internal: unscaled tables below the combined kernels' range");
-  if (comb) {
-    // shared C: bound inside the round kernel (every group binds its entries, group 0 stores them), except by the scaling first bind: once ahead of it
-    if (!st->scaled) LAUNCH(c, "k_bind_oop", k_bind_oop, stream_grid(len / 2), 256, st->cur[oC], dst[oC], len / 2, rs);
-    const bool scale_now = !st->scaled;
-    if ((rc = ensure(c, c->sc_partial, SC_PARTIAL_BYTES))) return rc;
-    const size_t jr = (size_t)st->binds;
-    if (jr >= st->grp_cnt.size()) return fail(c, SBN_EINVAL, "sumcheck: internal: no group plan for bind %zu", jr);
-    n_comb = st->grp_cnt[jr];
-    const ScCombGroup* d_grp = st->d_groups + st->grp_off[jr];
-    if (scale_now) {
-      // the first bind scales A: its groups (uploaded when the sumcheck began, u = c_i) get u = c (1 - r), v = c r on the device
-      if (jr != 0) return fail(c, SBN_EINVAL, "sumcheck: internal: unscaled tables after the first bind");
-      LAUNCH(c, "k_sc_first_uv", k_sc_first_uv, (unsigned)n_comb, 64, (ScCombGroup*)d_grp, rs);
-    }
-    ScFusedPack seqpack; memset(&seqpack, 0, sizeof seqpack);
-    for (size_t j = 0; j < n_seq; j++) {
-      const size_t ids[3] = {o + j, o + n_seq + j, o + 2 * n_seq + j};
-      for (int t = 0; t < 3; t++) { seqpack.a[j].src[t] = st->cur[ids[t]]; seqpack.a[j].dst[t] = dst[ids[t]]; }
-      inst_ids.push_back(n_par + j);
-    }
-    // streaming rounds with both kinds of instance: ONE grid, the VALU-bound "seq" blocks interleaved with the memory-bound "par" blocks
-    const bool mixed = n_seq > 0 && q > SC_SINGLE_LAUNCH_MAX / 2;
-    if (n_seq && !mixed) { if ((rc = sc_launch_inst_fused(c, seqpack, n_seq, q, rs, seq))) return rc; }
-    // grid: 512 blocks for the "par" groups + 512 for the "seq" instances = two block rounds of the 512 resident blocks.  Every block
-    // ends in a ~7 us epilogue (three wave sums, write-through stores, the ticket), so the 3070 blocks of the first version cost ~40 us
-    // per launch whatever the table size (t = 40 us + bytes / 4.4 TB/s over the six streaming rounds); and EQUAL counts do best
-    // (tools/sc_blocks_sweep.sh: 512:512 3.77-3.95 ms per sumcheck, 1024:2048 3.99-4.02, 512:768 4.01, 512:256 4.26).  Both kinds end up
-    // evenly spread over the 8 XCDs and finish within 2 % of each other (per-block clocks: 930 / 912 us on the 2^21 tables);
-    // forcing one long + one short block per slot, or one kind per XCD, changes nothing (4.04 against 4.01 ms)
-    const size_t comb_blocks = c->sck.comb_blocks, seq_blocks = c->sck.seq_blocks;
-    size_t want = std::max<size_t>(1, comb_blocks / n_comb), cap = (q + 255) / 256;
-    if (c->sck.comb_grid) want = c->sck.comb_grid;
-    const unsigned gx = (unsigned)std::max<size_t>(1, std::min(std::min(want, cap), SC_PART_COMB_BLOCKS));
-    uint32_t* part2 = (uint32_t*)c->sc_partial.p + (size_t)SC_PACK_MAX * 1024 * 24;
-    if (mixed) {
-      const size_t capq = (q + 255) / 256;
-      const unsigned gx_seq = (unsigned)std::max<size_t>(1, std::min(std::min<size_t>(seq_blocks / n_seq, capq), SC_PART_INST_BLOCKS));
-      const unsigned total = (unsigned)(n_comb * gx + n_seq * gx_seq);
-      if (scale_now) LAUNCH(c, "k_sc_round_mixed_first", k_sc_round_mixed<true>, total, 256, d_grp, (uint32_t)n_comb, gx, seqpack, (uint32_t)n_seq, gx_seq, q, rs, (uint32_t*)c->sc_partial.p, part2, (uint32_t*)c->sc_tickets.p, c->mbox, seq);
-      else LAUNCH(c, "k_sc_round_mixed", k_sc_round_mixed<false>, total, 256, d_grp, (uint32_t)n_comb, gx, seqpack, (uint32_t)n_seq, gx_seq, q, rs, (uint32_t*)c->sc_partial.p, part2, (uint32_t*)c->sc_tickets.p, c->mbox, seq);
-    } else
-    if (scale_now) LAUNCH(c, "k_sc_comb_bind_eval_first", k_sc_comb_bind_eval<true>, dim3(gx, (unsigned)n_comb), 256, d_grp, q, rs, part2, (uint32_t*)c->sc_tickets.p, c->mbox, (uint32_t)n_seq, seq);
-    else LAUNCH(c, "k_sc_comb_bind_eval", k_sc_comb_bind_eval<false>, dim3(gx, (unsigned)n_comb), 256, d_grp, q, rs, part2, (uint32_t*)c->sc_tickets.p, c->mbox, (uint32_t)n_seq, seq);
-    LAUNCHCHK(c);
-  } else {
-    // per-instance kernels for everything; a shared C of a streaming round is bound ahead (every table needs a writer there)
-    const bool single = q <= SC_SINGLE_LAUNCH_MAX / 2;
-    const bool prebind = n_par >= 2 && !single;
-    if (prebind) LAUNCH(c, "k_bind_oop", k_bind_oop, stream_grid(len / 2), 256, st->cur[oC], dst[oC], len / 2, rs);
-    ScFusedPack pack; memset(&pack, 0, sizeof pack);
-    for (size_t i = 0; i < n_par; i++) {
-      pack.a[i].src[0] = st->cur[i]; pack.a[i].dst[0] = dst[i];
-      pack.a[i].src[1] = st->cur[n_par + i]; pack.a[i].dst[1] = dst[n_par + i];
-      if (prebind) { pack.a[i].src[2] = dst[oC]; pack.a[i].pre[2] = 1; }
-      else { pack.a[i].src[2] = st->cur[oC]; pack.a[i].dst[2] = i == 0 ? dst[oC] : nullptr; }
-      inst_ids.push_back(i);
-    }
-    for (size_t j = 0; j < n_seq; j++) {
-      const size_t ids[3] = {o + j, o + n_seq + j, o + 2 * n_seq + j};
-      for (int t = 0; t < 3; t++) { pack.a[n_par + j].src[t] = st->cur[ids[t]]; pack.a[n_par + j].dst[t] = dst[ids[t]]; }
-      inst_ids.push_back(n_par + j);
-    }
-    if ((rc = sc_launch_inst_fused(c, pack, ninst, q, rs, seq))) return rc;
-  }
-  if ((rc = sc_mbox_wait(c, inst_ids.size() + n_comb, seq))) return rc;
-  sc_combine_host(st, (const uint8_t*)c->mbox, inst_ids, n_comb, out_evals);
-  // the state moves on only now, all at once: tables, length, and (a combined round has folded c_i into A_i) the scaled flag
-  for (size_t t = 0; t < st->ntab; t++) st->cur[t] = dst[t];
-  st->len = len / 2; st->binds++;
-  if (comb) st->scaled = true;
+  ScRoundPlan plan;
+  if ((rc = sc_round_enqueue(c, st, rs, c->mbox, seq, plan))) return rc;
+  if ((rc = sc_mbox_wait(c, plan.inst_ids.size() + plan.n_comb, seq))) return rc;
+  sc_combine_host(st, (const uint8_t*)c->mbox, plan.inst_ids, plan.n_comb, out_evals);
+  sc_round_advance(st, plan);
   round_guard.ok = true;
   return SBN_OK;
 }
@@ -488,14 +532,7 @@ int sbn_sumcheck_finish(sbn_ctx* c, sbn_sumcheck* st, uint8_t* finals) {
   std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
   if (st->len != 1) return fail(c, SBN_EINVAL, "sumcheck finish: %zu entries left (bind every variable first)", st->len);
   if (st->finals_host.size() != st->ntab * 32) return fail(c, SBN_EINVAL, "sumcheck finish: internal: the last round left no final claims");
-  memcpy(finals, st->finals_host.data(), st->ntab * 32);          // delivered by the last round's launch (k_sc_bind_finals): nothing to launch or wait for here
-  if (st->scaled) {
-    // A_i[0] = A'_i[0] / c_i
-    using namespace sbn_host::fr;
-    if (st->co_inv_m.size() != st->n_par) return fail(c, SBN_EINVAL, "sumcheck finish: internal: scaled tables without the inverse coefficients");
-    for (size_t i = 0; i < st->n_par; i++) { const El a = mmul(st->co_inv_m[i], el_from(finals + 32 * i)); memcpy(finals + 32 * i, a.v, 32); }
-  }
-  return SBN_OK;
+  return sc_finals_deliver(c, st, finals);
 }
 
 int sbn_table_read0_many(sbn_ctx* c, const sbn_table* const* ts, size_t count, uint8_t* out) {
@@ -514,6 +551,109 @@ int sbn_table_read0_many(sbn_ctx* c, const sbn_table* const* ts, size_t count, u
     if ((rc = sc_flag_wait(c, c->mbox + SC_MBOX_FLAGS + SC_PACK_MAX, seq))) return rc;
     memcpy(out + 32 * o, hfin, m * 32);
   }
+  return SBN_OK;
+}
+
+}  // extern "C"
+
+// ---- the whole sumcheck in one call: every round's kernels and the transcript step between them queued at once ----------------
+// which mailbox slots bind round `binds` of a state fills (what sc_round_enqueue will do, known ahead: it depends on lengths only)
+static void sc_round_slots(const sbn_ctx* c, const sbn_sumcheck* st, size_t len, size_t binds, std::vector<size_t>& inst_ids, size_t& n_comb, bool& comb) {
+  inst_ids.clear(); n_comb = 0;
+  comb = st->mode == 2 && len / 4 >= sc_comb_min_q();
+  if (comb) { for (size_t j = 0; j < st->n_seq; j++) inst_ids.push_back(st->n_par + j); n_comb = binds < st->grp_cnt.size() ? st->grp_cnt[binds] : 0; }
+  else for (size_t i = 0; i < st->n_par + st->n_seq; i++) inst_ids.push_back(i);
+}
+extern "C" {
+
+int sbn_sumcheck_prove(sbn_ctx* c, sbn_sumcheck* st, sbn_transcript* tr, const uint8_t claim[32], uint8_t* out_polys, uint8_t* out_r, uint8_t* finals) {
+  if (!c || !st || !tr || !claim || !out_polys || !out_r || !finals) return SBN_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+  if (st->len < 2 || st->binds != 0 || st->len != st->len0) return fail(c, SBN_EINVAL, "sumcheck prove: the state has been advanced already (or is dead); it takes a state fresh from sbn_sumcheck_begin");
+  if (!fr_canonical(claim)) return fail(c, SBN_EINVAL, "sumcheck prove: the claim is not canonical (>= r)");
+  using namespace sbn_host::fr;
+  size_t rounds = 0; while (((size_t)1 << rounds) < st->len) rounds++;
+  int rc;
+  if ((rc = sc_tickets(c))) return rc;
+  // the transcript's plan: the first round starts at the caller's phase, every later one behind a PRF (pos 64)
+  std::vector<uint8_t> masks_first, masks_next; uint8_t end[3], end2[3];
+  transcript_plan_round(tr->t.s.pos, tr->t.s.pos_begin, tr->t.s.cur_flags, masks_first, end);
+  transcript_plan_round(end[0], end[1], end[2], masks_next, end2);
+  const size_t nblk_first = masks_first.size() / 200, nblk_next = masks_next.size() / 200;
+  if (nblk_first < 1 || nblk_first > 3 || nblk_next != 2 || memcmp(end, end2, 3)) return fail(c, SBN_EINVAL, "sumcheck prove: internal: unexpected transcript plan (%zu, %zu blocks)", nblk_first, nblk_next);
+  // device layout: [claim, round-0 sums | masks | weights per step] uploaded, [sponge state] both ways, [polys | r | finals | flag] downloaded, then r_j and the mailbox's twin
+  const size_t o_claim = 0, o_sums0 = 64, o_masks = 256, o_w = o_masks + 1280, o_strobe = o_w + rounds * SC_PACK_MAX * 32, o_polys = o_strobe + 256,
+               o_r = o_polys + rounds * 128, o_fin = o_r + rounds * 32, o_flag = o_fin + (size_t)SC_FINAL_MAX * 32, o_rm = o_flag + 256, o_mbox = o_rm + 256, total = o_mbox + (size_t)SC_MBOX_WORDS * 4;
+  if ((rc = ensure(c, c->sc_prove, total))) return rc;
+  if ((rc = ensure_pin(c, 4096 + total))) return rc;
+  uint8_t* d = (uint8_t*)c->sc_prove.p; uint8_t* h = (uint8_t*)c->pin + 4096;
+  memset(h, 0, o_polys);
+  {                                       // e travels as fp.cuh's nine 29-bit limbs (the step keeps it lazy between rounds)
+    const El cm = to_dev_mont(el_from(claim));
+    uint32_t limbs[9];
+    for (int k = 0; k < 9; k++) { const int bit = 29 * k, i = bit >> 6, sh = bit & 63; uint64_t x = cm.v[i] >> sh; if (sh > 35 && i + 1 < 4) x |= cm.v[i + 1] << (64 - sh); limbs[k] = (uint32_t)x & 0x1fffffffu; }
+    memcpy(h + o_claim, limbs, 36);
+  }
+  memcpy(h + o_sums0, st->evals0, 96);
+  memcpy(h + o_masks, masks_first.data(), masks_first.size());
+  memcpy(h + o_masks + 600, masks_next.data(), masks_next.size());
+  memcpy(h + o_strobe, tr->t.s.st, 200);
+  // weights of step j's slots: c_i R^2 where the host would weight the slot, R^2 where it would only add (the sums arrive as plain integers)
+  const El w_one = to_dev_mont(to_dev_mont(from_u64(1)));
+  std::vector<uint32_t> nslots(rounds, 1);
+  memcpy(h + o_w, w_one.v, 32);
+  {
+    size_t len = st->len, binds = 0; bool scaled = st->scaled;
+    std::vector<size_t> ids; size_t n_comb; bool comb;
+    for (size_t j = 1; j < rounds; j++, len /= 2, binds++) {
+      sc_round_slots(c, st, len, binds, ids, n_comb, comb);
+      uint8_t* w = h + o_w + j * SC_PACK_MAX * 32;
+      if (ids.size() + n_comb > (size_t)SC_PACK_MAX) return fail(c, SBN_EINVAL, "sumcheck prove: internal: %zu result slots", ids.size() + n_comb);
+      for (size_t s = 0; s < ids.size(); s++) {
+        const bool weighted = !(ids[s] < st->n_par && scaled);
+        const El x = weighted ? to_dev_mont(to_dev_mont(st->co[ids[s]])) : w_one;
+        memcpy(w + 32 * s, x.v, 32);
+      }
+      for (size_t k = 0; k < n_comb; k++) memcpy(w + 32 * (ids.size() + k), w_one.v, 32);
+      nslots[j] = (uint32_t)(ids.size() + n_comb);
+      if (comb) scaled = true;
+    }
+  }
+  HIPCHK(c, hipMemcpyAsync(d, h, o_polys, hipMemcpyHostToDevice, c->stream));
+  ScRoundGuard round_guard{st};         // from the first launch on a failure leaves tables half bound: the state is dead, the transcript untouched
+  const ScScalarDev rs{(const uint32_t*)(d + o_rm)};
+  uint32_t* dmbox = (uint32_t*)(d + o_mbox);
+  for (size_t j = 0; j < rounds; j++) {
+    TrStepArgs a;
+    a.sums = j == 0 ? (const uint32_t*)(d + o_sums0) : dmbox;
+    a.weights = (const uint32_t*)(d + o_w + j * SC_PACK_MAX * 32); a.nslots = nslots[j];
+    a.masks = d + o_masks + (j == 0 ? 0 : 600); a.nblk = (uint32_t)(j == 0 ? nblk_first : nblk_next); a.pos0 = j == 0 ? tr->t.s.pos : end[0];
+    a.strobe = d + o_strobe; a.claim = (uint32_t*)(d + o_claim); a.r_mont = (uint32_t*)(d + o_rm);
+    a.out_poly = (uint32_t*)(d + o_polys + j * 128); a.out_r = (uint32_t*)(d + o_r + j * 32);
+    LAUNCH(c, "k_tr_sumcheck_step", k_tr_sumcheck_step, 1, 64, a);
+    if (st->len >= 4) {
+      const uint32_t seq = ++c->mbox_seq;
+      ScRoundPlan plan;
+      if ((rc = sc_round_enqueue(c, st, rs, dmbox, seq, plan))) return rc;
+      if (j + 1 < rounds && plan.inst_ids.size() + plan.n_comb != nslots[j + 1]) return fail(c, SBN_EINVAL, "sumcheck prove: internal: round %zu filled %zu slots, %u were planned", j, plan.inst_ids.size() + plan.n_comb, nslots[j + 1]);
+      sc_round_advance(st, plan);
+    } else {
+      const uint32_t fseq = ++c->mbox_seq;
+      if ((rc = sc_final_enqueue(c, st, rs, (uint32_t*)(d + o_fin), (uint32_t*)(d + o_flag), fseq))) return rc;
+      sc_final_advance(st);
+    }
+  }
+  LAUNCHCHK(c);
+  // one copy back, one wait
+  HIPCHK(c, hipMemcpyAsync(h + o_strobe, d + o_strobe, o_flag - o_strobe, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->prof) prof_drain(c);
+  st->finals_host.assign(h + o_fin, h + o_fin + st->ntab * 32);
+  if ((rc = sc_finals_deliver(c, st, finals))) return rc;
+  memcpy(out_polys, h + o_polys, rounds * 128);
+  memcpy(out_r, h + o_r, rounds * 32);
+  memcpy(tr->t.s.st, h + o_strobe, 200); tr->t.s.pos = end[0]; tr->t.s.pos_begin = end[1]; tr->t.s.cur_flags = end[2];
+  round_guard.ok = true;
   return SBN_OK;
 }
 

@@ -1,0 +1,90 @@
+// abi_transcript.inc — C ABI: a Merlin v1.0 transcript (merlin::Transcript as src/transcript.rs uses it) on the host, and the
+// plan of a sumcheck round's transcript work that the device step executes (transcript_kernels.cuh).  No context, no device.
+
+struct sbn_transcript { sbn_host::MerlinTranscript t; };
+
+// 64 little-endian bytes mod r (Fr::from_le_bytes_mod_order, transcript.rs:56-67): lo + hi * 2^256, canonical
+static void transcript_wide_reduce(const uint8_t b[64], uint8_t out[32]) {
+  using namespace sbn_host::fr;
+  El lo, hi; memcpy(lo.v, b, 32); memcpy(hi.v, b + 32, 32);
+  const El zero = {{0, 0, 0, 0}};
+  auto fold = [&](El x) { while (geq(x.v)) { uint64_t br = 0; for (int i = 0; i < 4; i++) { sbn_host::u128 d = (sbn_host::u128)x.v[i] - P[i] - br; x.v[i] = (uint64_t)d; br = (uint64_t)(d >> 127); } } return x; };   // < 2^256 < 6 r
+  El r2; memcpy(r2.v, R2, 32);
+  const El res = add(add(fold(lo), zero), mmul(fold(hi), r2));                  // hi * 2^512 / 2^256
+  memcpy(out, res.v, 32);
+}
+
+// One sumcheck round's seven transcript operations (unipoly.rs:117-122 + challenge_scalar("challenge_nextround")) from the phase
+// (pos, pos_begin): the XOR mask of every block the round completes (200 bytes each; labels, lengths, operation headers, padding),
+// coefficient bytes left zero.  The round ends behind the PRF's 64 bytes: pos = 64, pos_begin = 0, cur_flags = I|A|C.
+static void transcript_plan_round(uint8_t pos, uint8_t pos_begin, uint8_t cur_flags, std::vector<uint8_t>& masks, uint8_t end[3]) {
+  sbn_host::MerlinTranscriptT<sbn_host::StrobePlan> p;
+  memset(p.s.st, 0, sizeof p.s.st);
+  p.s.pos = pos; p.s.pos_begin = pos_begin; p.s.cur_flags = cur_flags;
+  masks.clear(); p.s.perm.blocks = &masks;
+  const uint8_t zero[32] = {0};
+  uint8_t out[64];
+  p.append_message((const uint8_t*)"poly", 4, (const uint8_t*)"UniPoly_begin", 13);
+  for (int k = 0; k < 4; k++) p.append_message((const uint8_t*)"coeff", 5, zero, 32);
+  p.append_message((const uint8_t*)"poly", 4, (const uint8_t*)"UniPoly_end", 11);
+  p.challenge_bytes((const uint8_t*)"challenge_nextround", 19, out, 64);
+  end[0] = p.s.pos; end[1] = p.s.pos_begin; end[2] = p.s.cur_flags;
+}
+
+extern "C" {
+
+int sbn_transcript_new(const uint8_t* label, size_t label_len, sbn_transcript** out) {
+  if (!out || (!label && label_len) || label_len > 0xffffffffu) return SBN_EINVAL;
+  sbn_transcript* t = new (std::nothrow) sbn_transcript();
+  if (!t) return SBN_ENOMEM;
+  t->t.init(label, label_len);
+  *out = t;
+  return SBN_OK;
+}
+int sbn_transcript_clone(const sbn_transcript* t, sbn_transcript** out) {
+  if (!t || !out) return SBN_EINVAL;
+  sbn_transcript* n = new (std::nothrow) sbn_transcript(*t);
+  if (!n) return SBN_ENOMEM;
+  *out = n;
+  return SBN_OK;
+}
+void sbn_transcript_free(sbn_transcript* t) { delete t; }
+int sbn_transcript_append_message(sbn_transcript* t, const uint8_t* label, size_t label_len, const uint8_t* msg, size_t msg_len) {
+  if (!t || (!label && label_len) || (!msg && msg_len) || msg_len > 0xffffffffu) return SBN_EINVAL;
+  t->t.append_message(label, label_len, msg, msg_len);
+  return SBN_OK;
+}
+int sbn_transcript_challenge_bytes(sbn_transcript* t, const uint8_t* label, size_t label_len, uint8_t* out, size_t out_len) {
+  if (!t || (!label && label_len) || (!out && out_len) || out_len > 0xffffffffu) return SBN_EINVAL;
+  t->t.challenge_bytes(label, label_len, out, out_len);
+  return SBN_OK;
+}
+int sbn_transcript_challenge_scalar(sbn_transcript* t, const uint8_t* label, size_t label_len, uint8_t out[32]) {
+  if (!t || (!label && label_len) || !out) return SBN_EINVAL;
+  uint8_t b[64];
+  t->t.challenge_bytes(label, label_len, b, 64);
+  transcript_wide_reduce(b, out);
+  return SBN_OK;
+}
+int sbn_fr_from_wide(const uint8_t in[64], uint8_t out[32]) {
+  if (!in || !out) return SBN_EINVAL;
+  transcript_wide_reduce(in, out);
+  return SBN_OK;
+}
+int sbn_transcript_state(const sbn_transcript* t, uint8_t out[203]) {
+  if (!t || !out) return SBN_EINVAL;
+  memcpy(out, t->t.s.st, 200); out[200] = t->t.s.pos; out[201] = t->t.s.pos_begin; out[202] = t->t.s.cur_flags;
+  return SBN_OK;
+}
+int sbn_transcript_from_state(const uint8_t in[203], sbn_transcript** out) {
+  if (!in || !out) return SBN_EINVAL;
+  // what a STROBE-128 state can hold: pos inside the rate, pos_begin at most one past it, flags within the six defined bits
+  if (in[200] >= sbn_host::Strobe128::RATE || in[201] > sbn_host::Strobe128::RATE || (in[202] & 0xc0)) return SBN_EINVAL;
+  sbn_transcript* t = new (std::nothrow) sbn_transcript();
+  if (!t) return SBN_ENOMEM;
+  memcpy(t->t.s.st, in, 200); t->t.s.pos = in[200]; t->t.s.pos_begin = in[201]; t->t.s.cur_flags = in[202];
+  *out = t;
+  return SBN_OK;
+}
+
+}  // extern "C"

@@ -20,7 +20,9 @@
 #include "kzg_kernels.cuh"
 #include "r1cs_kernels.cuh"
 #include "dense_kernels.cuh"
+#include "transcript_kernels.cuh"
 #include "host_keccak.hpp"
+#include "host_strobe.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -45,6 +47,7 @@ using namespace sbn;
 
 #include "abi_msm.inc"
 #include "abi_tables.inc"
+#include "abi_transcript.inc"
 #include "abi_sumcheck.inc"
 #include "abi_bullet.inc"
 #include "abi_group.inc"

@@ -152,8 +152,8 @@ __device__ __forceinline__ void sc_comb_bind_eval_body(const ScCombGroup* __rest
   sc_block_sums_store_at(sc_lds_acc_get(acc, 0), sc_lds_acc_get(acc, 1), sc_lds_acc_get(acc, 2), partial, slot, bidx, nblk);
   sc_last_block_fold_at(partial, tickets, out, 3, seq, slot, nblk);
 }
-template <bool SCALE>
-__global__ void __launch_bounds__(256, 2) k_sc_comb_bind_eval(const ScCombGroup* __restrict__ groups, size_t q, ScScalar rmont, uint32_t* __restrict__ partial, uint32_t* __restrict__ tickets,
+template <bool SCALE, class RS = ScScalar>
+__global__ void __launch_bounds__(256, 2) k_sc_comb_bind_eval(const ScCombGroup* __restrict__ groups, size_t q, RS rmont, uint32_t* __restrict__ partial, uint32_t* __restrict__ tickets,
                                                               uint32_t* __restrict__ out, uint32_t slot0, uint32_t seq) {
   sc_comb_bind_eval_body<SCALE>(groups + blockIdx.y, q, fr_from_words(rmont), partial, tickets, out, slot0 + blockIdx.y, seq, blockIdx.x, gridDim.x);
 }
@@ -164,9 +164,9 @@ __global__ void __launch_bounds__(256, 2) k_sc_comb_bind_eval(const ScCombGroup*
 // block interleaved so that a CU holds one of each (both are 2-blocks-per-CU kernels), the VALU-bound blocks run in the memory-bound
 // blocks' shadow.  Block b of the 1-D grid is a "seq" block when floor((b + 1) Ts / T) > floor(b Ts / T) (Ts of the T blocks, evenly
 // spread); its index among its kind is dealt round-robin over the instances / groups.  Slots: seq instance j -> j, group g -> n_seq + g.
-template <bool SCALE>
+template <bool SCALE, class RS = ScScalar>
 __global__ void __launch_bounds__(256, 2) k_sc_round_mixed(const ScCombGroup* __restrict__ groups, uint32_t n_groups, uint32_t gx_comb, ScFusedPack seqpack, uint32_t n_seq, uint32_t gx_seq, size_t q,
-                                                           ScScalar rmont, uint32_t* __restrict__ partial_seq, uint32_t* __restrict__ partial_comb, uint32_t* __restrict__ tickets, uint32_t* __restrict__ out, uint32_t seq) {
+                                                           RS rmont, uint32_t* __restrict__ partial_seq, uint32_t* __restrict__ partial_comb, uint32_t* __restrict__ tickets, uint32_t* __restrict__ out, uint32_t seq) {
   const unsigned long long Ts = (unsigned long long)n_seq * gx_seq, T = Ts + (unsigned long long)n_groups * gx_comb, b = blockIdx.x;
   const unsigned long long s0 = b * Ts / T, s1 = (b + 1) * Ts / T;
   if (s1 > s0) {

@@ -52,6 +52,10 @@ __device__ __forceinline__ void fr_acc32(Fr& acc, const Fr& x, uint32_t& cnt) {
 constexpr int SC_PACK_MAX = 24;            // instances whose pointers fit in the kernel-argument block
 struct ScScalar { uint32_t v[8]; };        // a scalar passed by value: 8 x 32-bit words (memory format)
 __device__ __forceinline__ Fr fr_from_words(const ScScalar& s) { return fe_unpack<FrP>(s.v); }
+// the same scalar read from device memory (8 words, memory format): a challenge that an earlier launch of the stream wrote
+// (sbn_sumcheck_prove: the transcript step kernel).  The round kernels take either source as their last template argument.
+struct ScScalarDev { const uint32_t* p; };
+__device__ __forceinline__ Fr fr_from_words(const ScScalarDev& s) { return fe_load<FrP>(s.p); }
 
 __device__ __forceinline__ Fr fr_load_coherent(const uint32_t* p) {   // written by other blocks of this launch: bypass the CU's L1
   uint32_t w[8];
@@ -280,8 +284,8 @@ __device__ __forceinline__ void sc_minus(ScProd& P, const ScPair& t) {       // 
 }
 
 // WPS = waves per SIMD the register allocation is held to
-template <int KIND, int WPS>
-__global__ void __launch_bounds__(256, WPS) k_sc_bind_eval(const ScFusedArgs* __restrict__ args, ScFusedPack pack, size_t q /* old_len / 4 */, ScScalar rmont /* Montgomery form */, uint32_t* __restrict__ partial,
+template <int KIND, int WPS, class RS = ScScalar>
+__global__ void __launch_bounds__(256, WPS) k_sc_bind_eval(const ScFusedArgs* __restrict__ args, ScFusedPack pack, size_t q /* old_len / 4 */, RS rmont /* Montgomery form */, uint32_t* __restrict__ partial,
                                                       uint32_t* __restrict__ tickets, uint32_t* __restrict__ out, uint32_t seq) {
   ScFusedArgs a;
   if (args) a = args[blockIdx.y];
@@ -326,8 +330,8 @@ __global__ void __launch_bounds__(256, WPS) k_sc_bind_eval(const ScFusedArgs* __
 // all four lanes run the whole instruction stream, 2.4x the work per index of the lane-per-index kernel (measured: slower from
 // 512 indices on, and with several blocks per instance the ticketed fold costs 7 us: 16.8 us at 128 indices against 9.6 at 64).
 // Slot s = 2 * t + h: table t in the kind's order (cubic 0,1,2 - r1cs 1,2,3,0 - quad 0,1), half h (0: lo = Z'[i], 1: hi = Z'[i + q]).
-template <int KIND>
-__global__ void __launch_bounds__(512) k_sc_bind_eval_tiny(const ScFusedArgs* __restrict__ args, ScFusedPack pack, size_t q, ScScalar rmont, uint32_t* __restrict__ mbox, uint32_t seq) {
+template <int KIND, class RS = ScScalar>
+__global__ void __launch_bounds__(512) k_sc_bind_eval_tiny(const ScFusedArgs* __restrict__ args, ScFusedPack pack, size_t q, RS rmont, uint32_t* __restrict__ mbox, uint32_t seq) {
   constexpr int NT = KIND == KIND_QUAD ? 2 : KIND == KIND_CUBIC ? 3 : 4;
   ScFusedArgs a;
   if (args) a = args[blockIdx.y];
@@ -473,8 +477,8 @@ __device__ __forceinline__ void sc_pf_body(const ScFusedArgs& a, size_t q, const
 }
 // host side: the masks this kernel is built for (anything else takes the plain kernel)
 __host__ __device__ inline bool sc_pf_mask_supported(int kind, unsigned mask) { return mask == 0 || (kind == KIND_CUBIC && mask == 4u); }
-template <int KIND>
-__global__ void __launch_bounds__(256, 2) k_sc_bind_eval_pf(const ScFusedArgs* __restrict__ args, ScFusedPack pack, size_t q /* old_len / 4 */, ScScalar rmont /* Montgomery form */, uint32_t* __restrict__ partial,
+template <int KIND, class RS = ScScalar>
+__global__ void __launch_bounds__(256, 2) k_sc_bind_eval_pf(const ScFusedArgs* __restrict__ args, ScFusedPack pack, size_t q /* old_len / 4 */, RS rmont /* Montgomery form */, uint32_t* __restrict__ partial,
                                                             uint32_t* __restrict__ tickets /* null: the caller runs k_sc_finish */, uint32_t* __restrict__ out, uint32_t seq) {
   ScFusedArgs a;
   if (args) a = args[blockIdx.y];
@@ -492,7 +496,8 @@ __global__ void __launch_bounds__(256, 2) k_sc_bind_eval_pf(const ScFusedArgs* _
 
 // out-of-place bind of the top variable of ONE table: dst[i] = Z[i] + r (Z[i + half] - Z[i]), i < half.  Runs ahead of a fused
 // round for a table that several instances of the round share (see ScFusedArgs::pre).
-__global__ void __launch_bounds__(256) k_bind_oop(const uint32_t* __restrict__ Z, uint32_t* __restrict__ dst, size_t half, ScScalar rmont) {
+template <class RS>
+__global__ void __launch_bounds__(256) k_bind_oop(const uint32_t* __restrict__ Z, uint32_t* __restrict__ dst, size_t half, RS rmont) {
   const Fr r = fr_from_words(rmont);
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < half; i += (size_t)gridDim.x * blockDim.x) {
     const Fr lo = fe_load<FrP>(Z + 8 * i), hi = fe_load<FrP>(Z + 8 * (i + half));

@@ -1,0 +1,195 @@
+// transcript_kernels.cuh — the Merlin / STROBE-128 transcript step of a sumcheck round on the device (sbn_sumcheck_prove).
+//
+// One wavefront does, between two round kernels, what the host does between two sbn_sumcheck_round calls: combine the round's
+// sums (sumcheck.rs:269-271), UniPoly::from_evals (unipoly.rs:28-59), append the polynomial (unipoly.rs:117-122), draw
+// challenge_scalar("challenge_nextround") (transcript.rs:56-67), e = poly(r_j) (sumcheck.rs:301).  It is latency, not throughput:
+//   * Keccak-f[1600] runs with ONE 64-bit state lane per SIMD lane (25 of 64 active): theta's column parities, pi and chi's row
+//     neighbours are wave shuffles (ds_bpermute through __shfl, nine 64-bit exchanges per round in three dependent steps), rho a per-lane rotate count.
+//   * STROBE's bookkeeping (operation headers, lengths, labels, the run_f padding bytes, where the blocks end) depends on the
+//     phase `pos` alone, never on a value, so the host plans it with its own Strobe code (host_strobe.hpp, StrobePlan) as
+//     one 200-byte XOR mask per block; the step XORs mask and coefficient bytes into the state, eight bytes per lane, at
+//     whatever phase the round starts.  A round is two blocks (three when the first round starts at pos >= 78).
+//   * field work is laid out so that independent products share one instruction stream: different lanes, same fe_mul.
+// The state between steps is the 200 sponge bytes in device memory; pos / pos_begin / cur_flags are the plan's.
+#pragma once
+#include "fp.cuh"
+#include "sumcheck_kernels.cuh"
+
+namespace sbn {
+
+constexpr int TR_RATE = 166;                 // STROBE-128
+constexpr int TR_ROUND_STREAM = 255;         // bytes one sumcheck round absorbs ahead of the PRF's permutation
+constexpr int TR_COEFF_FIRST = 38;           // offset of the first coefficient's 32 bytes in that stream: 25 ("poly" / "UniPoly_begin") + 13
+constexpr int TR_COEFF_STRIDE = 45;          // 2 + 5 + 4 + 2 + 32 per "coeff" message
+
+struct TrConst { uint32_t rho[25]; uint32_t rc[24][2]; };
+__host__ __device__ constexpr TrConst tr_make_const() {
+  TrConst t{};
+  int x = 1, y = 0;
+  for (int k = 0; k < 24; k++) { t.rho[x + 5 * y] = (uint32_t)(((k + 1) * (k + 2) / 2) % 64); const int nx = y, ny = (2 * x + 3 * y) % 5; x = nx; y = ny; }
+  uint32_t lfsr = 1;
+  for (int r = 0; r < 24; r++) {
+    uint64_t c = 0;
+    for (int j = 0; j < 7; j++) { if (lfsr & 1) c |= (uint64_t)1 << ((1 << j) - 1); lfsr = ((lfsr << 1) ^ ((lfsr & 0x80) ? 0x71 : 0)) & 0xff; }
+    t.rc[r][0] = (uint32_t)c; t.rc[r][1] = (uint32_t)(c >> 32);
+  }
+  return t;
+}
+__device__ const TrConst TR_CONST = tr_make_const();
+
+__device__ __forceinline__ uint64_t tr_shfl64(uint64_t v, int src) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src, 64), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src, 64);
+  return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t tr_rol64(uint64_t x, uint32_t n) { return (x << n) | (x >> ((64u - n) & 63u)); }   // n in [0, 64)
+
+// per-lane indices of the permutation (lane i = state lane x + 5 y; lanes >= 25 mirror lane 0 and are ignored)
+struct TrLanes { int th1, th2, th3, th4, src, dm, dp, c1, c2; uint32_t rot; uint32_t rc_lo, rc_hi; };
+__device__ __forceinline__ TrLanes tr_lanes(int lane) {
+  const int i = lane < 25 ? lane : 0, x = i % 5, y = i / 5;
+  TrLanes L;
+  L.th1 = (i + 5) % 25; L.th2 = (i + 10) % 25; L.th3 = (i + 15) % 25; L.th4 = (i + 20) % 25;
+  L.src = (x + 3 * y) % 5 + 5 * x;                 // pi: (x', y') -> (y', 2 x' + 3 y'), read backwards
+  L.dm = (L.src % 5 + 4) % 5; L.dp = (L.src % 5 + 1) % 5;     // theta's two columns for the SOURCE lane (row 0 holds every column's parity)
+  L.rot = TR_CONST.rho[L.src];
+  L.c1 = 5 * y + (x + 1) % 5; L.c2 = 5 * y + (x + 2) % 5;
+  L.rc_lo = lane < 24 ? TR_CONST.rc[lane][0] : 0u; L.rc_hi = lane < 24 ? TR_CONST.rc[lane][1] : 0u;   // lane r keeps round r's constant
+  return L;
+}
+// Keccak-f[1600], `a` = this lane's 64-bit state lane.  Three dependent exchanges per round: (column parities, and the lane pi will
+// move here, fetched before theta); (theta's two parities for that source lane: theta is applied on arrival, fused with rho); (chi's neighbours).
+__device__ __forceinline__ uint64_t tr_keccak_f(uint64_t a, const TrLanes& L, int lane) {
+#pragma unroll 1
+  for (int r = 0; r < 24; r++) {
+    const uint64_t as = tr_shfl64(a, L.src);
+    const uint64_t c = a ^ tr_shfl64(a, L.th1) ^ tr_shfl64(a, L.th2) ^ tr_shfl64(a, L.th3) ^ tr_shfl64(a, L.th4);    // parity of this lane's column
+    const uint64_t b = tr_rol64(as ^ tr_shfl64(c, L.dm) ^ tr_rol64(tr_shfl64(c, L.dp), 1), L.rot);
+    a = b ^ (~tr_shfl64(b, L.c1) & tr_shfl64(b, L.c2));
+    const uint32_t klo = (uint32_t)__builtin_amdgcn_readlane((int)L.rc_lo, r), khi = (uint32_t)__builtin_amdgcn_readlane((int)L.rc_hi, r);
+    if (lane == 0) a ^= ((uint64_t)khi << 32) | klo;
+  }
+  return a;
+}
+
+// constants in fp.cuh's Montgomery domain (R = 2^261), 29-bit limbs
+struct TrFrC {
+  static constexpr uint32_t K778[9] = {0x1c00feeeu, 0x1c5573e0u, 0x18197feau, 0x08b5c34cu, 0x120f41aeu, 0x1a97f167u, 0x15f6b4bbu, 0x01454f10u, 0x00160937u};   // 2^256 R^2 = 2^778 mod r
+  static constexpr uint32_t INV2[9] = {0x1fffffacu, 0x0edb5ba9u, 0x09c4156eu, 0x0f90701eu, 0x1016ecefu, 0x100ec0c7u, 0x093e16a4u, 0x09c376eeu, 0x001f1642u};   // R / 2
+  static constexpr uint32_t INV6[9] = {0x1555553au, 0x0efe3c4du, 0x177eca05u, 0x15108601u, 0x090b85fcu, 0x1c971618u, 0x0383f30cu, 0x177e9672u, 0x002a9f9fu};   // R / 6
+};
+__device__ __forceinline__ Fr tr_fr_k778() { Fr r; for (int i = 0; i < NL; i++) r.v[i] = SBN_C9(TrFrC::K778, i); return r; }
+__device__ __forceinline__ Fr tr_fr_inv2() { Fr r; for (int i = 0; i < NL; i++) r.v[i] = SBN_C9(TrFrC::INV2, i); return r; }
+__device__ __forceinline__ Fr tr_fr_inv6() { Fr r; for (int i = 0; i < NL; i++) r.v[i] = SBN_C9(TrFrC::INV6, i); return r; }
+__device__ __forceinline__ Fr tr_shfl(const Fr& a, int src) { Fr r;
+#pragma unroll
+  for (int i = 0; i < NL; i++) r.v[i] = (uint32_t)__shfl((int)a.v[i], src, 64);
+  return r; }
+
+struct TrStepArgs {
+  const uint32_t* sums;       // the round kernel's results: nslots x 3 canonical integers (device copy of the mailbox layout)
+  const uint32_t* weights;    // nslots x 8 words: c_i R^2 for a slot the combination weights, R^2 otherwise (canonical)
+  uint32_t nslots;            // <= SC_PACK_MAX
+  const uint8_t* masks;       // nblk x 200 bytes: the host's plan of this round's STROBE blocks
+  uint32_t nblk, pos0;        // blocks of this round (each ends in a permutation); pos when the round starts
+  uint8_t* strobe;            // 200 bytes, 8-byte aligned: the sponge state, read and written
+  uint32_t* claim;            // e as its nine 29-bit limbs (Montgomery domain, lazy: no canonical form is needed between steps), read and written
+  uint32_t* r_mont;           // out: r_j for the launches behind this one (canonical Montgomery words)
+  uint32_t* out_poly;         // out: c0..c3 of this round, canonical integers
+  uint32_t* out_r;            // out: r_j, canonical integer
+};
+
+__global__ void __launch_bounds__(64) k_tr_sumcheck_step(TrStepArgs A) {
+  __shared__ uint32_t s_prod[3][SC_PACK_MAX][NL];
+  __shared__ uint32_t s_e[3][NL];
+  __shared__ __attribute__((aligned(16))) uint8_t s_cb[128];      // the four coefficients as the transcript reads them
+  __shared__ __attribute__((aligned(16))) uint32_t s_ch[16];      // the 64 challenge bytes
+  const int lane = threadIdx.x;
+  const TrLanes L = tr_lanes(lane);
+  // everything the step reads from memory is requested here, ahead of the first use: each dependent global load is a microsecond
+  uint64_t a = lane < 25 ? reinterpret_cast<const uint64_t*>(A.strobe)[lane] : 0;
+  uint64_t mk[3];
+#pragma unroll
+  for (int b = 0; b < 3; b++) mk[b] = (lane < 25 && b < (int)A.nblk) ? reinterpret_cast<const uint64_t*>(A.masks + 200 * b)[lane] : 0;
+  Fr e;
+#pragma unroll
+  for (int k = 0; k < NL; k++) e.v[k] = A.claim[k];
+
+  // 1. the combination: slot s, value t in lane 21 t + s (slots 21 .. 23 in a second pass), weights bring the sums into Montgomery form
+  {
+    const int t = lane / 21, s0 = lane % 21;
+    for (int s = s0; t < 3 && s < (int)A.nslots; s += 21) {
+      const Fr x = fe_load<FrP>(A.sums + 8 * (3 * s + t)), w = fe_load<FrP>(A.weights + 8 * s);
+      const Fr p = fe_mul(x, w);                                                         // (-r, 2r)
+#pragma unroll
+      for (int k = 0; k < NL; k++) s_prod[t][s][k] = p.v[k];
+    }
+  }
+  __syncthreads();
+  Fr acc = fe_zero<FrP>();
+  if (lane < 3) {
+    for (uint32_t s = 0; s < A.nslots; s++) { Fr x; for (int k = 0; k < NL; k++) x.v[k] = s_prod[lane][s][k]; acc = fe_add(acc, x); }      // within (-24 r, 48 r)
+  }
+  acc = fe_reduce(acc);                                                                  // lanes 0..2: e0, e2, e3 in (-r, 2r)
+  if (lane < 3) for (int k = 0; k < NL; k++) s_e[lane][k] = acc.v[k];
+  __syncthreads();
+  Fr e0, e2, e3;
+  for (int k = 0; k < NL; k++) { e0.v[k] = s_e[0][k]; e2.v[k] = s_e[1][k]; e3.v[k] = s_e[2][k]; }
+  const Fr e1 = fe_sub(e, e0);                                                           // sumcheck.rs:274; e within (-3 r, 6 r)
+  // 2. UniPoly::from_evals: lane 0: a = (e3 - 3 e2 + 3 e1 - e0) / 6, lane 1: b = (2 e0 - 5 e1 + 4 e2 - e3) / 2 — one product for both
+  Fr xa = fe_sub(e3, e0), d21 = fe_sub(e1, e2);
+  xa = fe_add(xa, fe_add(fe_dbl(d21), d21));                                             // |.| < 20 r
+  Fr xb = fe_sub(fe_dbl(fe_sub(e0, e1)), e3);                                            // 2 e0 - 2 e1 - e3
+  xb = fe_add(xb, fe_add(fe_dbl(fe_dbl(fe_sub(e2, e1))), e1));                           // + 4 e2 - 4 e1 + e1;  |.| < 30 r
+  const Fr ab = fe_mul(fe_sel2(lane == 1, xa, xb), fe_sel2(lane == 1, tr_fr_inv6(), tr_fr_inv2()));
+  const Fr ca = tr_shfl(ab, 0), cb = tr_shfl(ab, 1);
+  const Fr cc = fe_sub(fe_sub(e1, e0), fe_add(ca, cb));                                  // c = e1 - d - a - b
+  // lane k: coefficient k (d, c, b, a), canonical for the transcript and the proof
+  const Fr mine = fe_sel4(lane & 3, e0, cc, cb, ca);
+  const Fr plain = fe_from_mont(mine);
+  if (lane < 4) {
+    uint32_t w[8]; fe_pack<FrP>(plain, w);
+    uint4* o = reinterpret_cast<uint4*>(A.out_poly + 8 * lane);
+    o[0] = make_uint4(w[0], w[1], w[2], w[3]); o[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    uint4* sc = reinterpret_cast<uint4*>(s_cb + 32 * lane);
+    sc[0] = make_uint4(w[0], w[1], w[2], w[3]); sc[1] = make_uint4(w[4], w[5], w[6], w[7]);
+  }
+  __syncthreads();
+
+  // 3. the transcript: every block = mask (labels, lengths, operation headers, run_f's padding) ^ coefficient bytes, then Keccak-f
+#pragma unroll
+  for (int b = 0; b < 3; b++) {
+    if (b >= (int)A.nblk) break;
+    uint64_t m = mk[b];
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+      const int p = 8 * lane + q;                                      // position in the block
+      const int t = (int)(TR_RATE * b) + p - (int)A.pos0 - TR_COEFF_FIRST;      // offset from the first coefficient byte in the round's stream
+      const int k = t / TR_COEFF_STRIDE, o = t - k * TR_COEFF_STRIDE;
+      if (p < TR_RATE && t >= 0 && k < 4 && o < 32) m ^= (uint64_t)s_cb[32 * k + o] << (8 * q);
+    }
+    a = tr_keccak_f(a ^ m, L, lane);
+  }
+  // the PRF's 64 bytes: positions 0 .. 63 of the fresh block, read and cleared
+  if (lane < 8) { s_ch[2 * lane] = (uint32_t)a; s_ch[2 * lane + 1] = (uint32_t)(a >> 32); a = 0; }
+  if (lane < 25) reinterpret_cast<uint64_t*>(A.strobe)[lane] = a;
+  __syncthreads();
+
+  // 4. challenge_scalar: lo + hi 2^256 mod r, straight into Montgomery form: lane 0: lo R^2 / R, lane 1: hi (2^256 R^2) / R
+  uint32_t w[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) w[k] = s_ch[8 * (lane & 1) + k];
+  const Fr half = fe_mul(fe_unpack<FrP>(w), fe_sel2((lane & 1) != 0, fe_const_r2<FrP>(), tr_fr_k778()));        // inputs < 2^256 = 5.3 r
+  const Fr r = fe_add(tr_shfl(half, 0), tr_shfl(half, 1));                               // (-2 r, 4 r), every lane
+  // 5. one product in five lanes: r^2, c r, a r (for e = d + c r + r^2 (b + a r)), r canonical in both domains
+  const Fr op = fe_sel4(lane & 3, r, cc, ca, fe_small<FrP>(1u));
+  const Fr p1 = fe_mul(r, fe_sel2(lane == 4, op, fe_one<FrP>()));
+  const Fr canon = fe_canon_small(p1);                                                   // lane 3: r as an integer, lane 4: r R
+  if (lane == 3) fe_store_packed<FrP>(A.out_r, canon);
+  if (lane == 4) fe_store_packed<FrP>(A.r_mont, canon);
+  const Fr r2 = tr_shfl(p1, 0), cr = tr_shfl(p1, 1), ar = tr_shfl(p1, 2);
+  const Fr hi = fe_mul(r2, fe_add(cb, ar));
+  const Fr en = fe_add(fe_add(e0, cr), hi);                                              // (-3 r, 6 r), normalised
+  if (lane == 0) for (int k = 0; k < NL; k++) A.claim[k] = en.v[k];
+}
+
+}  // namespace sbn
