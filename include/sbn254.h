@@ -208,6 +208,24 @@ int sbn_fr_from_wide(const uint8_t in[64], uint8_t out[32]);
  * finals as sbn_sumcheck_finish.  `tr` moves on only if the whole call succeeded; a failure after the first launch leaves `st` dead
  * (later calls return SBN_EINVAL).  Same values as the loop over sbn_sumcheck_round with the same transcript on the host, bit for bit. */
 int sbn_sumcheck_prove(sbn_ctx* ctx, sbn_sumcheck* st, sbn_transcript* tr, const uint8_t claim[32], uint8_t* out_polys, uint8_t* out_r, uint8_t* finals);
+/* ProductCircuitEvalProofBatched::prove (product_tree.rs:251-392) in ONE call: every layer's coeff_vec and joint claim (:317-321), its
+ * prove_cubic_batched with poly_C_par = eq(rand) (:271, :323-332), the claim appends (:352-365), r_layer and the folded claims (:368-376),
+ * with the transcript, `rand`, coeff_vec and claims_to_verify on the device throughout.  Everything is queued at once; one wait, one copy back.
+ *   layers[i * n_layers + j]: circuit i's layer j as sbn_product_circuit{,_many} produce it (left || right, 2^(n_layers - j) entries; j = 0 is the
+ *   input, the last one has two entries); the call takes the halves as sbn_table_halves does.  dotp_*: n_dotp DotProductCircuits of
+ *   2^(n_layers - 1) entries, joined at layer 0 only (:296-309); n_dotp = 0 allowed.  ProductCircuit::evaluate (:262-264) and
+ *   DotProductCircuit::evaluate (:298) are computed inside.  n_circ >= 1, n_circ + n_dotp <= 24, n_layers >= 1.
+ * The layer whose halves have one entry (no sumcheck round) is part of the proof: coeff_vec, the 2 n_circ appends and r_layer are drawn there too.
+ *   out_polys:  sum_k k rounds (k = 0 .. n_layers - 1, top layer first) x 4 x 32: c0..c3 of every round polynomial
+ *   out_claims: per layer, top first: claims_prod_left[n_circ], claims_prod_right[n_circ]; behind the last layer claims_dotp left[n_dotp], right[n_dotp], weight[n_dotp]
+ *   out_rand:   n_layers x 32: the final `rand` (r_layer of the last layer first, :374-376)
+ *   out_claims_final: n_circ x 32: claims_to_verify behind the last layer (= layer 0 of circuit i evaluated at out_rand)
+ * All scalars out are canonical.  The caller's tables are only read.  `tr` moves on only if the whole call succeeded.  Same values, bit for bit, as
+ * the layer loop over sbn_table_halves, sbn_transcript_challenge_scalar, sbn_sumcheck_begin_eq, sbn_sumcheck_prove / _round, sbn_sumcheck_finish and
+ * sbn_transcript_append_message. */
+int sbn_product_proof_prove(sbn_ctx* ctx, const sbn_table* const* layers, size_t n_circ, size_t n_layers,
+                            const sbn_table* const* dotp_left, const sbn_table* const* dotp_right, const sbn_table* const* dotp_weight, size_t n_dotp,
+                            sbn_transcript* tr, uint8_t* out_polys, uint8_t* out_claims, uint8_t* out_rand, uint8_t* out_claims_final);
 /* EqPolynomial::evals (hyrax.rs:355-369) built on the device */
 int sbn_eq_evals(sbn_ctx* ctx, const uint8_t* r, size_t ell, sbn_table** out);
 

@@ -121,6 +121,7 @@ extern "C" {
     pub fn sbn_transcript_from_state(input: *const u8, out: *mut *mut sbn_transcript) -> c_int;
     pub fn sbn_fr_from_wide(input: *const u8, out: *mut u8) -> c_int;
     pub fn sbn_sumcheck_prove(ctx: *mut sbn_ctx, st: *mut sbn_sumcheck, tr: *mut sbn_transcript, claim: *const u8, out_polys: *mut u8, out_r: *mut u8, finals: *mut u8) -> c_int;
+    pub fn sbn_product_proof_prove(ctx: *mut sbn_ctx, layers: *const *const sbn_table, n_circ: usize, n_layers: usize, dotp_left: *const *const sbn_table, dotp_right: *const *const sbn_table, dotp_weight: *const *const sbn_table, n_dotp: usize, tr: *mut sbn_transcript, out_polys: *mut u8, out_claims: *mut u8, out_rand: *mut u8, out_claims_final: *mut u8) -> c_int;
     pub fn sbn_eq_evals(ctx: *mut sbn_ctx, r: *const u8, ell: usize, out: *mut *mut sbn_table) -> c_int;
     pub fn sbn_table_dot(ctx: *mut sbn_ctx, a: *const sbn_table, b: *const sbn_table, out: *mut u8) -> c_int;
     pub fn sbn_table_evaluate(ctx: *mut sbn_ctx, z: *const sbn_table, r: *const u8, ell: usize, out: *mut u8) -> c_int;

@@ -17,7 +17,7 @@ EXPORTED_SYMBOLS = [
     "sbn_sc_bind_eval_cubic_batched", "sbn_sc_bind_eval_r1cs", "sbn_sc_bind_eval_quad",
     "sbn_sumcheck_begin", "sbn_sumcheck_begin_eq", "sbn_sumcheck_round", "sbn_sumcheck_len", "sbn_sumcheck_finish", "sbn_sumcheck_free",
     "sbn_transcript_new", "sbn_transcript_clone", "sbn_transcript_free", "sbn_transcript_append_message", "sbn_transcript_challenge_bytes", "sbn_transcript_challenge_scalar",
-    "sbn_transcript_state", "sbn_transcript_from_state", "sbn_fr_from_wide", "sbn_sumcheck_prove",
+    "sbn_transcript_state", "sbn_transcript_from_state", "sbn_fr_from_wide", "sbn_sumcheck_prove", "sbn_product_proof_prove",
     "sbn_group_create", "sbn_group_destroy", "sbn_group_size", "sbn_group_ctx", "sbn_group_last_error", "sbn_group_bases_upload", "sbn_group_gens_new", "sbn_group_bases_precompute",
     "sbn_group_bases_free", "sbn_group_commit_rows", "sbn_group_commit_rows_dev", "sbn_group_gather_commit", "sbn_group_msm", "sbn_group_bases_upload_ranges", "sbn_group_bases_synthetic_ranges", "sbn_group_range", "sbn_group_msm_bases", "sbn_group_msm_bases_dev",
     "sbn_eq_evals", "sbn_hash_layer", "sbn_hash_layer_pair", "sbn_product_layer", "sbn_product_circuit", "sbn_product_circuit_many", "sbn_table_halves", "sbn_table_slice", "sbn_table_dot", "sbn_table_evaluate", "sbn_table_evaluate_many", "sbn_table_bound", "sbn_gather_merge", "sbn_gather_merge_rows", "sbn_commit_table", "sbn_bullet_begin", "sbn_bullet_begin_scaled", "sbn_bullet_free", "sbn_bullet_len", "sbn_bullet_cross", "sbn_bullet_fold_cross", "sbn_bullet_fold", "sbn_bullet_finish", "sbn_prof_enable", "sbn_prof_reset", "sbn_prof_count", "sbn_prof_get", "sbn_prof_last_job",
@@ -80,6 +80,7 @@ def lib():
             getattr(L, name).restype = C.c_void_p; getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_size_t]
         L.sbn_transcript_free.argtypes = [C.c_void_p]
         L.sbn_sumcheck_prove.argtypes = [C.c_void_p] * 7
+        L.sbn_product_proof_prove.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
         L.sbn_dense_audit_ts_dev.restype = C.c_void_p; L.sbn_dense_audit_ts_dev.argtypes = [C.c_void_p, C.c_int]
         for name in ("sbn_dense_comb_ops", "sbn_dense_comb_mem"):
             getattr(L, name).restype = C.c_void_p; getattr(L, name).argtypes = [C.c_void_p]
@@ -670,6 +671,19 @@ class Context:
         pb, rb = bytes(polys), bytes(rs)
         return ([[pb[128 * j + 32 * k:128 * j + 32 * k + 32] for k in range(4)] for j in range(rounds)], [rb[32 * j:32 * j + 32] for j in range(rounds)],
                 [bytes(fin[32 * t:32 * t + 32]) for t in range(st.ntab)])
+
+    def product_proof_prove(self, layers, dotps, tr):
+        """ProductCircuitEvalProofBatched::prove in one call (sbn_product_proof_prove).  layers[i][j]: circuit i's layer j (Table, left || right, the input
+        first: what product_circuit{,_many} return behind their input); dotps: [(left, right, weight)] Tables; `tr` (Transcript) moves on.
+        -> (out_polys, out_claims, out_rand, out_claims_final) as bytes, laid out as include/sbn254.h describes"""
+        n, L, nd = len(layers), len(layers[0]), len(dotps)
+        arr = (C.c_void_p * (n * L))(*[layers[i][j].h for i in range(n) for j in range(L)])
+        mk = lambda k: (C.c_void_p * max(1, nd))(*[d[k].h for d in dotps])
+        polys = (C.c_uint8 * (128 * max(1, L * (L - 1) // 2)))(); claims = (C.c_uint8 * (32 * (2 * n * L + 3 * nd)))()
+        rand = (C.c_uint8 * (32 * L))(); fin = (C.c_uint8 * (32 * n))()
+        self._chk(lib().sbn_product_proof_prove(self.h, arr, C.c_size_t(n), C.c_size_t(L), mk(0), mk(1), mk(2), C.c_size_t(nd), tr.h, polys, claims, rand, fin),
+                  "sbn_product_proof_prove")
+        return bytes(polys)[:128 * (L * (L - 1) // 2)], bytes(claims), bytes(rand), bytes(fin)
 
     def eq_evals(self, r):
         ell = len(r) // 32; ht = C.c_void_p()

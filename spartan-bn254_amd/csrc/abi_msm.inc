@@ -48,6 +48,7 @@ void sbn_ctx_destroy(sbn_ctx* c) {
   if (c->mbox) hipHostFree(c->mbox);
   for (hipEvent_t e : c->evt_pool) hipEventDestroy(e);
   if (c->copy_stream) hipStreamDestroy(c->copy_stream);
+  if (c->pp_stream) hipStreamDestroy(c->pp_stream);
   hipStreamDestroy(c->own_stream);
   delete c;
 }

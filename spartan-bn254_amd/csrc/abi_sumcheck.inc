@@ -150,12 +150,13 @@ static int sc_launch_inst_fused(sbn_ctx* c, ScFusedPack& pack, size_t count, siz
   LAUNCHCHK(c);
   return SBN_OK;
 }
-static int sc_launch_inst_eval(sbn_ctx* c, ScArgsPack& pack, size_t count, size_t half, uint32_t seq) {
+// mbox: where the sums and their flags go (null: the host mailbox; sbn_product_proof_prove passes the mailbox's device twin)
+static int sc_launch_inst_eval(sbn_ctx* c, ScArgsPack& pack, size_t count, size_t half, uint32_t seq, uint32_t* mbox = nullptr) {
   int rc;
   size_t want = (c->sck.eval_blocks + count - 1) / count, cap = (half + 255) / 256;
   const unsigned gx = (unsigned)std::max<size_t>(1, std::min(std::min(want, cap), SC_PART_INST_BLOCKS));
   if ((rc = ensure(c, c->sc_partial, SC_PARTIAL_BYTES))) return rc;
-  LAUNCH(c, "k_sc_eval_cubic", k_sc_eval<KIND_CUBIC>, dim3(gx, (unsigned)count), 256, (const ScArgs*)nullptr, pack, half, (uint32_t*)c->sc_partial.p, (uint32_t*)c->sc_tickets.p, c->mbox, seq);
+  LAUNCH(c, "k_sc_eval_cubic", k_sc_eval<KIND_CUBIC>, dim3(gx, (unsigned)count), 256, (const ScArgs*)nullptr, pack, half, (uint32_t*)c->sc_partial.p, (uint32_t*)c->sc_tickets.p, mbox ? mbox : c->mbox, seq);
   LAUNCHCHK(c);
   return SBN_OK;
 }

@@ -37,6 +37,7 @@ struct sbn_ctx {
   DevBuf scal_canon, hist, offs, sorted, buckets, red_a, red_b, wsum, stage_scal, stage_pts, out_small;
   DevBuf sc_args, sc_partial, sc_out, sc_r, sc_tabs, sc_tickets, sc_prove, gen_tmp, acc_ctr, extra_list, extra_out, big_list, digits, blockhist, perm, merged;
   hipStream_t copy_stream = nullptr;          // H2D of the next row chunk while the current one is being committed
+  hipStream_t pp_stream = nullptr;            // sbn_product_proof_prove: the inversion of a layer's coefficients, beside the layer's sumcheck
   hipEvent_t z_consumed = nullptr;            // set while a chunked commit is running: recorded when a chunk's scalars have been read
   DevBuf zstage[2], out_rows, comb_partial;
   DevBuf s2_cnt, s2_part, s2_idx, s2_lo;     // two-level sort of a large single MSM (sort2_kernels.cuh)

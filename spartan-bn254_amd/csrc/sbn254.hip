@@ -49,6 +49,7 @@ using namespace sbn;
 #include "abi_tables.inc"
 #include "abi_transcript.inc"
 #include "abi_sumcheck.inc"
+#include "abi_product_proof.inc"
 #include "abi_bullet.inc"
 #include "abi_group.inc"
 #include "abi_kzg.inc"

@@ -192,4 +192,116 @@ __global__ void __launch_bounds__(64) k_tr_sumcheck_step(TrStepArgs A) {
   if (lane == 0) for (int k = 0; k < NL; k++) A.claim[k] = en.v[k];
 }
 
+// ---- the layer-boundary step of ProductCircuitEvalProofBatched::prove (product_tree.rs:316-376), sbn_product_proof_prove -------
+// Between two layers' sumchecks the reference appends the final claims (:352-365), draws challenge_scalar("challenge_r_layer"),
+// folds claims_to_verify[i] = l_i + r_layer (r_i - l_i) (:370-372), then opens the next layer: n challenge_scalar("rand_coeffs_next_layer")
+// and the joint claim sum_i claims_to_verify[i] c_i (:317-321).  One wavefront does "close" and/or "open" in ONE launch.  No appended value
+// depends on a challenge of the same step, so the step runs the whole sponge first and does the field work behind it.
+// The host plans every block as one record (abi_product_proof.inc, transcript_plan_boundary): the XOR mask (labels, lengths, headers,
+// padding), a flag "a 64-byte challenge is read behind this block's permutation", and for each of the 166 rate bytes the index of the
+// data byte XORed there (the closing layer's final claims, canonical, 32 bytes each) or 0xffff.  Keccak-f and the lane layout are
+// k_tr_sumcheck_step's.
+constexpr int TR_REC_BYTES = 544;            // 200 mask, 8 flags, 168 x 2 byte sources
+constexpr int TR_REC_FLAGS = 200, TR_REC_SRC = 208;
+constexpr int TR_LAYER_DATA_MAX = 80;        // scalars staged for the appends (SC_FINAL_MAX: one per table of the largest sumcheck)
+constexpr int TR_LAYER_CHAL_MAX = SC_PACK_MAX + 1;
+struct TrLayerArgs {
+  const uint8_t* recs; uint32_t nblk;       // the host's plan of this step's STROBE blocks
+  uint8_t* strobe;                           // 200 sponge bytes, read and written
+  const uint32_t* data; uint32_t ndata;      // close: the closing layer's final claims as canonical integers (A_par.., B_par.., C_par, A_seq.., B_seq.., C_seq..)
+  uint32_t n_close;                          // close: the number of product circuits (0: this step closes nothing)
+  uint32_t n_open;                           // open: coefficients to draw (0: this step opens nothing)
+  uint32_t* claims;                          // claims_to_verify, table format (Montgomery): close writes [0, n_close), open reads [0, n_open)
+  uint32_t* out_r;                           // close: r_layer, canonical integer
+  uint32_t* out_claims;                      // close: the folded claims_to_verify, canonical integers
+  uint32_t* weights;                         // open: c_i R^2 (canonical words), what k_tr_sumcheck_step weights slot i's sums with
+  uint32_t* claim;                           // open: the joint claim as nine 29-bit limbs (Montgomery, lazy), k_tr_sumcheck_step's `claim`
+  // open of a layer whose sumcheck folds c_i into A_i (the combined kernels, abi_sumcheck.inc mode COMB); null otherwise
+  uint32_t n_par_open;                       //   the first n_par_open coefficients belong to the "par" instances, the rest to the "seq" instances
+  uint32_t* coeffs_mont;                     //   c_i in Montgomery form (canonical words): the groups' u and the inversion read them
+  uint32_t* weights_comb;                    //   SC_PACK_MAX slots of a combined round: the "seq" instances' c_i R^2, then R^2 (the groups' sums carry c_i)
+  uint32_t* weights_inst;                    //   the slots of a per-instance round on scaled tables: R^2 for the "par" instances, c_i R^2 for the "seq" ones
+};
+// lo + hi 2^256 mod r in Montgomery form from 64 challenge bytes (transcript.rs:56-67); (-2 r, 4 r), normalised
+__device__ __forceinline__ Fr tr_wide_mont(const uint32_t* ch) {
+  uint32_t lo[8], hi[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) { lo[k] = ch[k]; hi[k] = ch[8 + k]; }
+  return fe_add(fe_mul(fe_unpack<FrP>(lo), fe_const_r2<FrP>()), fe_mul(fe_unpack<FrP>(hi), tr_fr_k778()));
+}
+__global__ void __launch_bounds__(64) k_tr_layer_step(TrLayerArgs A) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_data[TR_LAYER_DATA_MAX * 32];
+  __shared__ __attribute__((aligned(16))) uint32_t s_ch[TR_LAYER_CHAL_MAX][16];
+  const int lane = threadIdx.x;
+  const TrLanes L = tr_lanes(lane);
+  uint64_t a = lane < 25 ? reinterpret_cast<const uint64_t*>(A.strobe)[lane] : 0;
+  const uint32_t ndata = A.ndata < (uint32_t)TR_LAYER_DATA_MAX ? A.ndata : (uint32_t)TR_LAYER_DATA_MAX;
+  for (uint32_t i = lane; i < ndata * 2; i += 64) reinterpret_cast<uint4*>(s_data)[i] = reinterpret_cast<const uint4*>(A.data)[i];
+  __syncthreads();
+  // 1. the sponge: every block = mask ^ data bytes, then Keccak-f; the next record is requested before the permutation runs
+  uint32_t nch = 0;
+  const uint8_t* rec = A.recs;
+  uint64_t mk = (lane < 25 && A.nblk) ? reinterpret_cast<const uint64_t*>(rec)[lane] : 0;
+  uint64_t fl = A.nblk ? *reinterpret_cast<const uint64_t*>(rec + TR_REC_FLAGS) : 0;
+  uint4 sr = (lane < 21 && A.nblk) ? reinterpret_cast<const uint4*>(rec + TR_REC_SRC)[lane] : make_uint4(~0u, ~0u, ~0u, ~0u);
+  for (uint32_t b = 0; b < A.nblk; b++) {
+    uint64_t m = mk; const uint64_t f = fl; const uint4 s = sr;
+    if (b + 1 < A.nblk) {
+      rec += TR_REC_BYTES;
+      mk = lane < 25 ? reinterpret_cast<const uint64_t*>(rec)[lane] : 0;
+      fl = *reinterpret_cast<const uint64_t*>(rec + TR_REC_FLAGS);
+      sr = lane < 21 ? reinterpret_cast<const uint4*>(rec + TR_REC_SRC)[lane] : make_uint4(~0u, ~0u, ~0u, ~0u);
+    }
+    const uint32_t sw[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+      const uint32_t idx = (sw[q >> 1] >> (16 * (q & 1))) & 0xffffu;
+      if (idx < ndata * 32u) m ^= (uint64_t)s_data[idx] << (8 * q);
+    }
+    a = tr_keccak_f(a ^ m, L, lane);
+    if ((f & 1) && nch < (uint32_t)TR_LAYER_CHAL_MAX) {        // the PRF's 64 bytes: positions 0 .. 63 of the fresh block, read and cleared
+      if (lane < 8) { s_ch[nch][2 * lane] = (uint32_t)a; s_ch[nch][2 * lane + 1] = (uint32_t)(a >> 32); a = 0; }
+      nch++;
+    }
+  }
+  if (lane < 25) reinterpret_cast<uint64_t*>(A.strobe)[lane] = a;
+  __syncthreads();
+  // 2. close: lane i folds circuit i's two claims with r_layer (the first challenge of the step)
+  const uint32_t first_coeff = A.n_close ? 1u : 0u;
+  Fr cv = fe_zero<FrP>();
+  if (A.n_close) {
+    const Fr rl = tr_wide_mont(s_ch[0]);
+    if (lane == 0) fe_store_packed<FrP>(A.out_r, fe_from_mont(rl));
+    if ((uint32_t)lane < A.n_close) {
+      const Fr l = fe_to_mont(fe_load<FrP>(s_data + 32 * lane)), r = fe_to_mont(fe_load<FrP>(s_data + 32 * (A.n_close + lane)));
+      cv = fe_add(l, fe_mul(rl, fe_sub(r, l)));                                          // (-2 r, 4 r)
+      fe_store_tab<FrP>(A.claims + 8 * lane, cv);
+      fe_store_packed<FrP>(A.out_claims + 8 * lane, fe_from_mont(cv));
+    }
+  }
+  // 3. open: lane i draws c_i; the joint claim is the wave's sum of claims_to_verify[i] c_i
+  if (A.n_open) {
+    Fr term = fe_zero<FrP>();
+    if ((uint32_t)lane < A.n_open) {
+      if ((uint32_t)lane >= A.n_close) cv = fe_load<FrP>(A.claims + 8 * lane);           // not folded by this step: first layer, dot-product circuits
+      const Fr ci = tr_wide_mont(s_ch[first_coeff + lane]);
+      fe_store<FrP>(A.weights + 8 * lane, fe_mul(ci, fe_const_r2<FrP>()));
+      term = fe_mul(cv, ci);                                                             // (-r, 2 r)
+      if (A.coeffs_mont) fe_store<FrP>(A.coeffs_mont + 8 * lane, ci);
+    }
+    if (A.weights_comb) {                                                                // (uniform branch: every lane takes part in the exchange)
+      const Fr ci = (uint32_t)lane < A.n_open ? tr_wide_mont(s_ch[first_coeff + lane]) : fe_one<FrP>();
+      const Fr w = fe_mul(ci, fe_const_r2<FrP>());
+      const uint32_t n_seq = A.n_open - A.n_par_open;
+      const Fr ws = tr_shfl(w, (int)((A.n_par_open + (uint32_t)lane) & 63u));           // the "seq" instance that owns combined-round slot `lane`
+      if (lane < SC_PACK_MAX) {
+        fe_store<FrP>(A.weights_comb + 8 * lane, (uint32_t)lane < n_seq ? ws : fe_const_r2<FrP>());
+        fe_store<FrP>(A.weights_inst + 8 * lane, ((uint32_t)lane < A.n_par_open || (uint32_t)lane >= A.n_open) ? fe_const_r2<FrP>() : w);
+      }
+    }
+    const Fr sum = fe_reduce(wave_sum_fr(term));                                         // at most 24 terms: (-24 r, 48 r) -> (-r, 2 r)
+    if (lane == 0) for (int k = 0; k < NL; k++) A.claim[k] = sum.v[k];
+  }
+}
+
 }  // namespace sbn
