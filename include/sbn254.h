@@ -276,6 +276,36 @@ int sbn_bullet_fold_cross(sbn_ctx* ctx, sbn_bullet* st, const uint8_t u[32], con
 /* After the last fold (length 1): a_hat, b_hat, g_hat (bullet.rs:114-120) */
 int sbn_bullet_finish(sbn_ctx* ctx, sbn_bullet* st, uint8_t a_hat[32], uint8_t b_hat[32], uint8_t g_hat_xy[64], int* g_hat_is_inf);
 
+/* ---- the Hyrax opening in ONE call: PolyEvalProof::prove (hyrax.rs:65-116) with DotProductProofLog::prove (nizk/mod.rs:439-522) and
+ *      BulletReductionProof::prove (nizk/bullet.rs:24-126) inside, the Merlin transcript included ----
+ * (L_size, R_size) = 2^sbn_factored_lens(ell), n = R_size, lg n = log2(n).
+ *   gens:   R_size + 1 generators with h, as sbn_gens_new(R_size + 1, label) gives them: gens_n = the first R_size, gens_1.G[0] = the last
+ *           (DotProductProofGens::new, nizk/mod.rs:412-415).  The derived set and its lookup table are built on the first call and owned by the handle.
+ *   Z:      2^ell entries, only read.   blinds: L_size x 32 canonical, or NULL = zeros (hyrax.rs:83-86).   r: ell x 32.   blind_Zr: or NULL = 0.
+ *   rnd:    (3 + 2 lg n) x 32 canonical: d, r_delta, r_beta, then blinds_vec as (v1[i], v2[i]) pairs, the caller's RandomTape draws in the
+ *           reference's order (nizk/mod.rs:458-468).
+ *   out_proof: lg n x 32 compressed L, lg n x 32 compressed R, delta, beta (32 each, compressed), z1, z2 (32 each, canonical).
+ *   out_Cx / out_Cy: the commitments C_LZ and C_Zr' (nizk/mod.rs:470-474) as canonical affine points.
+ * ell >= 1 (ell == 0 is SBN_EINVAL), ell <= 40; every scalar in is checked canonical; Zr is not checked against <L*Z, R> (the reference does not).
+ * Transcript, byte for byte the reference's: protocol-name x 2, Cx, Cy, every entry of a_vec = R as its own "a" message (transcript.rs:46-50),
+ * challenge r, per round L, R, challenge u, then delta, beta, challenge c; points in the form sbn_g1_compress gives.
+ * Every group element is a two-row commit over the one set G || Q_base with h: lg n + 2 commits, one host wait each; Gamma and g_hat are never
+ * formed.  `tr` moves on only if the whole call succeeded.  Same bytes as the loop over sbn_table_bound, sbn_bullet_*, sbn_msm,
+ * sbn_g1_compress and sbn_transcript_* with the same draws. */
+int sbn_polyeval_prove(sbn_ctx* ctx, const sbn_bases* gens, const sbn_table* Z, const uint8_t* blinds, const uint8_t* r, size_t ell, const uint8_t Zr[32],
+                       const uint8_t* blind_Zr, const uint8_t* rnd, sbn_transcript* tr, uint8_t* out_proof,
+                       uint8_t out_Cx_xy[64], int* Cx_is_inf, uint8_t out_Cy_xy[64], int* Cy_is_inf);
+/* The n-to-1 reduction the three HashLayerProof openings share (DerefsEvalProof::prove_single, sparse_mlpoly_full.rs:384-407; the comb_ops and
+ * comb_mem openings, :986-1009, :1013-1035), then sbn_polyeval_prove on the merged table: append `evals` (count a power of two, padded by the
+ * caller) under label_evals, challenge_vector(label_chal, log2 count), joint_claim = evals bound from the last challenge down
+ * (bound_poly_var_bot, hyrax.rs:206-214), append it under label_claim, open Z (2^(log2 count + ell_r) entries) at challenges || r with no
+ * blinds and blind_Zr = 0.  out_challenges: log2 count x 32 (may be NULL for count = 1); rnd, out_proof, out_Cx / out_Cy as above. */
+int sbn_joint_opening_prove(sbn_ctx* ctx, const sbn_bases* gens, const sbn_table* Z, const uint8_t* evals, size_t count,
+                            const uint8_t* label_evals, size_t label_evals_len, const uint8_t* label_chal, size_t label_chal_len,
+                            const uint8_t* label_claim, size_t label_claim_len, const uint8_t* r, size_t ell_r, const uint8_t* rnd, sbn_transcript* tr,
+                            uint8_t* out_challenges, uint8_t out_joint_claim[32], uint8_t* out_proof,
+                            uint8_t out_Cx_xy[64], int* Cx_is_inf, uint8_t out_Cy_xy[64], int* Cy_is_inf);
+
 /* ---- network construction pieces ----
  * sbn_hash_layer and sbn_product_layer only enqueue work (their outputs are consumed by later calls on the same context, which
  * are ordered behind them); every call that returns data to the host waits for it. ----
@@ -454,6 +484,10 @@ int sbn_prof_get(sbn_ctx* ctx, int i, const char** name, double* total_ms, uint6
 /* shape of the context's most recent bucket job (an MSM or a row commit): out = {window bits c, windows W, (digit, point)
  * slots = mixed additions when no digit is zero, buckets}; bench.py prices the accumulate kernel against the ALU roofline with it */
 int sbn_prof_last_job(sbn_ctx* ctx, uint64_t out[4]);
+
+/* host microseconds of the context's most recent opening: {a_vec = R computed on the host beside the first commit, the wait for that
+ * commit behind it, Cx + Cy + the n a_vec messages absorbed into the transcript} */
+int sbn_prof_last_polyeval(sbn_ctx* ctx, double out_us[3]);
 
 #ifdef __cplusplus
 }

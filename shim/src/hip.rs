@@ -135,6 +135,8 @@ extern "C" {
     pub fn sbn_bullet_fold(ctx: *mut sbn_ctx, st: *mut sbn_bullet, u: *const u8, u_inv: *const u8) -> c_int;
     pub fn sbn_bullet_fold_cross(ctx: *mut sbn_ctx, st: *mut sbn_bullet, u: *const u8, u_inv: *const u8, blind_l: *const u8, blind_r: *const u8, l_xy: *mut u8, l_is_inf: *mut c_int, r_xy: *mut u8, r_is_inf: *mut c_int, c_l: *mut u8, c_r: *mut u8) -> c_int;
     pub fn sbn_bullet_finish(ctx: *mut sbn_ctx, st: *mut sbn_bullet, a_hat: *mut u8, b_hat: *mut u8, g_hat_xy: *mut u8, g_hat_is_inf: *mut c_int) -> c_int;
+    pub fn sbn_polyeval_prove(ctx: *mut sbn_ctx, gens: *const sbn_bases, z: *const sbn_table, blinds: *const u8, r: *const u8, ell: usize, zr: *const u8, blind_zr: *const u8, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8, out_cx_xy: *mut u8, cx_is_inf: *mut c_int, out_cy_xy: *mut u8, cy_is_inf: *mut c_int) -> c_int;
+    pub fn sbn_joint_opening_prove(ctx: *mut sbn_ctx, gens: *const sbn_bases, z: *const sbn_table, evals: *const u8, count: usize, label_evals: *const u8, label_evals_len: usize, label_chal: *const u8, label_chal_len: usize, label_claim: *const u8, label_claim_len: usize, r: *const u8, ell_r: usize, rnd: *const u8, tr: *mut sbn_transcript, out_challenges: *mut u8, out_joint_claim: *mut u8, out_proof: *mut u8, out_cx_xy: *mut u8, cx_is_inf: *mut c_int, out_cy_xy: *mut u8, cy_is_inf: *mut c_int) -> c_int;
     pub fn sbn_hash_layer(ctx: *mut sbn_ctx, addr_dev: *const c_void, val: *const sbn_table, ts_dev: *const c_void, ts_add: u32, r_hash: *const u8, r_multiset: *const u8, out: *mut *mut sbn_table) -> c_int;
     pub fn sbn_hash_layer_pair(ctx: *mut sbn_ctx, addr_dev: *const c_void, val: *const sbn_table, ts_a_dev: *const c_void, ts_a_add: u32, ts_b_dev: *const c_void, ts_b_add: u32, r_hash: *const u8, r_multiset: *const u8, out_a: *mut *mut sbn_table, out_b: *mut *mut sbn_table) -> c_int;
     pub fn sbn_product_layer(ctx: *mut sbn_ctx, input: *const sbn_table, out: *mut *mut sbn_table) -> c_int;
@@ -189,6 +191,7 @@ extern "C" {
     pub fn sbn_prof_count(ctx: *mut sbn_ctx) -> c_int;
     pub fn sbn_prof_get(ctx: *mut sbn_ctx, i: c_int, name: *mut *const c_char, total_ms: *mut f64, launches: *mut u64) -> c_int;
     pub fn sbn_prof_last_job(ctx: *mut sbn_ctx, out: *mut u64) -> c_int;
+    pub fn sbn_prof_last_polyeval(ctx: *mut sbn_ctx, out_us: *mut f64) -> c_int;
     // GENERATED-END
 }
 

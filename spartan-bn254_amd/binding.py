@@ -18,6 +18,7 @@ EXPORTED_SYMBOLS = [
     "sbn_sumcheck_begin", "sbn_sumcheck_begin_eq", "sbn_sumcheck_round", "sbn_sumcheck_len", "sbn_sumcheck_finish", "sbn_sumcheck_free",
     "sbn_transcript_new", "sbn_transcript_clone", "sbn_transcript_free", "sbn_transcript_append_message", "sbn_transcript_challenge_bytes", "sbn_transcript_challenge_scalar",
     "sbn_transcript_state", "sbn_transcript_from_state", "sbn_fr_from_wide", "sbn_sumcheck_prove", "sbn_product_proof_prove",
+    "sbn_polyeval_prove", "sbn_joint_opening_prove", "sbn_prof_last_polyeval",
     "sbn_group_create", "sbn_group_destroy", "sbn_group_size", "sbn_group_ctx", "sbn_group_last_error", "sbn_group_bases_upload", "sbn_group_gens_new", "sbn_group_bases_precompute",
     "sbn_group_bases_free", "sbn_group_commit_rows", "sbn_group_commit_rows_dev", "sbn_group_gather_commit", "sbn_group_msm", "sbn_group_bases_upload_ranges", "sbn_group_bases_synthetic_ranges", "sbn_group_range", "sbn_group_msm_bases", "sbn_group_msm_bases_dev",
     "sbn_eq_evals", "sbn_hash_layer", "sbn_hash_layer_pair", "sbn_product_layer", "sbn_product_circuit", "sbn_product_circuit_many", "sbn_table_halves", "sbn_table_slice", "sbn_table_dot", "sbn_table_evaluate", "sbn_table_evaluate_many", "sbn_table_bound", "sbn_gather_merge", "sbn_gather_merge_rows", "sbn_commit_table", "sbn_bullet_begin", "sbn_bullet_begin_scaled", "sbn_bullet_free", "sbn_bullet_len", "sbn_bullet_cross", "sbn_bullet_fold_cross", "sbn_bullet_fold", "sbn_bullet_finish", "sbn_prof_enable", "sbn_prof_reset", "sbn_prof_count", "sbn_prof_get", "sbn_prof_last_job",
@@ -81,6 +82,8 @@ def lib():
         L.sbn_transcript_free.argtypes = [C.c_void_p]
         L.sbn_sumcheck_prove.argtypes = [C.c_void_p] * 7
         L.sbn_product_proof_prove.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
+        L.sbn_polyeval_prove.argtypes = [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 9
+        L.sbn_joint_opening_prove.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p, C.c_size_t] * 3 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 9
         L.sbn_dense_audit_ts_dev.restype = C.c_void_p; L.sbn_dense_audit_ts_dev.argtypes = [C.c_void_p, C.c_int]
         for name in ("sbn_dense_comb_ops", "sbn_dense_comb_mem"):
             getattr(L, name).restype = C.c_void_p; getattr(L, name).argtypes = [C.c_void_p]
@@ -794,6 +797,37 @@ class Context:
         ah, bh, gh = (C.c_uint8 * 32)(), (C.c_uint8 * 32)(), (C.c_uint8 * 64)(); gi = C.c_int(0)
         self._chk(lib().sbn_bullet_finish(self.h, st.h, ah, bh, gh, C.byref(gi)), "sbn_bullet_finish")
         return bytes(ah), bytes(bh), bytes(gh)
+
+    # ---- the Hyrax opening in one call (hyrax.rs:65-116, nizk/mod.rs:439-522, nizk/bullet.rs:24-126)
+    def polyeval_prove(self, gens, Z, r, Zr, rnd, tr, blinds=None, blind_Zr=None):
+        """PolyEvalProof::prove (sbn_polyeval_prove) -> (proof bytes, Cx_xy, Cy_xy); gens: R_size + 1 generators with h; `tr` (Transcript) moves on"""
+        ell = len(r) // 32
+        lg = ell - ell // 2
+        proof = (C.c_uint8 * (64 * lg + 128))(); cx, cy = (C.c_uint8 * 64)(), (C.c_uint8 * 64)(); xi, yi = C.c_int(0), C.c_int(0)
+        self._chk(lib().sbn_polyeval_prove(self.h, gens.h, Z.h, _ptr(blinds), _ptr(r), C.c_size_t(ell), _ptr(Zr), _ptr(blind_Zr), _ptr(rnd), tr.h,
+                                           proof, cx, C.byref(xi), cy, C.byref(yi)), "sbn_polyeval_prove")
+        return bytes(proof), bytes(cx), bytes(cy)
+
+    def joint_opening_prove(self, gens, Z, evals, labels, r, rnd, tr):
+        """the n-to-1 reduction + opening of sparse_mlpoly_full.rs:384-407 (sbn_joint_opening_prove); labels = (evals, challenge, claim)
+        -> (challenges, joint_claim, proof bytes, Cx_xy, Cy_xy)"""
+        count = len(evals) // 32
+        lc = count.bit_length() - 1
+        ell = lc + len(r) // 32
+        lg = ell - ell // 2
+        ch = (C.c_uint8 * max(32 * lc, 1))(); claim = (C.c_uint8 * 32)()
+        proof = (C.c_uint8 * (64 * lg + 128))(); cx, cy = (C.c_uint8 * 64)(), (C.c_uint8 * 64)(); xi, yi = C.c_int(0), C.c_int(0)
+        le, lch, lcl = labels
+        self._chk(lib().sbn_joint_opening_prove(self.h, gens.h, Z.h, _ptr(evals), C.c_size_t(count), _ptr(le), C.c_size_t(len(le)), _ptr(lch), C.c_size_t(len(lch)),
+                                                _ptr(lcl), C.c_size_t(len(lcl)), _ptr(r), C.c_size_t(len(r) // 32), _ptr(rnd), tr.h, ch, claim, proof,
+                                                cx, C.byref(xi), cy, C.byref(yi)), "sbn_joint_opening_prove")
+        return bytes(ch[:32 * lc]), bytes(claim), bytes(proof), bytes(cx), bytes(cy)
+
+    def prof_last_polyeval(self):
+        """host microseconds of the most recent opening: (R on the host, wait for the first commit, Cx + Cy + a_vec absorbed)"""
+        out = (C.c_double * 3)()
+        self._chk(lib().sbn_prof_last_polyeval(self.h, out), "sbn_prof_last_polyeval")
+        return tuple(out)
 
     # ---- KZG mode (kzg.rs): the SRS is a Bases handle, polynomials are the first n entries of a Table
     def kzg_srs_upload(self, powers_xy, flags=0):

@@ -223,6 +223,33 @@ int sbn_bullet_begin_scaled(sbn_ctx* c, const sbn_bases* G, const uint8_t* Q_bas
 }
 
 }  // extern "C"
+// The two rows in st->d_w (n + 1 canonical scalars each, the two blinds behind them) as ONE two-row commit over the derived set, the two XYZZ
+// sums and the 2 x 8 words of st->d_dots to the host mailbox behind it — launches only; *seq is what bullet_rows_collect waits for.
+static int bullet_rows_launch(sbn_ctx* c, sbn_bullet* st, uint32_t* seq) {
+  const size_t n = st->n; int rc;
+  uint8_t* WL = (uint8_t*)st->d_w; uint8_t* BL = WL + 64 * (n + 1);
+  if ((rc = ensure(c, c->wsum, 4096))) return rc;                       // (the commit asks for 2 x 128 B: sized here so that it never reallocates mid-round)
+  if ((rc = sc_tickets(c))) return rc;
+  { RowInfo ri; ri.internal_rows = true;
+    if ((rc = commit_rows_launch(c, st->ext, (const uint32_t*)WL, st->has_h ? (const uint32_t*)BL : nullptr, 2, n + 1, nullptr, nullptr, ri))) return rc; }   // sums stay XYZZ in c->wsum
+  *seq = ++c->mbox_seq;
+  LAUNCH(c, "k_points_to_host", k_bullet_to_host, 1, 128, (const uint32_t*)c->wsum.p, (const uint32_t*)st->d_dots, c->mbox + SC_MBOX_FINALS, c->mbox + SC_MBOX_FLAGS + SC_PACK_MAX, *seq);
+  LAUNCHCHK(c);
+  return SBN_OK;
+}
+// the one host wait of such a commit: the two points as canonical affine bytes, the two scalars that travelled with them
+static int bullet_rows_collect(sbn_ctx* c, uint32_t seq, uint8_t P0_xy[64], int* P0_inf, uint8_t P1_xy[64], int* P1_inf, uint8_t s0[32], uint8_t s1[32]) {
+  int rc;
+  uint32_t* hfin = c->mbox + SC_MBOX_FINALS;
+  if ((rc = sc_flag_wait(c, c->mbox + SC_MBOX_FLAGS + SC_PACK_MAX, seq))) return rc;
+  sbn_host::Pt S[2]; memcpy(S, hfin, 256);
+  int il = 0, ir = 0;
+  sbn_host::to_affine_bytes2(sbn_host::pt_from_device(S[0]), sbn_host::pt_from_device(S[1]), P0_xy, &il, P1_xy, &ir);   // one binary-Euclid inversion (2-3 us on a host core) for both points
+  if (P0_inf) *P0_inf = il;
+  if (P1_inf) *P1_inf = ir;
+  memcpy(s0, (const uint8_t*)hfin + 256, 32); memcpy(s1, (const uint8_t*)hfin + 288, 32);
+  return SBN_OK;
+}
 // One round's device work and its one host wait: [FOLD: the folds with the previous challenge] + the cross dot products + the two commit
 // rows in ONE launch (k_bullet_prep), the two-row commit over the original generators (bullet.rs:77-78: L = MSM(a_L, G_R) + c_L*Q + blind_L*H,
 // R likewise), and the results (two XYZZ sums, c_L, c_R) through the host mailbox — no copy, no stream synchronisation.
@@ -233,7 +260,7 @@ static int bullet_round_locked(sbn_ctx* c, sbn_bullet* st, bool fold, const uint
   uint8_t* WL = (uint8_t*)st->d_w; uint8_t* WR = WL + 32 * (n + 1); uint8_t* BL = WR + 32 * (n + 1);
   const uint32_t nbd = (uint32_t)std::max<size_t>(1, (h + 255) / 256);
   if ((rc = ensure(c, c->sc_partial, std::max<size_t>(4096, (size_t)nbd * 96)))) return rc;
-  if ((rc = ensure(c, c->wsum, 4096))) return rc;                       // (the commit asks for 2 x 128 B: sized here so that it never reallocates mid-round)
+  if ((rc = ensure(c, c->wsum, 4096))) return rc;                       // (sized ahead of the launches below, as bullet_rows_launch does)
   if ((rc = sc_tickets(c))) return rc;
   ScScalar su, si, sl, sr; memset(&su, 0, sizeof su); memset(&si, 0, sizeof si); memset(&sl, 0, sizeof sl); memset(&sr, 0, sizeof sr);
   if (fold) { su = scs_from(sbn_host::fr::to_dev_mont(el_from(u))); si = scs_from(sbn_host::fr::to_dev_mont(el_from(u_inv))); }
@@ -248,20 +275,9 @@ static int bullet_round_locked(sbn_ctx* c, sbn_bullet* st, bool fold, const uint
   if (fold) LAUNCH(c, "k_bullet_prep", k_bullet_prep<true>, gx, 256, A, n, m, su, si, qmode, st->qs, sl, sr, nbd);
   else LAUNCH(c, "k_bullet_prep", k_bullet_prep<false>, gx, 256, A, n, m, su, si, qmode, st->qs, sl, sr, nbd);
   if (fold) { std::swap(st->d_a, st->d_a2); std::swap(st->d_b, st->d_b2); st->m = m; }
-  { RowInfo ri; ri.internal_rows = true;
-    if ((rc = commit_rows_launch(c, st->ext, (const uint32_t*)WL, st->has_h ? (const uint32_t*)BL : nullptr, 2, n + 1, nullptr, nullptr, ri))) return rc; }   // sums stay XYZZ in c->wsum
-  const uint32_t seq = ++c->mbox_seq;
-  uint32_t* hfin = c->mbox + SC_MBOX_FINALS;
-  LAUNCH(c, "k_points_to_host", k_bullet_to_host, 1, 128, (const uint32_t*)c->wsum.p, (const uint32_t*)st->d_dots, hfin, c->mbox + SC_MBOX_FLAGS + SC_PACK_MAX, seq);
-  LAUNCHCHK(c);
-  if ((rc = sc_flag_wait(c, c->mbox + SC_MBOX_FLAGS + SC_PACK_MAX, seq))) return rc;
-  sbn_host::Pt S[2]; memcpy(S, hfin, 256);
-  int il = 0, ir = 0;
-  sbn_host::to_affine_bytes2(sbn_host::pt_from_device(S[0]), sbn_host::pt_from_device(S[1]), L_xy, &il, R_xy, &ir);   // one binary-Euclid inversion (2-3 us on a host core) for both points
-  if (L_inf) *L_inf = il;
-  if (R_inf) *R_inf = ir;
-  memcpy(c_L, (const uint8_t*)hfin + 256, 32); memcpy(c_R, (const uint8_t*)hfin + 288, 32);
-  return SBN_OK;
+  uint32_t seq = 0;
+  if ((rc = bullet_rows_launch(c, st, &seq))) return rc;
+  return bullet_rows_collect(c, seq, L_xy, L_inf, R_xy, R_inf, c_L, c_R);
 }
 extern "C" {
 

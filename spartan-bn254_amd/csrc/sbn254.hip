@@ -8,6 +8,7 @@
 //   KZG commit / open (--features kzg)  src/kzg.rs                                       -> sbn_kzg_* / sbn_poly_div_linear
 //   R1CSShape multiply_vec / evaluate, compute_eval_table_sparse  src/r1cs.rs:126-163  -> sbn_r1cs_*
 //   multi_sparse_to_dense_rep, AddrTimestamps::new      src/sparse_mlpoly_full.rs:120-174, 211-243  -> sbn_dense_*
+//   PolyEvalProof::prove, DotProductProofLog::prove     src/hyrax.rs:65-116, src/nizk/mod.rs:439-522 -> sbn_polyeval_prove / sbn_joint_opening_prove
 // There is no CPU fallback in this file: every entry point needs the gfx950 device.
 #include "../../include/sbn254.h"
 #include "host_field.hpp"
@@ -21,12 +22,14 @@
 #include "r1cs_kernels.cuh"
 #include "dense_kernels.cuh"
 #include "transcript_kernels.cuh"
+#include "polyeval_kernels.cuh"
 #include "host_keccak.hpp"
 #include "host_strobe.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -51,6 +54,7 @@ using namespace sbn;
 #include "abi_sumcheck.inc"
 #include "abi_product_proof.inc"
 #include "abi_bullet.inc"
+#include "abi_polyeval.inc"
 #include "abi_group.inc"
 #include "abi_kzg.inc"
 #include "abi_r1cs.inc"
