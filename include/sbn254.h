@@ -306,6 +306,37 @@ int sbn_joint_opening_prove(sbn_ctx* ctx, const sbn_bases* gens, const sbn_table
                             uint8_t* out_challenges, uint8_t out_joint_claim[32], uint8_t* out_proof,
                             uint8_t out_Cx_xy[64], int* Cx_is_inf, uint8_t out_Cy_xy[64], int* Cy_is_inf);
 
+/* ---- the two ZK sumchecks of R1CSProof::prove (r1csproof.rs:295, :394) in ONE call each: ZKSumcheckInstanceProof::
+ *      prove_cubic_with_additive_term (sumcheck.rs:465-649) and ::prove_quad (sumcheck.rs:657-811), with UniPoly::from_evals, the four
+ *      commitments of a round and DotProductProof::prove (nizk/mod.rs:306-366) inside, the Merlin transcript included ----
+ * num_rounds = log2 of the tables' length; n = the coefficient count of a round polynomial: 4 (r1cs), 3 (quad).
+ *   tables:  equal length, a power of two >= 2, distinct handles.  They are bound IN PLACE, as sbn_sc_bind_eval_* / sbn_bind_top do, and end with
+ *            length 1; out_finals = their [0] in argument order (sumcheck.rs:646, :808), canonical.
+ *   gens_1:  one generator with h.   gens_4 / gens_3: n generators with h.  The two h may differ (R1CSSumcheckGens::new clones gens_pc's gens_1
+ *            and derives gens_3 / gens_4 from its label): no shared h is assumed.  The derived set gens_n.G || gens_n.h || gens_1.G[0] || gens_1.h
+ *            and its lookup table are built on the first call with a (gens_1, gens_n) pair and owned by the gens_n handle.
+ *   rnd:     num_rounds * (n + 4) x 32 canonical, the caller's RandomTape draws in the reference's order: blinds_poly[num_rounds],
+ *            blinds_evals[num_rounds], then per round d_vec[n], r_delta, r_beta (nizk/mod.rs:326-328).
+ *   out_proof: num_rounds x (6 + n) x 32, round-major: comm_poly, comm_eval, delta, beta (compressed as sbn_g1_compress gives them), then
+ *            z[n], z_delta, z_beta (canonical).   out_r: num_rounds x 32.   out_blind = blinds_evals[num_rounds - 1].
+ * Transcript, byte for byte the reference's, per round: comm_poly, challenge_scalar("challenge_nextround"), comm_claim_per_round, comm_eval,
+ * challenge_vector("combine_two_claims_to_one", 2), protocol-name "dot product proof", Cx (= comm_poly, computed once), Cy, every entry of a as its
+ * own "a" message, delta, beta, challenge_scalar("c").
+ * Every group element is a row of a two-row commit over the derived set: three commits a round ({comm_poly, delta}, {comm_eval [, comm_claim]},
+ * {Cy, beta}), the first queued behind the round kernel with no host wait in between; no scalar multiplication runs on the CPU.
+ * SBN_EINVAL: a null pointer, unequal / non-power-of-two / < 2 lengths, a table passed twice, a generator handle of the wrong size or without h, any
+ * scalar in (claim, blind_claim, rnd) not canonical — nothing has been launched then: tables and `tr` are unchanged.  `tr` moves on only if the
+ * whole call succeeded; a failure after the first launch leaves the tables partly bound.  Same bytes as the round loop over sbn_sc_eval_*,
+ * sbn_sc_bind_eval_*, sbn_bind_top, sbn_unipoly_from_evals, one-row sbn_commit_rows and sbn_transcript_* with the same draws. */
+int sbn_zk_sumcheck_prove_r1cs(sbn_ctx* ctx, sbn_table* tau, sbn_table* Az, sbn_table* Bz, sbn_table* Cz,
+                               const sbn_bases* gens_1, const sbn_bases* gens_4,
+                               const uint8_t claim[32], const uint8_t blind_claim[32], const uint8_t* rnd, sbn_transcript* tr,
+                               uint8_t* out_proof, uint8_t* out_r, uint8_t out_finals[128], uint8_t out_blind[32]);
+int sbn_zk_sumcheck_prove_quad(sbn_ctx* ctx, sbn_table* Z, sbn_table* ABC,
+                               const sbn_bases* gens_1, const sbn_bases* gens_3,
+                               const uint8_t claim[32], const uint8_t blind_claim[32], const uint8_t* rnd, sbn_transcript* tr,
+                               uint8_t* out_proof, uint8_t* out_r, uint8_t out_finals[64], uint8_t out_blind[32]);
+
 /* ---- network construction pieces ----
  * sbn_hash_layer and sbn_product_layer only enqueue work (their outputs are consumed by later calls on the same context, which
  * are ordered behind them); every call that returns data to the host waits for it. ----

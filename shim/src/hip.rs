@@ -31,7 +31,11 @@ use crate::group::GroupElement;
 use crate::hyrax::DensePolynomial;
 use crate::scalar::Scalar;
 use crate::sparse_mlpoly::SparseMatPolynomial;
-use crate::sumcheck::SumcheckInstanceProof;
+use crate::group::CompressedGroup;
+use crate::nizk::DotProductProof;
+use crate::random::RandomTape;
+use crate::sumcheck::{SumcheckInstanceProof, ZKSumcheckInstanceProof};
+use ark_serialize::CanonicalDeserialize;
 use crate::transcript::{AppendToTranscript, ProofTranscript};
 use crate::unipoly::{CompressedUniPoly, UniPoly};
 
@@ -137,6 +141,8 @@ extern "C" {
     pub fn sbn_bullet_finish(ctx: *mut sbn_ctx, st: *mut sbn_bullet, a_hat: *mut u8, b_hat: *mut u8, g_hat_xy: *mut u8, g_hat_is_inf: *mut c_int) -> c_int;
     pub fn sbn_polyeval_prove(ctx: *mut sbn_ctx, gens: *const sbn_bases, z: *const sbn_table, blinds: *const u8, r: *const u8, ell: usize, zr: *const u8, blind_zr: *const u8, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8, out_cx_xy: *mut u8, cx_is_inf: *mut c_int, out_cy_xy: *mut u8, cy_is_inf: *mut c_int) -> c_int;
     pub fn sbn_joint_opening_prove(ctx: *mut sbn_ctx, gens: *const sbn_bases, z: *const sbn_table, evals: *const u8, count: usize, label_evals: *const u8, label_evals_len: usize, label_chal: *const u8, label_chal_len: usize, label_claim: *const u8, label_claim_len: usize, r: *const u8, ell_r: usize, rnd: *const u8, tr: *mut sbn_transcript, out_challenges: *mut u8, out_joint_claim: *mut u8, out_proof: *mut u8, out_cx_xy: *mut u8, cx_is_inf: *mut c_int, out_cy_xy: *mut u8, cy_is_inf: *mut c_int) -> c_int;
+    pub fn sbn_zk_sumcheck_prove_r1cs(ctx: *mut sbn_ctx, tau: *mut sbn_table, az: *mut sbn_table, bz: *mut sbn_table, cz: *mut sbn_table, gens_1: *const sbn_bases, gens_4: *const sbn_bases, claim: *const u8, blind_claim: *const u8, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8, out_r: *mut u8, out_finals: *mut u8, out_blind: *mut u8) -> c_int;
+    pub fn sbn_zk_sumcheck_prove_quad(ctx: *mut sbn_ctx, z: *mut sbn_table, abc: *mut sbn_table, gens_1: *const sbn_bases, gens_3: *const sbn_bases, claim: *const u8, blind_claim: *const u8, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8, out_r: *mut u8, out_finals: *mut u8, out_blind: *mut u8) -> c_int;
     pub fn sbn_hash_layer(ctx: *mut sbn_ctx, addr_dev: *const c_void, val: *const sbn_table, ts_dev: *const c_void, ts_add: u32, r_hash: *const u8, r_multiset: *const u8, out: *mut *mut sbn_table) -> c_int;
     pub fn sbn_hash_layer_pair(ctx: *mut sbn_ctx, addr_dev: *const c_void, val: *const sbn_table, ts_a_dev: *const c_void, ts_a_add: u32, ts_b_dev: *const c_void, ts_b_add: u32, r_hash: *const u8, r_multiset: *const u8, out_a: *mut *mut sbn_table, out_b: *mut *mut sbn_table) -> c_int;
     pub fn sbn_product_layer(ctx: *mut sbn_ctx, input: *const sbn_table, out: *mut *mut sbn_table) -> c_int;
@@ -672,6 +678,91 @@ impl QuadRounds {
         check(unsafe { sbn_table_read0_many(ctx(), ts.as_ptr(), ts.len(), out.as_mut_ptr()) });
         vec![sc(&out[..32]), sc(&out[32..64])]
     }
+}
+
+// ---- the two ZK sumchecks of R1CSProof::prove in ONE foreign call each (sbn_zk_sumcheck_prove_r1cs / _quad) -----------------------
+// The library runs the rounds, UniPoly::from_evals, the four commitments of a round, DotProductProof::prove and the transcript; this side
+// draws the RandomTape in the reference's order (blinds_poly, blinds_evals, then per round d_vec, r_delta, r_beta: sumcheck.rs:483-484,
+// nizk/mod.rs:326-328) and rebuilds ZKSumcheckInstanceProof from the bytes.  DotProductProof keeps its fields private: it is read back
+// through its own CanonicalDeserialize (delta, beta as compressed points, z as a length-prefixed vector, z_delta, z_beta).
+fn zk_draws(random_tape: &mut RandomTape, num_rounds: usize, n: usize) -> Vec<Scalar> {
+    let mut rnd = random_tape.random_vector(b"blinds_poly", num_rounds);
+    rnd.extend(random_tape.random_vector(b"blinds_evals", num_rounds));
+    for _ in 0..num_rounds {
+        rnd.extend(random_tape.random_vector(b"d_vec", n));
+        rnd.push(random_tape.random_scalar(b"r_delta"));
+        rnd.push(random_tape.random_scalar(b"r_beta"));
+    }
+    rnd
+}
+fn zk_proof_from_bytes(proof: &[u8], num_rounds: usize, n: usize) -> ZKSumcheckInstanceProof {
+    let stride = (6 + n) * 32;
+    let point = |b: &[u8]| CompressedGroup::from_bytes(b).decompress().expect("sbn254 returned a point that does not decompress");
+    let (mut comm_polys, mut comm_evals, mut proofs) = (Vec::new(), Vec::new(), Vec::new());
+    for j in 0..num_rounds {
+        let p = &proof[stride * j..stride * (j + 1)];
+        comm_polys.push(point(&p[..32]));
+        comm_evals.push(point(&p[32..64]));
+        let mut ser: Vec<u8> = p[64..128].to_vec();                                   // delta, beta
+        ser.extend_from_slice(&(n as u64).to_le_bytes());                             // z: Vec<Scalar>
+        ser.extend_from_slice(&p[128..stride]);                                       // z[n], z_delta, z_beta
+        proofs.push(DotProductProof::deserialize_compressed(&ser[..]).expect("DotProductProof from the library's bytes"));
+    }
+    ZKSumcheckInstanceProof::new(comm_polys, comm_evals, proofs)
+}
+/// ZKSumcheckInstanceProof::prove_cubic_with_additive_term (sumcheck.rs:465-649), comb_func = tau * (Az * Bz - Cz), with a `DevTranscript`
+#[allow(non_snake_case)]
+pub fn zk_prove_r1cs(
+    claim: &Scalar,
+    blind_claim: &Scalar,
+    num_rounds: usize,
+    poly_tau: &mut DensePolynomial,
+    poly_Az: &mut DensePolynomial,
+    poly_Bz: &mut DensePolynomial,
+    poly_Cz: &mut DensePolynomial,
+    gens_1: &MultiCommitGens,
+    gens_n: &MultiCommitGens,
+    transcript: &mut DevTranscript,
+    random_tape: &mut RandomTape,
+) -> (ZKSumcheckInstanceProof, Vec<Scalar>, Vec<Scalar>, Scalar) {
+    assert_eq!(poly_tau.len(), 1usize << num_rounds);
+    let rnd = scalars_canonical(&zk_draws(random_tape, num_rounds, 4));
+    let t = [Table::of(poly_tau), Table::of(poly_Az), Table::of(poly_Bz), Table::of(poly_Cz)];
+    let (mut proof, mut rs, mut fin, mut bl) = (vec![0u8; 320 * num_rounds], vec![0u8; 32 * num_rounds], [0u8; 128], [0u8; 32]);
+    check(unsafe {
+        sbn_zk_sumcheck_prove_r1cs(ctx(), t[0].0, t[1].0, t[2].0, t[3].0, gens_1.dev.bases(gens_1), gens_n.dev.bases(gens_n), claim.to_bytes().as_ptr(),
+                                   blind_claim.to_bytes().as_ptr(), rnd.as_ptr(), transcript.0, proof.as_mut_ptr(), rs.as_mut_ptr(), fin.as_mut_ptr(), bl.as_mut_ptr())
+    });
+    let r: Vec<Scalar> = (0..num_rounds).map(|j| sc(&rs[32 * j..32 * j + 32])).collect();
+    let finals: Vec<Scalar> = (0..4).map(|i| sc(&fin[32 * i..32 * i + 32])).collect();
+    poly_tau.set_final(finals[0]); poly_Az.set_final(finals[1]); poly_Bz.set_final(finals[2]); poly_Cz.set_final(finals[3]);
+    (zk_proof_from_bytes(&proof, num_rounds, 4), r, finals, sc(&bl))
+}
+/// ZKSumcheckInstanceProof::prove_quad (sumcheck.rs:657-811), comb_func = z * ABC, with a `DevTranscript`
+#[allow(non_snake_case)]
+pub fn zk_prove_quad(
+    claim: &Scalar,
+    blind_claim: &Scalar,
+    num_rounds: usize,
+    poly_z: &mut DensePolynomial,
+    poly_ABC: &mut DensePolynomial,
+    gens_1: &MultiCommitGens,
+    gens_n: &MultiCommitGens,
+    transcript: &mut DevTranscript,
+    random_tape: &mut RandomTape,
+) -> (ZKSumcheckInstanceProof, Vec<Scalar>, Vec<Scalar>, Scalar) {
+    assert_eq!(poly_z.len(), 1usize << num_rounds);
+    let rnd = scalars_canonical(&zk_draws(random_tape, num_rounds, 3));
+    let t = [Table::of(poly_z), Table::of(poly_ABC)];
+    let (mut proof, mut rs, mut fin, mut bl) = (vec![0u8; 288 * num_rounds], vec![0u8; 32 * num_rounds], [0u8; 64], [0u8; 32]);
+    check(unsafe {
+        sbn_zk_sumcheck_prove_quad(ctx(), t[0].0, t[1].0, gens_1.dev.bases(gens_1), gens_n.dev.bases(gens_n), claim.to_bytes().as_ptr(),
+                                   blind_claim.to_bytes().as_ptr(), rnd.as_ptr(), transcript.0, proof.as_mut_ptr(), rs.as_mut_ptr(), fin.as_mut_ptr(), bl.as_mut_ptr())
+    });
+    let r: Vec<Scalar> = (0..num_rounds).map(|j| sc(&rs[32 * j..32 * j + 32])).collect();
+    let finals = vec![sc(&fin[..32]), sc(&fin[32..64])];
+    poly_z.set_final(finals[0]); poly_ABC.set_final(finals[1]);
+    (zk_proof_from_bytes(&proof, num_rounds, 3), r, finals, sc(&bl))
 }
 
 // ---- BulletReductionProof::prove (nizk/bullet.rs:41-126) ---------------------------------------------------------------------

@@ -18,7 +18,7 @@ EXPORTED_SYMBOLS = [
     "sbn_sumcheck_begin", "sbn_sumcheck_begin_eq", "sbn_sumcheck_round", "sbn_sumcheck_len", "sbn_sumcheck_finish", "sbn_sumcheck_free",
     "sbn_transcript_new", "sbn_transcript_clone", "sbn_transcript_free", "sbn_transcript_append_message", "sbn_transcript_challenge_bytes", "sbn_transcript_challenge_scalar",
     "sbn_transcript_state", "sbn_transcript_from_state", "sbn_fr_from_wide", "sbn_sumcheck_prove", "sbn_product_proof_prove",
-    "sbn_polyeval_prove", "sbn_joint_opening_prove", "sbn_prof_last_polyeval",
+    "sbn_polyeval_prove", "sbn_joint_opening_prove", "sbn_prof_last_polyeval", "sbn_zk_sumcheck_prove_r1cs", "sbn_zk_sumcheck_prove_quad",
     "sbn_group_create", "sbn_group_destroy", "sbn_group_size", "sbn_group_ctx", "sbn_group_last_error", "sbn_group_bases_upload", "sbn_group_gens_new", "sbn_group_bases_precompute",
     "sbn_group_bases_free", "sbn_group_commit_rows", "sbn_group_commit_rows_dev", "sbn_group_gather_commit", "sbn_group_msm", "sbn_group_bases_upload_ranges", "sbn_group_bases_synthetic_ranges", "sbn_group_range", "sbn_group_msm_bases", "sbn_group_msm_bases_dev",
     "sbn_eq_evals", "sbn_hash_layer", "sbn_hash_layer_pair", "sbn_product_layer", "sbn_product_circuit", "sbn_product_circuit_many", "sbn_table_halves", "sbn_table_slice", "sbn_table_dot", "sbn_table_evaluate", "sbn_table_evaluate_many", "sbn_table_bound", "sbn_gather_merge", "sbn_gather_merge_rows", "sbn_commit_table", "sbn_bullet_begin", "sbn_bullet_begin_scaled", "sbn_bullet_free", "sbn_bullet_len", "sbn_bullet_cross", "sbn_bullet_fold_cross", "sbn_bullet_fold", "sbn_bullet_finish", "sbn_prof_enable", "sbn_prof_reset", "sbn_prof_count", "sbn_prof_get", "sbn_prof_last_job",
@@ -84,6 +84,8 @@ def lib():
         L.sbn_product_proof_prove.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
         L.sbn_polyeval_prove.argtypes = [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 9
         L.sbn_joint_opening_prove.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p, C.c_size_t] * 3 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 9
+        L.sbn_zk_sumcheck_prove_r1cs.argtypes = [C.c_void_p] * 15
+        L.sbn_zk_sumcheck_prove_quad.argtypes = [C.c_void_p] * 13
         L.sbn_dense_audit_ts_dev.restype = C.c_void_p; L.sbn_dense_audit_ts_dev.argtypes = [C.c_void_p, C.c_int]
         for name in ("sbn_dense_comb_ops", "sbn_dense_comb_mem"):
             getattr(L, name).restype = C.c_void_p; getattr(L, name).argtypes = [C.c_void_p]
@@ -828,6 +830,23 @@ class Context:
         out = (C.c_double * 3)()
         self._chk(lib().sbn_prof_last_polyeval(self.h, out), "sbn_prof_last_polyeval")
         return tuple(out)
+
+    # ---- the two ZK sumchecks of R1CSProof::prove in one call each (sumcheck.rs:465-811, nizk/mod.rs:306-366)
+    def _zk_sumcheck_prove(self, fn, name, tables, n, gens_1, gens_n, claim, blind_claim, rnd, tr):
+        rounds = max(len(tables[0]).bit_length() - 1, 0)
+        proof = (C.c_uint8 * max((6 + n) * 32 * rounds, 1))(); rs = (C.c_uint8 * max(32 * rounds, 1))()
+        fin = (C.c_uint8 * (32 * len(tables)))(); bl = (C.c_uint8 * 32)()
+        self._chk(fn(self.h, *[t.h for t in tables], gens_1.h, gens_n.h, _ptr(claim), _ptr(blind_claim), _ptr(rnd), tr.h, proof, rs, fin, bl), name)
+        return bytes(proof[:(6 + n) * 32 * rounds]), bytes(rs[:32 * rounds]), bytes(fin), bytes(bl)
+
+    def zk_sumcheck_prove_r1cs(self, tau, Az, Bz, Cz, gens_1, gens_4, claim, blind_claim, rnd, tr):
+        """prove_cubic_with_additive_term (sbn_zk_sumcheck_prove_r1cs) -> (proof: rounds x 10 x 32, challenges, finals [tau, Az, Bz, Cz], blinds_evals[-1]);
+        the tables are bound in place down to length 1; rnd: rounds x 8 scalars; `tr` (Transcript) moves on"""
+        return self._zk_sumcheck_prove(lib().sbn_zk_sumcheck_prove_r1cs, "sbn_zk_sumcheck_prove_r1cs", (tau, Az, Bz, Cz), 4, gens_1, gens_4, claim, blind_claim, rnd, tr)
+
+    def zk_sumcheck_prove_quad(self, Z, ABC, gens_1, gens_3, claim, blind_claim, rnd, tr):
+        """prove_quad (sbn_zk_sumcheck_prove_quad) -> (proof: rounds x 9 x 32, challenges, finals [Z, ABC], blinds_evals[-1]); rnd: rounds x 7 scalars"""
+        return self._zk_sumcheck_prove(lib().sbn_zk_sumcheck_prove_quad, "sbn_zk_sumcheck_prove_quad", (Z, ABC), 3, gens_1, gens_3, claim, blind_claim, rnd, tr)
 
     # ---- KZG mode (kzg.rs): the SRS is a Bases handle, polynomials are the first n entries of a Table
     def kzg_srs_upload(self, powers_xy, flags=0):

@@ -109,6 +109,66 @@ int sbn_bind_top(sbn_ctx* c, sbn_table* t, const uint8_t r[32]) { sbn_table* one
 
 }  // extern "C" (templates need C++ linkage)
 #define SC_SINGLE_LAUNCH_MAX (c->sck.single_max)    // table halves up to this many entries take the single-launch round (SBN_SC_SINGLE_MAX overrides)
+// ---- the launch part of a round, shared by sbn_sc_eval_* / sbn_sc_bind_eval_* (results to the host mailbox) and the one-call provers that
+// keep a round's sums on the device (abi_zk_sumcheck.inc): grids, kernel-variant thresholds, second buffers.  `res` is where the last block
+// of an instance leaves its sums (ticketed fold), `seq` the sequence number written behind them.
+static inline unsigned sc_eval_grid(sbn_ctx* c, size_t half, size_t count) {      // a few block rounds over the chip: see sc_fused_grid
+  size_t want = (4096 + count - 1) / count, cap = (half + 255) / 256;
+  if (c->sck.grid) want = c->sck.grid;
+  return (unsigned)std::max<size_t>(1, std::min(std::min(want, cap), (size_t)1024));
+}
+static inline bool sc_fused_single(sbn_ctx* c, size_t q) { return q <= SC_SINGLE_LAUNCH_MAX / 2; }
+// grid: a few block rounds over the chip (256 CUs x 4 blocks), so that each thread runs many indices and the reduction at the
+// end of the kernel is amortised; never more blocks than there are groups of 256 indices
+static inline unsigned sc_fused_grid(sbn_ctx* c, size_t q, size_t count, bool single) {
+  // whole block rounds: count * gx just under a multiple of the resident blocks (256 CUs x waves per SIMD), so that no nearly
+  // empty last round is left (4104 blocks on 1024 slots would cost a fifth round for 8 blocks)
+  // Four block rounds (interleaved sweep on one box, all six streaming rounds of a 2^21 sumcheck, SBN_SC_BLOCK_ROUNDS = 1 / 2 / 3 /
+  // 4 / 6: 2.60-2.63 / 2.50-2.56 / 2.46-2.53 / 2.43-2.44 / 2.56-2.63 ms)
+  const size_t br = single ? 4 : c->sck.block_rounds;
+  size_t want = std::max<size_t>(1, br * 256 * 2 / count), cap = (q + 255) / 256;
+  if (c->sck.grid) want = c->sck.grid;
+  return (unsigned)std::max<size_t>(1, std::min(std::min(want, cap), (size_t)1024));
+}
+// the second buffer of a table about to be bound from `len` to len / 2 entries
+static int sc_second_buffer(sbn_ctx* c, sbn_table* t, size_t len) {
+  if (t->cap2 >= len / 2) return SBN_OK;
+  if (t->d2) { HIPCHK(c, hipStreamSynchronize(c->stream)); if (t->owned2) pool_put(c, t->d2, t->cap2 * 32); t->d2 = nullptr; t->cap2 = 0; }
+  t->owned2 = true;
+  size_t _gb2 = 0; hipError_t e = pool_get(c, (len / 2) * 32, &t->d2, &_gb2);
+  if (e != hipSuccess) return fail(c, SBN_ENOMEM, "hipMalloc second table buffer: %s", hipGetErrorString(e));
+  t->cap2 = _gb2 / 32;
+  return SBN_OK;
+}
+static inline void sc_swap_bound(sbn_table* t, size_t len) { std::swap(t->d, t->d2); std::swap(t->cap, t->cap2); std::swap(t->owned, t->owned2); t->len = len / 2; }
+// the packed (pointers as kernel arguments) eval round in one launch; c->sc_partial holds count * gx * 96 bytes, the tickets exist
+template <int KIND>
+static int sc_eval_launch(sbn_ctx* c, const ScArgsPack& pack, size_t count, size_t half, unsigned gx, uint32_t* res, uint32_t seq) {
+  const char* nm = KIND == KIND_CUBIC ? "k_sc_eval_cubic" : KIND == KIND_R1CS ? "k_sc_eval_r1cs" : "k_sc_eval_quad";
+  LAUNCH(c, nm, k_sc_eval<KIND>, dim3(gx, (unsigned)count), 256, (const ScArgs*)nullptr, pack, half, (uint32_t*)c->sc_partial.p, (uint32_t*)c->sc_tickets.p, res, seq);
+  LAUNCHCHK(c);
+  return SBN_OK;
+}
+// the packed fused bind + eval round in one launch: single (sc_fused_single) the four-lanes-per-index kernel up to q = 128 and the
+// lane-per-index kernel above, else the streaming kernel (the caller has checked that its table pattern is one it is built for)
+template <int KIND>
+static int sc_fused_launch(sbn_ctx* c, const ScFusedPack& pack, size_t count, size_t q, unsigned gx, bool single, const ScScalar& rs, uint32_t* res, uint32_t seq) {
+  const ScFusedArgs* dargs = nullptr;
+  const char* nm = KIND == KIND_CUBIC ? "k_sc_bind_eval_cubic" : KIND == KIND_R1CS ? "k_sc_bind_eval_r1cs" : "k_sc_bind_eval_quad";
+  const char* nms = KIND == KIND_CUBIC ? "k_sc_bind_eval_cubic_stream" : KIND == KIND_R1CS ? "k_sc_bind_eval_r1cs_stream" : "k_sc_bind_eval_quad_stream";   // profiled apart from the single-launch rounds
+  if (!single)
+    LAUNCH(c, nms, (k_sc_bind_eval_pf<KIND>), dim3(gx, (unsigned)count), 256, dargs, pack, q, rs, (uint32_t*)c->sc_partial.p, (uint32_t*)c->sc_tickets.p, res, seq);
+  else if (q <= 128) {
+    // the last rounds of a sumcheck: four lanes per index (k_sc_bind_eval_tiny), one block of up to 512 lanes per instance
+    // (measured per round at 18 instances: 64 / 128 / 256 indices 10.5 / 13.8 / 21.8 us against 16 us for the lane-per-index kernel)
+    const unsigned bt = (unsigned)std::max<size_t>(64, (4 * q + 63) / 64 * 64);
+    LAUNCH(c, nm, (k_sc_bind_eval_tiny<KIND>), dim3(1, (unsigned)count), bt, dargs, pack, q, rs, res, seq);
+  } else
+    // (the 2-waves-per-SIMD build: no spills, hence no scratch segment — these launches are latency, not occupancy)
+    LAUNCH(c, nm, (k_sc_bind_eval<KIND, 2>), dim3(gx, (unsigned)count), 256, dargs, pack, q, rs, (uint32_t*)c->sc_partial.p, (uint32_t*)c->sc_tickets.p, res, seq);
+  LAUNCHCHK(c);
+  return SBN_OK;
+}
 template <int KIND>
 static int sc_eval_common(sbn_ctx* c, const sbn_table* const* const* cols, int ncols, size_t count, uint8_t* out) {
   // cols[j][i] = table j of instance i
@@ -120,12 +180,7 @@ static int sc_eval_common(sbn_ctx* c, const sbn_table* const* const* cols, int n
   if (len < 2) return fail(c, SBN_EINVAL, "sumcheck eval: no variable left");
   const size_t half = len / 2;
   int rc;
-  unsigned gx;          // a few block rounds over the chip: see sc_bind_eval_common
-  {
-    size_t want = (4096 + count - 1) / count, cap = (half + 255) / 256;
-    if (c->sck.grid) want = c->sck.grid;
-    gx = (unsigned)std::max<size_t>(1, std::min(std::min(want, cap), (size_t)1024));
-  }
+  const unsigned gx = sc_eval_grid(c, half, count);
   if ((rc = ensure(c, c->sc_partial, (size_t)count * gx * 96))) return rc;
   const char* nm = KIND == KIND_CUBIC ? "k_sc_eval_cubic" : KIND == KIND_R1CS ? "k_sc_eval_r1cs" : "k_sc_eval_quad";
   uint8_t* hres;
@@ -148,8 +203,7 @@ static int sc_eval_common(sbn_ctx* c, const sbn_table* const* const* cols, int n
     if ((rc = sc_tickets(c))) return rc;
     hres = (uint8_t*)c->mbox;
     const uint32_t seq = ++c->mbox_seq;
-    LAUNCH(c, nm, k_sc_eval<KIND>, dim3(gx, (unsigned)count), 256, dargs, pack, half, (uint32_t*)c->sc_partial.p, (uint32_t*)c->sc_tickets.p, c->mbox, seq);
-    LAUNCHCHK(c);
+    if ((rc = sc_eval_launch<KIND>(c, pack, count, half, gx, c->mbox, seq))) return rc;
     if ((rc = sc_mbox_wait(c, count, seq))) return rc;
   } else {
     if ((rc = ensure(c, c->sc_out, std::max<size_t>(4096, count * 96)))) return rc;
@@ -202,7 +256,7 @@ static int sc_bind_eval_common(sbn_ctx* c, sbn_table* const* const* cols, int nc
   int rc;
   if (!fr_canonical(r)) return fail(c, SBN_EINVAL, "challenge scalar is not canonical (>= r)");
   const bool packed = count <= (size_t)SC_PACK_MAX;
-  const bool single = packed && q <= SC_SINGLE_LAUNCH_MAX / 2;      // see sc_eval_common
+  const bool single = packed && sc_fused_single(c, q);
   if ((rc = ensure_pin(c, 4096 + count * sizeof(ScFusedArgs) + count * 96))) return rc;
   // the challenge in Montgomery form, once, on the host (r * 2^261 mod the group order: this library's R)
   ScScalar rs;
@@ -215,15 +269,7 @@ static int sc_bind_eval_common(sbn_ctx* c, sbn_table* const* const* cols, int nc
     auto it = std::find(distinct.begin(), distinct.end(), t);
     if (it == distinct.end()) { distinct.push_back(t); uses.push_back(1); } else uses[(size_t)(it - distinct.begin())]++;
   }
-  for (sbn_table* t : distinct) {
-    if (t->cap2 < len / 2) {
-      if (t->d2) { HIPCHK(c, hipStreamSynchronize(c->stream)); if (t->owned2) pool_put(c, t->d2, t->cap2 * 32); t->d2 = nullptr; t->cap2 = 0; }
-      t->owned2 = true;
-      size_t _gb2 = 0; hipError_t e = pool_get(c, (len / 2) * 32, &t->d2, &_gb2);
-      if (e != hipSuccess) return fail(c, SBN_ENOMEM, "hipMalloc second table buffer: %s", hipGetErrorString(e));
-      t->cap2 = _gb2 / 32;
-    }
-  }
+  for (sbn_table* t : distinct) if ((rc = sc_second_buffer(c, t, len))) return rc;
   std::vector<char> prebound(distinct.size(), 0);
   if (!single)
     for (size_t k = 0; k < distinct.size(); k++) if (uses[k] >= 2) {
@@ -242,19 +288,7 @@ static int sc_bind_eval_common(sbn_ctx* c, sbn_table* const* const* cols, int nc
     ha[i].src[j] = (const uint32_t*)t->d;
     if (!has_writer[k]) { ha[i].dst[j] = (uint32_t*)t->d2; has_writer[k] = 1; }
   }
-  // grid: a few block rounds over the chip (256 CUs x 4 blocks), so that each thread runs many indices and the reduction at the
-  // end of the kernel is amortised; never more blocks than there are groups of 256 indices
-  unsigned gx;
-  {
-    // whole block rounds: count * gx just under a multiple of the resident blocks (256 CUs x waves per SIMD), so that no nearly
-    // empty last round is left (4104 blocks on 1024 slots would cost a fifth round for 8 blocks)
-    // Four block rounds (interleaved sweep on one box, all six streaming rounds of a 2^21 sumcheck, SBN_SC_BLOCK_ROUNDS = 1 / 2 / 3 /
-    // 4 / 6: 2.60-2.63 / 2.50-2.56 / 2.46-2.53 / 2.43-2.44 / 2.56-2.63 ms)
-    const size_t br = single ? 4 : c->sck.block_rounds;
-    size_t want = std::max<size_t>(1, br * 256 * 2 / count), cap = (q + 255) / 256;
-    if (c->sck.grid) want = c->sck.grid;
-    gx = (unsigned)std::max<size_t>(1, std::min(std::min(want, cap), (size_t)1024));
-  }
+  const unsigned gx = sc_fused_grid(c, q, count, single);
   if ((rc = ensure(c, c->sc_partial, (size_t)count * gx * 96))) return rc;
   const char* nm = KIND == KIND_CUBIC ? "k_sc_bind_eval_cubic" : KIND == KIND_R1CS ? "k_sc_bind_eval_r1cs" : "k_sc_bind_eval_quad";
   uint8_t* hres;
@@ -267,15 +301,7 @@ static int sc_bind_eval_common(sbn_ctx* c, sbn_table* const* const* cols, int nc
     if ((rc = sc_tickets(c))) return rc;
     hres = (uint8_t*)c->mbox;
     const uint32_t seq = ++c->mbox_seq;
-    if (q <= 128) {
-      // the last rounds of a sumcheck: four lanes per index (k_sc_bind_eval_tiny), one block of up to 512 lanes per instance
-      // (measured per round at 18 instances: 64 / 128 / 256 indices 10.5 / 13.8 / 21.8 us against 16 us for the lane-per-index kernel)
-      const unsigned bt = (unsigned)std::max<size_t>(64, (4 * q + 63) / 64 * 64);
-      LAUNCH(c, nm, (k_sc_bind_eval_tiny<KIND>), dim3(1, (unsigned)count), bt, dargs, pack, q, rs, c->mbox, seq);
-    } else
-    // (the 2-waves-per-SIMD build: no spills, hence no scratch segment — these launches are latency, not occupancy)
-    LAUNCH(c, nm, (k_sc_bind_eval<KIND, 2>), dim3(gx, (unsigned)count), 256, dargs, pack, q, rs, (uint32_t*)c->sc_partial.p, (uint32_t*)c->sc_tickets.p, c->mbox, seq);
-    LAUNCHCHK(c);
+    if ((rc = sc_fused_launch<KIND>(c, pack, count, q, gx, true, rs, c->mbox, seq))) return rc;
     if ((rc = sc_mbox_wait(c, count, seq))) return rc;
   } else {
     if ((rc = ensure(c, c->sc_out, std::max<size_t>(4096, count * 96)))) return rc;
@@ -291,8 +317,7 @@ static int sc_bind_eval_common(sbn_ctx* c, sbn_table* const* const* cols, int nc
       // the streaming round finishes in the kernel too (ticketed fold into the host mailbox): no finishing launch, no copy, no stream wait
       if ((rc = sc_tickets(c))) return rc;
       const uint32_t seq = ++c->mbox_seq;
-      LAUNCH(c, nms, (k_sc_bind_eval_pf<KIND>), dim3(gx, (unsigned)count), 256, dargs, pack, q, rs, (uint32_t*)c->sc_partial.p, (uint32_t*)c->sc_tickets.p, c->mbox, seq);
-      LAUNCHCHK(c);
+      if ((rc = sc_fused_launch<KIND>(c, pack, count, q, gx, false, rs, c->mbox, seq))) return rc;
       if ((rc = sc_mbox_wait(c, count, seq))) return rc;
       hres = (uint8_t*)c->mbox;
     } else {
@@ -306,7 +331,7 @@ static int sc_bind_eval_common(sbn_ctx* c, sbn_table* const* const* cols, int nc
     if (c->prof) prof_drain(c);
     }
   }
-  for (sbn_table* t : distinct) { std::swap(t->d, t->d2); std::swap(t->cap, t->cap2); std::swap(t->owned, t->owned2); t->len = len / 2; }
+  for (sbn_table* t : distinct) sc_swap_bound(t, len);
   if (KIND == KIND_QUAD) { for (size_t i = 0; i < count; i++) memcpy(out + 64 * i, hres + 96 * i, 64); }
   else memcpy(out, hres, count * 96);
   return SBN_OK;

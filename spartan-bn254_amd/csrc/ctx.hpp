@@ -80,6 +80,9 @@ struct sbn_bases {
   // GLV table (glv_kernels.cuh): the n + has_h points, then their images phi(P) = (beta x, y); built by the first single MSM that takes the
   // GLV path and owned by this handle (a derived handle never shares it)
   mutable void* d_glv = nullptr;
+  // ZK sumchecks (abi_zk_sumcheck.inc): this handle's first two points (G[0], h) as bytes, the key of the derived sets it is the gens_1 of;
+  // read back once, on the first such call (the points of a handle never change)
+  mutable std::string zk_key;
 };
 static const uint32_t MERGE_BIG = 64;
 extern "C" void sbn_bases_free(sbn_ctx* c, sbn_bases* b);

@@ -9,6 +9,7 @@
 //   R1CSShape multiply_vec / evaluate, compute_eval_table_sparse  src/r1cs.rs:126-163  -> sbn_r1cs_*
 //   multi_sparse_to_dense_rep, AddrTimestamps::new      src/sparse_mlpoly_full.rs:120-174, 211-243  -> sbn_dense_*
 //   PolyEvalProof::prove, DotProductProofLog::prove     src/hyrax.rs:65-116, src/nizk/mod.rs:439-522 -> sbn_polyeval_prove / sbn_joint_opening_prove
+//   ZKSumcheckInstanceProof::prove_cubic_with_additive_term, ::prove_quad, DotProductProof::prove  src/sumcheck.rs:465-811, src/nizk/mod.rs:306-366 -> sbn_zk_sumcheck_prove_r1cs / _quad
 // There is no CPU fallback in this file: every entry point needs the gfx950 device.
 #include "../../include/sbn254.h"
 #include "host_field.hpp"
@@ -23,6 +24,7 @@
 #include "dense_kernels.cuh"
 #include "transcript_kernels.cuh"
 #include "polyeval_kernels.cuh"
+#include "zk_sumcheck_kernels.cuh"
 #include "host_keccak.hpp"
 #include "host_strobe.hpp"
 
@@ -55,6 +57,7 @@ using namespace sbn;
 #include "abi_product_proof.inc"
 #include "abi_bullet.inc"
 #include "abi_polyeval.inc"
+#include "abi_zk_sumcheck.inc"
 #include "abi_group.inc"
 #include "abi_kzg.inc"
 #include "abi_r1cs.inc"
