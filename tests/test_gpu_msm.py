@@ -2,6 +2,7 @@
 Bit-exact bar: integer work — the 64-byte canonical affine output must equal the oracle's byte for byte."""
 import numpy as np
 import pytest
+import window_model
 from conftest import golden, rand_scalars
 
 pytestmark = pytest.mark.gpu
@@ -579,7 +580,7 @@ def test_commit_rows_with_lookup_table_vs_oracle(ctx, ol, pr, R, label, budget_m
                 before = ctx.commit_rows(b, Z, bl, L, R)[0]
                 assert before == want_b
                 cw = ctx.bases_precompute(b, budget_mb << 20)
-                assert 7 <= cw <= 17          # COMB_C_MAX (comb_kernels.cuh)
+                assert cw == window_model.lookup_width(window_model.lookup_points(gx[:64 * R], gx[64 * R:]), budget_mb << 20)   # the widest table the budget buys
             assert ctx.commit_rows(b, Z, bl, L, R)[0] == want_b, (L, "blinds")
             out, infs = ctx.commit_rows(b, Z, None, L, R)
             assert out == want_0, (L, "no blinds")
@@ -645,8 +646,9 @@ def test_fuzz_lookup_table_commits(ctx, ol, pr):
         Z = bytes(Z); bl = rand_scalars(L, 9200 + case)
         b = ctx.bases_upload(gx[:64 * R], gx[64 * R:])
         try:
-            cw = ctx.bases_precompute(b, rng.choice([64, 128, 512]) << 20)
-            assert 7 <= cw <= 17          # COMB_C_MAX (comb_kernels.cuh)
+            budget = rng.choice([64, 128, 512]) << 20
+            cw = ctx.bases_precompute(b, budget)
+            assert cw == window_model.lookup_width(window_model.lookup_points(gx[:64 * R], gx[64 * R:]), budget)   # the widest table the budget buys
             use_bl = case % 2 == 0
             got, infs = ctx.commit_rows(b, Z, bl if use_bl else None, L, R)
             want = ol.commit_rows(Z, bl if use_bl else None, L, R, gx[:64 * R], gx[64 * R:], 8)
@@ -800,10 +802,11 @@ def ctx_sort2(sbn, monkeypatch):
     c.close()
 
 
-@pytest.mark.parametrize("c_bits,n", [(13, 1024), (13, 9000), (16, 8192), (17, 8193), (19, 20000), (20, 30011), (22, 5000)])
+@pytest.mark.parametrize("c_bits,n", [(13, 1024), (13, 9000), (14, 2500), (16, 8192), (17, 8193), (19, 20000), (20, 30011), (21, 6000), (22, 5000)])
 def test_two_level_sort_vs_oracle(ctx_sort2, ol, pr, monkeypatch, c_bits, n):
-    """the large-MSM sort path at small sizes, every window width it is built for (2 .. 1024 partitions per window; chunks of 8192
-    scalars: one partial chunk, exactly one, one + 1, several): bit-exact vs the discrete-log identity and the CPU Pippenger"""
+    """the large-MSM sort path at small sizes, across the window widths it is built for (2 .. 1024 partitions per window; chunks of 8192
+    scalars: one partial chunk, exactly one, one + 1, several): bit-exact vs the discrete-log identity and the CPU Pippenger.
+    (15 and 18 run in the tests below; test_gpu_window_widths.py runs every width 13 .. 22 on the seam scalars of that width)"""
     monkeypatch.setenv("SBN_MSM_C", str(c_bits))
     sc = rand_scalars(n, 900 + n + c_bits)
     pts, dl = tiled_bases(ol, n, min(n, 4096), 5 + n)
