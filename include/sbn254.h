@@ -473,6 +473,37 @@ int sbn_r1cs_eval_table(sbn_ctx* ctx, const sbn_r1cs* m, const uint8_t* rx, size
  * ell_x = log2(num_cons), ell_y = log2(2 * num_vars) */
 int sbn_r1cs_evaluate(sbn_ctx* ctx, const sbn_r1cs* m, const uint8_t* rx, size_t ell_x, const uint8_t* ry, size_t ell_y, uint8_t out[96]);
 
+/* ---- R1CSProof::prove (r1csproof.rs:241-459) in ONE call: the witness commitment, both ZK sumchecks, the three Σ-protocols between them
+ * (KnowledgeProof, ProductProof, EqualityProof::prove, nizk/mod.rs:34-59, :167-227, :96-124), the Hyrax opening and every transcript line ----
+ * Notation: nx = log2(num_cons), ell = log2(num_vars), ny = ell + 1, (L, R) = 2^sbn_factored_lens(ell), lg = log2(R).
+ *   inst     its num_cons and num_vars (both >= 2) define the shape.
+ *   vars     a table of num_vars entries; only read, never bound.
+ *   input    num_inputs x 32 B canonical scalars (NULL with num_inputs == 0); num_inputs < num_vars (r1csproof.rs:253).
+ *   gens_pc  R + 1 generators with h, the handle sbn_polyeval_prove takes (sbn_gens_new(R + 1, label)): gens_n = the first R with h,
+ *            gens_1 = (G[R], h).  Both are derived inside the call on first use, owned by gens_pc and freed with it.  There is no gens_1
+ *            parameter: R1CSGens::new (r1csproof.rs:177-182) makes gens_sc.gens_1 a clone of gens_pc.gens.gens_1.
+ *   gens_3, gens_4   3 and 4 generators with h (R1CSSumcheckGens::new), as the ZK sumcheck calls take them.
+ *   rnd      the RandomTape draws, canonical, in the reference's order:
+ *              poly_blinds [L] | phase 1 [8 nx, as sbn_zk_sumcheck_prove_r1cs] | Az_blind, Bz_blind, Cz_blind, prod_Az_Bz_blind | t1, t2 |
+ *              b1 .. b5 | r of the first equality proof | phase 2 [7 ny, as sbn_zk_sumcheck_prove_quad] | blind_eval |
+ *              the opening [3 + 2 lg, as sbn_polyeval_prove] | r of the second equality proof
+ *            L + 8 nx + 7 ny + 2 lg + 17 scalars.
+ *   out_proof  the fields of R1CSProof in declaration order (r1csproof.rs:187-202), points as sbn_g1_compress gives them, scalars canonical:
+ *              comm_vars [L x 32] | sc_proof_phase1 [nx x 10 x 32, layout of sbn_zk_sumcheck_prove_r1cs] |
+ *              comm_Az_claim, comm_Bz_claim, comm_Cz_claim, comm_prod_Az_Bz_claims [4 x 32] |
+ *              pok_claims_phase2 [11 x 32: knowledge proof alpha, z1, z2; product proof alpha, beta, delta, z[5]] |
+ *              proof_eq_sc_phase1 [alpha, z] | sc_proof_phase2 [ny x 9 x 32, layout of sbn_zk_sumcheck_prove_quad] | comm_vars_at_ry [32] |
+ *              proof_eval_vars_at_ry [64 lg + 128, out_proof of sbn_polyeval_prove] | proof_eq_sc_phase2 [alpha, z]
+ *              32 (L + 10 nx + 9 ny + 20) + 64 lg + 128 bytes.
+ *   out_rx   nx x 32 B;  out_ry  ny x 32 B.
+ * `tr` is advanced exactly as the reference advances its transcript, and only when the call returns SBN_OK.  A refusal (a wrong length, a
+ * shape below 2, num_inputs >= num_vars, a generator set of the wrong size or without h, a scalar >= r) is SBN_EINVAL before any launch. */
+/* host only: the sizes of rnd (in scalars) and out_proof (in bytes) of a shape; SBN_EINVAL for a shape the call refuses */
+int sbn_r1cs_proof_sizes(size_t num_cons, size_t num_vars, size_t* rnd_scalars, size_t* proof_bytes);
+int sbn_r1cs_proof_prove(sbn_ctx* ctx, const sbn_r1cs* inst, const sbn_table* vars, const uint8_t* input, size_t num_inputs,
+                         const sbn_bases* gens_pc, const sbn_bases* gens_3, const sbn_bases* gens_4, const uint8_t* rnd, sbn_transcript* tr,
+                         uint8_t* out_proof, uint8_t* out_rx, uint8_t* out_ry);
+
 /* ---- MultiSparseMatPolynomialAsDense on the device: what SNARK::encode -> R1CSShape::commit (r1cs.rs:375-400) builds once per circuit ----
  * SparseMatPolynomial::multi_sparse_to_dense_rep -> AddrTimestamps::new (sparse_mlpoly_full.rs:89-101, 120-174, 211-243), from the same
  * (row, col, val) triplets sbn_r1cs_upload takes, in the caller's entry order.  `batch` matrices (1 .. 8; the reference uses 3), nnz[k] entries each.

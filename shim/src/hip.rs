@@ -34,6 +34,8 @@ use crate::sparse_mlpoly::SparseMatPolynomial;
 use crate::group::CompressedGroup;
 use crate::nizk::DotProductProof;
 use crate::random::RandomTape;
+use crate::r1cs::R1CSShape;
+use crate::r1csproof::{R1CSGens, R1CSProof};
 use crate::sumcheck::{SumcheckInstanceProof, ZKSumcheckInstanceProof};
 use ark_serialize::CanonicalDeserialize;
 use crate::transcript::{AppendToTranscript, ProofTranscript};
@@ -182,6 +184,8 @@ extern "C" {
     pub fn sbn_r1cs_multiply(ctx: *mut sbn_ctx, m: *const sbn_r1cs, z: *const sbn_table, az: *mut *mut sbn_table, bz: *mut *mut sbn_table, cz: *mut *mut sbn_table) -> c_int;
     pub fn sbn_r1cs_eval_table(ctx: *mut sbn_ctx, m: *const sbn_r1cs, rx: *const u8, ell_x: usize, ra: *const u8, rb: *const u8, rc: *const u8, out: *mut *mut sbn_table) -> c_int;
     pub fn sbn_r1cs_evaluate(ctx: *mut sbn_ctx, m: *const sbn_r1cs, rx: *const u8, ell_x: usize, ry: *const u8, ell_y: usize, out: *mut u8) -> c_int;
+    pub fn sbn_r1cs_proof_sizes(num_cons: usize, num_vars: usize, rnd_scalars: *mut usize, proof_bytes: *mut usize) -> c_int;
+    pub fn sbn_r1cs_proof_prove(ctx: *mut sbn_ctx, inst: *const sbn_r1cs, vars: *const sbn_table, input: *const u8, num_inputs: usize, gens_pc: *const sbn_bases, gens_3: *const sbn_bases, gens_4: *const sbn_bases, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8, out_rx: *mut u8, out_ry: *mut u8) -> c_int;
     pub fn sbn_dense_build(ctx: *mut sbn_ctx, num_vars_x: usize, num_vars_y: usize, rows: *const *const u32, cols: *const *const u32, vals: *const *const u8, nnz: *const usize, batch: usize, flags: u32, out: *mut *mut sbn_dense) -> c_int;
     pub fn sbn_dense_free(ctx: *mut sbn_ctx, d: *mut sbn_dense);
     pub fn sbn_dense_num_ops(d: *const sbn_dense) -> usize;
@@ -996,6 +1000,102 @@ pub fn r1cs_evaluate(m: *const sbn_r1cs, rx: &[Scalar], ry: &[Scalar]) -> (Scala
     check(unsafe { sbn_r1cs_evaluate(ctx(), m, rxb.as_ptr(), rx.len(), ryb.as_ptr(), ry.len(), out.as_mut_ptr()) });
     triple(&out)
 }
+
+// ---- R1CSProof::prove (r1csproof.rs:241-459) in ONE foreign call (sbn_r1cs_proof_prove) ------------------------------------------
+// The library commits the witness, builds z, runs both ZK sumchecks, the three Σ-protocols between them (KnowledgeProof, ProductProof,
+// EqualityProof::prove, nizk/mod.rs:34-59, :167-227, :96-124), the opening and the whole transcript.  This side draws the RandomTape in the
+// reference's order and rebuilds R1CSProof from the bytes.  Every piece of R1CSProof keeps its fields private and derives
+// CanonicalDeserialize, R1CSProof included, so the proof comes back through its own deserialisation: the library's fields in declaration
+// order, with the u64 length ark-serialize puts in front of each Vec.
+/// PolyCommitmentGens as ONE handle: gens_n.G ‖ gens_1.G[0] with their common h (DotProductProofGens::new cuts both out of
+/// MultiCommitGens::new(n + 1, label), nizk/mod.rs:412-415); cached per generator set
+fn pc_bases(gens_n: &MultiCommitGens, gens_1: &MultiCommitGens) -> Arc<Bases> {
+    static CACHE: OnceLock<Mutex<HashMap<(usize, [u8; 64], [u8; 64]), Arc<Bases>>>> = OnceLock::new();
+    let key = (gens_n.n, point_xy_mont(&gens_n.G_affine[0]), point_xy_mont(&gens_1.G_affine[0]));
+    let mut m = CACHE.get_or_init(|| Mutex::new(HashMap::new())).lock().unwrap();
+    if let Some(b) = m.get(&key) { return b.clone(); }
+    let mut g: Vec<u8> = gens_n.G_affine.iter().flat_map(point_xy_mont).collect();
+    g.extend_from_slice(&point_xy_mont(&gens_1.G_affine[0]));
+    let h = point_xy_mont(&gens_n.h_affine);
+    let mut b = null_mut();
+    check(unsafe { sbn_bases_upload(ctx(), g.as_ptr(), gens_n.n + 1, h.as_ptr(), SBN_POINTS_MONT, &mut b) });
+    let b = Arc::new(Bases(b));
+    m.insert(key, b.clone());
+    b
+}
+/// R1CSProof::prove with a `DevTranscript`; `inst_dev` is the instance's device handle (`R1csDev::get`, uploaded at encode time)
+#[allow(non_snake_case)]
+pub fn r1cs_prove(
+    inst: &R1CSShape,
+    inst_dev: *const sbn_r1cs,
+    vars: Vec<Scalar>,
+    input: &[Scalar],
+    gens: &R1CSGens,
+    transcript: &mut DevTranscript,
+    random_tape: &mut RandomTape,
+) -> (R1CSProof, Vec<Scalar>, Vec<Scalar>) {
+    assert!(input.len() < vars.len());                                                // r1csproof.rs:253
+    let (num_cons, num_vars) = (inst.get_num_cons(), inst.get_num_vars());
+    let (nx, ell) = (num_cons.trailing_zeros() as usize, num_vars.trailing_zeros() as usize);
+    let (ny, ml) = (ell + 1, ell / 2);
+    let lg = ell - ml;
+    let (mut n_rnd, mut n_proof) = (0usize, 0usize);
+    check(unsafe { sbn_r1cs_proof_sizes(num_cons, num_vars, &mut n_rnd, &mut n_proof) });
+    // the draws, in the order R1CSProof::prove and the functions it calls make them
+    let mut rnd = random_tape.random_vector(b"poly_blinds", 1usize << ml);            // commit_poly, r1csproof.rs:225
+    rnd.extend(zk_draws(random_tape, nx, 4));                                         // phase 1
+    for label in [&b"Az_blind"[..], &b"Bz_blind"[..], &b"Cz_blind"[..], &b"prod_Az_Bz_blind"[..]] { rnd.push(draw(random_tape, label)); }      // :317-322
+    for label in [&b"t1"[..], &b"t2"[..]] { rnd.push(draw(random_tape, label)); }     // KnowledgeProof::prove, nizk/mod.rs:44-45
+    for label in [&b"b1"[..], &b"b2"[..], &b"b3"[..], &b"b4"[..], &b"b5"[..]] { rnd.push(draw(random_tape, label)); }                         // ProductProof::prove, :181-185
+    rnd.push(random_tape.random_scalar(b"r"));                                        // EqualityProof::prove, :108
+    rnd.extend(zk_draws(random_tape, ny, 3));                                         // phase 2
+    rnd.push(random_tape.random_scalar(b"blind_eval"));                               // r1csproof.rs:410
+    rnd.push(random_tape.random_scalar(b"d"));                                        // DotProductProofLog::prove, nizk/mod.rs:458-468:
+    rnd.push(random_tape.random_scalar(b"r_delta"));
+    rnd.push(random_tape.random_scalar(b"r_delta"));                                  //   (r_beta is drawn under the label "r_delta" there)
+    let (v1, v2) = (random_tape.random_vector(b"blinds_vec_1", lg), random_tape.random_vector(b"blinds_vec_2", lg));
+    for i in 0..lg { rnd.push(v1[i]); rnd.push(v2[i]); }                              //   the library takes the pairs (v1[i], v2[i])
+    rnd.push(random_tape.random_scalar(b"r"));                                        // the last EqualityProof::prove
+    assert_eq!(rnd.len(), n_rnd);
+    let rnd = scalars_canonical(&rnd);
+    let inp = scalars_canonical(input);
+    let vt = Table::upload(&vars);
+    let pc = pc_bases(&gens.gens_pc.gens.gens_n, &gens.gens_pc.gens.gens_1);
+    let (g3, g4) = (&gens.gens_sc.gens_3, &gens.gens_sc.gens_4);
+    let (mut proof, mut rx, mut ry) = (vec![0u8; n_proof], vec![0u8; 32 * nx], vec![0u8; 32 * ny]);
+    check(unsafe {
+        sbn_r1cs_proof_prove(ctx(), inst_dev, vt.0, if input.is_empty() { null() } else { inp.as_ptr() }, input.len(), pc.0, g3.dev.bases(g3), g4.dev.bases(g4),
+                             rnd.as_ptr(), transcript.0, proof.as_mut_ptr(), rx.as_mut_ptr(), ry.as_mut_ptr())
+    });
+    // out_proof -> the stream R1CSProof's derived CanonicalDeserialize reads (r1csproof.rs:187-202)
+    let mut ser: Vec<u8> = Vec::with_capacity(n_proof + 128);
+    let mut at = 0usize;
+    let mut take = |n: usize| { let s = &proof[at..at + n]; at += n; s };
+    let len = |ser: &mut Vec<u8>, n: usize| ser.extend_from_slice(&(n as u64).to_le_bytes());
+    let zk = |ser: &mut Vec<u8>, p: &[u8], rounds: usize, n: usize| {                 // ZKSumcheckInstanceProof: comm_polys, comm_evals, proofs
+        let stride = (6 + n) * 32;
+        len(ser, rounds); for j in 0..rounds { ser.extend_from_slice(&p[stride * j..stride * j + 32]); }
+        len(ser, rounds); for j in 0..rounds { ser.extend_from_slice(&p[stride * j + 32..stride * j + 64]); }
+        len(ser, rounds);
+        for j in 0..rounds {
+            let q = &p[stride * j..stride * (j + 1)];
+            ser.extend_from_slice(&q[64..128]); len(ser, n); ser.extend_from_slice(&q[128..]);      // delta, beta, z: Vec<Scalar>, z_delta, z_beta
+        }
+    };
+    len(&mut ser, 1usize << ml); ser.extend_from_slice(take(32usize << ml));          // comm_vars: PolyCommitment { C }
+    zk(&mut ser, take(320 * nx), nx, 4);                                              // sc_proof_phase1
+    ser.extend_from_slice(take(128 + 352 + 64));                                      // claims_phase2, pok_claims_phase2 ([Scalar; 5] has no length), proof_eq_sc_phase1
+    zk(&mut ser, take(288 * ny), ny, 3);                                              // sc_proof_phase2
+    ser.extend_from_slice(take(32));                                                  // comm_vars_at_ry
+    let open = take(64 * lg + 128);                                                   // PolyEvalProof { DotProductProofLog { BulletReductionProof { L_vec, R_vec }, delta, beta, z1, z2 } }
+    len(&mut ser, lg); ser.extend_from_slice(&open[..32 * lg]);
+    len(&mut ser, lg); ser.extend_from_slice(&open[32 * lg..64 * lg]);
+    ser.extend_from_slice(&open[64 * lg..]);
+    ser.extend_from_slice(take(64));                                                  // proof_eq_sc_phase2
+    let r1cs_proof = R1CSProof::deserialize_compressed(&ser[..]).expect("R1CSProof from the library's bytes");
+    (r1cs_proof, rx.chunks(32).map(sc).collect(), ry.chunks(32).map(sc).collect())
+}
+fn draw(random_tape: &mut RandomTape, label: &'static [u8]) -> Scalar { random_tape.random_scalar(label) }
 
 // ---- the dense representation on the device (sparse_mlpoly_full.rs:120-174): built once per circuit at encode, next to R1csDev -------
 /// MultiSparseMatPolynomialAsDense on the device: padded addresses, read / audit timestamps, comb_ops and comb_mem, from the same triplets

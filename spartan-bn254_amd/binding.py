@@ -24,6 +24,7 @@ EXPORTED_SYMBOLS = [
     "sbn_eq_evals", "sbn_hash_layer", "sbn_hash_layer_pair", "sbn_product_layer", "sbn_product_circuit", "sbn_product_circuit_many", "sbn_table_halves", "sbn_table_slice", "sbn_table_dot", "sbn_table_evaluate", "sbn_table_evaluate_many", "sbn_table_bound", "sbn_gather_merge", "sbn_gather_merge_rows", "sbn_commit_table", "sbn_bullet_begin", "sbn_bullet_begin_scaled", "sbn_bullet_free", "sbn_bullet_len", "sbn_bullet_cross", "sbn_bullet_fold_cross", "sbn_bullet_fold", "sbn_bullet_finish", "sbn_prof_enable", "sbn_prof_reset", "sbn_prof_count", "sbn_prof_get", "sbn_prof_last_job",
     "sbn_kzg_srs_upload", "sbn_kzg_srs_from_tau", "sbn_kzg_commit", "sbn_poly_div_linear", "sbn_kzg_open", "sbn_kzg_open_batched",
     "sbn_r1cs_upload", "sbn_r1cs_free", "sbn_r1cs_multiply", "sbn_r1cs_eval_table", "sbn_r1cs_evaluate",
+    "sbn_r1cs_proof_sizes", "sbn_r1cs_proof_prove",
     "sbn_dense_build", "sbn_dense_free", "sbn_dense_num_ops", "sbn_dense_num_cells", "sbn_dense_batch", "sbn_dense_addr_dev", "sbn_dense_read_ts_dev",
     "sbn_dense_audit_ts_dev", "sbn_dense_comb_ops", "sbn_dense_comb_mem",
 ]
@@ -86,6 +87,8 @@ def lib():
         L.sbn_joint_opening_prove.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p, C.c_size_t] * 3 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 9
         L.sbn_zk_sumcheck_prove_r1cs.argtypes = [C.c_void_p] * 15
         L.sbn_zk_sumcheck_prove_quad.argtypes = [C.c_void_p] * 13
+        L.sbn_r1cs_proof_sizes.argtypes = [C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.sbn_r1cs_proof_prove.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 8
         L.sbn_dense_audit_ts_dev.restype = C.c_void_p; L.sbn_dense_audit_ts_dev.argtypes = [C.c_void_p, C.c_int]
         for name in ("sbn_dense_comb_ops", "sbn_dense_comb_mem"):
             getattr(L, name).restype = C.c_void_p; getattr(L, name).argtypes = [C.c_void_p]
@@ -180,6 +183,15 @@ def unipoly_eval(coeffs, r):
     if rc:
         raise SbnError(f"sbn_unipoly_eval rc={rc}")
     return bytes(out)
+
+
+def r1cs_proof_sizes(num_cons, num_vars):
+    """sbn_r1cs_proof_sizes -> (scalars of rnd, bytes of the proof) of sbn_r1cs_proof_prove at this shape"""
+    a, b = C.c_size_t(0), C.c_size_t(0)
+    rc = lib().sbn_r1cs_proof_sizes(C.c_size_t(num_cons), C.c_size_t(num_vars), C.byref(a), C.byref(b))
+    if rc != 0:
+        raise SbnError(f"sbn_r1cs_proof_sizes: {num_cons} x {num_vars} is a shape the call refuses (rc={rc})")
+    return a.value, b.value
 
 
 def factored_lens(ell):
@@ -847,6 +859,19 @@ class Context:
     def zk_sumcheck_prove_quad(self, Z, ABC, gens_1, gens_3, claim, blind_claim, rnd, tr):
         """prove_quad (sbn_zk_sumcheck_prove_quad) -> (proof: rounds x 9 x 32, challenges, finals [Z, ABC], blinds_evals[-1]); rnd: rounds x 7 scalars"""
         return self._zk_sumcheck_prove(lib().sbn_zk_sumcheck_prove_quad, "sbn_zk_sumcheck_prove_quad", (Z, ABC), 3, gens_1, gens_3, claim, blind_claim, rnd, tr)
+
+    # ---- R1CSProof::prove in one call (r1csproof.rs:241-459)
+    def r1cs_proof_prove(self, inst, vars, inputs, gens_pc, gens_3, gens_4, rnd, tr):
+        """R1CSProof::prove (sbn_r1cs_proof_prove) -> (proof bytes, rx, ry); vars: a Table of num_vars entries (only read); inputs: canonical
+        scalars, 32 bytes each (b"" for none); gens_pc: R + 1 generators with h; rnd: r1cs_proof_sizes(...)[0] scalars; `tr` (Transcript) moves on"""
+        n_rnd, n_proof = r1cs_proof_sizes(inst.num_cons, inst.num_vars)
+        if len(rnd) != 32 * n_rnd:
+            raise ValueError(f"r1cs_proof_prove: rnd holds {len(rnd)} bytes, the shape needs {32 * n_rnd}")
+        nx, ny = inst.num_cons.bit_length() - 1, inst.num_vars.bit_length()
+        proof = (C.c_uint8 * n_proof)(); rx = (C.c_uint8 * (32 * nx))(); ry = (C.c_uint8 * (32 * ny))()
+        self._chk(lib().sbn_r1cs_proof_prove(self.h, inst.h, vars.h, _ptr(inputs) if inputs else None, C.c_size_t(len(inputs) // 32 if inputs else 0),
+                                             gens_pc.h, gens_3.h, gens_4.h, _ptr(rnd), tr.h, proof, rx, ry), "sbn_r1cs_proof_prove")
+        return bytes(proof), bytes(rx), bytes(ry)
 
     # ---- KZG mode (kzg.rs): the SRS is a Bases handle, polynomials are the first n entries of a Table
     def kzg_srs_upload(self, powers_xy, flags=0):

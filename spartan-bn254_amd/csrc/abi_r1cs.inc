@@ -71,6 +71,41 @@ static int r1cs_new_table(sbn_ctx* c, size_t len, sbn_table** out) {
 }
 static void r1cs_drop_table(sbn_ctx* c, sbn_table*& t) { if (t) { pool_put(c, t->d, t->cap * 32); delete t; t = nullptr; } }
 
+// the launches of sbn_r1cs_multiply / sbn_r1cs_eval_table; arguments checked, the caller holds the context's mutex (sbn_r1cs_proof_prove runs them too)
+static int r1cs_multiply_locked(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* z, sbn_table** Az, sbn_table** Bz, sbn_table** Cz) {
+  sbn_table* t[3] = {nullptr, nullptr, nullptr};
+  int rc = SBN_OK;
+  for (int k = 0; k < 3 && rc == SBN_OK; k++) rc = r1cs_new_table(c, m->nc, &t[k]);
+  if (rc == SBN_OK) {
+    R1csOut o; o.p[0] = (uint32_t*)t[0]->d; o.p[1] = (uint32_t*)t[1]->d; o.p[2] = (uint32_t*)t[2]->d; o.shift = m->log_nc;
+    rc = r1cs_spmv_table(c, m->rowm, (const uint32_t*)z->d, o);
+  }
+  if (rc == SBN_OK && c->prof) { hipStreamSynchronize(c->stream); prof_drain(c); }
+  if (rc) { for (int k = 0; k < 3; k++) r1cs_drop_table(c, t[k]); return rc; }
+  *Az = t[0]; *Bz = t[1]; *Cz = t[2];
+  return SBN_OK;
+}
+static int r1cs_eval_table_locked(sbn_ctx* c, const sbn_r1cs* m, const uint8_t* rx, size_t ell_x, const uint8_t rA[32], const uint8_t rB[32], const uint8_t rC[32],
+                                  sbn_table** out) {
+  sbn_table *eq = nullptr, *x = nullptr, *t = nullptr;
+  int rc = eq_evals_locked(c, rx, ell_x, &eq);
+  if (rc == SBN_OK) rc = r1cs_new_table(c, 3 * m->nc, &x);
+  if (rc == SBN_OK) rc = r1cs_new_table(c, 2 * m->nv, &t);
+  if (rc == SBN_OK) {
+    // x = [r_A eq(rx) | r_B eq(rx) | r_C eq(rx)]: the combination of r1csproof.rs:376-387 folded into the gather
+    const ScScalar a = scs_from(sbn_host::fr::to_dev_mont(el_from(rA))), b = scs_from(sbn_host::fr::to_dev_mont(el_from(rB))),
+                   cc = scs_from(sbn_host::fr::to_dev_mont(el_from(rC)));
+    LAUNCH(c, "k_r1cs_scale3", k_r1cs_scale3, stream_grid(3 * m->nc), 256, (const uint32_t*)eq->d, m->log_nc, a, b, cc, (uint32_t*)x->d);
+    R1csOut o; o.p[0] = o.p[1] = o.p[2] = (uint32_t*)t->d; o.shift = m->log_z;
+    rc = r1cs_spmv_table(c, m->colm, (const uint32_t*)x->d, o);
+  }
+  if (rc == SBN_OK && c->prof) { hipStreamSynchronize(c->stream); prof_drain(c); }
+  r1cs_drop_table(c, eq); r1cs_drop_table(c, x);              // recycled in stream order (see sbn_table_free)
+  if (rc) { r1cs_drop_table(c, t); return rc; }
+  *out = t;
+  return SBN_OK;
+}
+
 extern "C" {
 
 void sbn_r1cs_free(sbn_ctx* c, sbn_r1cs* m) {
@@ -154,17 +189,7 @@ int sbn_r1cs_multiply(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* z, sbn_tab
   if (z->len != 2 * m->nv) return fail(c, SBN_EINVAL, "r1cs_multiply: z has %zu entries, the shape needs 2 num_vars = %zu (r1cs.rs:139)", z->len, 2 * m->nv);
   std::lock_guard<std::mutex> g(c->mu);
   hipSetDevice(c->device);
-  sbn_table* t[3] = {nullptr, nullptr, nullptr};
-  int rc = SBN_OK;
-  for (int k = 0; k < 3 && rc == SBN_OK; k++) rc = r1cs_new_table(c, m->nc, &t[k]);
-  if (rc == SBN_OK) {
-    R1csOut o; o.p[0] = (uint32_t*)t[0]->d; o.p[1] = (uint32_t*)t[1]->d; o.p[2] = (uint32_t*)t[2]->d; o.shift = m->log_nc;
-    rc = r1cs_spmv_table(c, m->rowm, (const uint32_t*)z->d, o);
-  }
-  if (rc == SBN_OK && c->prof) { hipStreamSynchronize(c->stream); prof_drain(c); }
-  if (rc) { for (int k = 0; k < 3; k++) r1cs_drop_table(c, t[k]); return rc; }
-  *Az = t[0]; *Bz = t[1]; *Cz = t[2];
-  return SBN_OK;
+  return r1cs_multiply_locked(c, m, z, Az, Bz, Cz);
 }
 
 int sbn_r1cs_eval_table(sbn_ctx* c, const sbn_r1cs* m, const uint8_t* rx, size_t ell_x, const uint8_t rA[32], const uint8_t rB[32], const uint8_t rC[32],
@@ -175,23 +200,7 @@ int sbn_r1cs_eval_table(sbn_ctx* c, const sbn_r1cs* m, const uint8_t* rx, size_t
   if (!fr_canonical(rA) || !fr_canonical(rB) || !fr_canonical(rC)) return fail(c, SBN_EINVAL, "r1cs_eval_table: r_A, r_B or r_C is not canonical (>= r)");
   std::lock_guard<std::mutex> g(c->mu);
   hipSetDevice(c->device);
-  sbn_table *eq = nullptr, *x = nullptr, *t = nullptr;
-  int rc = eq_evals_locked(c, rx, ell_x, &eq);
-  if (rc == SBN_OK) rc = r1cs_new_table(c, 3 * m->nc, &x);
-  if (rc == SBN_OK) rc = r1cs_new_table(c, 2 * m->nv, &t);
-  if (rc == SBN_OK) {
-    // x = [r_A eq(rx) | r_B eq(rx) | r_C eq(rx)]: the combination of r1csproof.rs:376-387 folded into the gather
-    const ScScalar a = scs_from(sbn_host::fr::to_dev_mont(el_from(rA))), b = scs_from(sbn_host::fr::to_dev_mont(el_from(rB))),
-                   cc = scs_from(sbn_host::fr::to_dev_mont(el_from(rC)));
-    LAUNCH(c, "k_r1cs_scale3", k_r1cs_scale3, stream_grid(3 * m->nc), 256, (const uint32_t*)eq->d, m->log_nc, a, b, cc, (uint32_t*)x->d);
-    R1csOut o; o.p[0] = o.p[1] = o.p[2] = (uint32_t*)t->d; o.shift = m->log_z;
-    rc = r1cs_spmv_table(c, m->colm, (const uint32_t*)x->d, o);
-  }
-  if (rc == SBN_OK && c->prof) { hipStreamSynchronize(c->stream); prof_drain(c); }
-  r1cs_drop_table(c, eq); r1cs_drop_table(c, x);              // recycled in stream order (see sbn_table_free)
-  if (rc) { r1cs_drop_table(c, t); return rc; }
-  *out = t;
-  return SBN_OK;
+  return r1cs_eval_table_locked(c, m, rx, ell_x, rA, rB, rC, out);
 }
 
 int sbn_r1cs_evaluate(sbn_ctx* c, const sbn_r1cs* m, const uint8_t* rx, size_t ell_x, const uint8_t* ry, size_t ell_y, uint8_t out[96]) {

@@ -150,6 +150,25 @@ static inline void to_affine_bytes2(const Pt& p, const Pt& q, uint8_t outp[64], 
   if (p_inf) *p_inf = 0;
   if (q_inf) *q_inf = 0;
 }
+// n <= 16 points with ONE inversion: prefix products of the finite points' ZZ * ZZZ, the inverse of the last, and back down
+static inline void to_affine_bytes_n(const Pt* p, size_t n, uint8_t* out /* n x 64 */, int* infs /* n, or null */) {
+  Fq z[16], pre[16];
+  size_t live[16], m = 0;
+  for (size_t i = 0; i < n && i < 16; i++) {
+    if (is_inf(p[i])) { memset(out + 64 * i, 0, 64); if (infs) infs[i] = 1; continue; }
+    if (infs) infs[i] = 0;
+    z[m] = mul(p[i].ZZ, p[i].ZZZ); pre[m] = m ? mul(pre[m - 1], z[m]) : z[m]; live[m++] = i;
+  }
+  if (!m) return;
+  Fq I = inv(pre[m - 1]);
+  for (size_t k = m; k-- > 0;) {
+    const Fq Ik = k ? mul(I, pre[k - 1]) : I;          // 1 / (ZZ ZZZ) of point live[k]
+    if (k) I = mul(I, z[k]);
+    const Pt& q = p[live[k]];
+    const Fq x = from_mont(mul(q.X, mul(Ik, q.ZZZ))), y = from_mont(mul(q.Y, mul(Ik, q.ZZ)));
+    memcpy(out + 64 * live[k], x.v, 32); memcpy(out + 64 * live[k] + 32, y.v, 32);
+  }
+}
 // sum_w 2^(c*w) * S[w], w = 0..W-1 (Horner from the top window)
 static inline Pt combine_windows(const Pt* S, int W, int c) {
   Pt acc = inf();

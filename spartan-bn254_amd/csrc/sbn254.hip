@@ -25,6 +25,7 @@
 #include "transcript_kernels.cuh"
 #include "polyeval_kernels.cuh"
 #include "zk_sumcheck_kernels.cuh"
+#include "r1cs_proof_kernels.cuh"
 #include "host_keccak.hpp"
 #include "host_strobe.hpp"
 
@@ -61,6 +62,7 @@ using namespace sbn;
 #include "abi_group.inc"
 #include "abi_kzg.inc"
 #include "abi_r1cs.inc"
+#include "abi_r1cs_proof.inc"
 #include "abi_dense.inc"
 
 extern "C" {
