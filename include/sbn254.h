@@ -546,6 +546,13 @@ int sbn_prof_get(sbn_ctx* ctx, int i, const char** name, double* total_ms, uint6
 /* shape of the context's most recent bucket job (an MSM or a row commit): out = {window bits c, windows W, (digit, point)
  * slots = mixed additions when no digit is zero, buckets}; bench.py prices the accumulate kernel against the ALU roofline with it */
 int sbn_prof_last_job(sbn_ctx* ctx, uint64_t out[4]);
+/* accumulate / reduction geometry of the context's most recent BUCKET job: out = {segment length SEG, lanes per bucket LPB (k_acc_first<LPB>),
+ * buckets per lane L of k_reduce_l1, chunks per problem, k_reduce_combine launches, 1 if they were the quad kernel, and the device counters
+ * extra_count (segments past the first, over all buckets) and big_count (buckets with more than SEG entries)}.  The call synchronises the
+ * context's stream to read the two counters; the MSM path itself stores six integers and reads nothing back.  A job that took the lookup
+ * table (sbn_bases_precompute) runs no bucket kernels and leaves these values as the last bucket job set them (all zero before the first).
+ * SBN_EINVAL on a null context or a null out. */
+int sbn_prof_last_acc(sbn_ctx* ctx, uint64_t out[8]);
 
 /* host microseconds of the context's most recent opening: {a_vec = R computed on the host beside the first commit, the wait for that
  * commit behind it, Cx + Cy + the n a_vec messages absorbed into the transcript} */

@@ -201,6 +201,7 @@ extern "C" {
     pub fn sbn_prof_count(ctx: *mut sbn_ctx) -> c_int;
     pub fn sbn_prof_get(ctx: *mut sbn_ctx, i: c_int, name: *mut *const c_char, total_ms: *mut f64, launches: *mut u64) -> c_int;
     pub fn sbn_prof_last_job(ctx: *mut sbn_ctx, out: *mut u64) -> c_int;
+    pub fn sbn_prof_last_acc(ctx: *mut sbn_ctx, out: *mut u64) -> c_int;
     pub fn sbn_prof_last_polyeval(ctx: *mut sbn_ctx, out_us: *mut f64) -> c_int;
     // GENERATED-END
 }

@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = [
     "sbn_polyeval_prove", "sbn_joint_opening_prove", "sbn_prof_last_polyeval", "sbn_zk_sumcheck_prove_r1cs", "sbn_zk_sumcheck_prove_quad",
     "sbn_group_create", "sbn_group_destroy", "sbn_group_size", "sbn_group_ctx", "sbn_group_last_error", "sbn_group_bases_upload", "sbn_group_gens_new", "sbn_group_bases_precompute",
     "sbn_group_bases_free", "sbn_group_commit_rows", "sbn_group_commit_rows_dev", "sbn_group_gather_commit", "sbn_group_msm", "sbn_group_bases_upload_ranges", "sbn_group_bases_synthetic_ranges", "sbn_group_range", "sbn_group_msm_bases", "sbn_group_msm_bases_dev",
-    "sbn_eq_evals", "sbn_hash_layer", "sbn_hash_layer_pair", "sbn_product_layer", "sbn_product_circuit", "sbn_product_circuit_many", "sbn_table_halves", "sbn_table_slice", "sbn_table_dot", "sbn_table_evaluate", "sbn_table_evaluate_many", "sbn_table_bound", "sbn_gather_merge", "sbn_gather_merge_rows", "sbn_commit_table", "sbn_bullet_begin", "sbn_bullet_begin_scaled", "sbn_bullet_free", "sbn_bullet_len", "sbn_bullet_cross", "sbn_bullet_fold_cross", "sbn_bullet_fold", "sbn_bullet_finish", "sbn_prof_enable", "sbn_prof_reset", "sbn_prof_count", "sbn_prof_get", "sbn_prof_last_job",
+    "sbn_eq_evals", "sbn_hash_layer", "sbn_hash_layer_pair", "sbn_product_layer", "sbn_product_circuit", "sbn_product_circuit_many", "sbn_table_halves", "sbn_table_slice", "sbn_table_dot", "sbn_table_evaluate", "sbn_table_evaluate_many", "sbn_table_bound", "sbn_gather_merge", "sbn_gather_merge_rows", "sbn_commit_table", "sbn_bullet_begin", "sbn_bullet_begin_scaled", "sbn_bullet_free", "sbn_bullet_len", "sbn_bullet_cross", "sbn_bullet_fold_cross", "sbn_bullet_fold", "sbn_bullet_finish", "sbn_prof_enable", "sbn_prof_reset", "sbn_prof_count", "sbn_prof_get", "sbn_prof_last_job", "sbn_prof_last_acc",
     "sbn_kzg_srs_upload", "sbn_kzg_srs_from_tau", "sbn_kzg_commit", "sbn_poly_div_linear", "sbn_kzg_open", "sbn_kzg_open_batched",
     "sbn_r1cs_upload", "sbn_r1cs_free", "sbn_r1cs_multiply", "sbn_r1cs_eval_table", "sbn_r1cs_evaluate",
     "sbn_r1cs_proof_sizes", "sbn_r1cs_proof_prove",
@@ -980,6 +980,12 @@ class Context:
         """{c, W, slots, buckets} of the most recent MSM / row commit on this context"""
         o = (C.c_uint64 * 4)(); self._chk(lib().sbn_prof_last_job(self.h, o), "prof_last_job")
         return {"c": int(o[0]), "W": int(o[1]), "slots": int(o[2]), "buckets": int(o[3])}
+
+    def prof_last_acc(self):
+        """accumulate / reduction geometry of the most recent BUCKET job on this context (a lookup-table commit leaves it unchanged):
+        {SEG, LPB, L, chunks, levels (k_reduce_combine launches), quad, extra_count, big_count}; synchronises the stream"""
+        o = (C.c_uint64 * 8)(); self._chk(lib().sbn_prof_last_acc(self.h, o), "prof_last_acc")
+        return dict(zip(("SEG", "LPB", "L", "chunks", "levels", "quad", "extra_count", "big_count"), (int(v) for v in o)))
 
     def prof_reset(self):
         self._chk(lib().sbn_prof_reset(self.h), "prof_reset")

@@ -56,6 +56,7 @@ struct sbn_ctx {
   uint32_t* mbox = nullptr; uint32_t mbox_seq = 0;   // coherent pinned mailbox of the single-launch sumcheck rounds (results + per-instance flags)
   std::vector<std::pair<void*, size_t>> pool; size_t pool_bytes = 0;   // cached table buffers (see pool_get)
   uint64_t last_job[4] = {0, 0, 0, 0};      // window bits, windows, (digit, point) slots, buckets of the most recent bucket job
+  uint64_t last_acc[6] = {0, 0, 0, 0, 0, 0};   // SEG, LPB, L, chunks, combine launches, quad combine of the most recent bucket job (sbn_prof_last_acc)
   double polyeval_us[3] = {0, 0, 0};        // host microseconds of the most recent opening (sbn_prof_last_polyeval)
   // profiling
   bool prof = false;

@@ -301,7 +301,9 @@ static int run_bucket_job(sbn_ctx* c, const BucketJob& J) {
   LAUNCH(c, "k_reduce_l1", k_reduce_l1, (unsigned)(J.P * chunks), 64, buckets, L, s.nb, (uint32_t*)c->red_a.p, skip, chunks, LPB);
   uint32_t* in = (uint32_t*)c->red_a.p; uint32_t* outb = (uint32_t*)c->red_b.p;
   int G = chunks, k64 = 1;
+  c->last_acc[0] = SEG; c->last_acc[1] = (uint64_t)LPB; c->last_acc[2] = (uint64_t)L; c->last_acc[3] = (uint64_t)chunks; c->last_acc[4] = 0; c->last_acc[5] = red_quad ? 1 : 0;
   for (;;) {
+    c->last_acc[4] += 1;
     int Gout = (G + 63) / 64;
     int final = (Gout == 1);
     if (red_quad) LAUNCH(c, "k_reduce_combine", k_reduce_combine_quad, (unsigned)(J.P * Gout), 256, in, G, Gout, k64, L, final, final ? (uint32_t*)c->wsum.p : outb);

@@ -83,5 +83,17 @@ int sbn_prof_last_job(sbn_ctx* c, uint64_t out[4]) {
   for (int i = 0; i < 4; i++) out[i] = c->last_job[i];
   return SBN_OK;
 }
+int sbn_prof_last_acc(sbn_ctx* c, uint64_t out[8]) {
+  if (!c || !out) return SBN_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  for (int i = 0; i < 6; i++) out[i] = c->last_acc[i];
+  out[6] = out[7] = 0;
+  if (!c->acc_ctr.p) return SBN_OK;          // no bucket job yet
+  AccCounters h;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(&h, c->acc_ctr.p, sizeof h, hipMemcpyDeviceToHost));
+  out[6] = h.extra_count; out[7] = h.big_count;
+  return SBN_OK;
+}
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 Bit-exact bar: integer work — the 64-byte canonical affine output must equal the oracle's byte for byte."""
 import numpy as np
 import pytest
+import acc_model
 import window_model
 from conftest import golden, rand_scalars
 
@@ -20,6 +21,19 @@ def tiled_bases(ol, n, distinct, seed):
 
 def expect_from_dlogs(ol, pr, scalars, dlogs):
     return ol.g1_mul(pr.point_to_xy(pr.G), ol.fr_dot(scalars, dlogs))
+
+
+def assert_acc_geometry(ctx, scalars=None, env=None):
+    """the accumulate / reduction geometry the most recent single MSM ran with is the one the model of run_bucket_job gives
+    (tests/acc_model.py), and, given the job's scalars (plain windows), its segment counters are the ones their bucket loads give"""
+    job, acc = ctx.prof_last_job(), ctx.prof_last_acc()
+    rec = job["slots"] // job["W"]                           # terms, or twice the terms under GLV
+    assert acc_model.geometry_of(acc) == acc_model.geometry(acc_model.SINGLE, rec, job["W"], rec, job["c"], env), (job, acc)
+    if scalars is not None:
+        assert rec * 32 == len(scalars)
+        loads = acc_model.loads_of_bytes(scalars, job["c"], job["W"])
+        assert (acc["extra_count"], acc["big_count"]) == acc_model.expected_counters(loads, acc["SEG"]), (job, acc)
+    return acc
 
 
 def test_golden_msm_cases(ctx):
@@ -388,9 +402,12 @@ def test_msm_large_skew(ctx, ol, pr):
         dl = _arith_dlogs(pr, 0, n)
         k = rand_scalars(1, 3) * n
         assert ctx.msm_bases(b, k)[0] == ol.g1_mul(pr.point_to_xy(pr.G), ol.fr_dot(k, dl))
+        acc = assert_acc_geometry(ctx, k)
+        assert acc["big_count"] <= ctx.prof_last_job()["W"] and acc["extra_count"] >= acc["big_count"] * (n // acc["SEG"] - 1)
         two = rand_scalars(2, 4)
         k2 = (two[:32] * (n // 2)) + (two[32:] * (n // 2))                                  # two distinct values
         assert ctx.msm_bases(b, k2)[0] == ol.g1_mul(pr.point_to_xy(pr.G), ol.fr_dot(k2, dl))
+        assert_acc_geometry(ctx, k2)
     finally:
         b.free()
 
@@ -408,6 +425,7 @@ def test_msm_large_skew_two_level_sort(ctx, ol, pr):
             k = torch.frombuffer(bytearray(blob), dtype=torch.uint8).cuda()
             out, inf = ctx.msm_bases_dev(b, k.data_ptr(), n)
             assert ctx.prof_last_job()["c"] > 16                                             # the two-level path (c = 17 at this size)
+            assert_acc_geometry(ctx, blob if ctx.prof_last_job()["slots"] == n * ctx.prof_last_job()["W"] else None)
             assert out == ol.g1_mul(pr.point_to_xy(pr.G), _dot_arith(pr, blob, 7, n)) and not inf
     finally:
         b.free()
@@ -868,6 +886,8 @@ def test_small_single_msm_rule(ctx, ol, pr, n):
     pts, dl = tiled_bases(ol, n, min(n, 256), 9 + n)
     out, inf = ctx.msm(sc, pts)
     assert ctx.prof_last_job()["c"] == (7 if 512 < n <= 4096 else 8 if n == 512 else ctx.prof_last_job()["c"])
+    acc = assert_acc_geometry(ctx, sc)
+    assert (acc["SEG"] == 8) == (512 <= n <= 4096) and acc["big_count"] >= 1
     assert out == ol.msm_pippenger(sc, pts, 8) and not inf
 
 
@@ -884,6 +904,8 @@ def test_bucket_reduction_any_buckets_per_lane(ctx, ol, pr, monkeypatch, L):
         pts, dl = tiled_bases(ol, n, min(n, 4096), 3 + n)
         out, inf = ctx.msm(sc, pts)
         assert ctx.prof_last_job()["c"] == c_bits
+        acc = assert_acc_geometry(ctx, sc, {"SBN_RED_L": str(L)})
+        assert acc["L"] == L and acc["SEG"] == (8 if n == 3000 else 32)
         assert out == expect_from_dlogs(ol, pr, sc, dl) and not inf, (L, c_bits, n)
     monkeypatch.delenv("SBN_MSM_C")
     Lr, R = 5, 1000
@@ -891,4 +913,8 @@ def test_bucket_reduction_any_buckets_per_lane(ctx, ol, pr, monkeypatch, L):
     Z = rand_scalars(Lr * R, 77 + L); bl = rand_scalars(Lr, 78 + L)
     b = ctx.bases_upload(gx[:64 * R], gx[64 * R:])
     assert ctx.commit_rows(b, Z, bl, Lr, R)[0] == ol.commit_rows(Z, bl, Lr, R, gx[:64 * R], gx[64 * R:], 8)
+    job, acc = ctx.prof_last_job(), ctx.prof_last_acc()
+    assert job["buckets"] == Lr << (job["c"] - 1) and job["slots"] % (Lr * job["W"]) == 0
+    cols = job["slots"] // (Lr * job["W"])                  # R + 1, or the unique bases of a merged set and their sum
+    assert acc_model.geometry_of(acc) == acc_model.geometry(acc_model.ROWS, cols, Lr, cols * job["W"], job["c"], {"SBN_RED_L": str(L)}) and acc["L"] == L
     b.free()

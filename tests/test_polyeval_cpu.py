@@ -91,7 +91,7 @@ def test_model_joint_opening_verifies(ol):
 def test_library_exports_the_one_call_opening_and_checks_its_arguments(sbn):
     """no device here: the symbols exist, and a call without a context (whatever else is wrong with it) is SBN_EINVAL, never a crash"""
     L = sbn.lib()
-    for name in ("sbn_polyeval_prove", "sbn_joint_opening_prove", "sbn_prof_last_polyeval"):
+    for name in ("sbn_polyeval_prove", "sbn_joint_opening_prove", "sbn_prof_last_polyeval", "sbn_prof_last_acc"):
         assert hasattr(L, name)
     tr = sbn.Transcript(b"polyeval")
     before = tr.state()
@@ -107,4 +107,5 @@ def test_library_exports_the_one_call_opening_and_checks_its_arguments(sbn):
                                    good_rnd, tr.h, buf(32), buf(32), buf(256), buf(64), C.byref(xi), buf(64), C.byref(yi))
     assert rc == -1
     assert L.sbn_prof_last_polyeval(None, (C.c_double * 3)()) == -1
+    assert L.sbn_prof_last_acc(None, (C.c_uint64 * 8)()) == -1
     assert tr.state() == before                             # a failed call leaves the transcript as it was
