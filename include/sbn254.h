@@ -350,6 +350,12 @@ int sbn_hash_layer(sbn_ctx* ctx, const void* addr_dev, const sbn_table* val, con
  * out_a / out_b = what two sbn_hash_layer calls with (ts_a, ts_a_add) / (ts_b, ts_b_add) return. */
 int sbn_hash_layer_pair(sbn_ctx* ctx, const void* addr_dev, const sbn_table* val, const void* ts_a_dev, uint32_t ts_a_add, const void* ts_b_dev, uint32_t ts_b_add,
                         const uint8_t r_hash[32], const uint8_t r_multiset[32], sbn_table** out_a, sbn_table** out_b);
+/* The same pair AND the first layer of both product circuits (ProductCircuit::compute_layer, product_tree.rs:21-37) in one pass: a hashed set is
+ * otherwise written by this call and read back at once by the first sbn_product_layer.  out_a / out_b as sbn_hash_layer_pair gives them (the
+ * sumcheck needs layer 0); prod_a[i] = out_a[i] * out_a[i + n/2], prod_b likewise: what sbn_product_layer(out_a) / (out_b) return, n/2 entries.
+ * n = sbn_table_len(val) must be a power of two >= 2, else SBN_EINVAL.  Enqueued only. */
+int sbn_hash_layer_pair_product(sbn_ctx* ctx, const void* addr_dev, const sbn_table* val, const void* ts_a_dev, uint32_t ts_a_add, const void* ts_b_dev, uint32_t ts_b_add,
+                                const uint8_t r_hash[32], const uint8_t r_multiset[32], sbn_table** out_a, sbn_table** out_b, sbn_table** prod_a, sbn_table** prod_b);
 /* ProductCircuit::compute_layer (product_tree.rs:21-37): the next layer's full vector out[i] = in[i] * in[i + len/2] */
 int sbn_product_layer(sbn_ctx* ctx, const sbn_table* in, sbn_table** out);
 /* ProductCircuit::new (product_tree.rs:39-57): every layer above `in` in one call — layers[0] = compute_layer(in) (len/2 entries),
@@ -536,6 +542,46 @@ const void* sbn_dense_audit_ts_dev(const sbn_dense* d, int side);            /* 
 /* the two merged polynomials as tables (for sbn_commit_table, sbn_table_slice, sbn_table_evaluate_many, sbn_table_bound, sbn_table_download) */
 const sbn_table* sbn_dense_comb_ops(const sbn_dense* d);
 const sbn_table* sbn_dense_comb_mem(const sbn_dense* d);
+
+/* ---- SparseMatPolyEvalProof::prove (sparse_mlpoly_full.rs:1700-1755, the Hyrax build) in ONE call: what R1CSEvalProof::prove (r1cs.rs:435-462) wraps —
+ *      equalize, the two eq tables, derefs and their commitment, challenge_r_hash, PolyEvalNetwork::new, ProductLayerProof::prove (:1306-1428) and
+ *      HashLayerProof::prove (:922-1046) with DerefsEvalProof::prove (:412-432) and the three joint openings, every transcript line included ----
+ * Notation: b = sbn_dense_batch(dense) (1 .. 4), N = sbn_dense_num_ops (>= 2), cells = sbn_dense_num_cells (>= 2), m = log2 cells = max(nx, ny),
+ * n = log2 N; per opened polynomial k in {ops, mem, derefs}: ell_ops = n + log2 npo2(5 b), ell_mem = m + 1, ell_derefs = n + log2 npo2(2 b)
+ * (:619-627), (L_k, R_k) = 2^sbn_factored_lens(ell_k), lg_k = log2 R_k; npo2 = next power of two.
+ *   dense    only read: its tables, addresses and timestamps are left as they are.
+ *   rx, ry   nx / ny canonical scalars; the shorter point is padded with zeros at the front (equalize, :1681-1697).
+ *   evals    b canonical scalars: the claimed evaluations, one per matrix.
+ *   gens_k   R_k + 1 generators with h, the handle sbn_polyeval_prove takes.  The derefs commitment runs over the first R_derefs of gens_derefs
+ *            with no blinds; that subset is derived on first use, owned by gens_derefs and freed with it.
+ *   rnd      the RandomTape draws of the three openings in the reference's order: derefs [3 + 2 lg_derefs] | ops [3 + 2 lg_ops] | mem [3 + 2 lg_mem],
+ *            each as sbn_polyeval_prove takes them.     rnd_scalars = 9 + 2 (lg_derefs + lg_ops + lg_mem).
+ *   out_proof  the fields of SparseMatPolyEvalProof in declaration order, nested structs likewise; points as sbn_g1_compress gives them, scalars canonical.
+ *              PCEPB(c, l, d) = a ProductCircuitEvalProofBatched of c circuits, l layers, d dot-product circuits: sbn_product_proof_prove's out_polys
+ *              (128 l (l - 1) / 2 bytes) followed by its out_claims (32 (2 c l + 3 d) bytes).  OPEN(lg) = sbn_polyeval_prove's out_proof (64 lg + 128 bytes).
+ *                comm_derefs                  [L_derefs x 32]
+ *                proof_prod_layer.eval_row    [init, read[b], write[b], audit]
+ *                proof_prod_layer.eval_col    [init, read[b], write[b], audit]
+ *                proof_prod_layer.eval_val    [eval_dotp_left[b], eval_dotp_right[b]]
+ *                proof_prod_layer.proof_mem   PCEPB(4, m, 0): row init, row audit, col init, col audit   (declared before proof_ops, proved after it)
+ *                proof_prod_layer.proof_ops   PCEPB(4 b, n, 2 b): row read[b], row write[b], col read[b], col write[b]; dot-product halves left_0, right_0, left_1, ...
+ *                proof_hash_layer.eval_row    [addr[b], read_ts[b], audit_ts]
+ *                proof_hash_layer.eval_col    [addr[b], read_ts[b], audit_ts]
+ *                proof_hash_layer.eval_val    [b]
+ *                proof_hash_layer.eval_derefs [row[b], col[b]]
+ *                proof_hash_layer.proof_ops   OPEN(lg_ops)
+ *                proof_hash_layer.proof_mem   OPEN(lg_mem)
+ *                proof_hash_layer.proof_derefs OPEN(lg_derefs)
+ *              proof_bytes = 32 L_derefs + 32 (13 b + 6) + 64 (m (m - 1) + n (n - 1)) + 256 (m + b n) + 192 b + 64 (lg_ops + lg_mem + lg_derefs) + 384.
+ * `tr` is advanced exactly as the reference advances its transcript, and only when the call returns SBN_OK; out_proof is written only then.
+ * SBN_EINVAL before any launch (text cites the reference's assert): a null pointer, batch > 4 (6 b instances must fit one product proof), N < 2, max(nx, ny) !=
+ * log2 cells, a generator handle of the wrong size or without h, a scalar of rx, ry, evals or rnd >= r.  After launches: eval_dotp_left + eval_dotp_right !=
+ * evals[i] is SBN_EINVAL (the reference panics, :1366); a failed subset check init * writes == reads * audit (:1324, :1339; impossible on a handle
+ * sbn_dense_build made) is SBN_EHIP.  Same bytes as the loop over the calls above with the same draws (tests/sparse_eval_loop.py). */
+/* host only: the sizes of rnd (in scalars) and out_proof (in bytes); SBN_EINVAL for a shape the call refuses (batch outside 1 .. 4, N < 2 or not a power of two) */
+int sbn_sparse_eval_sizes(size_t num_vars_x, size_t num_vars_y, size_t num_ops /* N */, size_t batch, size_t* rnd_scalars, size_t* proof_bytes);
+int sbn_sparse_eval_prove(sbn_ctx* ctx, const sbn_dense* dense, const uint8_t* rx, size_t nx, const uint8_t* ry, size_t ny, const uint8_t* evals /* batch x 32 */,
+                          const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_bases* gens_derefs, const uint8_t* rnd, sbn_transcript* tr, uint8_t* out_proof);
 
 /* ---- per-kernel timing (HIP events on the context's stream), for bench.py's roofline line ---- */
 int sbn_prof_enable(sbn_ctx* ctx, int on);

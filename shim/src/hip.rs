@@ -36,6 +36,7 @@ use crate::nizk::DotProductProof;
 use crate::random::RandomTape;
 use crate::r1cs::R1CSShape;
 use crate::r1csproof::{R1CSGens, R1CSProof};
+use crate::sparse_mlpoly_full::{SparseMatPolyCommitmentGens, SparseMatPolyEvalProof};
 use crate::sumcheck::{SumcheckInstanceProof, ZKSumcheckInstanceProof};
 use ark_serialize::CanonicalDeserialize;
 use crate::transcript::{AppendToTranscript, ProofTranscript};
@@ -147,6 +148,7 @@ extern "C" {
     pub fn sbn_zk_sumcheck_prove_quad(ctx: *mut sbn_ctx, z: *mut sbn_table, abc: *mut sbn_table, gens_1: *const sbn_bases, gens_3: *const sbn_bases, claim: *const u8, blind_claim: *const u8, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8, out_r: *mut u8, out_finals: *mut u8, out_blind: *mut u8) -> c_int;
     pub fn sbn_hash_layer(ctx: *mut sbn_ctx, addr_dev: *const c_void, val: *const sbn_table, ts_dev: *const c_void, ts_add: u32, r_hash: *const u8, r_multiset: *const u8, out: *mut *mut sbn_table) -> c_int;
     pub fn sbn_hash_layer_pair(ctx: *mut sbn_ctx, addr_dev: *const c_void, val: *const sbn_table, ts_a_dev: *const c_void, ts_a_add: u32, ts_b_dev: *const c_void, ts_b_add: u32, r_hash: *const u8, r_multiset: *const u8, out_a: *mut *mut sbn_table, out_b: *mut *mut sbn_table) -> c_int;
+    pub fn sbn_hash_layer_pair_product(ctx: *mut sbn_ctx, addr_dev: *const c_void, val: *const sbn_table, ts_a_dev: *const c_void, ts_a_add: u32, ts_b_dev: *const c_void, ts_b_add: u32, r_hash: *const u8, r_multiset: *const u8, out_a: *mut *mut sbn_table, out_b: *mut *mut sbn_table, prod_a: *mut *mut sbn_table, prod_b: *mut *mut sbn_table) -> c_int;
     pub fn sbn_product_layer(ctx: *mut sbn_ctx, input: *const sbn_table, out: *mut *mut sbn_table) -> c_int;
     pub fn sbn_product_circuit(ctx: *mut sbn_ctx, input: *const sbn_table, layers: *mut *mut sbn_table, cap: usize, count: *mut usize) -> c_int;
     pub fn sbn_product_circuit_many(ctx: *mut sbn_ctx, ins: *const *const sbn_table, n: usize, layers: *mut *mut sbn_table, cap: usize, count: *mut usize) -> c_int;
@@ -196,6 +198,8 @@ extern "C" {
     pub fn sbn_dense_audit_ts_dev(d: *const sbn_dense, side: c_int) -> *const c_void;
     pub fn sbn_dense_comb_ops(d: *const sbn_dense) -> *const sbn_table;
     pub fn sbn_dense_comb_mem(d: *const sbn_dense) -> *const sbn_table;
+    pub fn sbn_sparse_eval_sizes(num_vars_x: usize, num_vars_y: usize, num_ops: usize, batch: usize, rnd_scalars: *mut usize, proof_bytes: *mut usize) -> c_int;
+    pub fn sbn_sparse_eval_prove(ctx: *mut sbn_ctx, dense: *const sbn_dense, rx: *const u8, nx: usize, ry: *const u8, ny: usize, evals: *const u8, gens_ops: *const sbn_bases, gens_mem: *const sbn_bases, gens_derefs: *const sbn_bases, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8) -> c_int;
     pub fn sbn_prof_enable(ctx: *mut sbn_ctx, on: c_int) -> c_int;
     pub fn sbn_prof_reset(ctx: *mut sbn_ctx) -> c_int;
     pub fn sbn_prof_count(ctx: *mut sbn_ctx) -> c_int;
@@ -1137,3 +1141,103 @@ pub fn dense_side(d: *const sbn_dense, side: c_int) -> (Vec<(*const c_void, *con
 }
 /// comb_ops and comb_mem: read-only tables that belong to the handle (never wrapped in `Table`, whose Drop frees)
 pub fn dense_tables(d: *const sbn_dense) -> (*const sbn_table, *const sbn_table) { unsafe { (sbn_dense_comb_ops(d), sbn_dense_comb_mem(d)) } }
+
+// ---- SparseMatPolyEvalProof::prove (sparse_mlpoly_full.rs:1700-1755) in ONE foreign call (sbn_sparse_eval_prove) -----------------------
+// The library runs equalize, the eq tables, derefs and their commitment, the network's hash layers and product circuits, both product proofs,
+// the 7 b + 2 evaluations, the three joint openings and the whole transcript.  This side draws the RandomTape in the reference's order and
+// rebuilds the proof from the bytes through its derived CanonicalDeserialize: the library's fields in declaration order, with the u64 length
+// ark-serialize puts in front of each Vec (tuples are their members one after the other).
+/// the RandomTape draws of one PolyEvalProof::prove with lg bullet rounds (DotProductProofLog::prove, nizk/mod.rs:458-468)
+fn open_draws(random_tape: &mut RandomTape, lg: usize) -> Vec<Scalar> {
+    let mut rnd = vec![random_tape.random_scalar(b"d"), random_tape.random_scalar(b"r_delta"), random_tape.random_scalar(b"r_delta")];      // (r_beta is drawn under "r_delta")
+    let (v1, v2) = (random_tape.random_vector(b"blinds_vec_1", lg), random_tape.random_vector(b"blinds_vec_2", lg));
+    for i in 0..lg { rnd.push(v1[i]); rnd.push(v2[i]); }
+    rnd
+}
+/// SparseMatPolyEvalProof::prove with a `DevTranscript`; `dense_dev` is the dense representation's device handle (`DenseDev::get`, built at encode time)
+pub fn sparse_eval_prove(
+    dense_dev: *const sbn_dense,
+    rx: &[Scalar],
+    ry: &[Scalar],
+    evals: &[Scalar],
+    gens: &SparseMatPolyCommitmentGens,
+    transcript: &mut DevTranscript,
+    random_tape: &mut RandomTape,
+) -> SparseMatPolyEvalProof {
+    let (num_ops, num_cells, b) = dense_shape(dense_dev);
+    assert_eq!(evals.len(), b);                                                       // sparse_mlpoly_full.rs:1711
+    let (n, m) = (num_ops.trailing_zeros() as usize, num_cells.trailing_zeros() as usize);
+    let lg_of = |g: &crate::hyrax::PolyCommitmentGens| g.gens.gens_n.n.trailing_zeros() as usize;
+    let (lg_o, lg_m, lg_d) = (lg_of(&gens.gens_ops), lg_of(&gens.gens_mem), lg_of(&gens.gens_derefs));
+    let (mut n_rnd, mut n_proof) = (0usize, 0usize);
+    check(unsafe { sbn_sparse_eval_sizes(rx.len(), ry.len(), num_ops, b, &mut n_rnd, &mut n_proof) });
+    // HashLayerProof::prove opens derefs, then comb_ops, then comb_mem (:945-1035)
+    let mut rnd = open_draws(random_tape, lg_d);
+    rnd.extend(open_draws(random_tape, lg_o));
+    rnd.extend(open_draws(random_tape, lg_m));
+    assert_eq!(rnd.len(), n_rnd);
+    let (rnd, rxb, ryb, evb) = (scalars_canonical(&rnd), scalars_canonical(rx), scalars_canonical(ry), scalars_canonical(evals));
+    let g_ops = pc_bases(&gens.gens_ops.gens.gens_n, &gens.gens_ops.gens.gens_1);
+    let g_mem = pc_bases(&gens.gens_mem.gens.gens_n, &gens.gens_mem.gens.gens_1);
+    let g_der = pc_bases(&gens.gens_derefs.gens.gens_n, &gens.gens_derefs.gens.gens_1);
+    let mut proof = vec![0u8; n_proof];
+    check(unsafe {
+        sbn_sparse_eval_prove(ctx(), dense_dev, rxb.as_ptr(), rx.len(), ryb.as_ptr(), ry.len(), evb.as_ptr(), g_ops.0, g_mem.0, g_der.0, rnd.as_ptr(), transcript.0,
+                              proof.as_mut_ptr())
+    });
+    // out_proof -> the stream the derived CanonicalDeserialize reads
+    let mut ser: Vec<u8> = Vec::with_capacity(2 * n_proof);
+    let mut at = 0usize;
+    let mut take = |k: usize| { let s = &proof[at..at + k]; at += k; s };
+    let len = |ser: &mut Vec<u8>, k: usize| ser.extend_from_slice(&(k as u64).to_le_bytes());
+    let vec32 = |ser: &mut Vec<u8>, p: &[u8]| { len(ser, p.len() / 32); ser.extend_from_slice(p); };
+    // ProductCircuitEvalProofBatched { proof: Vec<LayerProofBatched { SumcheckInstanceProof, claims_prod_left, claims_prod_right }>, claims_dotp }
+    let pcepb = |ser: &mut Vec<u8>, polys: &[u8], claims: &[u8], c: usize, l: usize, d: usize| {
+        len(ser, l);
+        let mut po = 0usize;
+        for k in 0..l {
+            len(ser, k);                                                              // compressed_polys: k rounds
+            for _ in 0..k {
+                let q = &polys[po..po + 128]; po += 128;
+                len(ser, 3); ser.extend_from_slice(&q[..32]); ser.extend_from_slice(&q[64..128]);      // CompressedUniPoly: c0, c2, c3 (unipoly.rs:87-99)
+            }
+            let cl = &claims[64 * c * k..64 * c * (k + 1)];
+            vec32(ser, &cl[..32 * c]); vec32(ser, &cl[32 * c..]);
+        }
+        let dp = &claims[64 * c * l..];
+        for j in 0..3 { vec32(ser, &dp[32 * d * j..32 * d * (j + 1)]); }
+    };
+    let open = |ser: &mut Vec<u8>, p: &[u8], lg: usize| {                             // PolyEvalProof { DotProductProofLog { BulletReductionProof { L_vec, R_vec }, delta, beta, z1, z2 } }
+        len(ser, lg); ser.extend_from_slice(&p[..32 * lg]);
+        len(ser, lg); ser.extend_from_slice(&p[32 * lg..64 * lg]);
+        ser.extend_from_slice(&p[64 * lg..]);
+    };
+    let l_d = n_proof - (32 * (13 * b + 6) + 64 * (m * (m - 1) + n * (n - 1)) + 256 * (m + b * n) + 192 * b + 64 * (lg_o + lg_m + lg_d) + 384);
+    vec32(&mut ser, take(l_d));                                                       // comm_derefs: DerefsCommitment { PolyCommitment { C } }
+    for _ in 0..2 {                                                                   // ProductLayerProof.eval_row, eval_col: (Scalar, Vec, Vec, Scalar)
+        ser.extend_from_slice(take(32)); vec32(&mut ser, take(32 * b)); vec32(&mut ser, take(32 * b)); ser.extend_from_slice(take(32));
+    }
+    vec32(&mut ser, take(32 * b)); vec32(&mut ser, take(32 * b));                     // eval_val: (Vec, Vec)
+    { let polys = take(64 * m * (m - 1)).to_vec(); let claims = take(256 * m); pcepb(&mut ser, &polys, claims, 4, m, 0); }                             // proof_mem
+    { let polys = take(64 * n * (n - 1)).to_vec(); let claims = take(256 * b * n + 192 * b); pcepb(&mut ser, &polys, claims, 4 * b, n, 2 * b); }       // proof_ops
+    for _ in 0..2 {                                                                   // HashLayerProof.eval_row, eval_col: (Vec, Vec, Scalar)
+        vec32(&mut ser, take(32 * b)); vec32(&mut ser, take(32 * b)); ser.extend_from_slice(take(32));
+    }
+    vec32(&mut ser, take(32 * b));                                                    // eval_val
+    vec32(&mut ser, take(32 * b)); vec32(&mut ser, take(32 * b));                     // eval_derefs
+    open(&mut ser, take(64 * lg_o + 128), lg_o);                                      // proof_ops
+    open(&mut ser, take(64 * lg_m + 128), lg_m);                                      // proof_mem
+    open(&mut ser, take(64 * lg_d + 128), lg_d);                                      // proof_derefs: DerefsEvalProof { PolyEvalProof }
+    SparseMatPolyEvalProof::deserialize_compressed(&ser[..]).expect("SparseMatPolyEvalProof from the library's bytes")
+}
+
+/// One pair of hashed sets of Layers::build_hash_layer (sparse_mlpoly_full.rs:762-790) and the first layer of both product circuits
+/// (ProductCircuit::compute_layer, product_tree.rs:21-37) in one pass: (out_a, out_b, prod_a, prod_b).  `addr` / `ts_*` are device arrays of
+/// `dense_side` (null: the cell index / zeros); `val` must hold a power of two >= 2 of entries.
+pub fn hash_layer_pair_product(addr: *const c_void, val: *const sbn_table, ts_a: *const c_void, ts_a_add: u32, ts_b: *const c_void, ts_b_add: u32,
+                               r_hash: &Scalar, r_multiset: &Scalar) -> (Table, Table, Table, Table) {
+    let (g, tau) = (r_hash.to_bytes(), r_multiset.to_bytes());
+    let (mut a, mut b, mut pa, mut pb) = (null_mut(), null_mut(), null_mut(), null_mut());
+    check(unsafe { sbn_hash_layer_pair_product(ctx(), addr, val, ts_a, ts_a_add, ts_b, ts_b_add, g.as_ptr(), tau.as_ptr(), &mut a, &mut b, &mut pa, &mut pb) });
+    (Table(a), Table(b), Table(pa), Table(pb))
+}

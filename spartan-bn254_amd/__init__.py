@@ -6,5 +6,5 @@ gfx950 device is missing, loading / context creation raises.
 """
 from .binding import (  # noqa: F401
     Context, Group, Bases, Table, Dense, SbnError, lib, lib_path, build_library,
-    SBN_SCALARS_MONT, SBN_POINTS_MONT, g1_compress, g1_sum, Transcript, fr_from_wide, unipoly_from_evals, unipoly_eval, factored_lens, r1cs_proof_sizes, EXPORTED_SYMBOLS,
+    SBN_SCALARS_MONT, SBN_POINTS_MONT, g1_compress, g1_sum, Transcript, fr_from_wide, unipoly_from_evals, unipoly_eval, factored_lens, r1cs_proof_sizes, sparse_eval_sizes, EXPORTED_SYMBOLS,
 )

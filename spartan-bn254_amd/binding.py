@@ -21,10 +21,10 @@ EXPORTED_SYMBOLS = [
     "sbn_polyeval_prove", "sbn_joint_opening_prove", "sbn_prof_last_polyeval", "sbn_zk_sumcheck_prove_r1cs", "sbn_zk_sumcheck_prove_quad",
     "sbn_group_create", "sbn_group_destroy", "sbn_group_size", "sbn_group_ctx", "sbn_group_last_error", "sbn_group_bases_upload", "sbn_group_gens_new", "sbn_group_bases_precompute",
     "sbn_group_bases_free", "sbn_group_commit_rows", "sbn_group_commit_rows_dev", "sbn_group_gather_commit", "sbn_group_msm", "sbn_group_bases_upload_ranges", "sbn_group_bases_synthetic_ranges", "sbn_group_range", "sbn_group_msm_bases", "sbn_group_msm_bases_dev",
-    "sbn_eq_evals", "sbn_hash_layer", "sbn_hash_layer_pair", "sbn_product_layer", "sbn_product_circuit", "sbn_product_circuit_many", "sbn_table_halves", "sbn_table_slice", "sbn_table_dot", "sbn_table_evaluate", "sbn_table_evaluate_many", "sbn_table_bound", "sbn_gather_merge", "sbn_gather_merge_rows", "sbn_commit_table", "sbn_bullet_begin", "sbn_bullet_begin_scaled", "sbn_bullet_free", "sbn_bullet_len", "sbn_bullet_cross", "sbn_bullet_fold_cross", "sbn_bullet_fold", "sbn_bullet_finish", "sbn_prof_enable", "sbn_prof_reset", "sbn_prof_count", "sbn_prof_get", "sbn_prof_last_job", "sbn_prof_last_acc",
+    "sbn_eq_evals", "sbn_hash_layer", "sbn_hash_layer_pair", "sbn_hash_layer_pair_product", "sbn_product_layer", "sbn_product_circuit", "sbn_product_circuit_many", "sbn_table_halves", "sbn_table_slice", "sbn_table_dot", "sbn_table_evaluate", "sbn_table_evaluate_many", "sbn_table_bound", "sbn_gather_merge", "sbn_gather_merge_rows", "sbn_commit_table", "sbn_bullet_begin", "sbn_bullet_begin_scaled", "sbn_bullet_free", "sbn_bullet_len", "sbn_bullet_cross", "sbn_bullet_fold_cross", "sbn_bullet_fold", "sbn_bullet_finish", "sbn_prof_enable", "sbn_prof_reset", "sbn_prof_count", "sbn_prof_get", "sbn_prof_last_job", "sbn_prof_last_acc",
     "sbn_kzg_srs_upload", "sbn_kzg_srs_from_tau", "sbn_kzg_commit", "sbn_poly_div_linear", "sbn_kzg_open", "sbn_kzg_open_batched",
     "sbn_r1cs_upload", "sbn_r1cs_free", "sbn_r1cs_multiply", "sbn_r1cs_eval_table", "sbn_r1cs_evaluate",
-    "sbn_r1cs_proof_sizes", "sbn_r1cs_proof_prove",
+    "sbn_r1cs_proof_sizes", "sbn_r1cs_proof_prove", "sbn_sparse_eval_sizes", "sbn_sparse_eval_prove",
     "sbn_dense_build", "sbn_dense_free", "sbn_dense_num_ops", "sbn_dense_num_cells", "sbn_dense_batch", "sbn_dense_addr_dev", "sbn_dense_read_ts_dev",
     "sbn_dense_audit_ts_dev", "sbn_dense_comb_ops", "sbn_dense_comb_mem",
 ]
@@ -89,6 +89,8 @@ def lib():
         L.sbn_zk_sumcheck_prove_quad.argtypes = [C.c_void_p] * 13
         L.sbn_r1cs_proof_sizes.argtypes = [C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
         L.sbn_r1cs_proof_prove.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 8
+        L.sbn_sparse_eval_sizes.argtypes = [C.c_size_t] * 4 + [C.c_void_p] * 2
+        L.sbn_sparse_eval_prove.argtypes = [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_void_p] * 7
         L.sbn_dense_audit_ts_dev.restype = C.c_void_p; L.sbn_dense_audit_ts_dev.argtypes = [C.c_void_p, C.c_int]
         for name in ("sbn_dense_comb_ops", "sbn_dense_comb_mem"):
             getattr(L, name).restype = C.c_void_p; getattr(L, name).argtypes = [C.c_void_p]
@@ -352,6 +354,15 @@ class R1cs:
         if self.h:
             lib().sbn_r1cs_free(self.ctx.h, self.h)
             self.h = None
+
+
+def sparse_eval_sizes(num_vars_x, num_vars_y, num_ops, batch):
+    """sbn_sparse_eval_sizes -> (scalars of rnd, bytes of the proof) of sbn_sparse_eval_prove at this shape"""
+    a, b = C.c_size_t(0), C.c_size_t(0)
+    rc = lib().sbn_sparse_eval_sizes(C.c_size_t(num_vars_x), C.c_size_t(num_vars_y), C.c_size_t(num_ops), C.c_size_t(batch), C.byref(a), C.byref(b))
+    if rc:
+        raise SbnError(f"sbn_sparse_eval_sizes: ({num_vars_x}, {num_vars_y}, N = {num_ops}, batch = {batch}) is a shape the call refuses (rc={rc})")
+    return a.value, b.value
 
 
 class Dense:
@@ -717,6 +728,13 @@ class Context:
                                             _ptr(r_hash), _ptr(r_multiset), C.byref(ha), C.byref(hb)), "sbn_hash_layer_pair")
         return Table(self, ha), Table(self, hb)
 
+    def hash_layer_pair_product(self, addr_dev_ptr, val, ts_a_ptr, ts_a_add, ts_b_ptr, ts_b_add, r_hash, r_multiset):
+        """hash_layer_pair and the first product layer of both sets in one pass -> (out_a, out_b, prod_a, prod_b)"""
+        hs = [C.c_void_p() for _ in range(4)]
+        self._chk(lib().sbn_hash_layer_pair_product(self.h, C.c_void_p(addr_dev_ptr or 0), val.h, C.c_void_p(ts_a_ptr or 0), C.c_uint32(ts_a_add), C.c_void_p(ts_b_ptr or 0),
+                                                    C.c_uint32(ts_b_add), _ptr(r_hash), _ptr(r_multiset), *[C.byref(h) for h in hs]), "sbn_hash_layer_pair_product")
+        return tuple(Table(self, h) for h in hs)
+
     def product_layer(self, t):
         ht = C.c_void_p(); self._chk(lib().sbn_product_layer(self.h, t.h, C.byref(ht)), "sbn_product_layer"); return Table(self, ht)
 
@@ -872,6 +890,21 @@ class Context:
         self._chk(lib().sbn_r1cs_proof_prove(self.h, inst.h, vars.h, _ptr(inputs) if inputs else None, C.c_size_t(len(inputs) // 32 if inputs else 0),
                                              gens_pc.h, gens_3.h, gens_4.h, _ptr(rnd), tr.h, proof, rx, ry), "sbn_r1cs_proof_prove")
         return bytes(proof), bytes(rx), bytes(ry)
+
+    # ---- SparseMatPolyEvalProof::prove in one call (sparse_mlpoly_full.rs:1700-1755)
+    def sparse_eval_prove(self, dense, rx, ry, evals, gens_ops, gens_mem, gens_derefs, rnd, tr):
+        """SparseMatPolyEvalProof::prove (sbn_sparse_eval_prove) -> proof bytes, laid out as include/sbn254.h describes.  dense: a Dense (only read);
+        rx, ry, evals: canonical scalars, 32 bytes each; gens_*: R + 1 generators with h; rnd: sparse_eval_sizes(...)[0] scalars; `tr` (Transcript) moves on"""
+        nx, ny = len(rx) // 32, len(ry) // 32
+        n_rnd, n_proof = sparse_eval_sizes(nx, ny, dense.num_ops, dense.batch)
+        if len(rnd) != 32 * n_rnd:
+            raise ValueError(f"sparse_eval_prove: rnd holds {len(rnd)} bytes, the shape needs {32 * n_rnd}")
+        if len(evals) != 32 * dense.batch:
+            raise ValueError(f"sparse_eval_prove: evals holds {len(evals)} bytes, the batch needs {32 * dense.batch}  [sparse_mlpoly_full.rs:1711 assert_eq]")
+        proof = (C.c_uint8 * n_proof)()
+        self._chk(lib().sbn_sparse_eval_prove(self.h, dense.h, _ptr(rx) if rx else None, C.c_size_t(nx), _ptr(ry) if ry else None, C.c_size_t(ny), _ptr(evals),
+                                              gens_ops.h, gens_mem.h, gens_derefs.h, _ptr(rnd), tr.h, proof), "sbn_sparse_eval_prove")
+        return bytes(proof)
 
     # ---- KZG mode (kzg.rs): the SRS is a Bases handle, polynomials are the first n entries of a Table
     def kzg_srs_upload(self, powers_xy, flags=0):

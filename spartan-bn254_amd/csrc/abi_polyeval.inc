@@ -193,21 +193,16 @@ int sbn_polyeval_prove(sbn_ctx* c, const sbn_bases* gens, const sbn_table* Z, co
   return SBN_OK;
 }
 
-int sbn_joint_opening_prove(sbn_ctx* c, const sbn_bases* gens, const sbn_table* Z, const uint8_t* evals, size_t count,
-                            const uint8_t* label_evals, size_t label_evals_len, const uint8_t* label_chal, size_t label_chal_len,
-                            const uint8_t* label_claim, size_t label_claim_len, const uint8_t* r, size_t ell_r, const uint8_t* rnd, sbn_transcript* tr,
-                            uint8_t* out_challenges, uint8_t out_joint_claim[32], uint8_t* out_proof,
-                            uint8_t out_Cx_xy[64], int* Cx_is_inf, uint8_t out_Cy_xy[64], int* Cy_is_inf) {
+}  // extern "C"
+// the reduction and the opening on the transcript `t` (a copy of the caller's); count = 2^lc evals, canonical as r is; the caller holds the
+// context's mutex.  out_challenges: lc x 32 or NULL
+static int joint_opening_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_table* Z, const uint8_t* evals, size_t count, size_t lc,
+                                const uint8_t* label_evals, size_t label_evals_len, const uint8_t* label_chal, size_t label_chal_len,
+                                const uint8_t* label_claim, size_t label_claim_len, const uint8_t* r, size_t ell_r, const uint8_t* rnd, sbn_host::MerlinTranscript& t,
+                                uint8_t* out_challenges, uint8_t out_joint_claim[32], uint8_t* out_proof,
+                                uint8_t out_Cx_xy[64], int* Cx_is_inf, uint8_t out_Cy_xy[64], int* Cy_is_inf) {
   using namespace sbn_host::fr;
-  if (!c || !gens || !Z || !evals || !label_evals || !label_chal || !label_claim || (!r && ell_r) || !rnd || !tr || !out_joint_claim || !out_proof || !out_Cx_xy || !out_Cy_xy) return SBN_EINVAL;
-  if (count == 0 || (count & (count - 1)) || count > ((size_t)1 << 20)) return fail(c, SBN_EINVAL, "joint opening: %zu evals (a power of two is needed: the caller pads)", count);
-  size_t lc = 0; while (((size_t)1 << lc) < count) lc++;
-  if (lc && !out_challenges) return SBN_EINVAL;
-  for (size_t i = 0; i < count; i++) if (!fr_canonical(evals + 32 * i)) return fail(c, SBN_EINVAL, "joint opening: evals[%zu] is not canonical", i);
   const size_t ell = lc + ell_r;
-  if (ell > 2 * (size_t)PE_SIDE_MAX) return fail(c, SBN_EINVAL, "joint opening: %zu variables", ell);
-  for (size_t j = 0; j < ell_r; j++) if (!fr_canonical(r + 32 * j)) return fail(c, SBN_EINVAL, "joint opening: r[%zu] is not canonical", j);
-  sbn_host::MerlinTranscript t = tr->t;
   for (size_t i = 0; i < count; i++) t.append_message(label_evals, label_evals_len, evals + 32 * i, 32);      // sparse_mlpoly_full.rs:384
   std::vector<uint8_t> rj(32 * ell);
   for (size_t j = 0; j < lc; j++) { uint8_t b[64]; t.challenge_bytes(label_chal, label_chal_len, b, 64); transcript_wide_reduce(b, &rj[32 * j]); }     // :387
@@ -224,12 +219,32 @@ int sbn_joint_opening_prove(sbn_ctx* c, const sbn_bases* gens, const sbn_table* 
   t.append_message(label_claim, label_claim_len, claim, 32);       // :397
   int rc;
   if ((rc = polyeval_check(c, gens, Z, nullptr, rj.data(), ell, claim, nullptr, rnd))) return rc;
-  {
-    std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
-    if ((rc = polyeval_prove_locked(c, gens, Z, nullptr, rj.data(), ell, claim, nullptr, rnd, t, out_proof, out_Cx_xy, Cx_is_inf, out_Cy_xy, Cy_is_inf))) return rc;
-  }
-  if (lc) memcpy(out_challenges, rj.data(), 32 * lc);
+  if ((rc = polyeval_prove_locked(c, gens, Z, nullptr, rj.data(), ell, claim, nullptr, rnd, t, out_proof, out_Cx_xy, Cx_is_inf, out_Cy_xy, Cy_is_inf))) return rc;
+  if (lc && out_challenges) memcpy(out_challenges, rj.data(), 32 * lc);
   memcpy(out_joint_claim, claim, 32);
+  return SBN_OK;
+}
+
+extern "C" {
+
+int sbn_joint_opening_prove(sbn_ctx* c, const sbn_bases* gens, const sbn_table* Z, const uint8_t* evals, size_t count,
+                            const uint8_t* label_evals, size_t label_evals_len, const uint8_t* label_chal, size_t label_chal_len,
+                            const uint8_t* label_claim, size_t label_claim_len, const uint8_t* r, size_t ell_r, const uint8_t* rnd, sbn_transcript* tr,
+                            uint8_t* out_challenges, uint8_t out_joint_claim[32], uint8_t* out_proof,
+                            uint8_t out_Cx_xy[64], int* Cx_is_inf, uint8_t out_Cy_xy[64], int* Cy_is_inf) {
+  if (!c || !gens || !Z || !evals || !label_evals || !label_chal || !label_claim || (!r && ell_r) || !rnd || !tr || !out_joint_claim || !out_proof || !out_Cx_xy || !out_Cy_xy) return SBN_EINVAL;
+  if (count == 0 || (count & (count - 1)) || count > ((size_t)1 << 20)) return fail(c, SBN_EINVAL, "joint opening: %zu evals (a power of two is needed: the caller pads)", count);
+  size_t lc = 0; while (((size_t)1 << lc) < count) lc++;
+  if (lc && !out_challenges) return SBN_EINVAL;
+  for (size_t i = 0; i < count; i++) if (!fr_canonical(evals + 32 * i)) return fail(c, SBN_EINVAL, "joint opening: evals[%zu] is not canonical", i);
+  const size_t ell = lc + ell_r;
+  if (ell > 2 * (size_t)PE_SIDE_MAX) return fail(c, SBN_EINVAL, "joint opening: %zu variables", ell);
+  for (size_t j = 0; j < ell_r; j++) if (!fr_canonical(r + 32 * j)) return fail(c, SBN_EINVAL, "joint opening: r[%zu] is not canonical", j);
+  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+  sbn_host::MerlinTranscript t = tr->t;
+  const int rc = joint_opening_locked(c, gens, Z, evals, count, lc, label_evals, label_evals_len, label_chal, label_chal_len, label_claim, label_claim_len, r, ell_r, rnd, t,
+                                      out_challenges, out_joint_claim, out_proof, out_Cx_xy, Cx_is_inf, out_Cy_xy, Cy_is_inf);
+  if (rc) return rc;
   tr->t = t;
   return SBN_OK;
 }

@@ -154,6 +154,9 @@ __global__ void __launch_bounds__(64) k_pp_unscale(uint32_t* __restrict__ fin, c
   fe_store_packed<FrP>(fin + 8 * i, fe_from_mont(fe_mul(x, fe_load<FrP>(inv + 8 * i))));
 }
 
+// blocks per dot-product circuit of k_pp_dotp over tables of `len` entries; the partial sums need SC_PACK_MAX * pp_dotp_grid(len) * 32 bytes of c->sc_partial
+static inline size_t pp_dotp_grid(size_t len) { return std::min<size_t>(std::max<size_t>(1, (len + 255) / 256), 1024); }
+
 // One boundary's transcript work from the phase (pos, pos_begin, cur_flags): the records k_tr_layer_step executes.
 //   close (n_close > 0): append_scalar("claim_prod_left" / "claim_prod_right") per circuit, ("claim_dotp_left" / "_right" / "_weight") per
 //   dot-product circuit (product_tree.rs:352-365; append_scalar = append_message of the 32 canonical bytes, transcript.rs:28-32), then
@@ -209,11 +212,13 @@ static int transcript_plan_boundary(uint8_t pos, uint8_t pos_begin, uint8_t cur_
   return SBN_OK;
 }
 
-// the job itself; the caller holds the mutex and has checked the arguments.  force_plain: every layer in PLAIN mode (the rerun behind a zero
+// the job itself; the caller holds the mutex and has checked the arguments.  dotp_partials_present: the caller has just run k_pp_dotp over these
+// dot-product circuits with this job's grid (dotp_grid) into c->sc_partial and nothing has written there since: the pass is not repeated.  force_plain: every layer in PLAIN mode (the rerun behind a zero
 // coefficient).  *zero_coeff: a COMB layer met c_i = 0 — the outputs are not valid and nothing was written to them or to the transcript.
 static int product_proof_run(sbn_ctx* c, const sbn_table* const* layers, size_t n_circ, size_t n_layers,
                              const sbn_table* const* dotp_left, const sbn_table* const* dotp_right, const sbn_table* const* dotp_weight, size_t n_dotp,
-                             sbn_transcript* tr, uint8_t* out_polys, uint8_t* out_claims, uint8_t* out_rand, uint8_t* out_claims_final, bool force_plain, bool* zero_coeff) {
+                             sbn_transcript* tr, uint8_t* out_polys, uint8_t* out_claims, uint8_t* out_rand, uint8_t* out_claims_final, bool force_plain, bool* zero_coeff,
+                             bool dotp_partials_present = false) {
   *zero_coeff = false;
   using namespace sbn_host::fr;
   int rc;
@@ -316,7 +321,7 @@ static int product_proof_run(sbn_ctx* c, const sbn_table* const* layers, size_t 
   const size_t o_tfin = off; off += al((size_t)SC_FINAL_MAX * 32);       // the sumcheck state's d_finals (table format)
   const size_t o_mbox = off; off += al((size_t)SC_MBOX_WORDS * 4);
   const size_t total = off;
-  const size_t gx_dot = std::min<size_t>(std::max<size_t>(1, (len_max + 255) / 256), 1024);
+  const size_t gx_dot = pp_dotp_grid(len_max);
   if ((rc = ensure(c, c->sc_prove, total))) return rc;
   if ((rc = ensure_pin(c, 4096 + total))) return rc;
   if ((rc = ensure(c, c->sc_partial, std::max(SC_PARTIAL_BYTES, (size_t)SC_PACK_MAX * gx_dot * 32)))) return rc;
@@ -342,7 +347,7 @@ static int product_proof_run(sbn_ctx* c, const sbn_table* const* layers, size_t 
   {
     PpRead0Pack top; memset(&top, 0, sizeof top);
     for (size_t i = 0; i < n_circ; i++) top.p[i] = left_of(i, L - 1);
-    if (n_dotp) {
+    if (n_dotp && !dotp_partials_present) {
       ScArgsPack pack; memset(&pack, 0, sizeof pack);
       for (size_t k = 0; k < n_dotp; k++) { pack.a[k].t[0] = (const uint32_t*)dotp_left[k]->d; pack.a[k].t[1] = (const uint32_t*)dotp_right[k]->d; pack.a[k].t[2] = (const uint32_t*)dotp_weight[k]->d; }
       LAUNCH(c, "k_pp_dotp", k_pp_dotp, dim3((unsigned)gx_dot, (unsigned)n_dotp), 256, pack, len_max, (uint32_t*)c->sc_partial.p);
@@ -475,6 +480,21 @@ static int product_proof_run(sbn_ctx* c, const sbn_table* const* layers, size_t 
   return SBN_OK;
 }
 
+// the job, and the rerun behind a zero coefficient; the caller holds the mutex and has checked the arguments
+static int product_proof_locked(sbn_ctx* c, const sbn_table* const* layers, size_t n_circ, size_t n_layers,
+                                const sbn_table* const* dotp_left, const sbn_table* const* dotp_right, const sbn_table* const* dotp_weight, size_t n_dotp,
+                                sbn_transcript* tr, uint8_t* out_polys, uint8_t* out_claims, uint8_t* out_rand, uint8_t* out_claims_final,
+                                bool dotp_partials_present = false) {
+  bool zero_coeff = false;
+  int rc = product_proof_run(c, layers, n_circ, n_layers, dotp_left, dotp_right, dotp_weight, n_dotp, tr, out_polys, out_claims, out_rand, out_claims_final, false, &zero_coeff,
+                             dotp_partials_present);
+  // a coefficient was zero in a layer that divides by it: the same job with every layer in PLAIN mode (reviewed, not tested: 2^-254); the first
+  // run's sumchecks have used c->sc_partial, so the dot-product pass runs again
+  if (rc == SBN_OK && zero_coeff) rc = product_proof_run(c, layers, n_circ, n_layers, dotp_left, dotp_right, dotp_weight, n_dotp, tr, out_polys, out_claims, out_rand, out_claims_final, true, &zero_coeff);
+  if (rc == SBN_OK && zero_coeff) return fail(c, SBN_EHIP, "product proof: internal: zero-coefficient flag raised in PLAIN mode");
+  return rc;
+}
+
 extern "C" {
 
 int sbn_product_proof_prove(sbn_ctx* c, const sbn_table* const* layers, size_t n_circ, size_t n_layers,
@@ -495,12 +515,7 @@ int sbn_product_proof_prove(sbn_ctx* c, const sbn_table* const* layers, size_t n
     const size_t want = (size_t)1 << (n_layers - 1);
     if (dotp_left[k]->len != want || dotp_right[k]->len != want || dotp_weight[k]->len != want) return fail(c, SBN_EINVAL, "product proof: dot-product circuit %zu does not have 2^%zu entries  [product_tree.rs:299-301 assert_eq]", k, n_layers - 1);
   }
-  bool zero_coeff = false;
-  int rc = product_proof_run(c, layers, n_circ, n_layers, dotp_left, dotp_right, dotp_weight, n_dotp, tr, out_polys, out_claims, out_rand, out_claims_final, false, &zero_coeff);
-  // a coefficient was zero in a layer that divides by it: the same job with every layer in PLAIN mode (reviewed, not tested: 2^-254)
-  if (rc == SBN_OK && zero_coeff) rc = product_proof_run(c, layers, n_circ, n_layers, dotp_left, dotp_right, dotp_weight, n_dotp, tr, out_polys, out_claims, out_rand, out_claims_final, true, &zero_coeff);
-  if (rc == SBN_OK && zero_coeff) return fail(c, SBN_EHIP, "product proof: internal: zero-coefficient flag raised in PLAIN mode");
-  return rc;
+  return product_proof_locked(c, layers, n_circ, n_layers, dotp_left, dotp_right, dotp_weight, n_dotp, tr, out_polys, out_claims, out_rand, out_claims_final);
 }
 
 }  // extern "C"

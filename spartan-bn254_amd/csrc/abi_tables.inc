@@ -377,11 +377,10 @@ int sbn_hash_layer(sbn_ctx* c, const void* addr_dev, const sbn_table* val, const
   *out = t;
   return SBN_OK;
 }
-int sbn_hash_layer_pair(sbn_ctx* c, const void* addr_dev, const sbn_table* val, const void* ts_a_dev, uint32_t ts_a_add, const void* ts_b_dev, uint32_t ts_b_add,
-                        const uint8_t r_hash[32], const uint8_t r_multiset[32], sbn_table** out_a, sbn_table** out_b) {
-  if (!c || !val || !r_hash || !r_multiset || !out_a || !out_b) return SBN_EINVAL;
-  if (!fr_canonical(r_hash) || !fr_canonical(r_multiset)) return fail(c, SBN_EINVAL, "hash layer: challenges not canonical");
-  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+}  // extern "C"
+// (the caller holds the context's mutex and has checked the arguments)
+static int hash_layer_pair_locked(sbn_ctx* c, const void* addr_dev, const sbn_table* val, const void* ts_a_dev, uint32_t ts_a_add, const void* ts_b_dev, uint32_t ts_b_add,
+                                  const uint8_t r_hash[32], const uint8_t r_multiset[32], sbn_table** out_a, sbn_table** out_b) {
   const size_t n = val->len;
   ScScalar gs, g2s, nts;
   {
@@ -401,6 +400,56 @@ int sbn_hash_layer_pair(sbn_ctx* c, const void* addr_dev, const sbn_table* val, 
   if (c->prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); prof_drain(c); }
   *out_a = t[0]; *out_b = t[1];
   return SBN_OK;
+}
+// the pair and the first layer of both product circuits in one pass (k_hash_pair_prod); n = val->len is a power of two >= 2; the caller holds
+// the context's mutex and has checked the arguments
+static int hash_layer_pair_product_locked(sbn_ctx* c, const void* addr_dev, const sbn_table* val, const void* ts_a_dev, uint32_t ts_a_add, const void* ts_b_dev, uint32_t ts_b_add,
+                                          const uint8_t r_hash[32], const uint8_t r_multiset[32], sbn_table** out_a, sbn_table** out_b, sbn_table** prod_a, sbn_table** prod_b) {
+  const size_t n = val->len, half = n / 2;
+  ScScalar gs, g2s, nts;
+  {
+    using namespace sbn_host::fr;
+    const El g = el_from(r_hash), tau = el_from(r_multiset), zero = {{0, 0, 0, 0}};
+    gs = scs_from(to_dev_mont(g)); g2s = scs_from(to_dev_mont(to_dev_mont(mmul(to_m(g), g)))); nts = scs_from(to_dev_mont(sub(zero, tau)));
+  }
+  sbn_table* t[4] = {nullptr, nullptr, nullptr, nullptr};           // out_a, out_b (n entries), prod_a, prod_b (n / 2)
+  for (int k = 0; k < 4; k++) {
+    const size_t len = k < 2 ? n : half;
+    t[k] = new sbn_table(); t[k]->len = len; t[k]->cap = len;
+    size_t gb = 0; hipError_t e = pool_get(c, len * 32, &t[k]->d, &gb); t[k]->cap = gb / 32;
+    if (e != hipSuccess) {
+      delete t[k];
+      for (int j = 0; j < k; j++) { pool_put(c, t[j]->d, t[j]->cap * 32); delete t[j]; }
+      return fail(c, SBN_ENOMEM, "hipMalloc hash layer: %s", hipGetErrorString(e));
+    }
+  }
+  LAUNCH(c, "k_hash_pair_prod", k_hash_pair_prod, stream_grid(half), 256, (const uint32_t*)addr_dev, (const uint32_t*)val->d, (const uint32_t*)ts_a_dev, ts_a_add, (const uint32_t*)ts_b_dev, ts_b_add,
+         gs, g2s, nts, half, (uint32_t*)t[0]->d, (uint32_t*)t[1]->d, (uint32_t*)t[2]->d, (uint32_t*)t[3]->d);
+  hipError_t le = hipGetLastError();          // asynchronous, as sbn_hash_layer
+  if (le == hipSuccess && c->prof) { le = hipStreamSynchronize(c->stream); prof_drain(c); }
+  if (le != hipSuccess) {                     // the tables were not handed out: back to the pool, behind whatever is still queued
+    hipStreamSynchronize(c->stream);
+    for (int k = 0; k < 4; k++) { pool_put(c, t[k]->d, t[k]->cap * 32); delete t[k]; }
+    return fail(c, SBN_EHIP, "hash layer pair + product: %s", hipGetErrorString(le));
+  }
+  *out_a = t[0]; *out_b = t[1]; *prod_a = t[2]; *prod_b = t[3];
+  return SBN_OK;
+}
+extern "C" {
+int sbn_hash_layer_pair_product(sbn_ctx* c, const void* addr_dev, const sbn_table* val, const void* ts_a_dev, uint32_t ts_a_add, const void* ts_b_dev, uint32_t ts_b_add,
+                                const uint8_t r_hash[32], const uint8_t r_multiset[32], sbn_table** out_a, sbn_table** out_b, sbn_table** prod_a, sbn_table** prod_b) {
+  if (!c || !val || !r_hash || !r_multiset || !out_a || !out_b || !prod_a || !prod_b) return SBN_EINVAL;
+  if (!fr_canonical(r_hash) || !fr_canonical(r_multiset)) return fail(c, SBN_EINVAL, "hash layer: challenges not canonical");
+  if (val->len < 2 || (val->len & (val->len - 1))) return fail(c, SBN_EINVAL, "hash layer pair + product: %zu entries (a power of two >= 2 is needed: the first product layer halves them)", val->len);
+  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+  return hash_layer_pair_product_locked(c, addr_dev, val, ts_a_dev, ts_a_add, ts_b_dev, ts_b_add, r_hash, r_multiset, out_a, out_b, prod_a, prod_b);
+}
+int sbn_hash_layer_pair(sbn_ctx* c, const void* addr_dev, const sbn_table* val, const void* ts_a_dev, uint32_t ts_a_add, const void* ts_b_dev, uint32_t ts_b_add,
+                        const uint8_t r_hash[32], const uint8_t r_multiset[32], sbn_table** out_a, sbn_table** out_b) {
+  if (!c || !val || !r_hash || !r_multiset || !out_a || !out_b) return SBN_EINVAL;
+  if (!fr_canonical(r_hash) || !fr_canonical(r_multiset)) return fail(c, SBN_EINVAL, "hash layer: challenges not canonical");
+  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+  return hash_layer_pair_locked(c, addr_dev, val, ts_a_dev, ts_a_add, ts_b_dev, ts_b_add, r_hash, r_multiset, out_a, out_b);
 }
 int sbn_product_layer(sbn_ctx* c, const sbn_table* in, sbn_table** out) {
   if (!c || !in || !out) return SBN_EINVAL;
@@ -450,15 +499,9 @@ int sbn_product_circuit(sbn_ctx* c, const sbn_table* in, sbn_table** layers, siz
   *count = made;
   return SBN_OK;
 }
-int sbn_product_circuit_many(sbn_ctx* c, const sbn_table* const* ins, size_t n, sbn_table** layers, size_t cap, size_t* count) {
-  if (!c || !ins || !layers || !count || n == 0) return SBN_EINVAL;
-  for (size_t i = 0; i < n; i++) if (!ins[i]) return SBN_EINVAL;
-  const size_t len0 = ins[0]->len;
-  for (size_t i = 1; i < n; i++) if (ins[i]->len != len0) return fail(c, SBN_EINVAL, "product circuits: table %zu has %zu entries, table 0 has %zu", i, ins[i]->len, len0);
-  size_t need = 0; for (size_t l = len0; l > 1; l >>= 1) need++;
-  if (need == 0) return fail(c, SBN_EINVAL, "product circuit: nothing to multiply");
-  if (cap < need) return fail(c, SBN_EINVAL, "product circuit: %zu layers do not fit the caller's rows of %zu", need, cap);
-  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+}  // extern "C"
+// (the caller holds the context's mutex and has checked the arguments: n tables of len0 = 2^need entries, need >= 1, cap >= need)
+static int product_circuit_many_locked(sbn_ctx* c, const sbn_table* const* ins, size_t n, sbn_table** layers, size_t cap, size_t len0, size_t need) {
   // the tables first (so that a failed allocation leaves nothing enqueued); layers[i * cap + k]
   std::vector<sbn_table*> made;
   for (size_t i = 0; i < n; i++) {
@@ -494,10 +537,29 @@ int sbn_product_circuit_many(sbn_ctx* c, const sbn_table* const* ins, size_t n, 
       LAUNCH(c, "k_product_layer", k_product_tail_many, (unsigned)m, 1024, pt, len);
     }
   }
-  LAUNCHCHK(c);                              // asynchronous, as sbn_product_layer
-  if (c->prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); prof_drain(c); }
-  *count = need;
+  hipError_t le = hipGetLastError();          // asynchronous, as sbn_product_layer
+  if (le == hipSuccess && c->prof) { le = hipStreamSynchronize(c->stream); prof_drain(c); }
+  if (le != hipSuccess) {                     // nothing is handed out behind a failed launch: the layer tables go back to the pool
+    hipStreamSynchronize(c->stream);
+    for (sbn_table* x : made) { pool_put(c, x->d, x->cap * 32); delete x; }
+    for (size_t a = 0; a < n * cap; a++) layers[a] = nullptr;
+    return fail(c, SBN_EHIP, "product circuits: %s", hipGetErrorString(le));
+  }
   return SBN_OK;
+}
+extern "C" {
+int sbn_product_circuit_many(sbn_ctx* c, const sbn_table* const* ins, size_t n, sbn_table** layers, size_t cap, size_t* count) {
+  if (!c || !ins || !layers || !count || n == 0) return SBN_EINVAL;
+  for (size_t i = 0; i < n; i++) if (!ins[i]) return SBN_EINVAL;
+  const size_t len0 = ins[0]->len;
+  for (size_t i = 1; i < n; i++) if (ins[i]->len != len0) return fail(c, SBN_EINVAL, "product circuits: table %zu has %zu entries, table 0 has %zu", i, ins[i]->len, len0);
+  size_t need = 0; for (size_t l = len0; l > 1; l >>= 1) need++;
+  if (need == 0) return fail(c, SBN_EINVAL, "product circuit: nothing to multiply");
+  if (cap < need) return fail(c, SBN_EINVAL, "product circuit: %zu layers do not fit the caller's rows of %zu", need, cap);
+  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+  const int rc = product_circuit_many_locked(c, ins, n, layers, cap, len0, need);
+  if (rc == SBN_OK) *count = need;
+  return rc;
 }
 int sbn_table_halves(sbn_ctx* c, const sbn_table* t, sbn_table** left, sbn_table** right) {
   if (!c || !t || !left || !right) return SBN_EINVAL;
@@ -550,17 +612,14 @@ int sbn_table_evaluate(sbn_ctx* c, const sbn_table* Z, const uint8_t* r, size_t 
   sbn_table_free(c, chi);
   return rc;
 }
-int sbn_table_evaluate_many(sbn_ctx* c, const sbn_table* const* Z, size_t count, const uint8_t* r, size_t ell, uint8_t* out) {
-  if (!c || !Z || !out || (!r && ell) || count == 0) return SBN_EINVAL;
-  for (size_t i = 0; i < count; i++) {
-    if (!Z[i]) return SBN_EINVAL;
-    if (((size_t)1 << ell) != Z[i]->len) return fail(c, SBN_EINVAL, "evaluate: r.len() != num_vars of table %zu (hyrax.rs:218 assert_eq)", i);
-  }
+}  // extern "C"
+static int eq_evals_locked(sbn_ctx* c, const uint8_t* r, size_t ell, sbn_table** out);
+// (the caller holds the context's mutex and has checked the arguments)
+static int table_evaluate_many_locked(sbn_ctx* c, const sbn_table* const* Z, size_t count, const uint8_t* r, size_t ell, uint8_t* out) {
   sbn_table* chi = nullptr;
-  int rc = sbn_eq_evals(c, r, ell, &chi);          // ONE eq table for all of them (the reference rebuilds it per call, hyrax.rs:217-222)
+  int rc = eq_evals_locked(c, r, ell, &chi);       // ONE eq table for all of them (the reference rebuilds it per call, hyrax.rs:217-222)
   if (rc) return rc;
   {
-    std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
     const size_t n = chi->len;
     unsigned gx = stream_grid(n); if (gx > 1024) gx = 1024;
     for (size_t i0 = 0; i0 < count && rc == SBN_OK; i0 += SC_PACK_MAX) {
@@ -580,8 +639,19 @@ int sbn_table_evaluate_many(sbn_ctx* c, const sbn_table* const* Z, size_t count,
       for (size_t i = 0; i < m; i++) memcpy(out + 32 * (i0 + i), (uint8_t*)c->pin + 96 * i, 32);
     }
   }
-  sbn_table_free(c, chi);
+  if (chi->d && chi->owned) pool_put(c, chi->d, chi->cap * 32);      // (every chunk above ended in a stream wait or failed)
+  delete chi;
   return rc;
+}
+extern "C" {
+int sbn_table_evaluate_many(sbn_ctx* c, const sbn_table* const* Z, size_t count, const uint8_t* r, size_t ell, uint8_t* out) {
+  if (!c || !Z || !out || (!r && ell) || count == 0 || ell > 40) return SBN_EINVAL;
+  for (size_t i = 0; i < count; i++) {
+    if (!Z[i]) return SBN_EINVAL;
+    if (((size_t)1 << ell) != Z[i]->len) return fail(c, SBN_EINVAL, "evaluate: r.len() != num_vars of table %zu (hyrax.rs:218 assert_eq)", i);
+  }
+  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+  return table_evaluate_many_locked(c, Z, count, r, ell, out);
 }
 int sbn_table_bound(sbn_ctx* c, const sbn_table* Z, const sbn_table* Lv, sbn_table** out) {
   if (!c || !Z || !Lv || !out) return SBN_EINVAL;
@@ -609,10 +679,8 @@ int sbn_table_bound(sbn_ctx* c, const sbn_table* Z, const sbn_table* Lv, sbn_tab
 }
 }  // extern "C"
 // rshift < 0: the whole polynomial (padded to a power of two); else the rows row0, row0 + rstep, ... (nrows of them) of its L x 2^rshift view
-static int gather_merge_impl(sbn_ctx* c, const sbn_table* const* mem, const void* const* addr_dev, size_t count, size_t n, int rshift, size_t row0, size_t rstep, size_t nrows, sbn_table** out) {
-  if (!c || !mem || !addr_dev || !out || count == 0 || n == 0) return SBN_EINVAL;
-  for (size_t k = 0; k < count; k++) if (!mem[k] || !addr_dev[k]) return SBN_EINVAL;
-  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+// (the caller holds the context's mutex and has checked the pointers)
+static int gather_merge_locked(sbn_ctx* c, const sbn_table* const* mem, const void* const* addr_dev, size_t count, size_t n, int rshift, size_t row0, size_t rstep, size_t nrows, sbn_table** out) {
   size_t padded = 1; while (padded < count * n) padded <<= 1;              // Z.resize(len.next_power_of_two()) (hyrax.rs:245)
   size_t out_len = padded;
   if (rshift >= 0) {
@@ -641,6 +709,12 @@ static int gather_merge_impl(sbn_ctx* c, const sbn_table* const* mem, const void
   if (oob) { pool_put(c, t->d, t->cap * 32); delete t; return fail(c, SBN_EINVAL, "gather: %u addresses are outside their memory table (sparse_mlpoly_full.rs:228 assert)", oob); }
   *out = t;
   return SBN_OK;
+}
+static int gather_merge_impl(sbn_ctx* c, const sbn_table* const* mem, const void* const* addr_dev, size_t count, size_t n, int rshift, size_t row0, size_t rstep, size_t nrows, sbn_table** out) {
+  if (!c || !mem || !addr_dev || !out || count == 0 || n == 0) return SBN_EINVAL;
+  for (size_t k = 0; k < count; k++) if (!mem[k] || !addr_dev[k]) return SBN_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+  return gather_merge_locked(c, mem, addr_dev, count, n, rshift, row0, rstep, nrows, out);
 }
 extern "C" {
 int sbn_gather_merge(sbn_ctx* c, const sbn_table* const* mem, const void* const* addr_dev, size_t count, size_t n, sbn_table** out) {
