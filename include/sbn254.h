@@ -583,6 +583,50 @@ int sbn_sparse_eval_sizes(size_t num_vars_x, size_t num_vars_y, size_t num_ops /
 int sbn_sparse_eval_prove(sbn_ctx* ctx, const sbn_dense* dense, const uint8_t* rx, size_t nx, const uint8_t* ry, size_t ny, const uint8_t* evals /* batch x 32 */,
                           const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_bases* gens_derefs, const uint8_t* rnd, sbn_transcript* tr, uint8_t* out_proof);
 
+/* ---- sbn_derefs_key: the KZG build's derefs commitment (Derefs::commit_kzg, sparse_mlpoly_full.rs:307-312) as a sum over memory cells ----
+ * derefs[i] = eq[addr[i]], so  sum_i derefs[i] [tau^i]G = sum_a eq(rx)[a] S[0][a] + sum_a eq(ry)[a] S[1][a]  with
+ *   S[side][a] = sum_{k < b} sum_{i < N, addr[side][k][i] = a} srs[(side b + k) N + i]
+ * (coefficient i of polynomial k of that side in Derefs::new's merge order, :293-297).  S depends on the circuit and the SRS only: it is built once,
+ * at encode time, and a proof's commitment becomes an MSM over the cells read at least once (at most 2 cells points) instead of npo2(2 b) N.
+ * The group element is the same, bit for bit.
+ *   build     enqueued on the context's stream, synchronised before it returns: the per-cell lists come from the handle's audit_ts (count) and read_ts
+ *             (rank), the sums from the MSM's bucket accumulate (segments of SEG entries; sbn_prof_last_acc reports SEG, LPB = 1 and the two counters
+ *             as for a bucket job).  Cells never read are dropped: they have no affine form.
+ *             SBN_EINVAL before any launch: srs has an h, srs has fewer than n' = 2 b N points, 2 b N >= 2^31.
+ *   lifetime  the key borrows nothing after the build, but records dense's shape, the SRS length and both handles' addresses so that
+ *             sbn_sparse_eval_prove_kzg can refuse a foreign key: free it BEFORE the dense handle and the SRS.
+ *   len       cells read at least once, row side + column side (>= 2: N >= 2 reads cell 0 on both sides).
+ *   download  cells [first, first + count): out_cell[j] = side << 31 | a (row side first, a ascending), out_xy[64 j ..] = S[side][a], canonical affine x || y.
+ *   commit    from the two eq tables (sbn_eq_evals of the equalized points, cells entries each): the point sbn_kzg_commit gives on the gathered,
+ *             merged table.  SBN_EINVAL for a table shorter than cells. */
+typedef struct sbn_derefs_key sbn_derefs_key;
+int sbn_derefs_key_build(sbn_ctx* ctx, const sbn_dense* dense, const sbn_bases* srs, sbn_derefs_key** out);
+void sbn_derefs_key_free(sbn_ctx* ctx, sbn_derefs_key* key);
+size_t sbn_derefs_key_len(const sbn_derefs_key* key);
+int sbn_derefs_key_download(sbn_ctx* ctx, const sbn_derefs_key* key, size_t first, size_t count, uint32_t* out_cell, uint8_t* out_xy);
+int sbn_derefs_key_commit(sbn_ctx* ctx, const sbn_derefs_key* key, const sbn_table* mem_rx, const sbn_table* mem_ry, uint8_t out_xy[64], int* out_is_inf);
+
+/* ---- SparseMatPolyEvalProof::prove, the KZG build (--features kzg, sparse_mlpoly_full.rs:1757-1813) in ONE call ----
+ * Everything of sbn_sparse_eval_prove above holds (notation, dense, rx, ry, evals, gens_ops, gens_mem, the transcript and out_proof rules) except:
+ *   srs      the KZG SRS (sbn_kzg_srs_upload / _from_tau: no h) in place of gens_derefs.  n_d = npo2(2 b) N is the derefs polynomial's length,
+ *            n' = 2 b N its non-zero prefix; the SRS must hold n_d - 1 points (the reference slices the quotient's bases, kzg.rs:186).
+ *   key      sbn_derefs_key_build(dense, srs), or NULL.  The bytes are the same with and without it.
+ *   the commitment  (:1781-1785, :349-356, kzg.rs:386-404) ONE point.  With a key: sbn_derefs_key_commit's body.  Without: the MSM of the first
+ *            min(n', srs->n) entries of the gathered table (KZGPolyCommitment::commit's truncation, restricted to the non-zero prefix).  Transcript:
+ *            derefs_commitment / begin_derefs_commitment, comm_poly_row_col_ops_val <- the 32 compressed bytes, derefs_commitment / end_derefs_commitment.
+ *   DerefsEvalProof::prove  (:503-550) protocol name "Derefs evaluation proof (KZG)", evals_ops_val per scalar, log2 npo2(2 b) challenges
+ *            challenge_combine_n_to_one, joint_claim_eval, the challenge kzg_eval_point, then KZGProof::prove on the derefs table: the division over
+ *            n' coefficients and the MSM of the n' - 1 quotient coefficients (q_i = 0 from n' - 1 on).  Nothing is appended afterwards, no draw is used.
+ *   rnd      ops [3 + 2 lg_ops] | mem [3 + 2 lg_mem].     rnd_scalars = 6 + 2 (lg_ops + lg_mem).
+ *   out_proof  the Hyrax layout with  comm_derefs [32]  and  proof_hash_layer.proof_derefs [proof 32 | eval 32]  (the identity as sbn_g1_compress writes it).
+ *              proof_bytes = 32 (13 b + 6) + 64 (m (m - 1) + n (n - 1)) + 256 (m + b n) + 192 b + 64 (lg_ops + lg_mem) + 352.
+ * SBN_EINVAL before any launch: the Hyrax call's refusals (without gens_derefs), an SRS with h, srs->n < n_d - 1, a key whose recorded shape, SRS length or
+ * handles are not this call's.  Pairings and verification stay with the caller. */
+int sbn_sparse_eval_kzg_sizes(size_t num_vars_x, size_t num_vars_y, size_t num_ops /* N */, size_t batch, size_t* rnd_scalars, size_t* proof_bytes);
+int sbn_sparse_eval_prove_kzg(sbn_ctx* ctx, const sbn_dense* dense, const uint8_t* rx, size_t nx, const uint8_t* ry, size_t ny, const uint8_t* evals /* batch x 32 */,
+                              const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_bases* srs, const sbn_derefs_key* key /* or NULL */,
+                              const uint8_t* rnd, sbn_transcript* tr, uint8_t* out_proof);
+
 /* ---- per-kernel timing (HIP events on the context's stream), for bench.py's roofline line ---- */
 int sbn_prof_enable(sbn_ctx* ctx, int on);
 int sbn_prof_reset(sbn_ctx* ctx);

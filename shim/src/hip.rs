@@ -52,6 +52,7 @@ use crate::unipoly::{CompressedUniPoly, UniPoly};
 #[repr(C)] pub struct sbn_group_bases { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_r1cs { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_dense { _p: [u8; 0] }
+#[repr(C)] pub struct sbn_derefs_key { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_transcript { _p: [u8; 0] }
 
 pub const SBN_OK: c_int = 0;
@@ -200,6 +201,13 @@ extern "C" {
     pub fn sbn_dense_comb_mem(d: *const sbn_dense) -> *const sbn_table;
     pub fn sbn_sparse_eval_sizes(num_vars_x: usize, num_vars_y: usize, num_ops: usize, batch: usize, rnd_scalars: *mut usize, proof_bytes: *mut usize) -> c_int;
     pub fn sbn_sparse_eval_prove(ctx: *mut sbn_ctx, dense: *const sbn_dense, rx: *const u8, nx: usize, ry: *const u8, ny: usize, evals: *const u8, gens_ops: *const sbn_bases, gens_mem: *const sbn_bases, gens_derefs: *const sbn_bases, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8) -> c_int;
+    pub fn sbn_derefs_key_build(ctx: *mut sbn_ctx, dense: *const sbn_dense, srs: *const sbn_bases, out: *mut *mut sbn_derefs_key) -> c_int;
+    pub fn sbn_derefs_key_free(ctx: *mut sbn_ctx, key: *mut sbn_derefs_key);
+    pub fn sbn_derefs_key_len(key: *const sbn_derefs_key) -> usize;
+    pub fn sbn_derefs_key_download(ctx: *mut sbn_ctx, key: *const sbn_derefs_key, first: usize, count: usize, out_cell: *mut u32, out_xy: *mut u8) -> c_int;
+    pub fn sbn_derefs_key_commit(ctx: *mut sbn_ctx, key: *const sbn_derefs_key, mem_rx: *const sbn_table, mem_ry: *const sbn_table, out_xy: *mut u8, out_is_inf: *mut c_int) -> c_int;
+    pub fn sbn_sparse_eval_kzg_sizes(num_vars_x: usize, num_vars_y: usize, num_ops: usize, batch: usize, rnd_scalars: *mut usize, proof_bytes: *mut usize) -> c_int;
+    pub fn sbn_sparse_eval_prove_kzg(ctx: *mut sbn_ctx, dense: *const sbn_dense, rx: *const u8, nx: usize, ry: *const u8, ny: usize, evals: *const u8, gens_ops: *const sbn_bases, gens_mem: *const sbn_bases, srs: *const sbn_bases, key: *const sbn_derefs_key, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8) -> c_int;
     pub fn sbn_prof_enable(ctx: *mut sbn_ctx, on: c_int) -> c_int;
     pub fn sbn_prof_reset(ctx: *mut sbn_ctx) -> c_int;
     pub fn sbn_prof_count(ctx: *mut sbn_ctx) -> c_int;
@@ -1154,7 +1162,62 @@ fn open_draws(random_tape: &mut RandomTape, lg: usize) -> Vec<Scalar> {
     for i in 0..lg { rnd.push(v1[i]); rnd.push(v2[i]); }
     rnd
 }
-/// SparseMatPolyEvalProof::prove with a `DevTranscript`; `dense_dev` is the dense representation's device handle (`DenseDev::get`, built at encode time)
+/// out_proof (include/sbn254.h) -> the stream the derived CanonicalDeserialize of SparseMatPolyEvalProof reads.  hyrax_derefs: Some((bytes of
+/// comm_derefs, lg_derefs)) in the Hyrax build, None in the KZG build (comm_derefs one point, proof_derefs [proof | eval])
+fn sparse_eval_stream(proof: &[u8], b: usize, m: usize, n: usize, lg_o: usize, lg_m: usize, hyrax_derefs: Option<(usize, usize)>) -> Vec<u8> {
+    let mut ser: Vec<u8> = Vec::with_capacity(2 * proof.len());
+    let mut at = 0usize;
+    let mut take = |k: usize| { let s = &proof[at..at + k]; at += k; s };
+    let len = |ser: &mut Vec<u8>, k: usize| ser.extend_from_slice(&(k as u64).to_le_bytes());
+    let vec32 = |ser: &mut Vec<u8>, p: &[u8]| { len(ser, p.len() / 32); ser.extend_from_slice(p); };
+    // ProductCircuitEvalProofBatched { proof: Vec<LayerProofBatched { SumcheckInstanceProof, claims_prod_left, claims_prod_right }>, claims_dotp }
+    let pcepb = |ser: &mut Vec<u8>, polys: &[u8], claims: &[u8], c: usize, l: usize, d: usize| {
+        len(ser, l);
+        let mut po = 0usize;
+        for k in 0..l {
+            len(ser, k);                                                              // compressed_polys: k rounds
+            for _ in 0..k {
+                let q = &polys[po..po + 128]; po += 128;
+                len(ser, 3); ser.extend_from_slice(&q[..32]); ser.extend_from_slice(&q[64..128]);      // CompressedUniPoly: c0, c2, c3 (unipoly.rs:87-99)
+            }
+            let cl = &claims[64 * c * k..64 * c * (k + 1)];
+            vec32(ser, &cl[..32 * c]); vec32(ser, &cl[32 * c..]);
+        }
+        let dp = &claims[64 * c * l..];
+        for j in 0..3 { vec32(ser, &dp[32 * d * j..32 * d * (j + 1)]); }
+    };
+    let open = |ser: &mut Vec<u8>, p: &[u8], lg: usize| {                             // PolyEvalProof { DotProductProofLog { BulletReductionProof { L_vec, R_vec }, delta, beta, z1, z2 } }
+        len(ser, lg); ser.extend_from_slice(&p[..32 * lg]);
+        len(ser, lg); ser.extend_from_slice(&p[32 * lg..64 * lg]);
+        ser.extend_from_slice(&p[64 * lg..]);
+    };
+    match hyrax_derefs {
+        Some((l_d, _)) => vec32(&mut ser, take(l_d)),                                 // comm_derefs: DerefsCommitment { PolyCommitment { C } }
+        None => ser.extend_from_slice(take(32)),                                      // KZG build: DerefsCommitment { KZGPolyCommitment { commitment } }, one point, no length
+    }
+    for _ in 0..2 {                                                                   // ProductLayerProof.eval_row, eval_col: (Scalar, Vec, Vec, Scalar)
+        ser.extend_from_slice(take(32)); vec32(&mut ser, take(32 * b)); vec32(&mut ser, take(32 * b)); ser.extend_from_slice(take(32));
+    }
+    vec32(&mut ser, take(32 * b)); vec32(&mut ser, take(32 * b));                     // eval_val: (Vec, Vec)
+    { let polys = take(64 * m * (m - 1)).to_vec(); let claims = take(256 * m); pcepb(&mut ser, &polys, claims, 4, m, 0); }                             // proof_mem
+    { let polys = take(64 * n * (n - 1)).to_vec(); let claims = take(256 * b * n + 192 * b); pcepb(&mut ser, &polys, claims, 4 * b, n, 2 * b); }       // proof_ops
+    for _ in 0..2 {                                                                   // HashLayerProof.eval_row, eval_col: (Vec, Vec, Scalar)
+        vec32(&mut ser, take(32 * b)); vec32(&mut ser, take(32 * b)); ser.extend_from_slice(take(32));
+    }
+    vec32(&mut ser, take(32 * b));                                                    // eval_val
+    vec32(&mut ser, take(32 * b)); vec32(&mut ser, take(32 * b));                     // eval_derefs
+    open(&mut ser, take(64 * lg_o + 128), lg_o);                                      // proof_ops
+    open(&mut ser, take(64 * lg_m + 128), lg_m);                                      // proof_mem
+    match hyrax_derefs {
+        Some((_, lg_d)) => open(&mut ser, take(64 * lg_d + 128), lg_d),               // proof_derefs: DerefsEvalProof { PolyEvalProof }
+        None => ser.extend_from_slice(take(64)),                                      // KZG build: DerefsEvalProof { proof: G1Affine, eval: Scalar }
+    }
+    assert_eq!(at, proof.len());
+    ser
+}
+/// SparseMatPolyEvalProof::prove with a `DevTranscript`; `dense_dev` is the dense representation's device handle (`DenseDev::get`, built at encode time).
+/// The Hyrax build: with `--features kzg` gens has no gens_derefs and `sparse_eval_prove_kzg` below takes its place.
+#[cfg(not(feature = "kzg"))]
 pub fn sparse_eval_prove(
     dense_dev: *const sbn_dense,
     rx: &[Scalar],
@@ -1185,50 +1248,67 @@ pub fn sparse_eval_prove(
         sbn_sparse_eval_prove(ctx(), dense_dev, rxb.as_ptr(), rx.len(), ryb.as_ptr(), ry.len(), evb.as_ptr(), g_ops.0, g_mem.0, g_der.0, rnd.as_ptr(), transcript.0,
                               proof.as_mut_ptr())
     });
-    // out_proof -> the stream the derived CanonicalDeserialize reads
-    let mut ser: Vec<u8> = Vec::with_capacity(2 * n_proof);
-    let mut at = 0usize;
-    let mut take = |k: usize| { let s = &proof[at..at + k]; at += k; s };
-    let len = |ser: &mut Vec<u8>, k: usize| ser.extend_from_slice(&(k as u64).to_le_bytes());
-    let vec32 = |ser: &mut Vec<u8>, p: &[u8]| { len(ser, p.len() / 32); ser.extend_from_slice(p); };
-    // ProductCircuitEvalProofBatched { proof: Vec<LayerProofBatched { SumcheckInstanceProof, claims_prod_left, claims_prod_right }>, claims_dotp }
-    let pcepb = |ser: &mut Vec<u8>, polys: &[u8], claims: &[u8], c: usize, l: usize, d: usize| {
-        len(ser, l);
-        let mut po = 0usize;
-        for k in 0..l {
-            len(ser, k);                                                              // compressed_polys: k rounds
-            for _ in 0..k {
-                let q = &polys[po..po + 128]; po += 128;
-                len(ser, 3); ser.extend_from_slice(&q[..32]); ser.extend_from_slice(&q[64..128]);      // CompressedUniPoly: c0, c2, c3 (unipoly.rs:87-99)
-            }
-            let cl = &claims[64 * c * k..64 * c * (k + 1)];
-            vec32(ser, &cl[..32 * c]); vec32(ser, &cl[32 * c..]);
-        }
-        let dp = &claims[64 * c * l..];
-        for j in 0..3 { vec32(ser, &dp[32 * d * j..32 * d * (j + 1)]); }
-    };
-    let open = |ser: &mut Vec<u8>, p: &[u8], lg: usize| {                             // PolyEvalProof { DotProductProofLog { BulletReductionProof { L_vec, R_vec }, delta, beta, z1, z2 } }
-        len(ser, lg); ser.extend_from_slice(&p[..32 * lg]);
-        len(ser, lg); ser.extend_from_slice(&p[32 * lg..64 * lg]);
-        ser.extend_from_slice(&p[64 * lg..]);
-    };
     let l_d = n_proof - (32 * (13 * b + 6) + 64 * (m * (m - 1) + n * (n - 1)) + 256 * (m + b * n) + 192 * b + 64 * (lg_o + lg_m + lg_d) + 384);
-    vec32(&mut ser, take(l_d));                                                       // comm_derefs: DerefsCommitment { PolyCommitment { C } }
-    for _ in 0..2 {                                                                   // ProductLayerProof.eval_row, eval_col: (Scalar, Vec, Vec, Scalar)
-        ser.extend_from_slice(take(32)); vec32(&mut ser, take(32 * b)); vec32(&mut ser, take(32 * b)); ser.extend_from_slice(take(32));
-    }
-    vec32(&mut ser, take(32 * b)); vec32(&mut ser, take(32 * b));                     // eval_val: (Vec, Vec)
-    { let polys = take(64 * m * (m - 1)).to_vec(); let claims = take(256 * m); pcepb(&mut ser, &polys, claims, 4, m, 0); }                             // proof_mem
-    { let polys = take(64 * n * (n - 1)).to_vec(); let claims = take(256 * b * n + 192 * b); pcepb(&mut ser, &polys, claims, 4 * b, n, 2 * b); }       // proof_ops
-    for _ in 0..2 {                                                                   // HashLayerProof.eval_row, eval_col: (Vec, Vec, Scalar)
-        vec32(&mut ser, take(32 * b)); vec32(&mut ser, take(32 * b)); ser.extend_from_slice(take(32));
-    }
-    vec32(&mut ser, take(32 * b));                                                    // eval_val
-    vec32(&mut ser, take(32 * b)); vec32(&mut ser, take(32 * b));                     // eval_derefs
-    open(&mut ser, take(64 * lg_o + 128), lg_o);                                      // proof_ops
-    open(&mut ser, take(64 * lg_m + 128), lg_m);                                      // proof_mem
-    open(&mut ser, take(64 * lg_d + 128), lg_d);                                      // proof_derefs: DerefsEvalProof { PolyEvalProof }
+    let ser = sparse_eval_stream(&proof, b, m, n, lg_o, lg_m, Some((l_d, lg_d)));
     SparseMatPolyEvalProof::deserialize_compressed(&ser[..]).expect("SparseMatPolyEvalProof from the library's bytes")
+}
+
+// ---- the KZG build (--features hip,kzg): SparseMatPolyEvalProof::prove (sparse_mlpoly_full.rs:1757-1813) in ONE foreign call ---------------
+/// per-cell SRS sums of one (circuit, SRS) pair (sbn_derefs_key_build): built at encode time next to `DenseDev`, dropped BEFORE the dense
+/// handle and the SRS it was built from
+#[cfg(feature = "kzg")]
+pub struct DerefsKey(pub *mut sbn_derefs_key);
+#[cfg(feature = "kzg")]
+unsafe impl Send for DerefsKey {}
+#[cfg(feature = "kzg")]
+unsafe impl Sync for DerefsKey {}
+#[cfg(feature = "kzg")]
+impl Drop for DerefsKey { fn drop(&mut self) { if !self.0.is_null() { unsafe { sbn_derefs_key_free(ctx(), self.0) } } } }
+#[cfg(feature = "kzg")]
+impl DerefsKey {
+    pub fn build(dense_dev: *const sbn_dense, srs: &KzgSrs) -> DerefsKey {
+        let mut k = null_mut();
+        check(unsafe { sbn_derefs_key_build(ctx(), dense_dev, srs.0, &mut k) });
+        DerefsKey(k)
+    }
+    pub fn len(&self) -> usize { unsafe { sbn_derefs_key_len(self.0) } }
+    pub fn is_empty(&self) -> bool { self.len() == 0 }
+}
+/// SparseMatPolyEvalProof::prove of the KZG build with a `DevTranscript`.  `srs` is gens.gens_derefs_kzg.srs.powers_g1 on the device; `key` is
+/// optional (the bytes are the same with and without it).  The derefs opening draws nothing from the RandomTape (:510); pairings and
+/// verification stay in the reference's code.
+#[cfg(feature = "kzg")]
+pub fn sparse_eval_prove_kzg(
+    dense_dev: *const sbn_dense,
+    rx: &[Scalar],
+    ry: &[Scalar],
+    evals: &[Scalar],
+    gens: &SparseMatPolyCommitmentGens,
+    srs: &KzgSrs,
+    key: Option<&DerefsKey>,
+    transcript: &mut DevTranscript,
+    random_tape: &mut RandomTape,
+) -> SparseMatPolyEvalProof {
+    let (num_ops, num_cells, b) = dense_shape(dense_dev);
+    assert_eq!(evals.len(), b);                                                       // sparse_mlpoly_full.rs:1769
+    let (n, m) = (num_ops.trailing_zeros() as usize, num_cells.trailing_zeros() as usize);
+    let lg_of = |g: &crate::hyrax::PolyCommitmentGens| g.gens.gens_n.n.trailing_zeros() as usize;
+    let (lg_o, lg_m) = (lg_of(&gens.gens_ops), lg_of(&gens.gens_mem));
+    let (mut n_rnd, mut n_proof) = (0usize, 0usize);
+    check(unsafe { sbn_sparse_eval_kzg_sizes(rx.len(), ry.len(), num_ops, b, &mut n_rnd, &mut n_proof) });
+    let mut rnd = open_draws(random_tape, lg_o);                                      // HashLayerProof::prove: comb_ops, then comb_mem (:978-1035)
+    rnd.extend(open_draws(random_tape, lg_m));
+    assert_eq!(rnd.len(), n_rnd);
+    let (rnd, rxb, ryb, evb) = (scalars_canonical(&rnd), scalars_canonical(rx), scalars_canonical(ry), scalars_canonical(evals));
+    let g_ops = pc_bases(&gens.gens_ops.gens.gens_n, &gens.gens_ops.gens.gens_1);
+    let g_mem = pc_bases(&gens.gens_mem.gens.gens_n, &gens.gens_mem.gens.gens_1);
+    let mut proof = vec![0u8; n_proof];
+    check(unsafe {
+        sbn_sparse_eval_prove_kzg(ctx(), dense_dev, rxb.as_ptr(), rx.len(), ryb.as_ptr(), ry.len(), evb.as_ptr(), g_ops.0, g_mem.0, srs.0 as *const sbn_bases,
+                                  key.map_or(null(), |k| k.0 as *const sbn_derefs_key), rnd.as_ptr(), transcript.0, proof.as_mut_ptr())
+    });
+    let ser = sparse_eval_stream(&proof, b, m, n, lg_o, lg_m, None);
+    SparseMatPolyEvalProof::deserialize_compressed(&ser[..]).expect("SparseMatPolyEvalProof (KZG) from the library's bytes")
 }
 
 /// One pair of hashed sets of Layers::build_hash_layer (sparse_mlpoly_full.rs:762-790) and the first layer of both product circuits

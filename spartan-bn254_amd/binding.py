@@ -25,6 +25,8 @@ EXPORTED_SYMBOLS = [
     "sbn_kzg_srs_upload", "sbn_kzg_srs_from_tau", "sbn_kzg_commit", "sbn_poly_div_linear", "sbn_kzg_open", "sbn_kzg_open_batched",
     "sbn_r1cs_upload", "sbn_r1cs_free", "sbn_r1cs_multiply", "sbn_r1cs_eval_table", "sbn_r1cs_evaluate",
     "sbn_r1cs_proof_sizes", "sbn_r1cs_proof_prove", "sbn_sparse_eval_sizes", "sbn_sparse_eval_prove",
+    "sbn_derefs_key_build", "sbn_derefs_key_free", "sbn_derefs_key_len", "sbn_derefs_key_download", "sbn_derefs_key_commit",
+    "sbn_sparse_eval_kzg_sizes", "sbn_sparse_eval_prove_kzg",
     "sbn_dense_build", "sbn_dense_free", "sbn_dense_num_ops", "sbn_dense_num_cells", "sbn_dense_batch", "sbn_dense_addr_dev", "sbn_dense_read_ts_dev",
     "sbn_dense_audit_ts_dev", "sbn_dense_comb_ops", "sbn_dense_comb_mem",
 ]
@@ -91,6 +93,13 @@ def lib():
         L.sbn_r1cs_proof_prove.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 8
         L.sbn_sparse_eval_sizes.argtypes = [C.c_size_t] * 4 + [C.c_void_p] * 2
         L.sbn_sparse_eval_prove.argtypes = [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_void_p] * 7
+        L.sbn_sparse_eval_kzg_sizes.argtypes = [C.c_size_t] * 4 + [C.c_void_p] * 2
+        L.sbn_sparse_eval_prove_kzg.argtypes = [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_void_p] * 8
+        L.sbn_derefs_key_build.argtypes = [C.c_void_p] * 4
+        L.sbn_derefs_key_free.restype = None; L.sbn_derefs_key_free.argtypes = [C.c_void_p] * 2
+        L.sbn_derefs_key_len.restype = C.c_size_t; L.sbn_derefs_key_len.argtypes = [C.c_void_p]
+        L.sbn_derefs_key_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.sbn_derefs_key_commit.argtypes = [C.c_void_p] * 6
         L.sbn_dense_audit_ts_dev.restype = C.c_void_p; L.sbn_dense_audit_ts_dev.argtypes = [C.c_void_p, C.c_int]
         for name in ("sbn_dense_comb_ops", "sbn_dense_comb_mem"):
             getattr(L, name).restype = C.c_void_p; getattr(L, name).argtypes = [C.c_void_p]
@@ -363,6 +372,38 @@ def sparse_eval_sizes(num_vars_x, num_vars_y, num_ops, batch):
     if rc:
         raise SbnError(f"sbn_sparse_eval_sizes: ({num_vars_x}, {num_vars_y}, N = {num_ops}, batch = {batch}) is a shape the call refuses (rc={rc})")
     return a.value, b.value
+
+
+def sparse_eval_kzg_sizes(num_vars_x, num_vars_y, num_ops, batch):
+    """sbn_sparse_eval_kzg_sizes -> (scalars of rnd, bytes of the proof) of sbn_sparse_eval_prove_kzg at this shape"""
+    a, b = C.c_size_t(0), C.c_size_t(0)
+    rc = lib().sbn_sparse_eval_kzg_sizes(C.c_size_t(num_vars_x), C.c_size_t(num_vars_y), C.c_size_t(num_ops), C.c_size_t(batch), C.byref(a), C.byref(b))
+    if rc:
+        raise SbnError(f"sbn_sparse_eval_kzg_sizes: ({num_vars_x}, {num_vars_y}, N = {num_ops}, batch = {batch}) is a shape the call refuses (rc={rc})")
+    return a.value, b.value
+
+
+class DerefsKey:
+    """the per-cell SRS sums of one (Dense, SRS) pair (sbn_derefs_key_build).  Free it before the Dense and the SRS."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    def __len__(self):
+        return lib().sbn_derefs_key_len(self.h)
+
+    def download(self, first=0, count=None):
+        """-> ([side << 31 | a], [64-byte canonical affine S[side][a]]) of cells [first, first + count)"""
+        count = len(self) - first if count is None else count
+        ids = (C.c_uint32 * max(count, 1))(); xy = (C.c_uint8 * (64 * max(count, 1)))()
+        self.ctx._chk(lib().sbn_derefs_key_download(self.ctx.h, self.h, C.c_size_t(first), C.c_size_t(count), ids, xy), "sbn_derefs_key_download")
+        raw = bytes(xy)
+        return [int(ids[j]) for j in range(count)], [raw[64 * j:64 * j + 64] for j in range(count)]
+
+    def free(self):
+        if self.h:
+            lib().sbn_derefs_key_free(self.ctx.h, self.h)
+            self.h = None
 
 
 class Dense:
@@ -904,6 +945,34 @@ class Context:
         proof = (C.c_uint8 * n_proof)()
         self._chk(lib().sbn_sparse_eval_prove(self.h, dense.h, _ptr(rx) if rx else None, C.c_size_t(nx), _ptr(ry) if ry else None, C.c_size_t(ny), _ptr(evals),
                                               gens_ops.h, gens_mem.h, gens_derefs.h, _ptr(rnd), tr.h, proof), "sbn_sparse_eval_prove")
+        return bytes(proof)
+
+    # ---- the KZG build's SparseMatPolyEvalProof::prove in one call (sparse_mlpoly_full.rs:1757-1813) and its derefs key
+    def derefs_key_build(self, dense, srs):
+        """S[side][a] = the sum of the SRS powers at the ops of cell a (sbn_derefs_key_build) -> DerefsKey"""
+        h = C.c_void_p()
+        self._chk(lib().sbn_derefs_key_build(self.h, dense.h, srs.h, C.byref(h)), "sbn_derefs_key_build")
+        return DerefsKey(self, h)
+
+    def derefs_key_commit(self, key, mem_rx, mem_ry):
+        """Derefs::commit_kzg from the two eq tables -> (xy, is_inf): the point kzg_commit gives on the gathered, merged table"""
+        out = (C.c_uint8 * 64)(); inf = C.c_int()
+        self._chk(lib().sbn_derefs_key_commit(self.h, key.h, mem_rx.h, mem_ry.h, out, C.byref(inf)), "sbn_derefs_key_commit")
+        return bytes(out), bool(inf.value)
+
+    def sparse_eval_prove_kzg(self, dense, rx, ry, evals, gens_ops, gens_mem, srs, key, rnd, tr):
+        """SparseMatPolyEvalProof::prove of the KZG build (sbn_sparse_eval_prove_kzg) -> proof bytes, laid out as include/sbn254.h describes.
+        srs: a KZG SRS (no h) of at least npo2(2 batch) N - 1 points; key: a DerefsKey of (dense, srs) or None; rnd: sparse_eval_kzg_sizes(...)[0]
+        scalars; `tr` (Transcript) moves on"""
+        nx, ny = len(rx) // 32, len(ry) // 32
+        n_rnd, n_proof = sparse_eval_kzg_sizes(nx, ny, dense.num_ops, dense.batch)
+        if len(rnd) != 32 * n_rnd:
+            raise ValueError(f"sparse_eval_prove_kzg: rnd holds {len(rnd)} bytes, the shape needs {32 * n_rnd}")
+        if len(evals) != 32 * dense.batch:
+            raise ValueError(f"sparse_eval_prove_kzg: evals holds {len(evals)} bytes, the batch needs {32 * dense.batch}  [sparse_mlpoly_full.rs:1769 assert_eq]")
+        proof = (C.c_uint8 * n_proof)()
+        self._chk(lib().sbn_sparse_eval_prove_kzg(self.h, dense.h, _ptr(rx) if rx else None, C.c_size_t(nx), _ptr(ry) if ry else None, C.c_size_t(ny), _ptr(evals),
+                                                  gens_ops.h, gens_mem.h, srs.h, key.h if key is not None else None, _ptr(rnd), tr.h, proof), "sbn_sparse_eval_prove_kzg")
         return bytes(proof)
 
     # ---- KZG mode (kzg.rs): the SRS is a Bases handle, polynomials are the first n entries of a Table

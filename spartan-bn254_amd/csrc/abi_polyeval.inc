@@ -194,17 +194,15 @@ int sbn_polyeval_prove(sbn_ctx* c, const sbn_bases* gens, const sbn_table* Z, co
 }
 
 }  // extern "C"
-// the reduction and the opening on the transcript `t` (a copy of the caller's); count = 2^lc evals, canonical as r is; the caller holds the
-// context's mutex.  out_challenges: lc x 32 or NULL
-static int joint_opening_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_table* Z, const uint8_t* evals, size_t count, size_t lc,
-                                const uint8_t* label_evals, size_t label_evals_len, const uint8_t* label_chal, size_t label_chal_len,
-                                const uint8_t* label_claim, size_t label_claim_len, const uint8_t* r, size_t ell_r, const uint8_t* rnd, sbn_host::MerlinTranscript& t,
-                                uint8_t* out_challenges, uint8_t out_joint_claim[32], uint8_t* out_proof,
-                                uint8_t out_Cx_xy[64], int* Cx_is_inf, uint8_t out_Cy_xy[64], int* Cy_is_inf) {
+// the reduction both builds' joint openings start with (sparse_mlpoly_full.rs:384-397, :514-535): the evals under `label_evals`, lc challenges, the fold
+// of the evals from the last challenge down, the joint claim under `label_claim`.  rj: the lc challenges, then r; claim: canonical
+static void joint_reduce(const uint8_t* evals, size_t count, size_t lc, const uint8_t* label_evals, size_t label_evals_len, const uint8_t* label_chal, size_t label_chal_len,
+                         const uint8_t* label_claim, size_t label_claim_len, const uint8_t* r, size_t ell_r, sbn_host::MerlinTranscript& t,
+                         std::vector<uint8_t>& rj, uint8_t claim[32]) {
   using namespace sbn_host::fr;
   const size_t ell = lc + ell_r;
   for (size_t i = 0; i < count; i++) t.append_message(label_evals, label_evals_len, evals + 32 * i, 32);      // sparse_mlpoly_full.rs:384
-  std::vector<uint8_t> rj(32 * ell);
+  rj.assign(32 * ell, 0);
   for (size_t j = 0; j < lc; j++) { uint8_t b[64]; t.challenge_bytes(label_chal, label_chal_len, b, 64); transcript_wide_reduce(b, &rj[32 * j]); }     // :387
   if (ell_r) memcpy(&rj[32 * lc], r, 32 * ell_r);
   std::vector<El> pe(count);
@@ -215,8 +213,20 @@ static int joint_opening_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_tab
     len /= 2;
     for (size_t i = 0; i < len; i++) pe[i] = add(pe[2 * i], mmul(cj, sub(pe[2 * i + 1], pe[2 * i])));
   }
-  uint8_t claim[32]; memcpy(claim, pe[0].v, 32);
+  memcpy(claim, pe[0].v, 32);
   t.append_message(label_claim, label_claim_len, claim, 32);       // :397
+}
+
+// the reduction and the opening on the transcript `t` (a copy of the caller's); count = 2^lc evals, canonical as r is; the caller holds the
+// context's mutex.  out_challenges: lc x 32 or NULL
+static int joint_opening_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_table* Z, const uint8_t* evals, size_t count, size_t lc,
+                                const uint8_t* label_evals, size_t label_evals_len, const uint8_t* label_chal, size_t label_chal_len,
+                                const uint8_t* label_claim, size_t label_claim_len, const uint8_t* r, size_t ell_r, const uint8_t* rnd, sbn_host::MerlinTranscript& t,
+                                uint8_t* out_challenges, uint8_t out_joint_claim[32], uint8_t* out_proof,
+                                uint8_t out_Cx_xy[64], int* Cx_is_inf, uint8_t out_Cy_xy[64], int* Cy_is_inf) {
+  const size_t ell = lc + ell_r;
+  std::vector<uint8_t> rj; uint8_t claim[32];
+  joint_reduce(evals, count, lc, label_evals, label_evals_len, label_chal, label_chal_len, label_claim, label_claim_len, r, ell_r, t, rj, claim);
   int rc;
   if ((rc = polyeval_check(c, gens, Z, nullptr, rj.data(), ell, claim, nullptr, rnd))) return rc;
   if ((rc = polyeval_prove_locked(c, gens, Z, nullptr, rj.data(), ell, claim, nullptr, rnd, t, out_proof, out_Cx_xy, Cx_is_inf, out_Cy_xy, Cy_is_inf))) return rc;

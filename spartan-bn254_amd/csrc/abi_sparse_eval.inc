@@ -1,4 +1,5 @@
-// abi_sparse_eval.inc — C ABI: SparseMatPolyEvalProof::prove (sparse_mlpoly_full.rs:1700-1755, the Hyrax build) in ONE call.
+// abi_sparse_eval.inc — C ABI: SparseMatPolyEvalProof::prove in ONE call: sbn_sparse_eval_prove (sparse_mlpoly_full.rs:1700-1755, the Hyrax build) and
+// sbn_sparse_eval_prove_kzg (:1757-1813, --features kzg).  The two builds share sparse_eval_locked; where the KZG build differs is listed below.
 // sbn_sparse_eval_prove composes, on one working copy of the caller's Merlin transcript, the bodies of the calls that already hold its parts:
 //   equalize, eq(rx), eq(ry)          eq_evals_locked on the zero-padded points                       (:1681-1697, :1713-1718)
 //   dense.deref + Derefs::new         gather_merge_locked: ONE gathered, merged table                  (:275-279, :293-297)
@@ -10,6 +11,11 @@
 //   HashLayerProof::prove             table_evaluate_many_locked (7 batch at rand_ops, 2 at rand_mem), joint_opening_locked three times   (:922-1046)
 // The host does the transcript lines between them, the subset and split checks on the claims, and the proof's byte layout (include/sbn254.h).
 // The dense representation and its two tables are only read.  Included by sbn254.hip.
+// The KZG build (an SRS instead of gens_derefs) differs in two places:
+//   derefs.commit_kzg                 ONE point: with a key, sum_a eq[a] S_a over the cells read at least once (abi_derefs_key.inc); without, the MSM of
+//                                     the first min(n', srs->n) entries of the gathered table, n' = 2 b N its non-zero prefix   (:307-312, :349-356, kzg.rs:386-404)
+//   DerefsEvalProof::prove (KZG)      joint_reduce, kzg_eval_point, kzg_div_enqueue over n' coefficients and the MSM of the n' - 1 quotient
+//                                     coefficients: q_i = 0 for i >= n' - 1, the padding contributes nothing   (:503-550, kzg.rs:174-192)
 
 struct SparseEvalShape {
   size_t batch, N, ell_m, cells, L_ops;                 // L_ops = log2 N = the layers of an ops circuit; ell_m = log2 cells = the layers of a mem circuit
@@ -18,6 +24,8 @@ struct SparseEvalShape {
   size_t Ld, Rd, lg_d, lg_o, lg_m;
   size_t pp_mem_polys, pp_mem_claims, pp_ops_polys, pp_ops_claims;   // bytes of the two product proofs' out_polys / out_claims
   size_t rnd_scalars, proof_bytes;
+  size_t n_d, n_prefix;                                 // the derefs polynomial's length cnt_d * N and its non-zero prefix 2 b N
+  size_t rnd_scalars_kzg, proof_bytes_kzg;              // the KZG build: no derefs draws, comm_derefs one point, proof_derefs [proof | eval]
 };
 static bool sparse_eval_shape(size_t nx, size_t ny, size_t N, size_t batch, SparseEvalShape* s) {
   if (batch < 1 || batch > (size_t)SE_BATCH_MAX || N < 2 || (N & (N - 1)) || nx > 31 || ny > 31 || std::max(nx, ny) < 1) return false;
@@ -35,6 +43,10 @@ static bool sparse_eval_shape(size_t nx, size_t ny, size_t N, size_t batch, Spar
   s->rnd_scalars = 9 + 2 * (s->lg_d + s->lg_o + s->lg_m);
   s->proof_bytes = 32 * s->Ld + 32 * (4 + 6 * batch) + s->pp_mem_polys + s->pp_mem_claims + s->pp_ops_polys + s->pp_ops_claims + 32 * (7 * batch + 2)
                  + 64 * (s->lg_d + s->lg_o + s->lg_m) + 3 * 128;
+  s->n_d = s->cnt_d * N; s->n_prefix = 2 * batch * N;
+  s->rnd_scalars_kzg = 6 + 2 * (s->lg_o + s->lg_m);
+  s->proof_bytes_kzg = 32 + 32 * (4 + 6 * batch) + s->pp_mem_polys + s->pp_mem_claims + s->pp_ops_polys + s->pp_ops_claims + 32 * (7 * batch + 2)
+                     + 64 * (s->lg_o + s->lg_m) + 2 * 128 + 64;
   return true;
 }
 
@@ -71,21 +83,22 @@ static int sparse_eval_commit(sbn_ctx* c, const sbn_bases* gn, const sbn_table* 
   return commit_rows_device(c, gn, o, nullptr, L, R, out_xy, nullptr);
 }
 
-// the proof on the transcript `t` (a copy of the caller's); arguments already checked
+// the proof on the transcript `t` (a copy of the caller's); arguments already checked.  srs != null: the KZG build (gens_derefs is null, key may be)
 static int sparse_eval_locked(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx, size_t nx, const uint8_t* ry, size_t ny, const uint8_t* evals,
-                              const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_bases* gens_derefs, const SparseEvalShape& s,
-                              const uint8_t* rnd, sbn_host::MerlinTranscript& t, uint8_t* out_proof, SparseEvalTabs& T) {
+                              const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_bases* gens_derefs, const sbn_bases* srs, const sbn_derefs_key* key,
+                              const SparseEvalShape& s, const uint8_t* rnd, sbn_host::MerlinTranscript& t, uint8_t* out_proof, SparseEvalTabs& T) {
   using namespace sbn_host::fr;
   auto fmul = [](const El& a, const El& b) { return mmul(to_m(a), b); };
   int rc;
   const size_t b = s.batch, N = s.N;
   // rnd: the three openings' draws in the reference's order (HashLayerProof::prove: derefs, ops, mem)
-  const uint8_t* rnd_d = rnd;
-  const uint8_t* rnd_o = rnd_d + 32 * (3 + 2 * s.lg_d);
+  const bool kzg = srs != nullptr;
+  const uint8_t* rnd_d = rnd;                                      // (the KZG build's derefs opening draws nothing: ops | mem)
+  const uint8_t* rnd_o = kzg ? rnd : rnd_d + 32 * (3 + 2 * s.lg_d);
   const uint8_t* rnd_m = rnd_o + 32 * (3 + 2 * s.lg_o);
   // out_proof: the fields of SparseMatPolyEvalProof in declaration order, nested structs likewise (:1659-1662, :1529-1532, :1293-1299, :874-882)
   uint8_t* o_comm = out_proof;
-  uint8_t* o_pl_row = o_comm + 32 * s.Ld;                         // init, read[b], write[b], audit
+  uint8_t* o_pl_row = o_comm + 32 * (kzg ? 1 : s.Ld);             // init, read[b], write[b], audit
   uint8_t* o_pl_col = o_pl_row + 32 * (2 + 2 * b);
   uint8_t* o_pl_val = o_pl_col + 32 * (2 + 2 * b);                // eval_dotp_left[b], eval_dotp_right[b]
   uint8_t* o_pp_mem = o_pl_val + 32 * (2 * b);                    // proof_mem is declared before proof_ops
@@ -118,7 +131,18 @@ static int sparse_eval_locked(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx
   }
 
   // ---- 2. the derefs commitment (:1723-1727, :341-347; PolyCommitment's lines hyrax.rs:44-51) ----
-  {
+  if (kzg) {                                                       // :1781-1785, :349-356, kzg.rs:386-404
+    uint8_t xy[64]; int inf = 0;
+    const size_t m = std::min(s.n_prefix, srs->n);                 // KZGPolyCommitment::commit truncates to the SRS (kzg.rs:388); the padding behind n' is zero
+    if (key) rc = derefs_key_commit_locked(c, key, mem_rx, mem_ry, xy, &inf);
+    else rc = kzg_msm_internal(c, srs, (const uint32_t*)derefs->d, m, xy, &inf);
+    if (rc) return rc;
+    if (inf) memset(xy, 0, 64);
+    sbn_g1_compress(xy, 1, o_comm);                                // the identity as serialize_compressed writes it
+    t.append_message((const uint8_t*)"derefs_commitment", 17, (const uint8_t*)"begin_derefs_commitment", 23);
+    t.append_message((const uint8_t*)"comm_poly_row_col_ops_val", 25, o_comm, 32);
+    t.append_message((const uint8_t*)"derefs_commitment", 17, (const uint8_t*)"end_derefs_commitment", 21);
+  } else {
     const sbn_bases *gn = nullptr, *g1 = nullptr;
     if ((rc = r1cs_proof_gens(c, gens_derefs, s.Rd, &gn, &g1))) return rc;
     std::vector<uint8_t> xy(64 * s.Ld);
@@ -259,12 +283,35 @@ static int sparse_eval_locked(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx
     memcpy(o_hl_col, e_ops + 32 * 2 * b, 32 * 2 * b); memcpy(o_hl_col + 32 * 2 * b, evm + 32, 32);
     memcpy(o_hl_val, e_ops + 32 * 4 * b, 32 * b);
     uint8_t cx[64], cy[64], jc[32]; int xi = 0, yi = 0;
-    // DerefsEvalProof::prove (:412-432)
-    r1cs_proof_name(t, "Derefs evaluation proof");
     std::vector<uint8_t> pad(32 * std::max(s.cnt_d, s.cnt_o), 0);
     memcpy(pad.data(), ev.data(), 32 * 2 * b);
+    if (kzg) {
+      // DerefsEvalProof::prove, KZG (:503-550): the reduction's claim is absorbed, then KZGProof::prove on the derefs table at kzg_eval_point
+      r1cs_proof_name(t, "Derefs evaluation proof (KZG)");
+      std::vector<uint8_t> rj;
+      joint_reduce(pad.data(), s.cnt_d, s.lc_d, (const uint8_t*)"evals_ops_val", 13, (const uint8_t*)"challenge_combine_n_to_one", 26, (const uint8_t*)"joint_claim_eval", 16,
+                   rand_ops.data(), L_ops, t, rj, jc);
+      uint8_t z[32], pxy[64]; int pinf = 0;
+      polyeval_challenge(t, "kzg_eval_point", z);
+      const size_t n = s.n_prefix;                                 // >= 4
+      if ((rc = ensure(c, c->kzg_ws, 64 + kzg_levels_bytes(n)))) return rc;
+      uint32_t* evd = (uint32_t*)c->kzg_ws.p;
+      ScScalar p2[64]; kzg_pow2_table(z, p2);
+      void* qd = nullptr; size_t qbytes = 0;
+      if ((rc = kzg_qbuf(c, n - 1, &qd, &qbytes))) return rc;
+      rc = kzg_div_enqueue(c, (const uint32_t*)derefs->d, n, p2, (uint32_t*)qd, n - 1, evd, evd + 16);
+      if (rc == SBN_OK) rc = kzg_fetch(c, evd, 1, o_open_d + 32);
+      if (rc == SBN_OK) rc = kzg_msm_internal(c, srs, (const uint32_t*)qd, n - 1, pxy, &pinf);
+      hipStreamSynchronize(c->stream); pool_put(c, qd, qbytes);
+      if (rc) return rc;
+      if (pinf) memset(pxy, 0, 64);
+      sbn_g1_compress(pxy, 1, o_open_d);
+    } else {
+    // DerefsEvalProof::prove (:412-432)
+    r1cs_proof_name(t, "Derefs evaluation proof");
     if ((rc = joint_opening_locked(c, gens_derefs, derefs, pad.data(), s.cnt_d, s.lc_d, (const uint8_t*)"evals_ops_val", 13, (const uint8_t*)"challenge_combine_n_to_one", 26,
                                    (const uint8_t*)"joint_claim_eval", 16, rand_ops.data(), L_ops, rnd_d, t, nullptr, jc, o_open_d, cx, &xi, cy, &yi))) return rc;
+    }
     // comb_ops (:978-1009)
     std::fill(pad.begin(), pad.end(), 0);
     memcpy(pad.data(), e_ops, 32 * 5 * b);
@@ -311,11 +358,57 @@ int sbn_sparse_eval_prove(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx, si
   int rc;
   {
     SparseEvalTabs T(c);
-    rc = sparse_eval_locked(c, dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, gens_derefs, s, rnd, t, proof.data(), T);
+    rc = sparse_eval_locked(c, dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, gens_derefs, nullptr, nullptr, s, rnd, t, proof.data(), T);
     T.ok = rc == SBN_OK;
   }
   if (rc) return rc;
   memcpy(out_proof, proof.data(), s.proof_bytes);
+  tr->t = t;
+  return SBN_OK;
+}
+
+int sbn_sparse_eval_kzg_sizes(size_t num_vars_x, size_t num_vars_y, size_t num_ops, size_t batch, size_t* rnd_scalars, size_t* proof_bytes) {
+  SparseEvalShape s;
+  if (!sparse_eval_shape(num_vars_x, num_vars_y, num_ops, batch, &s)) return SBN_EINVAL;
+  if (rnd_scalars) *rnd_scalars = s.rnd_scalars_kzg;
+  if (proof_bytes) *proof_bytes = s.proof_bytes_kzg;
+  return SBN_OK;
+}
+
+int sbn_sparse_eval_prove_kzg(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx, size_t nx, const uint8_t* ry, size_t ny, const uint8_t* evals,
+                              const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_bases* srs, const sbn_derefs_key* key,
+                              const uint8_t* rnd, sbn_transcript* tr, uint8_t* out_proof) {
+  if (!c || !dn || (!rx && nx) || (!ry && ny) || !evals || !gens_ops || !gens_mem || !srs || !rnd || !tr || !out_proof) return SBN_EINVAL;
+  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+  SparseEvalShape s;
+  if (dn->batch > (size_t)SE_BATCH_MAX) return fail(c, SBN_EINVAL, "sparse eval (KZG): batch = %zu: proof_ops would hold %zu instances, at most %d fit one product proof", dn->batch, 6 * dn->batch, SC_PACK_MAX);
+  if (dn->N < 2) return fail(c, SBN_EINVAL, "sparse eval (KZG): N = %zu: the dot-product circuits cannot be split  [product_tree.rs:89 assert_eq]", dn->N);
+  if (nx > 31 || ny > 31 || ((size_t)1 << std::max(nx, ny)) != dn->cells)
+    return fail(c, SBN_EINVAL, "sparse eval (KZG): rx has %zu and ry %zu variables, the memories have %zu cells  [sparse_mlpoly_full.rs:226 assert, hyrax.rs:218 assert_eq]", nx, ny, dn->cells);
+  if (!sparse_eval_shape(nx, ny, dn->N, dn->batch, &s)) return fail(c, SBN_EINVAL, "sparse eval (KZG): shape (%zu, %zu, N = %zu, batch = %zu) is outside what the openings take", nx, ny, dn->N, dn->batch);
+  const struct { const sbn_bases* g; size_t lg; const char* name; } gs[2] = {{gens_ops, s.lg_o, "gens_ops"}, {gens_mem, s.lg_m, "gens_mem"}};
+  for (const auto& x : gs)
+    if (x.g->n != ((size_t)1 << x.lg) + 1 || !x.g->has_h)
+      return fail(c, SBN_EINVAL, "sparse eval (KZG): %s has %zu points%s, the opening needs %zu + 1 with h  [nizk/mod.rs:412-415, :455]", x.name, x.g->n, x.g->has_h ? "" : " and no h", (size_t)1 << x.lg);
+  if (srs->has_h) return fail(c, SBN_EINVAL, "sparse eval (KZG): the SRS handle has an h; an SRS is sbn_kzg_srs_upload's or sbn_kzg_srs_from_tau's");
+  if (srs->n < s.n_d - 1)
+    return fail(c, SBN_EINVAL, "sparse eval (KZG): the derefs quotient has %zu coefficients, the SRS %zu points  [kzg.rs:186 slices past its end]", s.n_d - 1, srs->n);
+  if (key && (key->dense != dn || key->srs != srs || key->srs_n != srs->n || key->batch != dn->batch || key->N != dn->N || key->cells != dn->cells))
+    return fail(c, SBN_EINVAL, "sparse eval (KZG): the derefs key was built for another dense handle or another SRS");
+  for (size_t i = 0; i < nx; i++) if (!fr_canonical(rx + 32 * i)) return fail(c, SBN_EINVAL, "sparse eval (KZG): rx[%zu] is not canonical  [scalar.rs:87-95]", i);
+  for (size_t i = 0; i < ny; i++) if (!fr_canonical(ry + 32 * i)) return fail(c, SBN_EINVAL, "sparse eval (KZG): ry[%zu] is not canonical  [scalar.rs:87-95]", i);
+  for (size_t i = 0; i < s.batch; i++) if (!fr_canonical(evals + 32 * i)) return fail(c, SBN_EINVAL, "sparse eval (KZG): evals[%zu] is not canonical  [scalar.rs:87-95]", i);
+  for (size_t i = 0; i < s.rnd_scalars_kzg; i++) if (!fr_canonical(rnd + 32 * i)) return fail(c, SBN_EINVAL, "sparse eval (KZG): rnd[%zu] is not canonical  [scalar.rs:87-95]", i);
+  sbn_host::MerlinTranscript t = tr->t;
+  std::vector<uint8_t> proof(s.proof_bytes_kzg);                   // the caller's buffer is written only by a call that succeeded
+  int rc;
+  {
+    SparseEvalTabs T(c);
+    rc = sparse_eval_locked(c, dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, nullptr, srs, key, s, rnd, t, proof.data(), T);
+    T.ok = rc == SBN_OK;
+  }
+  if (rc) return rc;
+  memcpy(out_proof, proof.data(), s.proof_bytes_kzg);
   tr->t = t;
   return SBN_OK;
 }

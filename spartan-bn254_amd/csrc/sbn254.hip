@@ -10,6 +10,7 @@
 //   multi_sparse_to_dense_rep, AddrTimestamps::new      src/sparse_mlpoly_full.rs:120-174, 211-243  -> sbn_dense_*
 //   PolyEvalProof::prove, DotProductProofLog::prove     src/hyrax.rs:65-116, src/nizk/mod.rs:439-522 -> sbn_polyeval_prove / sbn_joint_opening_prove
 //   SparseMatPolyEvalProof::prove                        src/sparse_mlpoly_full.rs:1700-1755 -> sbn_sparse_eval_prove
+//   SparseMatPolyEvalProof::prove (--features kzg), Derefs::commit_kzg  src/sparse_mlpoly_full.rs:1757-1813, 307-312 -> sbn_sparse_eval_prove_kzg / sbn_derefs_key_*
 //   ZKSumcheckInstanceProof::prove_cubic_with_additive_term, ::prove_quad, DotProductProof::prove  src/sumcheck.rs:465-811, src/nizk/mod.rs:306-366 -> sbn_zk_sumcheck_prove_r1cs / _quad
 // There is no CPU fallback in this file: every entry point needs the gfx950 device.
 #include "../../include/sbn254.h"
@@ -28,6 +29,7 @@
 #include "zk_sumcheck_kernels.cuh"
 #include "r1cs_proof_kernels.cuh"
 #include "sparse_eval_kernels.cuh"
+#include "derefs_key_kernels.cuh"
 #include "host_keccak.hpp"
 #include "host_strobe.hpp"
 
@@ -66,6 +68,7 @@ using namespace sbn;
 #include "abi_r1cs.inc"
 #include "abi_r1cs_proof.inc"
 #include "abi_dense.inc"
+#include "abi_derefs_key.inc"
 #include "abi_sparse_eval.inc"
 
 extern "C" {
