@@ -230,6 +230,17 @@ template <class M, bool SQR> __device__ __forceinline__ Fe<M> fe_mulu_impl(const
   }
   return r;
 }
+// 32-bit value barrier (no instruction: an empty asm per limb).  A product widens its limbs to 64 bits where it multiplies, and
+// hipcc selects v_mad_u64_u32 only when it sees that widening in the multiply's own basic block.  When an element also feeds a
+// rare-path product behind a branch (the exact zero test of a sum's P), the widened limbs are shared across the branch as 64-bit
+// values whose upper halves the later block no longer knows to be zero: every product of that element then becomes a full
+// 64 x 64 multiply (a second v_mad_u64_u32 or v_mul_lo_u32 with a register holding the constant 0) and the column's halves are
+// moved into and out of that multiply's tied operand.  Called on the element behind the branch, this makes the common path widen
+// it again, locally.  tools/isa_stats.py counts both patterns (`zero*`, `mov>mad`); tests/test_isa_field_products.py pins them.
+template <class M> __device__ __forceinline__ void fe_pin32(Fe<M>& a) {
+#pragma unroll
+  for (int i = 0; i < NL; i++) asm volatile("" : "+v"(a.v[i]));
+}
 template <class M> __device__ __forceinline__ Fe<M> fe_mulu(const Fe<M>& a, const Fe<M>& b) { return fe_mulu_impl<M, false>(a, b); }
 template <class M> __device__ __forceinline__ Fe<M> fe_squ(const Fe<M>& a) { return fe_mulu_impl<M, true>(a, a); }
 

@@ -39,6 +39,18 @@ __device__ __forceinline__ XYZZ xyzz_from_affine(const Affine& p) {
 __device__ __forceinline__ Affine aff_load(const void* p) {
   Affine a; a.x = fe_load<FqP>(p); a.y = fe_load<FqP>(reinterpret_cast<const uint8_t*>(p) + 32); return a;
 }
+// The same load in two halves, for loops that prefetch: the 16 dwords as they come from memory (the load stays in flight until
+// aff_unpack reads them; aff_load's shifts and masks would wait for it on the spot)
+struct AffineRaw { uint4 x0, x1, y0, y1; };
+__device__ __forceinline__ AffineRaw aff_load_raw(const void* p) {
+  const uint4* q = reinterpret_cast<const uint4*>(p);
+  AffineRaw r; r.x0 = q[0]; r.x1 = q[1]; r.y0 = q[2]; r.y1 = q[3]; return r;
+}
+__device__ __forceinline__ Affine aff_unpack(const AffineRaw& r) {
+  const uint32_t wx[8] = {r.x0.x, r.x0.y, r.x0.z, r.x0.w, r.x1.x, r.x1.y, r.x1.z, r.x1.w};
+  const uint32_t wy[8] = {r.y0.x, r.y0.y, r.y0.z, r.y0.w, r.y1.x, r.y1.y, r.y1.z, r.y1.w};
+  Affine a; a.x = fe_unpack<FqP>(wx); a.y = fe_unpack<FqP>(wy); return a;
+}
 __device__ __forceinline__ void aff_store(void* p, const Affine& a) {      // canonical (tables, results)
   fe_store<FqP>(p, a.x); fe_store<FqP>(reinterpret_cast<uint8_t*>(p) + 32, a.y);
 }
@@ -91,12 +103,13 @@ __device__ __forceinline__ void xyzz_madd(XYZZ& acc, const Affine& q_in, bool ne
   const Fq qy = neg ? fe_negb<FqP, 2>(q_in.y) : q_in.y;                    // 2p - y: limbs below 2^30
   if (acc.ZZ.v[0] == 0) { if (xyzz_is_inf(acc)) { acc.X = q_in.x; acc.Y = fe_normu(qy); acc.ZZ = fe_one<FqP>(); acc.ZZZ = acc.ZZ; return; } }
   const Fq U2 = fe_mulu(q_in.x, acc.ZZ), S2 = fe_mulu(qy, acc.ZZZ);        // [0, 1.2p)
-  const Fq P = fe_normu(fe_subb<FqP, 6, 1>(U2, acc.X));                    // U2 - X + 6p in (0.8p, 7.2p)
+  Fq P = fe_normu(fe_subb<FqP, 6, 1>(U2, acc.X));                          // U2 - X + 6p in (0.8p, 7.2p)
   const Fq R = fe_normu(fe_subb<FqP, 4, 1>(S2, acc.Y));                    // S2 - Y + 4p in (0.8p, 5.2p)
   if (fe_maybe_zero(P) && fe_is_zero(P)) {                                 // same x: doubling or cancellation
     if (fe_is_zero(R)) { Affine q; q.x = q_in.x; q.y = fe_normu(qy); acc = xyzz_dbl_affine(q); } else acc = xyzz_inf();
     return;
   }
+  fe_pin32(P);                                                             // P fed the exact test: widen it afresh for the products below (fp.cuh)
   const Fq PP = fe_squ(P), PPP = fe_mulu(P, PP), Q = fe_mulu(acc.X, PP);
   const Fq X3 = fe_normu(fe_subb<FqP, 4, 3>(fe_squ(R), fe_add_lazy(fe_add_lazy(PPP, Q), Q)));        // R^2 - PPP - 2Q + 4p in (0.4p, 5.2p)
   // Y3 = R (Q - X3) - Y PPP as ONE sum of two products with ONE Montgomery reduction (fp.cuh: Cols): R (Q - X3 + 6p) + (4p - Y) PPP.
@@ -113,11 +126,12 @@ __device__ __forceinline__ XYZZ xyzz_add_inl(const XYZZ& a, const XYZZ& b) {
   if (xyzz_is_inf(a)) return b;
   if (xyzz_is_inf(b)) return a;
   const Fq U1 = fe_mulu(a.X, b.ZZ), U2 = fe_mulu(b.X, a.ZZ), S1 = fe_mulu(a.Y, b.ZZZ), S2 = fe_mulu(b.Y, a.ZZZ);   // [0, 1.2p)
-  const Fq P = fe_normu(fe_subb<FqP, 2, 1>(U2, U1)), R = fe_normu(fe_subb<FqP, 2, 1>(S2, S1));                  // (0.8p, 3.2p)
+  Fq P = fe_normu(fe_subb<FqP, 2, 1>(U2, U1)); const Fq R = fe_normu(fe_subb<FqP, 2, 1>(S2, S1));               // (0.8p, 3.2p)
   if (fe_maybe_zero(P) && fe_is_zero(P)) {
     if (fe_is_zero(R)) return xyzz_dbl(a);
     return xyzz_inf();
   }
+  fe_pin32(P);                                       // (see xyzz_madd)
   const Fq PP = fe_squ(P), PPP = fe_mulu(P, PP), Q = fe_mulu(U1, PP);
   XYZZ r;
   r.X = fe_normu(fe_subb<FqP, 4, 3>(fe_squ(R), fe_add_lazy(fe_add_lazy(PPP, Q), Q)));
@@ -163,11 +177,12 @@ __device__ __forceinline__ XYZZ xyzz_add_quad(const XYZZ& a, const XYZZ& b, int 
   // step 1: U1 = X1 ZZ2 | U2 = X2 ZZ1 | S1 = Y1 ZZZ2 | S2 = Y2 ZZZ1
   const Fq t1 = fe_mulu(fe_sel4(role, a.X, b.X, a.Y, b.Y), fe_sel4(role, b.ZZ, a.ZZ, b.ZZZ, a.ZZZ));
   const Fq U1 = fe_quad_bcast<0>(t1), U2 = fe_quad_bcast<1>(t1), S1 = fe_quad_bcast<2>(t1), S2 = fe_quad_bcast<3>(t1);
-  const Fq P = fe_normu(fe_subb<FqP, 2, 1>(U2, U1)), R = fe_normu(fe_subb<FqP, 2, 1>(S2, S1));
+  Fq P = fe_normu(fe_subb<FqP, 2, 1>(U2, U1)); const Fq R = fe_normu(fe_subb<FqP, 2, 1>(S2, S1));
   if (fe_maybe_zero(P) && fe_is_zero(P)) {
     if (fe_is_zero(R)) return xyzz_dbl(a);           // (inlined: an out-of-line copy gives the kernel a scratch segment, measured +15 us per launch)
     return xyzz_inf();
   }
+  fe_pin32(P);                                       // (see xyzz_madd)
   // step 2: PP = P P | RR = R R | Z12 = ZZ1 ZZ2 | Z123 = ZZZ1 ZZZ2   (the last two stay with their lanes)
   const Fq t2 = fe_mulu(fe_sel4(role, P, R, a.ZZ, a.ZZZ), fe_sel4(role, P, R, b.ZZ, b.ZZZ));
   const Fq PP = fe_quad_bcast<0>(t2), RR = fe_quad_bcast<1>(t2);

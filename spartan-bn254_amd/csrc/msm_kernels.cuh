@@ -324,21 +324,34 @@ struct AccCounters { uint32_t extra_count, big_count; };
 struct ExtraItem { uint32_t bucket, seg; };
 struct BigItem { uint32_t bucket, base, k; };
 
-// software-pipelined: the index two entries ahead and the point one entry ahead are in flight during each mixed add
+// software-pipelined: the index two entries ahead and the point one entry ahead are in flight during each mixed add.
+// Unrolled by two so that nothing is copied on the back edge: the point as LOADED (16 dwords) ping-pongs between two register
+// sets (r0 / r1) and the entries between e0 / e1; with one body the compiler rotated 20 registers per iteration (the unpacked
+// next point into the current one's registers).  A point is unpacked into limbs at the top of the half that adds it, so its
+// gather is not waited for ahead of the addition before it.  The gather is unconditional: past the end of the segment it
+// fetches the segment's last entry once more (e0 / e1 always name an entry of this segment), because a load under `if` makes the
+// 16 dwords a two-way merge that is resolved by copying them.  The body (two inlined additions) is 2 x 5 000 instructions.
 __device__ __forceinline__ XYZZ acc_segment(const uint32_t* __restrict__ points, const uint32_t* __restrict__ lst, uint32_t from, uint32_t to) {
   XYZZ acc = xyzz_inf();
   if (from >= to) return acc;
-  uint32_t e_cur = lst[from];
-  uint32_t e_nxt = (from + 1 < to) ? lst[from + 1] : 0;
-  Affine p_cur = aff_load(points + 16 * (size_t)(e_cur & 0x7fffffffu));
-  for (uint32_t j = from; j < to; j++) {
-    const uint32_t e = e_cur; const Affine p = p_cur;
-    if (j + 1 < to) {
-      e_cur = e_nxt;
-      p_cur = aff_load(points + 16 * (size_t)(e_cur & 0x7fffffffu));
-      if (j + 2 < to) e_nxt = lst[j + 2];
+  uint32_t e0 = lst[from];
+  uint32_t e1 = (from + 1 < to) ? lst[from + 1] : e0;
+  AffineRaw r0 = aff_load_raw(points + 16 * (size_t)(e0 & 0x7fffffffu)), r1;
+  for (uint32_t j = from;; j += 2) {
+    {
+      const Affine p = aff_unpack(r0); const bool neg = (e0 >> 31) != 0;
+      r1 = aff_load_raw(points + 16 * (size_t)(e1 & 0x7fffffffu));
+      e0 = (j + 2 < to) ? lst[j + 2] : e1;
+      xyzz_madd(acc, p, neg);
     }
-    xyzz_madd(acc, p, (e >> 31) != 0);
+    if (j + 1 >= to) break;
+    {
+      const Affine p = aff_unpack(r1); const bool neg = (e1 >> 31) != 0;
+      r0 = aff_load_raw(points + 16 * (size_t)(e0 & 0x7fffffffu));
+      e1 = (j + 3 < to) ? lst[j + 3] : e0;
+      xyzz_madd(acc, p, neg);
+    }
+    if (j + 2 >= to) break;
   }
   return acc;
 }
