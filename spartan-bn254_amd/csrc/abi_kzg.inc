@@ -135,19 +135,15 @@ int sbn_poly_div_linear(sbn_ctx* c, const sbn_table* t, size_t n, const uint8_t 
   if ((rc = ensure(c, c->kzg_ws, 64 + kzg_levels_bytes(n)))) return rc;
   uint32_t* ev = (uint32_t*)c->kzg_ws.p;
   ScScalar p2[64]; kzg_pow2_table(z, p2);
-  sbn_table* qt = nullptr;
+  TableScope S(c); sbn_table* qt = nullptr;
   if (n >= 2) {
     size_t qlen = 1; while (qlen < n - 1) qlen <<= 1;
-    qt = new sbn_table(); qt->len = qlen;
-    size_t got = 0;
-    if ((rc = kzg_qbuf(c, qlen, &qt->d, &got))) { delete qt; return rc; }
-    qt->cap = got / 32;
+    if ((rc = S.alloc(qlen, "quotient", &qt))) return rc;
   }
-  rc = kzg_div_enqueue(c, (const uint32_t*)t->d, n, p2, qt ? (uint32_t*)qt->d : nullptr, qt ? qt->len : 0, ev, ev + 16);
-  if (rc == SBN_OK) rc = kzg_fetch(c, ev, 1, eval);
-  if (rc) { if (qt) { hipStreamSynchronize(c->stream); pool_put(c, qt->d, qt->cap * 32); delete qt; } return rc; }
-  *q = qt;
-  return SBN_OK;
+  if ((rc = kzg_div_enqueue(c, (const uint32_t*)t->d, n, p2, qt ? (uint32_t*)qt->d : nullptr, qt ? qt->len : 0, ev, ev + 16))) return rc;
+  if ((rc = kzg_fetch(c, ev, 1, eval))) return rc;
+  if (qt) *q = S.give(qt);
+  return S.done();
 }
 
 int sbn_kzg_open(sbn_ctx* c, const sbn_bases* srs, const sbn_table* t, size_t n, const uint8_t z[32], uint8_t eval[32], uint8_t proof_xy[64], int* proof_is_inf) {

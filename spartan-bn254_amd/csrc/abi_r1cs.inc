@@ -61,49 +61,34 @@ static int r1cs_spmv_table(sbn_ctx* c, const R1csCsr& m, const uint32_t* x, cons
   LAUNCHCHK(c);
   return SBN_OK;
 }
-static int r1cs_new_table(sbn_ctx* c, size_t len, sbn_table** out) {
-  sbn_table* t = new sbn_table(); t->len = len;
-  size_t got = 0; hipError_t e = pool_get(c, len * 32, &t->d, &got);
-  if (e != hipSuccess) { delete t; *out = nullptr; return fail(c, SBN_ENOMEM, "hipMalloc r1cs table (%zu entries): %s", len, hipGetErrorString(e)); }
-  t->cap = got / 32;
-  *out = t;
-  return SBN_OK;
-}
-static void r1cs_drop_table(sbn_ctx* c, sbn_table*& t) { if (t) { pool_put(c, t->d, t->cap * 32); delete t; t = nullptr; } }
 
 // the launches of sbn_r1cs_multiply / sbn_r1cs_eval_table; arguments checked, the caller holds the context's mutex (sbn_r1cs_proof_prove runs them too)
 static int r1cs_multiply_locked(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* z, sbn_table** Az, sbn_table** Bz, sbn_table** Cz) {
-  sbn_table* t[3] = {nullptr, nullptr, nullptr};
-  int rc = SBN_OK;
-  for (int k = 0; k < 3 && rc == SBN_OK; k++) rc = r1cs_new_table(c, m->nc, &t[k]);
-  if (rc == SBN_OK) {
-    R1csOut o; o.p[0] = (uint32_t*)t[0]->d; o.p[1] = (uint32_t*)t[1]->d; o.p[2] = (uint32_t*)t[2]->d; o.shift = m->log_nc;
-    rc = r1cs_spmv_table(c, m->rowm, (const uint32_t*)z->d, o);
-  }
-  if (rc == SBN_OK && c->prof) { hipStreamSynchronize(c->stream); prof_drain(c); }
-  if (rc) { for (int k = 0; k < 3; k++) r1cs_drop_table(c, t[k]); return rc; }
+  TableScope S(c); sbn_table* t[3]; int rc;
+  for (int k = 0; k < 3; k++) if ((rc = S.alloc(m->nc, "r1cs table", &t[k]))) return rc;
+  R1csOut o; o.p[0] = (uint32_t*)t[0]->d; o.p[1] = (uint32_t*)t[1]->d; o.p[2] = (uint32_t*)t[2]->d; o.shift = m->log_nc;
+  if ((rc = r1cs_spmv_table(c, m->rowm, (const uint32_t*)z->d, o))) return rc;
+  if (c->prof) { hipStreamSynchronize(c->stream); prof_drain(c); }
   *Az = t[0]; *Bz = t[1]; *Cz = t[2];
-  return SBN_OK;
+  S.give_all();
+  return S.done();
 }
 static int r1cs_eval_table_locked(sbn_ctx* c, const sbn_r1cs* m, const uint8_t* rx, size_t ell_x, const uint8_t rA[32], const uint8_t rB[32], const uint8_t rC[32],
                                   sbn_table** out) {
-  sbn_table *eq = nullptr, *x = nullptr, *t = nullptr;
-  int rc = eq_evals_locked(c, rx, ell_x, &eq);
-  if (rc == SBN_OK) rc = r1cs_new_table(c, 3 * m->nc, &x);
-  if (rc == SBN_OK) rc = r1cs_new_table(c, 2 * m->nv, &t);
-  if (rc == SBN_OK) {
-    // x = [r_A eq(rx) | r_B eq(rx) | r_C eq(rx)]: the combination of r1csproof.rs:376-387 folded into the gather
-    const ScScalar a = scs_from(sbn_host::fr::to_dev_mont(el_from(rA))), b = scs_from(sbn_host::fr::to_dev_mont(el_from(rB))),
-                   cc = scs_from(sbn_host::fr::to_dev_mont(el_from(rC)));
-    LAUNCH(c, "k_r1cs_scale3", k_r1cs_scale3, stream_grid(3 * m->nc), 256, (const uint32_t*)eq->d, m->log_nc, a, b, cc, (uint32_t*)x->d);
-    R1csOut o; o.p[0] = o.p[1] = o.p[2] = (uint32_t*)t->d; o.shift = m->log_z;
-    rc = r1cs_spmv_table(c, m->colm, (const uint32_t*)x->d, o);
-  }
-  if (rc == SBN_OK && c->prof) { hipStreamSynchronize(c->stream); prof_drain(c); }
-  r1cs_drop_table(c, eq); r1cs_drop_table(c, x);              // recycled in stream order (see sbn_table_free)
-  if (rc) { r1cs_drop_table(c, t); return rc; }
-  *out = t;
-  return SBN_OK;
+  TableScope S(c); sbn_table *eq = nullptr, *x = nullptr, *t = nullptr; int rc;
+  if ((rc = eq_evals_locked(c, rx, ell_x, &eq))) return rc;
+  S.keep(eq);
+  if ((rc = S.alloc(3 * m->nc, "r1cs table", &x))) return rc;
+  if ((rc = S.alloc(2 * m->nv, "r1cs table", &t))) return rc;
+  // x = [r_A eq(rx) | r_B eq(rx) | r_C eq(rx)]: the combination of r1csproof.rs:376-387 folded into the gather
+  const ScScalar a = scs_from(sbn_host::fr::to_dev_mont(el_from(rA))), b = scs_from(sbn_host::fr::to_dev_mont(el_from(rB))),
+                 cc = scs_from(sbn_host::fr::to_dev_mont(el_from(rC)));
+  LAUNCH(c, "k_r1cs_scale3", k_r1cs_scale3, stream_grid(3 * m->nc), 256, (const uint32_t*)eq->d, m->log_nc, a, b, cc, (uint32_t*)x->d);
+  R1csOut o; o.p[0] = o.p[1] = o.p[2] = (uint32_t*)t->d; o.shift = m->log_z;
+  if ((rc = r1cs_spmv_table(c, m->colm, (const uint32_t*)x->d, o))) return rc;
+  if (c->prof) { hipStreamSynchronize(c->stream); prof_drain(c); }
+  *out = S.give(t);
+  return S.done();                                            // eq and x: recycled in stream order
 }
 
 extern "C" {
@@ -211,9 +196,11 @@ int sbn_r1cs_evaluate(sbn_ctx* c, const sbn_r1cs* m, const uint8_t* rx, size_t e
   hipSetDevice(c->device);
   const R1csCsr& rm = m->rowm;
   const unsigned nblk = (unsigned)std::max<size_t>(1, std::min<size_t>(R1CS_EVAL_BLOCKS, ((size_t)rm.nchunks + 255) / 256));
-  sbn_table *ex = nullptr, *ey = nullptr;
+  TableScope S(c); sbn_table *ex = nullptr, *ey = nullptr;
   int rc = eq_evals_locked(c, rx, ell_x, &ex);
+  S.keep(ex);
   if (rc == SBN_OK) rc = eq_evals_locked(c, ry, ell_y, &ey);
+  S.keep(ey);
   if (rc == SBN_OK) rc = ensure(c, c->r1cs_ws, r1cs_align((size_t)nblk * 96) + 256);
   if (rc == SBN_OK) rc = ensure_pin(c, 4096);
   if (rc == SBN_OK) {
@@ -235,8 +222,7 @@ int sbn_r1cs_evaluate(sbn_ctx* c, const sbn_r1cs* m, const uint8_t* rx, size_t e
       else memcpy(out, c->pin, 96);
     }
   }
-  r1cs_drop_table(c, ex); r1cs_drop_table(c, ey);
-  return rc;
+  return rc ? rc : S.done();
 }
 
 }  // extern "C"

@@ -38,25 +38,6 @@ static int r1cs_proof_gens(sbn_ctx* c, const sbn_bases* pc, size_t R, const sbn_
   return SBN_OK;
 }
 
-static void r1cs_proof_drop(sbn_ctx* c, sbn_table*& t) {
-  if (!t) return;
-  if (t->d && t->owned) pool_put(c, t->d, t->cap * 32);
-  if (t->d2 && t->owned2) pool_put(c, t->d2, t->cap2 * 32);
-  delete t; t = nullptr;
-}
-// every intermediate table of one call: back to the pool on every path
-struct R1csProofTabs {
-  sbn_ctx* c; bool ok = false;
-  sbn_table *eq = nullptr, *z = nullptr, *Az = nullptr, *Bz = nullptr, *Cz = nullptr, *abc = nullptr, *chi = nullptr;
-  void* d_in = nullptr; size_t in_bytes = 0;
-  explicit R1csProofTabs(sbn_ctx* c_) : c(c_) {}
-  ~R1csProofTabs() {
-    if (!ok) hipStreamSynchronize(c->stream);                      // nothing of this call stays queued behind a failure
-    r1cs_proof_drop(c, eq); r1cs_proof_drop(c, z); r1cs_proof_drop(c, Az); r1cs_proof_drop(c, Bz); r1cs_proof_drop(c, Cz); r1cs_proof_drop(c, abc); r1cs_proof_drop(c, chi);
-    if (d_in) pool_put(c, d_in, in_bytes);
-  }
-};
-
 // nrows <= 11 elements v * G + b * h over gens_1 as ONE commit over the (gens_1, gens_4) set and ONE host wait; vb: v, b per row, canonical.
 // out: nrows compressed points
 static int r1cs_proof_sigma_rows(sbn_ctx* c, const sbn_bases* ext, const sbn_host::fr::El (*vb)[2], uint32_t nrows, uint8_t* out) {
@@ -87,8 +68,10 @@ static void r1cs_proof_name(sbn_host::MerlinTranscript& t, const char* name) { t
 // the proof on the transcript `t` (a copy of the caller's); arguments already checked
 static int r1cs_proof_locked(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* vars, const uint8_t* input, size_t num_inputs, const sbn_bases* gens_pc,
                              const sbn_bases* gens_3, const sbn_bases* gens_4, const R1csProofShape& s, const uint8_t* rnd, sbn_host::MerlinTranscript& t,
-                             uint8_t* out_proof, uint8_t* out_rx, uint8_t* out_ry, R1csProofTabs& T) {
+                             uint8_t* out_proof, uint8_t* out_rx, uint8_t* out_ry) {
   using namespace sbn_host::fr;
+  TableScope T(c);                                                 // every intermediate table of the call
+  sbn_table *eq = nullptr, *z = nullptr, *in = nullptr, *Az = nullptr, *Bz = nullptr, *Cz = nullptr, *abc = nullptr, *chi = nullptr;
   auto fmul = [](const El& a, const El& b) { return mmul(to_m(a), b); };
   auto put = [](uint8_t* o, const El& e) { memcpy(o, e.v, 32); };
   int rc;
@@ -149,19 +132,20 @@ static int r1cs_proof_locked(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* var
   // ---- 3. phase 1 (r1csproof.rs:268-313) ----
   std::vector<uint8_t> tau(32 * s.nx);
   for (size_t j = 0; j < s.nx; j++) polyeval_challenge(t, "challenge_tau", &tau[32 * j]);     // challenge_vector, transcript.rs:66-70
-  if ((rc = eq_evals_locked(c, tau.data(), s.nx, &T.eq))) return rc;
-  if ((rc = r1cs_new_table(c, 2 * m->nv, &T.z))) return rc;
-  if (num_inputs) {
-    hipError_t e = pool_get(c, num_inputs * 32, &T.d_in, &T.in_bytes);
-    if (e != hipSuccess) { T.d_in = nullptr; return fail(c, SBN_ENOMEM, "hipMalloc r1cs proof inputs: %s", hipGetErrorString(e)); }
-    HIPCHK(c, hipMemcpyAsync(T.d_in, input, num_inputs * 32, hipMemcpyHostToDevice, c->stream));
+  if ((rc = eq_evals_locked(c, tau.data(), s.nx, &eq))) return rc;
+  T.keep(eq);
+  if ((rc = T.alloc(2 * m->nv, "r1cs table", &z))) return rc;
+  if (num_inputs) {                                                 // (canonical bytes, not table entries: k_r1cs_build_z converts them)
+    if ((rc = T.alloc(num_inputs, "r1cs proof inputs", &in))) return rc;
+    HIPCHK(c, hipMemcpyAsync(in->d, input, num_inputs * 32, hipMemcpyHostToDevice, c->stream));
   }
-  LAUNCH(c, "k_r1cs_build_z", k_r1cs_build_z, stream_grid(2 * m->nv), 256, (const uint32_t*)vars->d, (const uint32_t*)T.d_in, m->nv, num_inputs, (uint32_t*)T.z->d);
+  LAUNCH(c, "k_r1cs_build_z", k_r1cs_build_z, stream_grid(2 * m->nv), 256, (const uint32_t*)vars->d, (const uint32_t*)(in ? in->d : nullptr), m->nv, num_inputs, (uint32_t*)z->d);
   LAUNCHCHK(c);
-  if ((rc = r1cs_multiply_locked(c, m, T.z, &T.Az, &T.Bz, &T.Cz))) return rc;
+  if ((rc = r1cs_multiply_locked(c, m, z, &Az, &Bz, &Cz))) return rc;
+  T.keep(Az); T.keep(Bz); T.keep(Cz);
   uint8_t fin1[128], blind_post1[32], zero32[32] = {0};
   {
-    sbn_table* tabs[4] = {T.eq, T.Az, T.Bz, T.Cz};
+    sbn_table* tabs[4] = {eq, Az, Bz, Cz};
     if ((rc = zk_prove_locked<KIND_R1CS>(c, tabs, gens_1, gens_4, s.nx, zero32, zero32, rnd_sc1, t, o_sc1, out_rx, fin1, blind_post1))) return rc;
   }
   if ((rc = zk_ext(c, gens_1, gens_4, &ext))) return rc;           // phase 1 built it
@@ -216,18 +200,20 @@ static int r1cs_proof_locked(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* var
   polyeval_challenge(t, "challenge_Az", rA); polyeval_challenge(t, "challenge_Bz", rB); polyeval_challenge(t, "challenge_Cz", rC);
   const El claim2 = add(add(fmul(el_from(rA), Az_c), fmul(el_from(rB), Bz_c)), fmul(el_from(rC), Cz_c));              // :373
   const El blind2 = add(add(fmul(el_from(rA), Az_b), fmul(el_from(rB), Bz_b)), fmul(el_from(rC), Cz_b));              // :374
-  if ((rc = r1cs_eval_table_locked(c, m, out_rx, s.nx, rA, rB, rC, &T.abc))) return rc;
+  if ((rc = r1cs_eval_table_locked(c, m, out_rx, s.nx, rA, rB, rC, &abc))) return rc;
+  T.keep(abc);
   uint8_t fin2[64], blind_post2[32];
   {
-    sbn_table* tabs[2] = {T.z, T.abc};
+    sbn_table* tabs[2] = {z, abc};
     uint8_t c2[32], b2[32]; put(c2, claim2); put(b2, blind2);
     if ((rc = zk_prove_locked<KIND_QUAD>(c, tabs, gens_1, gens_3, s.ny, c2, b2, rnd_sc2, t, o_sc2, out_ry, fin2, blind_post2))) return rc;
   }
 
   // ---- 6. vars(ry[1..]) and its opening (r1csproof.rs:409-420) ----
   uint8_t eval_vars[32];
-  if ((rc = eq_evals_locked(c, out_ry + 32, s.ell, &T.chi))) return rc;
-  if ((rc = table_dot_locked(c, (const uint32_t*)vars->d, (const uint32_t*)T.chi->d, vars->len, eval_vars))) return rc;
+  if ((rc = eq_evals_locked(c, out_ry + 32, s.ell, &chi))) return rc;
+  T.keep(chi);
+  if ((rc = table_dot_locked(c, (const uint32_t*)vars->d, (const uint32_t*)chi->d, vars->len, eval_vars))) return rc;
   {
     uint8_t cx[64], cy[64]; int xi = 0, yi = 0;
     if ((rc = polyeval_prove_locked(c, gens_pc, vars, poly_blinds, out_ry + 32, s.ell, eval_vars, blind_eval, rnd_open, t, o_open, cx, &xi, cy, &yi))) return rc;
@@ -249,7 +235,7 @@ static int r1cs_proof_locked(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* var
     memcpy(o_eq2, P + 64, 32); put(o_eq2 + 32, add(fmul(el_from(cb), sub(blind_expected, el_from(blind_post2))), r2));
   }
   if (c->prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); prof_drain(c); }
-  return SBN_OK;
+  return T.done();
 }
 
 extern "C" {
@@ -280,12 +266,7 @@ int sbn_r1cs_proof_prove(sbn_ctx* c, const sbn_r1cs* inst, const sbn_table* vars
   for (size_t i = 0; i < num_inputs; i++) if (!fr_canonical(input + 32 * i)) return fail(c, SBN_EINVAL, "r1cs proof: input[%zu] is not canonical  [scalar.rs:87-95]", i);
   for (size_t i = 0; i < s.rnd_scalars; i++) if (!fr_canonical(rnd + 32 * i)) return fail(c, SBN_EINVAL, "r1cs proof: rnd[%zu] is not canonical  [scalar.rs:87-95]", i);
   sbn_host::MerlinTranscript t = tr->t;
-  int rc;
-  {
-    R1csProofTabs T(c);
-    rc = r1cs_proof_locked(c, inst, vars, input, num_inputs, gens_pc, gens_3, gens_4, s, rnd, t, out_proof, out_rx, out_ry, T);
-    T.ok = rc == SBN_OK;
-  }
+  const int rc = r1cs_proof_locked(c, inst, vars, input, num_inputs, gens_pc, gens_3, gens_4, s, rnd, t, out_proof, out_rx, out_ry);
   if (rc) return rc;
   tr->t = t;
   return SBN_OK;

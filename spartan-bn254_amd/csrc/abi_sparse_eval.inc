@@ -50,26 +50,6 @@ static bool sparse_eval_shape(size_t nx, size_t ny, size_t N, size_t batch, Spar
   return true;
 }
 
-// every intermediate of one call — the two eq tables, the derefs table, the 4 batch + 4 hashed sets and their layers: back to the pool on every
-// path, behind a stream synchronisation when the call failed.  Views (slices of derefs, comb_ops, comb_mem) own nothing.
-struct SparseEvalTabs {
-  sbn_ctx* c; bool ok = false;
-  std::vector<sbn_table*> owned;
-  std::vector<std::unique_ptr<sbn_table>> views;
-  explicit SparseEvalTabs(sbn_ctx* c_) : c(c_) {}
-  sbn_table* keep(sbn_table* t) { if (t) owned.push_back(t); return t; }
-  const sbn_table* view(const sbn_table* t, size_t first, size_t len) {
-    views.emplace_back(new sbn_table());
-    sbn_table* v = views.back().get();
-    v->d = (uint8_t*)t->d + first * 32; v->len = v->cap = len; v->owned = false;
-    return v;
-  }
-  ~SparseEvalTabs() {
-    if (!ok) hipStreamSynchronize(c->stream);                      // nothing of this call stays queued behind a failure
-    for (sbn_table*& t : owned) r1cs_proof_drop(c, t);
-  }
-};
-
 static void sparse_eval_scalar(sbn_host::MerlinTranscript& t, const char* label, const uint8_t* s) { t.append_message((const uint8_t*)label, strlen(label), s, 32); }
 
 // DensePolynomial::commit of a device table with no blinds (hyrax.rs:283-308), as sbn_commit_table's launches; the caller holds the mutex
@@ -86,8 +66,11 @@ static int sparse_eval_commit(sbn_ctx* c, const sbn_bases* gn, const sbn_table* 
 // the proof on the transcript `t` (a copy of the caller's); arguments already checked.  srs != null: the KZG build (gens_derefs is null, key may be)
 static int sparse_eval_locked(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx, size_t nx, const uint8_t* ry, size_t ny, const uint8_t* evals,
                               const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_bases* gens_derefs, const sbn_bases* srs, const sbn_derefs_key* key,
-                              const SparseEvalShape& s, const uint8_t* rnd, sbn_host::MerlinTranscript& t, uint8_t* out_proof, SparseEvalTabs& T) {
+                              const SparseEvalShape& s, const uint8_t* rnd, sbn_host::MerlinTranscript& t, uint8_t* out_proof) {
   using namespace sbn_host::fr;
+  // every intermediate of the call: the two eq tables, the derefs table, the 4 batch + 4 hashed sets and their layers, and the views (slices of
+  // derefs, comb_ops, comb_mem), which own nothing
+  TableScope T(c);
   auto fmul = [](const El& a, const El& b) { return mmul(to_m(a), b); };
   int rc;
   const size_t b = s.batch, N = s.N;
@@ -322,6 +305,33 @@ static int sparse_eval_locked(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx
                                    (const uint8_t*)"joint_claim_eval_mem", 20, rand_mem.data(), L_mem, rnd_m, t, nullptr, jc, o_open_m, cx, &xi, cy, &yi))) return rc;
   }
   if (c->prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); prof_drain(c); }
+  return T.done();
+}
+
+// the shape, generator and canonicity checks of both builds, under the build's name `pfx`.  srs != null: the KZG build (gens_derefs is null, key may be)
+static int sparse_eval_check(sbn_ctx* c, const char* pfx, const sbn_dense* dn, const uint8_t* rx, size_t nx, const uint8_t* ry, size_t ny, const uint8_t* evals,
+                             const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_bases* gens_derefs, const sbn_bases* srs, const sbn_derefs_key* key,
+                             const uint8_t* rnd, SparseEvalShape* sp) {
+  SparseEvalShape& s = *sp;
+  if (dn->batch > (size_t)SE_BATCH_MAX) return fail(c, SBN_EINVAL, "%s: batch = %zu: proof_ops would hold %zu instances, at most %d fit one product proof", pfx, dn->batch, 6 * dn->batch, SC_PACK_MAX);
+  if (dn->N < 2) return fail(c, SBN_EINVAL, "%s: N = %zu: the dot-product circuits cannot be split  [product_tree.rs:89 assert_eq]", pfx, dn->N);
+  if (nx > 31 || ny > 31 || ((size_t)1 << std::max(nx, ny)) != dn->cells)
+    return fail(c, SBN_EINVAL, "%s: rx has %zu and ry %zu variables, the memories have %zu cells  [sparse_mlpoly_full.rs:226 assert, hyrax.rs:218 assert_eq]", pfx, nx, ny, dn->cells);
+  if (!sparse_eval_shape(nx, ny, dn->N, dn->batch, &s)) return fail(c, SBN_EINVAL, "%s: shape (%zu, %zu, N = %zu, batch = %zu) is outside what the openings take", pfx, nx, ny, dn->N, dn->batch);
+  const struct { const sbn_bases* g; size_t lg; const char* name; } gs[3] = {{gens_ops, s.lg_o, "gens_ops"}, {gens_mem, s.lg_m, "gens_mem"}, {gens_derefs, s.lg_d, "gens_derefs"}};
+  for (const auto& x : gs)
+    if (x.g && (x.g->n != ((size_t)1 << x.lg) + 1 || !x.g->has_h))
+      return fail(c, SBN_EINVAL, "%s: %s has %zu points%s, the opening needs %zu + 1 with h  [nizk/mod.rs:412-415, :455]", pfx, x.name, x.g->n, x.g->has_h ? "" : " and no h", (size_t)1 << x.lg);
+  if (srs) {
+    if (srs->has_h) return fail(c, SBN_EINVAL, "%s: the SRS handle has an h; an SRS is sbn_kzg_srs_upload's or sbn_kzg_srs_from_tau's", pfx);
+    if (srs->n < s.n_d - 1)
+      return fail(c, SBN_EINVAL, "%s: the derefs quotient has %zu coefficients, the SRS %zu points  [kzg.rs:186 slices past its end]", pfx, s.n_d - 1, srs->n);
+    if (key && (key->dense != dn || key->srs != srs || key->srs_n != srs->n || key->batch != dn->batch || key->N != dn->N || key->cells != dn->cells))
+      return fail(c, SBN_EINVAL, "%s: the derefs key was built for another dense handle or another SRS", pfx);
+  }
+  const struct { const uint8_t* p; size_t n; const char* name; } sc[4] = {{rx, nx, "rx"}, {ry, ny, "ry"}, {evals, s.batch, "evals"}, {rnd, srs ? s.rnd_scalars_kzg : s.rnd_scalars, "rnd"}};
+  for (const auto& x : sc)
+    for (size_t i = 0; i < x.n; i++) if (!fr_canonical(x.p + 32 * i)) return fail(c, SBN_EINVAL, "%s: %s[%zu] is not canonical  [scalar.rs:87-95]", pfx, x.name, i);
   return SBN_OK;
 }
 
@@ -340,28 +350,11 @@ int sbn_sparse_eval_prove(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx, si
   if (!c || !dn || (!rx && nx) || (!ry && ny) || !evals || !gens_ops || !gens_mem || !gens_derefs || !rnd || !tr || !out_proof) return SBN_EINVAL;
   std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
   SparseEvalShape s;
-  if (dn->batch > (size_t)SE_BATCH_MAX) return fail(c, SBN_EINVAL, "sparse eval: batch = %zu: proof_ops would hold %zu instances, at most %d fit one product proof", dn->batch, 6 * dn->batch, SC_PACK_MAX);
-  if (dn->N < 2) return fail(c, SBN_EINVAL, "sparse eval: N = %zu: the dot-product circuits cannot be split  [product_tree.rs:89 assert_eq]", dn->N);
-  if (nx > 31 || ny > 31 || ((size_t)1 << std::max(nx, ny)) != dn->cells)
-    return fail(c, SBN_EINVAL, "sparse eval: rx has %zu and ry %zu variables, the memories have %zu cells  [sparse_mlpoly_full.rs:226 assert, hyrax.rs:218 assert_eq]", nx, ny, dn->cells);
-  if (!sparse_eval_shape(nx, ny, dn->N, dn->batch, &s)) return fail(c, SBN_EINVAL, "sparse eval: shape (%zu, %zu, N = %zu, batch = %zu) is outside what the openings take", nx, ny, dn->N, dn->batch);
-  const struct { const sbn_bases* g; size_t lg; const char* name; } gs[3] = {{gens_ops, s.lg_o, "gens_ops"}, {gens_mem, s.lg_m, "gens_mem"}, {gens_derefs, s.lg_d, "gens_derefs"}};
-  for (const auto& x : gs)
-    if (x.g->n != ((size_t)1 << x.lg) + 1 || !x.g->has_h)
-      return fail(c, SBN_EINVAL, "sparse eval: %s has %zu points%s, the opening needs %zu + 1 with h  [nizk/mod.rs:412-415, :455]", x.name, x.g->n, x.g->has_h ? "" : " and no h", (size_t)1 << x.lg);
-  for (size_t i = 0; i < nx; i++) if (!fr_canonical(rx + 32 * i)) return fail(c, SBN_EINVAL, "sparse eval: rx[%zu] is not canonical  [scalar.rs:87-95]", i);
-  for (size_t i = 0; i < ny; i++) if (!fr_canonical(ry + 32 * i)) return fail(c, SBN_EINVAL, "sparse eval: ry[%zu] is not canonical  [scalar.rs:87-95]", i);
-  for (size_t i = 0; i < s.batch; i++) if (!fr_canonical(evals + 32 * i)) return fail(c, SBN_EINVAL, "sparse eval: evals[%zu] is not canonical  [scalar.rs:87-95]", i);
-  for (size_t i = 0; i < s.rnd_scalars; i++) if (!fr_canonical(rnd + 32 * i)) return fail(c, SBN_EINVAL, "sparse eval: rnd[%zu] is not canonical  [scalar.rs:87-95]", i);
+  int rc;
+  if ((rc = sparse_eval_check(c, "sparse eval", dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, gens_derefs, nullptr, nullptr, rnd, &s))) return rc;
   sbn_host::MerlinTranscript t = tr->t;
   std::vector<uint8_t> proof(s.proof_bytes);                       // the caller's buffer is written only by a call that succeeded
-  int rc;
-  {
-    SparseEvalTabs T(c);
-    rc = sparse_eval_locked(c, dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, gens_derefs, nullptr, nullptr, s, rnd, t, proof.data(), T);
-    T.ok = rc == SBN_OK;
-  }
-  if (rc) return rc;
+  if ((rc = sparse_eval_locked(c, dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, gens_derefs, nullptr, nullptr, s, rnd, t, proof.data()))) return rc;
   memcpy(out_proof, proof.data(), s.proof_bytes);
   tr->t = t;
   return SBN_OK;
@@ -381,33 +374,11 @@ int sbn_sparse_eval_prove_kzg(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx
   if (!c || !dn || (!rx && nx) || (!ry && ny) || !evals || !gens_ops || !gens_mem || !srs || !rnd || !tr || !out_proof) return SBN_EINVAL;
   std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
   SparseEvalShape s;
-  if (dn->batch > (size_t)SE_BATCH_MAX) return fail(c, SBN_EINVAL, "sparse eval (KZG): batch = %zu: proof_ops would hold %zu instances, at most %d fit one product proof", dn->batch, 6 * dn->batch, SC_PACK_MAX);
-  if (dn->N < 2) return fail(c, SBN_EINVAL, "sparse eval (KZG): N = %zu: the dot-product circuits cannot be split  [product_tree.rs:89 assert_eq]", dn->N);
-  if (nx > 31 || ny > 31 || ((size_t)1 << std::max(nx, ny)) != dn->cells)
-    return fail(c, SBN_EINVAL, "sparse eval (KZG): rx has %zu and ry %zu variables, the memories have %zu cells  [sparse_mlpoly_full.rs:226 assert, hyrax.rs:218 assert_eq]", nx, ny, dn->cells);
-  if (!sparse_eval_shape(nx, ny, dn->N, dn->batch, &s)) return fail(c, SBN_EINVAL, "sparse eval (KZG): shape (%zu, %zu, N = %zu, batch = %zu) is outside what the openings take", nx, ny, dn->N, dn->batch);
-  const struct { const sbn_bases* g; size_t lg; const char* name; } gs[2] = {{gens_ops, s.lg_o, "gens_ops"}, {gens_mem, s.lg_m, "gens_mem"}};
-  for (const auto& x : gs)
-    if (x.g->n != ((size_t)1 << x.lg) + 1 || !x.g->has_h)
-      return fail(c, SBN_EINVAL, "sparse eval (KZG): %s has %zu points%s, the opening needs %zu + 1 with h  [nizk/mod.rs:412-415, :455]", x.name, x.g->n, x.g->has_h ? "" : " and no h", (size_t)1 << x.lg);
-  if (srs->has_h) return fail(c, SBN_EINVAL, "sparse eval (KZG): the SRS handle has an h; an SRS is sbn_kzg_srs_upload's or sbn_kzg_srs_from_tau's");
-  if (srs->n < s.n_d - 1)
-    return fail(c, SBN_EINVAL, "sparse eval (KZG): the derefs quotient has %zu coefficients, the SRS %zu points  [kzg.rs:186 slices past its end]", s.n_d - 1, srs->n);
-  if (key && (key->dense != dn || key->srs != srs || key->srs_n != srs->n || key->batch != dn->batch || key->N != dn->N || key->cells != dn->cells))
-    return fail(c, SBN_EINVAL, "sparse eval (KZG): the derefs key was built for another dense handle or another SRS");
-  for (size_t i = 0; i < nx; i++) if (!fr_canonical(rx + 32 * i)) return fail(c, SBN_EINVAL, "sparse eval (KZG): rx[%zu] is not canonical  [scalar.rs:87-95]", i);
-  for (size_t i = 0; i < ny; i++) if (!fr_canonical(ry + 32 * i)) return fail(c, SBN_EINVAL, "sparse eval (KZG): ry[%zu] is not canonical  [scalar.rs:87-95]", i);
-  for (size_t i = 0; i < s.batch; i++) if (!fr_canonical(evals + 32 * i)) return fail(c, SBN_EINVAL, "sparse eval (KZG): evals[%zu] is not canonical  [scalar.rs:87-95]", i);
-  for (size_t i = 0; i < s.rnd_scalars_kzg; i++) if (!fr_canonical(rnd + 32 * i)) return fail(c, SBN_EINVAL, "sparse eval (KZG): rnd[%zu] is not canonical  [scalar.rs:87-95]", i);
+  int rc;
+  if ((rc = sparse_eval_check(c, "sparse eval (KZG)", dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, nullptr, srs, key, rnd, &s))) return rc;
   sbn_host::MerlinTranscript t = tr->t;
   std::vector<uint8_t> proof(s.proof_bytes_kzg);                   // the caller's buffer is written only by a call that succeeded
-  int rc;
-  {
-    SparseEvalTabs T(c);
-    rc = sparse_eval_locked(c, dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, nullptr, srs, key, s, rnd, t, proof.data(), T);
-    T.ok = rc == SBN_OK;
-  }
-  if (rc) return rc;
+  if ((rc = sparse_eval_locked(c, dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, nullptr, srs, key, s, rnd, t, proof.data()))) return rc;
   memcpy(out_proof, proof.data(), s.proof_bytes_kzg);
   tr->t = t;
   return SBN_OK;

@@ -214,7 +214,7 @@ void sbn_sumcheck_free(sbn_ctx* c, sbn_sumcheck* st) {
   std::unique_lock<std::mutex> g;
   if (c) { g = std::unique_lock<std::mutex>(c->mu); hipSetDevice(c->device); }
   if (st->slab) pool_put(c, st->slab, st->slab_bytes);                 // recycled in stream order (see sbn_table_free)
-  if (st->owned_c) { if (st->owned_c->d && st->owned_c->owned) pool_put(c, st->owned_c->d, st->owned_c->cap * 32); delete st->owned_c; }
+  table_release(c, st->owned_c);
   delete st;
 }
 size_t sbn_sumcheck_len(const sbn_sumcheck* st) { return st ? st->len : 0; }
@@ -224,7 +224,7 @@ size_t sbn_sumcheck_len(const sbn_sumcheck* st) { return st ? st->len : 0; }
 static int sumcheck_begin_locked(sbn_ctx* c, const sbn_table* const* A_par, const sbn_table* const* B_par, const sbn_table* C_par, size_t n_par,
                                  const sbn_table* const* A_seq, const sbn_table* const* B_seq, const sbn_table* const* C_seq, size_t n_seq,
                                  const uint8_t* coeffs, uint8_t out_evals[96], sbn_sumcheck** out, sbn_table* owned_c) {
-  struct OwnedC { sbn_ctx* c; sbn_table* t; ~OwnedC() { if (t) { if (t->d && t->owned) pool_put(c, t->d, t->cap * 32); delete t; } } } own{c, owned_c};
+  TableScope own(c); own.keep(owned_c);
   const size_t ninst = n_par + n_seq;
   if (ninst > (size_t)SC_PACK_MAX) return fail(c, SBN_EINVAL, "sumcheck: %zu instances (at most %d)", ninst, SC_PACK_MAX);
   if (!n_par && !C_seq[0]) return SBN_EINVAL;
@@ -353,9 +353,9 @@ static int sumcheck_begin_locked(sbn_ctx* c, const sbn_table* const* A_par, cons
   sc_combine_host(st.get(), (const uint8_t*)c->mbox, inst_ids, n_comb, out_evals);
   memcpy(st->evals0, out_evals, 96);
   slab_guard.armed = false;
-  st->owned_c = own.t; own.t = nullptr;
+  if (owned_c) st->owned_c = own.give(owned_c);
   *out = st.release();
-  return SBN_OK;
+  return own.done();
 }
 // ---- one round's launches, shared by sbn_sumcheck_round (challenge in the kernel arguments, sums to the host mailbox) and
 // sbn_sumcheck_prove (challenge in device memory, sums to the mailbox's device twin): the same kernels, grids and order ----

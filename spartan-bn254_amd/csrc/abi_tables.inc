@@ -2,6 +2,15 @@
 // ---- tables + sumcheck rounds ----
 static inline sbn_host::fr::El el_from(const uint8_t b[32]) { sbn_host::fr::El e; memcpy(e.v, b, 32); return e; }
 static inline ScScalar scs_from(const sbn_host::fr::El& e) { ScScalar s; memcpy(s.v, e.v, 32); return s; }
+// the three constants of a hash layer on the host (a lone GPU lane took 11 us for them, once per call): g R, g^2 R^2 (one Montgomery product with
+// the plain integer ts gives ts g^2 R), (r - tau) R — canonical, passed as kernel arguments
+struct HashConsts { ScScalar gs, g2s, nts; };
+static HashConsts hash_consts(const uint8_t r_hash[32], const uint8_t r_multiset[32]) {
+  using namespace sbn_host::fr;
+  const El g = el_from(r_hash), tau = el_from(r_multiset), zero = {{0, 0, 0, 0}};
+  return {scs_from(to_dev_mont(g)), scs_from(to_dev_mont(to_dev_mont(mmul(to_m(g), g)))), scs_from(to_dev_mont(sub(zero, tau)))};
+}
+static int eq_evals_locked(sbn_ctx* c, const uint8_t* r, size_t ell, sbn_table** out);
 extern "C" {
 static unsigned stream_grid(size_t work_items) {
   size_t blocks = (work_items + 255) / 256;
@@ -11,16 +20,15 @@ static unsigned stream_grid(size_t work_items) {
 }
 static int table_make(sbn_ctx* c, const void* src, bool src_is_host, size_t len, uint32_t flags, sbn_table** out) {
   if (len == 0 || (len & (len - 1))) return fail(c, SBN_EINVAL, "table length %zu is not a power of two", len);
-  sbn_table* t = new sbn_table(); t->len = len; t->cap = len;
-  size_t _gb = 0; hipError_t e = pool_get(c, (len) * 32, &t->d, &_gb); t->cap = _gb / 32;
-  if (e != hipSuccess) { delete t; return fail(c, SBN_ENOMEM, "hipMalloc table: %s", hipGetErrorString(e)); }
+  TableScope S(c); sbn_table* t; int rc;
+  if ((rc = S.alloc(len, "table", &t))) return rc;
   HIPCHK(c, hipMemcpyAsync(t->d, src, len * 32, src_is_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
   if (!(flags & SBN_SCALARS_MONT)) LAUNCH(c, "k_fr_to_mont", k_fr_to_mont, stream_grid(len), 256, (const uint32_t*)t->d, (uint32_t*)t->d, len);
   else LAUNCH(c, "k_fr_to_mont", k_fr_from_ark, stream_grid(len), 256, (const uint32_t*)t->d, (uint32_t*)t->d, len);      // ark-ff's R = 2^256 -> R = 2^261
   LAUNCHCHK(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  *out = t;
-  return SBN_OK;
+  *out = S.give(t);
+  return S.done();
 }
 int sbn_table_upload(sbn_ctx* c, const uint8_t* Z, size_t len, uint32_t flags, sbn_table** out) {
   if (!c || !Z || !out) return SBN_EINVAL;
@@ -38,9 +46,7 @@ void sbn_table_free(sbn_ctx* c, sbn_table* t) {
   if (!t) return;
   std::unique_lock<std::mutex> g;
   if (c) { g = std::unique_lock<std::mutex>(c->mu); hipSetDevice(c->device); }
-  if (t->d && t->owned) pool_put(c, t->d, t->cap * 32);
-  if (t->d2 && t->owned2) pool_put(c, t->d2, t->cap2 * 32);
-  delete t;
+  table_release(c, t);
 }
 size_t sbn_table_len(const sbn_table* t) { return t ? t->len : 0; }
 int sbn_table_download(sbn_ctx* c, const sbn_table* t, uint8_t* out) {
@@ -360,80 +366,47 @@ int sbn_hash_layer(sbn_ctx* c, const void* addr_dev, const sbn_table* val, const
   if (!fr_canonical(r_hash) || !fr_canonical(r_multiset)) return fail(c, SBN_EINVAL, "hash layer: challenges not canonical");
   std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
   const size_t n = val->len;
-  // the three constants of the layer on the host (a lone GPU lane took 11 us for them, once per call): g R, g^2 R^2 (one Montgomery product with
-  // the plain integer ts gives ts g^2 R), (r - tau) R — canonical, passed as kernel arguments
-  ScScalar gs, g2s, nts;
-  {
-    using namespace sbn_host::fr;
-    const El g = el_from(r_hash), tau = el_from(r_multiset), zero = {{0, 0, 0, 0}};
-    gs = scs_from(to_dev_mont(g)); g2s = scs_from(to_dev_mont(to_dev_mont(mmul(to_m(g), g)))); nts = scs_from(to_dev_mont(sub(zero, tau)));
-  }
-  sbn_table* t = new sbn_table(); t->len = n; t->cap = n;
-  size_t _gb = 0; hipError_t e = pool_get(c, (n) * 32, &t->d, &_gb); t->cap = _gb / 32;
-  if (e != hipSuccess) { delete t; return fail(c, SBN_ENOMEM, "hipMalloc hash layer: %s", hipGetErrorString(e)); }
-  LAUNCH(c, "k_hash_layer", k_hash_layer, stream_grid(n), 256, (const uint32_t*)addr_dev, (const uint32_t*)val->d, (const uint32_t*)ts_dev, ts_add, gs, g2s, nts, n, (uint32_t*)t->d);
+  const HashConsts k = hash_consts(r_hash, r_multiset);
+  TableScope S(c); sbn_table* t; int rc;
+  if ((rc = S.alloc(n, "hash layer", &t))) return rc;
+  LAUNCH(c, "k_hash_layer", k_hash_layer, stream_grid(n), 256, (const uint32_t*)addr_dev, (const uint32_t*)val->d, (const uint32_t*)ts_dev, ts_add, k.gs, k.g2s, k.nts, n, (uint32_t*)t->d);
   LAUNCHCHK(c);                              // asynchronous: the table is consumed by later calls on the same stream
   if (c->prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); prof_drain(c); }
-  *out = t;
-  return SBN_OK;
+  *out = S.give(t);
+  return S.done();
 }
 }  // extern "C"
 // (the caller holds the context's mutex and has checked the arguments)
 static int hash_layer_pair_locked(sbn_ctx* c, const void* addr_dev, const sbn_table* val, const void* ts_a_dev, uint32_t ts_a_add, const void* ts_b_dev, uint32_t ts_b_add,
                                   const uint8_t r_hash[32], const uint8_t r_multiset[32], sbn_table** out_a, sbn_table** out_b) {
   const size_t n = val->len;
-  ScScalar gs, g2s, nts;
-  {
-    using namespace sbn_host::fr;
-    const El g = el_from(r_hash), tau = el_from(r_multiset), zero = {{0, 0, 0, 0}};
-    gs = scs_from(to_dev_mont(g)); g2s = scs_from(to_dev_mont(to_dev_mont(mmul(to_m(g), g)))); nts = scs_from(to_dev_mont(sub(zero, tau)));
-  }
-  sbn_table* t[2] = {nullptr, nullptr};
-  for (int k = 0; k < 2; k++) {
-    t[k] = new sbn_table(); t[k]->len = n; t[k]->cap = n;
-    size_t gb = 0; hipError_t e = pool_get(c, n * 32, &t[k]->d, &gb); t[k]->cap = gb / 32;
-    if (e != hipSuccess) { delete t[k]; if (k) { pool_put(c, t[0]->d, t[0]->cap * 32); delete t[0]; } return fail(c, SBN_ENOMEM, "hipMalloc hash layer: %s", hipGetErrorString(e)); }
-  }
+  const HashConsts hc = hash_consts(r_hash, r_multiset);
+  TableScope S(c); sbn_table* t[2]; int rc;
+  for (int k = 0; k < 2; k++) if ((rc = S.alloc(n, "hash layer", &t[k]))) return rc;
   LAUNCH(c, "k_hash_layer", k_hash_layer_pair, stream_grid(n), 256, (const uint32_t*)addr_dev, (const uint32_t*)val->d, (const uint32_t*)ts_a_dev, ts_a_add, (const uint32_t*)ts_b_dev, ts_b_add,
-         gs, g2s, nts, n, (uint32_t*)t[0]->d, (uint32_t*)t[1]->d);
+         hc.gs, hc.g2s, hc.nts, n, (uint32_t*)t[0]->d, (uint32_t*)t[1]->d);
   LAUNCHCHK(c);                              // asynchronous, as sbn_hash_layer
   if (c->prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); prof_drain(c); }
   *out_a = t[0]; *out_b = t[1];
-  return SBN_OK;
+  S.give_all();
+  return S.done();
 }
 // the pair and the first layer of both product circuits in one pass (k_hash_pair_prod); n = val->len is a power of two >= 2; the caller holds
 // the context's mutex and has checked the arguments
 static int hash_layer_pair_product_locked(sbn_ctx* c, const void* addr_dev, const sbn_table* val, const void* ts_a_dev, uint32_t ts_a_add, const void* ts_b_dev, uint32_t ts_b_add,
                                           const uint8_t r_hash[32], const uint8_t r_multiset[32], sbn_table** out_a, sbn_table** out_b, sbn_table** prod_a, sbn_table** prod_b) {
   const size_t n = val->len, half = n / 2;
-  ScScalar gs, g2s, nts;
-  {
-    using namespace sbn_host::fr;
-    const El g = el_from(r_hash), tau = el_from(r_multiset), zero = {{0, 0, 0, 0}};
-    gs = scs_from(to_dev_mont(g)); g2s = scs_from(to_dev_mont(to_dev_mont(mmul(to_m(g), g)))); nts = scs_from(to_dev_mont(sub(zero, tau)));
-  }
-  sbn_table* t[4] = {nullptr, nullptr, nullptr, nullptr};           // out_a, out_b (n entries), prod_a, prod_b (n / 2)
-  for (int k = 0; k < 4; k++) {
-    const size_t len = k < 2 ? n : half;
-    t[k] = new sbn_table(); t[k]->len = len; t[k]->cap = len;
-    size_t gb = 0; hipError_t e = pool_get(c, len * 32, &t[k]->d, &gb); t[k]->cap = gb / 32;
-    if (e != hipSuccess) {
-      delete t[k];
-      for (int j = 0; j < k; j++) { pool_put(c, t[j]->d, t[j]->cap * 32); delete t[j]; }
-      return fail(c, SBN_ENOMEM, "hipMalloc hash layer: %s", hipGetErrorString(e));
-    }
-  }
+  const HashConsts hc = hash_consts(r_hash, r_multiset);
+  TableScope S(c); sbn_table* t[4]; int rc;                         // out_a, out_b (n entries), prod_a, prod_b (n / 2)
+  for (int k = 0; k < 4; k++) if ((rc = S.alloc(k < 2 ? n : half, "hash layer", &t[k]))) return rc;
   LAUNCH(c, "k_hash_pair_prod", k_hash_pair_prod, stream_grid(half), 256, (const uint32_t*)addr_dev, (const uint32_t*)val->d, (const uint32_t*)ts_a_dev, ts_a_add, (const uint32_t*)ts_b_dev, ts_b_add,
-         gs, g2s, nts, half, (uint32_t*)t[0]->d, (uint32_t*)t[1]->d, (uint32_t*)t[2]->d, (uint32_t*)t[3]->d);
+         hc.gs, hc.g2s, hc.nts, half, (uint32_t*)t[0]->d, (uint32_t*)t[1]->d, (uint32_t*)t[2]->d, (uint32_t*)t[3]->d);
   hipError_t le = hipGetLastError();          // asynchronous, as sbn_hash_layer
   if (le == hipSuccess && c->prof) { le = hipStreamSynchronize(c->stream); prof_drain(c); }
-  if (le != hipSuccess) {                     // the tables were not handed out: back to the pool, behind whatever is still queued
-    hipStreamSynchronize(c->stream);
-    for (int k = 0; k < 4; k++) { pool_put(c, t[k]->d, t[k]->cap * 32); delete t[k]; }
-    return fail(c, SBN_EHIP, "hash layer pair + product: %s", hipGetErrorString(le));
-  }
+  if (le != hipSuccess) return fail(c, SBN_EHIP, "hash layer pair + product: %s", hipGetErrorString(le));
   *out_a = t[0]; *out_b = t[1]; *prod_a = t[2]; *prod_b = t[3];
-  return SBN_OK;
+  S.give_all();
+  return S.done();
 }
 extern "C" {
 int sbn_hash_layer_pair_product(sbn_ctx* c, const void* addr_dev, const sbn_table* val, const void* ts_a_dev, uint32_t ts_a_add, const void* ts_b_dev, uint32_t ts_b_add,
@@ -456,14 +429,13 @@ int sbn_product_layer(sbn_ctx* c, const sbn_table* in, sbn_table** out) {
   if (in->len < 2) return fail(c, SBN_EINVAL, "product layer: nothing left to multiply");
   std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
   const size_t half = in->len / 2;
-  sbn_table* t = new sbn_table(); t->len = half; t->cap = half;
-  size_t _gb = 0; hipError_t e = pool_get(c, (half) * 32, &t->d, &_gb); t->cap = _gb / 32;
-  if (e != hipSuccess) { delete t; return fail(c, SBN_ENOMEM, "hipMalloc product layer: %s", hipGetErrorString(e)); }
+  TableScope S(c); sbn_table* t; int rc;
+  if ((rc = S.alloc(half, "product layer", &t))) return rc;
   LAUNCH(c, "k_product_layer", k_product_layer, stream_grid(half), 256, (const uint32_t*)in->d, half, (uint32_t*)t->d);
   LAUNCHCHK(c);                              // asynchronous, as sbn_hash_layer
   if (c->prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); prof_drain(c); }
-  *out = t;
-  return SBN_OK;
+  *out = S.give(t);
+  return S.done();
 }
 int sbn_product_circuit(sbn_ctx* c, const sbn_table* in, sbn_table** layers, size_t cap, size_t* count) {
   if (!c || !in || !layers || !count) return SBN_EINVAL;
@@ -472,80 +444,62 @@ int sbn_product_circuit(sbn_ctx* c, const sbn_table* in, sbn_table** layers, siz
   if (cap < need) return fail(c, SBN_EINVAL, "product circuit: %zu layers do not fit the caller's array of %zu", need, cap);
   std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
   const uint32_t* src = (const uint32_t*)in->d;
-  size_t made = 0;
-  for (size_t half = in->len / 2; half >= 1; half >>= 1) {            // the tables first (so that a failed allocation leaves nothing enqueued)
-    sbn_table* t = new sbn_table(); t->len = half;
-    size_t gb = 0; hipError_t e = pool_get(c, half * 32, &t->d, &gb); t->cap = gb / 32;
-    if (e != hipSuccess) {
-      delete t;
-      for (size_t i = 0; i < made; i++) { pool_put(c, layers[i]->d, layers[i]->cap * 32); delete layers[i]; layers[i] = nullptr; }
-      return fail(c, SBN_ENOMEM, "hipMalloc product layer: %s", hipGetErrorString(e));
-    }
-    layers[made++] = t;
-    if (half == 1) break;
-  }
+  for (size_t k = 0; k < need; k++) layers[k] = nullptr;                // filled at the successful end only
+  TableScope S(c); sbn_table* t; int rc;
+  for (size_t k = 0; k < need; k++)                                     // the tables first (so that a failed allocation leaves nothing enqueued)
+    if ((rc = S.alloc(in->len >> (k + 1), "product layer", &t))) return rc;
+  const std::vector<sbn_table*>& made = S.held;
   size_t k = 0, len = in->len;
-  for (; k < made && len > 2048; k++, len >>= 1) {                      // large layers: one streaming launch each
-    LAUNCH(c, "k_product_layer", k_product_layer, stream_grid(len / 2), 256, src, len / 2, (uint32_t*)layers[k]->d);
-    src = (const uint32_t*)layers[k]->d;
+  for (; k < need && len > 2048; k++, len >>= 1) {                      // large layers: one streaming launch each
+    LAUNCH(c, "k_product_layer", k_product_layer, stream_grid(len / 2), 256, src, len / 2, (uint32_t*)made[k]->d);
+    src = (const uint32_t*)made[k]->d;
   }
-  if (k < made) {                                                       // the rest (<= 2048 entries) in one launch
+  if (k < need) {                                                       // the rest (<= 2048 entries) in one launch
     ProductTail pt; memset(&pt, 0, sizeof pt);
-    for (size_t j = k; j < made; j++) pt.out[j - k] = (uint32_t*)layers[j]->d;
+    for (size_t j = k; j < need; j++) pt.out[j - k] = (uint32_t*)made[j]->d;
     LAUNCH(c, "k_product_layer", k_product_tail, 1, 1024, src, len, pt);
   }
   LAUNCHCHK(c);                              // asynchronous, as sbn_product_layer
   if (c->prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); prof_drain(c); }
-  *count = made;
-  return SBN_OK;
+  for (size_t j = 0; j < need; j++) layers[j] = made[j];
+  S.give_all();
+  *count = need;
+  return S.done();
 }
 }  // extern "C"
 // (the caller holds the context's mutex and has checked the arguments: n tables of len0 = 2^need entries, need >= 1, cap >= need)
 static int product_circuit_many_locked(sbn_ctx* c, const sbn_table* const* ins, size_t n, sbn_table** layers, size_t cap, size_t len0, size_t need) {
-  // the tables first (so that a failed allocation leaves nothing enqueued); layers[i * cap + k]
-  std::vector<sbn_table*> made;
-  for (size_t i = 0; i < n; i++) {
-    size_t k = 0;
-    for (size_t half = len0 / 2; half >= 1; half >>= 1, k++) {
-      sbn_table* t = new sbn_table(); t->len = half;
-      size_t gb = 0; hipError_t e = pool_get(c, half * 32, &t->d, &gb); t->cap = gb / 32;
-      if (e != hipSuccess) {
-        delete t;
-        for (sbn_table* x : made) { pool_put(c, x->d, x->cap * 32); delete x; }
-        for (size_t a = 0; a < n * cap; a++) layers[a] = nullptr;
-        return fail(c, SBN_ENOMEM, "hipMalloc product layer: %s", hipGetErrorString(e));
-      }
-      layers[i * cap + k] = t; made.push_back(t);
-      if (half == 1) break;
-    }
-  }
+  // the tables first (so that a failed allocation leaves nothing enqueued): layer k of circuit i is made[i * need + k] until the successful end
+  // fills the caller's layers[i * cap + k]
+  for (size_t i = 0; i < n; i++) for (size_t k = 0; k < need; k++) layers[i * cap + k] = nullptr;
+  TableScope S(c); sbn_table* t; int rc;
+  for (size_t i = 0; i < n; i++)
+    for (size_t k = 0; k < need; k++) if ((rc = S.alloc(len0 >> (k + 1), "product layer", &t))) return rc;
+  const std::vector<sbn_table*>& made = S.held;
   for (size_t o = 0; o < n; o += PC_MANY_MAX) {
     const size_t m = std::min<size_t>(PC_MANY_MAX, n - o);
     size_t k = 0, len = len0;
     for (; k < need && len > 2048; k++, len >>= 1) {                    // large layers: one streaming launch each, all circuits
       ProductLayerPack pk; memset(&pk, 0, sizeof pk);
-      for (size_t i = 0; i < m; i++) { pk.in[i] = (const uint32_t*)(k ? layers[(o + i) * cap + k - 1]->d : ins[o + i]->d); pk.out[i] = (uint32_t*)layers[(o + i) * cap + k]->d; }
+      for (size_t i = 0; i < m; i++) { pk.in[i] = (const uint32_t*)(k ? made[(o + i) * need + k - 1]->d : ins[o + i]->d); pk.out[i] = (uint32_t*)made[(o + i) * need + k]->d; }
       unsigned gx = stream_grid(len / 2); gx = std::max(1u, gx / (unsigned)m);
       LAUNCH(c, "k_product_layer", k_product_layer_many, dim3(gx, (unsigned)m), 256, pk, len / 2);
     }
     if (k < need) {                                                     // the rest (<= 2048 entries): one block per circuit
       ProductTailPack pt; memset(&pt, 0, sizeof pt);
       for (size_t i = 0; i < m; i++) {
-        pt.in[i] = (const uint32_t*)(k ? layers[(o + i) * cap + k - 1]->d : ins[o + i]->d);
-        for (size_t j = k; j < need; j++) pt.out[i][j - k] = (uint32_t*)layers[(o + i) * cap + j]->d;
+        pt.in[i] = (const uint32_t*)(k ? made[(o + i) * need + k - 1]->d : ins[o + i]->d);
+        for (size_t j = k; j < need; j++) pt.out[i][j - k] = (uint32_t*)made[(o + i) * need + j]->d;
       }
       LAUNCH(c, "k_product_layer", k_product_tail_many, (unsigned)m, 1024, pt, len);
     }
   }
   hipError_t le = hipGetLastError();          // asynchronous, as sbn_product_layer
   if (le == hipSuccess && c->prof) { le = hipStreamSynchronize(c->stream); prof_drain(c); }
-  if (le != hipSuccess) {                     // nothing is handed out behind a failed launch: the layer tables go back to the pool
-    hipStreamSynchronize(c->stream);
-    for (sbn_table* x : made) { pool_put(c, x->d, x->cap * 32); delete x; }
-    for (size_t a = 0; a < n * cap; a++) layers[a] = nullptr;
-    return fail(c, SBN_EHIP, "product circuits: %s", hipGetErrorString(le));
-  }
-  return SBN_OK;
+  if (le != hipSuccess) return fail(c, SBN_EHIP, "product circuits: %s", hipGetErrorString(le));
+  for (size_t i = 0; i < n; i++) for (size_t k = 0; k < need; k++) layers[i * cap + k] = made[i * need + k];
+  S.give_all();
+  return S.done();
 }
 extern "C" {
 int sbn_product_circuit_many(sbn_ctx* c, const sbn_table* const* ins, size_t n, sbn_table** layers, size_t cap, size_t* count) {
@@ -565,10 +519,7 @@ int sbn_table_halves(sbn_ctx* c, const sbn_table* t, sbn_table** left, sbn_table
   if (!c || !t || !left || !right) return SBN_EINVAL;
   if (t->len < 2) return fail(c, SBN_EINVAL, "halves: table has one entry");
   const size_t half = t->len / 2;
-  sbn_table* l = new sbn_table(); sbn_table* r = new sbn_table();
-  l->d = t->d; l->len = l->cap = half; l->owned = false;
-  r->d = (uint8_t*)t->d + half * 32; r->len = r->cap = half; r->owned = false;
-  *left = l; *right = r;
+  *left = table_view(t, 0, half); *right = table_view(t, half, half);
   return SBN_OK;
 }
 // entries [first, first + len) of t as a view (len a power of two): the polynomials DensePolynomial::merge laid end to end (hyrax.rs:237-247)
@@ -576,9 +527,7 @@ int sbn_table_halves(sbn_ctx* c, const sbn_table* t, sbn_table** left, sbn_table
 int sbn_table_slice(sbn_ctx* c, const sbn_table* t, size_t first, size_t len, sbn_table** out) {
   if (!c || !t || !out) return SBN_EINVAL;
   if (len == 0 || (len & (len - 1)) || first > t->len || len > t->len - first) return fail(c, SBN_EINVAL, "slice: [%zu, +%zu) of a table of %zu entries (a power-of-two length inside the table is needed)", first, len, t->len);
-  sbn_table* v = new sbn_table();
-  v->d = (uint8_t*)t->d + first * 32; v->len = v->cap = len; v->owned = false;
-  *out = v;
+  *out = table_view(t, first, len);
   return SBN_OK;
 }
 static int table_dot_locked(sbn_ctx* c, const uint32_t* a, const uint32_t* b, size_t n, uint8_t out[32]) {
@@ -603,22 +552,22 @@ int sbn_table_dot(sbn_ctx* c, const sbn_table* a, const sbn_table* b, uint8_t ou
   return table_dot_locked(c, (const uint32_t*)a->d, (const uint32_t*)b->d, a->len, out);
 }
 int sbn_table_evaluate(sbn_ctx* c, const sbn_table* Z, const uint8_t* r, size_t ell, uint8_t out[32]) {
-  if (!c || !Z || (!r && ell) || !out) return SBN_EINVAL;
+  if (!c || !Z || (!r && ell) || !out || ell > 40) return SBN_EINVAL;
   if (((size_t)1 << ell) != Z->len) return fail(c, SBN_EINVAL, "evaluate: r.len() != num_vars (hyrax.rs:218 assert_eq)");
-  sbn_table* chi = nullptr;
-  int rc = sbn_eq_evals(c, r, ell, &chi);
-  if (rc) return rc;
-  rc = sbn_table_dot(c, Z, chi, out);
-  sbn_table_free(c, chi);
-  return rc;
+  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+  TableScope S(c); sbn_table* chi = nullptr; int rc;
+  if ((rc = eq_evals_locked(c, r, ell, &chi))) return rc;
+  S.keep(chi);
+  if ((rc = table_dot_locked(c, (const uint32_t*)Z->d, (const uint32_t*)chi->d, Z->len, out))) return rc;
+  return S.done();
 }
 }  // extern "C"
-static int eq_evals_locked(sbn_ctx* c, const uint8_t* r, size_t ell, sbn_table** out);
 // (the caller holds the context's mutex and has checked the arguments)
 static int table_evaluate_many_locked(sbn_ctx* c, const sbn_table* const* Z, size_t count, const uint8_t* r, size_t ell, uint8_t* out) {
-  sbn_table* chi = nullptr;
+  TableScope S(c); sbn_table* chi = nullptr;
   int rc = eq_evals_locked(c, r, ell, &chi);       // ONE eq table for all of them (the reference rebuilds it per call, hyrax.rs:217-222)
   if (rc) return rc;
+  S.keep(chi);
   {
     const size_t n = chi->len;
     unsigned gx = stream_grid(n); if (gx > 1024) gx = 1024;
@@ -639,9 +588,7 @@ static int table_evaluate_many_locked(sbn_ctx* c, const sbn_table* const* Z, siz
       for (size_t i = 0; i < m; i++) memcpy(out + 32 * (i0 + i), (uint8_t*)c->pin + 96 * i, 32);
     }
   }
-  if (chi->d && chi->owned) pool_put(c, chi->d, chi->cap * 32);      // (every chunk above ended in a stream wait or failed)
-  delete chi;
-  return rc;
+  return rc ? rc : S.done();
 }
 extern "C" {
 int sbn_table_evaluate_many(sbn_ctx* c, const sbn_table* const* Z, size_t count, const uint8_t* r, size_t ell, uint8_t* out) {
@@ -666,16 +613,15 @@ int sbn_table_bound(sbn_ctx* c, const sbn_table* Z, const sbn_table* Lv, sbn_tab
   if (col_tiles > 0x7fffffff || nslices > 65535) return fail(c, SBN_EINVAL, "bound: grid too large");
   int rc;
   if ((rc = ensure(c, c->sc_partial, nslices * R_size * 32))) return rc;
-  sbn_table* t = new sbn_table(); t->len = R_size; t->cap = R_size;
-  size_t _gb = 0; hipError_t e = pool_get(c, (R_size) * 32, &t->d, &_gb); t->cap = _gb / 32;
-  if (e != hipSuccess) { delete t; return fail(c, SBN_ENOMEM, "hipMalloc bound table: %s", hipGetErrorString(e)); }
+  TableScope S(c); sbn_table* t;
+  if ((rc = S.alloc(R_size, "bound table", &t))) return rc;
   LAUNCH(c, "k_bound_partial", k_bound_partial, dim3((unsigned)col_tiles, (unsigned)nslices), 256, (const uint32_t*)Z->d, (const uint32_t*)Lv->d, L_size, R_size, rows_per_slice, (uint32_t*)c->sc_partial.p);
   LAUNCH(c, "k_bound_fold", k_bound_fold, (unsigned)((R_size + 255) / 256), 256, (const uint32_t*)c->sc_partial.p, nslices, R_size, (uint32_t*)t->d);
   LAUNCHCHK(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->prof) prof_drain(c);
-  *out = t;
-  return SBN_OK;
+  *out = S.give(t);
+  return S.done();
 }
 }  // extern "C"
 // rshift < 0: the whole polynomial (padded to a power of two); else the rows row0, row0 + rstep, ... (nrows of them) of its L x 2^rshift view
@@ -696,9 +642,8 @@ static int gather_merge_locked(sbn_ctx* c, const sbn_table* const* mem, const vo
   uint8_t* d_args = (uint8_t*)c->sc_args.p; uint32_t* d_oob = (uint32_t*)(d_args + count * sizeof(GatherArgs));
   HIPCHK(c, hipMemcpyAsync(d_args, ha, count * sizeof(GatherArgs), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(d_oob, 0, 4, c->stream));
-  sbn_table* t = new sbn_table(); t->len = out_len; t->cap = out_len;
-  size_t _gb = 0; hipError_t e = pool_get(c, out_len * 32, &t->d, &_gb); t->cap = _gb / 32;
-  if (e != hipSuccess) { delete t; return fail(c, SBN_ENOMEM, "hipMalloc gather table: %s", hipGetErrorString(e)); }
+  TableScope S(c); sbn_table* t;
+  if ((rc = S.alloc(out_len, "gather table", &t))) return rc;
   LAUNCH(c, "k_gather_merge", k_gather_merge, stream_grid(out_len), 256, (const GatherArgs*)d_args, count, n, out_len, (uint32_t*)t->d, d_oob, rshift, row0, rstep);
   LAUNCHCHK(c);
   uint32_t oob = 0;
@@ -706,9 +651,9 @@ static int gather_merge_locked(sbn_ctx* c, const sbn_table* const* mem, const vo
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->prof) prof_drain(c);
   memcpy(&oob, c->pin, 4);
-  if (oob) { pool_put(c, t->d, t->cap * 32); delete t; return fail(c, SBN_EINVAL, "gather: %u addresses are outside their memory table (sparse_mlpoly_full.rs:228 assert)", oob); }
-  *out = t;
-  return SBN_OK;
+  if (oob) return fail(c, SBN_EINVAL, "gather: %u addresses are outside their memory table (sparse_mlpoly_full.rs:228 assert)", oob);
+  *out = S.give(t);
+  return S.done();
 }
 static int gather_merge_impl(sbn_ctx* c, const sbn_table* const* mem, const void* const* addr_dev, size_t count, size_t n, int rshift, size_t row0, size_t rstep, size_t nrows, sbn_table** out) {
   if (!c || !mem || !addr_dev || !out || count == 0 || n == 0) return SBN_EINVAL;
@@ -747,9 +692,8 @@ static int eq_evals_locked(sbn_ctx* c, const uint8_t* r, size_t ell, sbn_table**
   const size_t N = (size_t)1 << ell;
   int rc;
   if ((rc = ensure(c, c->stage_scal, std::max<size_t>(N * 32, 64)))) return rc;     // ping-pong partner
-  sbn_table* t = new sbn_table(); t->len = N; t->cap = N;
-  size_t _gb = 0; hipError_t e = pool_get(c, (N) * 32, &t->d, &_gb); t->cap = _gb / 32;
-  if (e != hipSuccess) { delete t; return fail(c, SBN_ENOMEM, "hipMalloc eq table: %s", hipGetErrorString(e)); }
+  TableScope S(c); sbn_table* t;
+  if ((rc = S.alloc(N, "eq table", &t))) return rc;
   // No staging copy, no conversion launch and no host wait: the point travels as kernel arguments in Montgomery form (one host product
   // per coordinate), the table is consumed in stream order.  Levels: the first m <= 12 in one launch (direct product per entry), then
   // two levels per pass.
@@ -772,8 +716,8 @@ static int eq_evals_locked(sbn_ctx* c, const uint8_t* r, size_t ell, sbn_table**
   }
   LAUNCHCHK(c);
   if (c->prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); prof_drain(c); }
-  *out = t;
-  return SBN_OK;
+  *out = S.give(t);
+  return S.done();
 }
 extern "C" {
 int sbn_eq_evals(sbn_ctx* c, const uint8_t* r, size_t ell, sbn_table** out) {

@@ -128,6 +128,48 @@ static int fail(sbn_ctx* c, int code, const char* fmt, ...) {
 }
 #define HIPCHK(c, call) do { hipError_t _e = (call); if (_e != hipSuccess) return fail((c), SBN_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); } while (0)
 
+// ---- table lifetime ("table lifetime"): the only code that creates, shares out and releases an sbn_table ----
+static void table_release(sbn_ctx* c, sbn_table* t) {
+  if (!t) return;
+  if (t->d && t->owned) pool_put(c, t->d, t->cap * 32);
+  if (t->d2 && t->owned2) pool_put(c, t->d2, t->cap2 * 32);
+  delete t;
+}
+// a table of `len` entries that owns its buffer; `what` names it in the out-of-memory message
+static int table_alloc(sbn_ctx* c, size_t len, const char* what, sbn_table** out) {
+  sbn_table* t = new sbn_table(); t->len = len;
+  size_t got = 0; const hipError_t e = pool_get(c, len * 32, &t->d, &got);
+  if (e != hipSuccess) { delete t; *out = nullptr; return fail(c, SBN_ENOMEM, "hipMalloc %s: %s", what, hipGetErrorString(e)); }
+  t->cap = got / 32;
+  *out = t;
+  return SBN_OK;
+}
+// entries [first, first + len) of t as a handle that owns nothing
+static sbn_table* table_view(const sbn_table* t, size_t first, size_t len) {
+  sbn_table* v = new sbn_table();
+  v->d = (uint8_t*)t->d + first * 32; v->len = v->cap = len; v->owned = false;
+  return v;
+}
+// The tables a call has made and not handed out.  A call that ends without done() failed: the scope waits for the stream, so that nothing of the
+// call stays queued behind the failure, and releases what it holds.  A producer fills its out-parameters at its successful end, through give().
+struct TableScope {
+  sbn_ctx* c; bool ok = false;
+  std::vector<sbn_table*> held;
+  explicit TableScope(sbn_ctx* c_) : c(c_) {}
+  TableScope(const TableScope&) = delete;
+  TableScope& operator=(const TableScope&) = delete;
+  ~TableScope() {
+    if (!ok) hipStreamSynchronize(c->stream);
+    for (sbn_table* t : held) table_release(c, t);
+  }
+  sbn_table* keep(sbn_table* t) { if (t) held.push_back(t); return t; }
+  int alloc(size_t len, const char* what, sbn_table** out) { const int rc = table_alloc(c, len, what, out); keep(*out); return rc; }
+  const sbn_table* view(const sbn_table* t, size_t first, size_t len) { return keep(table_view(t, first, len)); }
+  sbn_table* give(sbn_table* t) { held.erase(std::find(held.begin(), held.end(), t)); return t; }     // to the caller: no longer the scope's
+  void give_all() { held.clear(); }
+  int done() { ok = true; return SBN_OK; }
+};
+
 static int ensure(sbn_ctx* c, DevBuf& b, size_t bytes) {
   if (bytes <= b.cap) return SBN_OK;
   if (b.p) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
