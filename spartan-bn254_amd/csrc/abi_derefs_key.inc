@@ -2,8 +2,8 @@
 // commitment from them (Derefs::commit_kzg, sparse_mlpoly_full.rs:307-312 -> KZGPolyCommitment::commit, kzg.rs:386-397).
 //   derefs[i] = eq[addr[i]]  =>  sum_i derefs[i] [tau^i]G = sum_a eq[a] S_a,   S[side][a] = sum_{k < b} sum_{i < N, addr[side][k][i] = a} srs[(side b + k) N + i]
 // The build is a segmented point sum over the counting sort sbn_dense already holds (audit_ts = count per cell, read_ts = rank within the cell): the
-// bucket accumulate of run_bucket_job (k_size_hist/_scan/_scatter, k_acc_first<1>, k_acc_extra, k_acc_merge) launched from here over P = 2 problems of
-// nb = cells buckets, estride = batch * N, stopped before the reduction: the buckets are the result.  Cell 0 takes every padding op, so the heaviest
+// bucket accumulate of run_bucket_job (launch_accumulate, msm_host.hpp) over P = 2 problems of nb = cells buckets, estride = batch * N, one lane per
+// bucket, stopped before the reduction: the buckets are the result.  Cell 0 takes every padding op, so the heaviest
 // bucket holds most of a side: it is cut into segments of SEG entries like any oversized bucket.  Included by sbn254.hip.
 
 struct sbn_derefs_key {
@@ -15,12 +15,10 @@ struct sbn_derefs_key {
   std::vector<uint32_t> ids;
 };
 
-// SEG of the key build: run_bucket_job's rule for (P = 2, nb = cells, estride = bN), then raised until the heaviest cell's merge chain fits a lane:
+// SEG of the key build: the bucket job's rule (acc_seg, msm_plan.hpp) for (P = 2, nb = cells, estride = bN), then raised until the heaviest cell's merge chain fits a lane:
 // k_acc_merge folds k = ceil(cnt / SEG) - 1 partials lane-strided over one wave, k / 64 additions per lane, and no lane may run more than ACC_SEG_MAX
 static uint32_t derefs_key_seg(size_t cells, size_t bN, uint32_t maxcnt) {
-  const size_t NB = 2 * cells, mean = bN / cells + 1;
-  uint32_t SEG = 32; while (SEG < 2 * mean && SEG < ACC_SEG_MAX) SEG <<= 1;
-  if (NB < 262144) { const size_t total = 2 * bN; uint32_t cap = 32; while ((size_t)cap * 262144 < total && cap < ACC_SEG_MAX) cap <<= 1; if (SEG > cap) SEG = cap; }
+  uint32_t SEG = acc_seg(2, bN, cells);
   while ((size_t)maxcnt / SEG / 64 > ACC_SEG_MAX && SEG < ACC_SEG_MAX) SEG <<= 1;
   return SEG;
 }
@@ -68,42 +66,25 @@ int sbn_derefs_key_build(sbn_ctx* c, const sbn_dense* dn, const sbn_bases* srs, 
     if (sum != bN) return fail(c, SBN_EINVAL, "derefs key: the %s side's audit_ts sum to %zu, not batch * N = %zu", side ? "column" : "row", sum, bN);
   }
   const size_t len = kp->ids.size();
-  const uint32_t SEG = derefs_key_seg(cells, bN, maxcnt);
-  const size_t max_extra = 2 * bN / SEG + 1, max_big = std::min(NB, max_extra);
-  if ((rc = ensure(c, c->offs, NB * 4))) return rc;
-  if ((rc = ensure(c, c->sorted, 2 * bN * 4))) return rc;
-  if ((rc = ensure(c, c->buckets, NB * 128))) return rc;
-  if ((rc = ensure(c, c->acc_ctr, 64 + (ACC_SEG_MAX + 2) * 4))) return rc;
-  if ((rc = ensure(c, c->extra_list, max_extra * sizeof(ExtraItem)))) return rc;
-  if ((rc = ensure(c, c->extra_out, max_extra * 128))) return rc;
-  if ((rc = ensure(c, c->big_list, max_big * sizeof(BigItem)))) return rc;
-  if ((rc = ensure(c, c->perm, NB * 4))) return rc;
+  AccPlan a; memset(&a, 0, sizeof a);          // no reduction: L, chunks, levels and quad stay 0, as sbn_prof_last_acc reports them
+  a.LPB = 1; acc_set_seg(a, derefs_key_seg(cells, bN, maxcnt), 2, bN, cells);
+  if ((rc = ensure_accumulate(c, NB, 2 * bN, a))) return rc;
   if ((rc = ensure(c, c->gen_tmp, len * 128))) return rc;
   const uint32_t* hist = dense_audit(dn, 0);
-  uint32_t* offs = (uint32_t*)c->offs.p; uint32_t* sorted = (uint32_t*)c->sorted.p; uint32_t* buckets = (uint32_t*)c->buckets.p;
-  AccCounters* ctr = (AccCounters*)c->acc_ctr.p;
-  const uint32_t* points = (const uint32_t*)srs->d_pts;
+  uint32_t* offs = (uint32_t*)c->offs.p; uint32_t* sorted = (uint32_t*)c->sorted.p;
   sbn_bases* pts = new sbn_bases(); pts->n = len; pts->has_h = false;
   kp->pts = pts;
   auto bail = [&](int code) { hipStreamSynchronize(c->stream); sbn_derefs_key* k = kp.release(); derefs_key_release(nullptr, k); return code; };
   if (hipMalloc(&pts->d_pts, len * 64) != hipSuccess || hipMalloc(&kp->d_ids, len * 4) != hipSuccess) { (void)hipGetLastError(); return bail(fail(c, SBN_ENOMEM, "derefs key: hipMalloc of %zu points", len)); }
   if (hipMemcpyAsync(kp->d_ids, kp->ids.data(), len * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) return bail(fail(c, SBN_EHIP, "derefs key: upload of the cell ids"));
-  if (hipMemsetAsync(ctr, 0, 64 + (ACC_SEG_MAX + 2) * 4, c->stream) != hipSuccess) return bail(fail(c, SBN_EHIP, "derefs key: clearing the counters"));
+  if (hipMemsetAsync(c->acc_ctr.p, 0, ACC_CTR_BYTES, c->stream) != hipSuccess) return bail(fail(c, SBN_EHIP, "derefs key: clearing the counters"));
   c->last_job[0] = 0; c->last_job[1] = 2; c->last_job[2] = (uint64_t)(2 * bN); c->last_job[3] = (uint64_t)NB;
-  c->last_acc[0] = SEG; c->last_acc[1] = 1; c->last_acc[2] = 0; c->last_acc[3] = 0; c->last_acc[4] = 0; c->last_acc[5] = 0;
+  store_last_acc(c, a);
   LAUNCH(c, "k_scan", k_scan, 2, 1024, hist, offs, (int)cells);
   LAUNCH(c, "k_dk_place", k_dk_place, stream_grid(2 * bN), 256, (const uint32_t*)dn->u32s, bN, (uint32_t)cells, hist, (const uint32_t*)offs, sorted);
-  uint32_t* size_bins = (uint32_t*)((uint8_t*)c->acc_ctr.p + 64);
-  LAUNCH(c, "k_size_sort", k_size_hist, (unsigned)((NB + 1023) / 1024), 1024, hist, NB, SEG, size_bins);
-  LAUNCH(c, "k_size_sort", k_size_scan, 1, 64, size_bins, SEG);
-  LAUNCH(c, "k_size_sort", k_size_scatter, (unsigned)((NB + 1023) / 1024), 1024, hist, NB, SEG, size_bins, (uint32_t*)c->perm.p);
-  LAUNCH(c, "k_acc_first", k_acc_first<1>, (unsigned)((NB + 255) / 256), 256, points, NB, (int)cells, bN, SEG, hist, (const uint32_t*)offs, (const uint32_t*)sorted,
-         (const uint32_t*)c->perm.p, buckets, ctr, (ExtraItem*)c->extra_list.p, (BigItem*)c->big_list.p);
-  LAUNCH(c, "k_acc_extra", k_acc_extra, 2048, 256, points, (int)cells, bN, SEG, hist, (const uint32_t*)offs, (const uint32_t*)sorted, (const AccCounters*)ctr,
-         (const ExtraItem*)c->extra_list.p, (uint32_t*)c->extra_out.p);
-  LAUNCH(c, "k_acc_merge", k_acc_merge, 4096, 64, (const AccCounters*)ctr, (const BigItem*)c->big_list.p, (const uint32_t*)c->extra_out.p, buckets, 1);
+  launch_accumulate(c, (const uint32_t*)srs->d_pts, NB, (int)cells, bN, a, hist);
   // the cells with audit_ts > 0 (a cell never read is the identity: it has no affine form), as a base set
-  LAUNCH(c, "k_dk_gather", k_dk_gather, stream_grid(len), 256, (const uint32_t*)buckets, (const uint32_t*)kp->d_ids, (uint32_t)cells, len, (uint32_t*)c->gen_tmp.p);
+  LAUNCH(c, "k_dk_gather", k_dk_gather, stream_grid(len), 256, (const uint32_t*)c->buckets.p, (const uint32_t*)kp->d_ids, (uint32_t)cells, len, (uint32_t*)c->gen_tmp.p);
   LAUNCH(c, "k_xyzz_to_affine", k_xyzz_to_affine, (unsigned)((len + 63) / 64), 64, (const uint32_t*)c->gen_tmp.p, (uint32_t*)pts->d_pts, (uint32_t*)nullptr, (uint8_t*)nullptr, len);
   const hipError_t le = hipGetLastError(), se = hipStreamSynchronize(c->stream);
   if (c->prof) prof_drain(c);

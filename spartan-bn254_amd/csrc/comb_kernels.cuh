@@ -13,7 +13,6 @@
 namespace sbn {
 
 constexpr int COMB_CH = 64;      // multiples per lane in the table build (one batched inversion per lane)
-constexpr int COMB_C_MAX = 17;   // widest lookup window (c = 17: 15 windows; 177 GB for the 2814 unique points of the 8193-generator set)
 
 // One window slab of the table.  Lane t -> (column j, chunk a): entries d = 64 a + 1 .. 64 a + 64 of column j.
 // tmp_xyzz / tmp_pref: COMB_CH x lanes records (k-major, so a wave's accesses are contiguous).

@@ -1,95 +1,32 @@
-// msm_host.hpp — launch code of the MSM / commitment path: window choice, the bucket pipeline (digits -> LDS counting sort ->
-// load-ordered accumulation -> reduction), window tables, merging of equal bases, row-chunk launches.
+// msm_host.hpp — launch code of the MSM / commitment path: the bucket pipeline (digits -> LDS counting sort -> load-ordered accumulation ->
+// reduction) run from a plan (msm_plan.hpp: window choice, overrides, geometry), window tables, merging of equal bases, row-chunk launches.
 // Reference boundary: group.rs:171-175, commitments.rs:144-154, hyrax.rs:253-308 (included by sbn254.hip only).
 #pragma once
-// ------------------------------------------------------------------------------------------------
-static int ilog2_ceil(size_t n) { int l = 0; while (((size_t)1 << l) < n) l++; return l; }
-
-// Signed radix-2^c digits: W windows cover `bits` bits (254: canonical scalars; 127: GLV half-scalars), the top digit (+ carry)
-// must stay <= 2^(c-1).
-static MsmShape make_shape(int c, int bits = 254) {
-  MsmShape s; s.c = c; s.nb = 1 << (c - 1);
-  int W = (bits + c - 1) / c;
-  int tb = bits - (W - 1) * c;         // bits in the top window
-  if (tb > c - 1) W += 1;
-  s.W = W;
-  return s;
-}
-// Window size from a cost model in modular products: `terms`*W mixed adds (10 each) into `sets` bucket sets of 2^(c-1)
-// buckets, each bucket costing ~2 full adds (14 each) in the running-sum reduction (x2 for the wave-level part).
-// SBN_MSM_C overrides for experiments.
-// Small jobs (`problems` x `terms` far below the chip's lane count) are latency-bound: what counts is the length of the longest
-// bucket chain, not the number of products, so they take the smallest window with a mean bucket load <= 4.
-// `chard`: the widest window the caller's sort can take (MSM_C_MAX for the one-level LDS sort, S2_C_MAX for the two-level one).
-static MsmShape choose_shape(size_t terms, bool shared_bucket_set, int cmax, size_t problems = 0, int chard = MSM_C_MAX) {
-  const char* env = getenv("SBN_MSM_C");
-  if (env && atoi(env) >= 7 && atoi(env) <= chard) return make_shape(atoi(env));
-  if (cmax > chard) cmax = chard;
-  if (problems && problems * terms <= 32768) {
-    // one MSM of 512 .. 4096 terms: the narrowest windows, their overloaded buckets (16 - 64 points, the top window's two with n / 2 each) cut into
-    // segments of 8 (run_bucket_job) — 64 buckets per window keep the two reduction levels short: 353 / 371 / 407 us at 2^10 / 2^11 / 2^12 against
-    // 479 / 474 / 478 with the rule below (c = 15, segments of 32); profiles/r04_small_msm_window_sweep.txt
-    if (!shared_bucket_set && problems == 1 && terms >= 512 && terms <= 4096 && cmax >= 8) return make_shape(terms <= 512 ? 8 : 7);
-    // expected longest chain ~ mean load + the load of the top window's few buckets (it holds only 254 - (W-1)c bits)
-    double bl = 1e300; int bcl = 7;
-    for (int c = 7; c <= cmax; c++) {
-      MsmShape s = make_shape(c);
-      const int tb = 254 - (s.W - 1) * c;
-      const double top = (double)terms / (double)(1u << (tb > 0 ? (tb < 20 ? tb : 20) : 0));
-      const double load = (shared_bucket_set ? (double)terms * s.W / s.nb : (double)terms / s.nb) + top;
-      if (load <= 6.0) return s;
-      if (load < bl) { bl = load; bcl = c; }
-    }
-    return make_shape(bcl);
-  }
-  // One MSM between the latency regime and 2^20 terms: c = 15 (254 = 16 x 15 + 14: the top window is as wide as the others).  The product count below
-  // would pick windows whose top digit has 2 - 7 bits (c = 8, 12, 13): their handful of top buckets take n / 2^tb points each, a chain of segments and
-  // merges that runs AFTER the main pass — measured (tools/sweep_small_msm_c.py, profiles/r04_small_msm_window_sweep.txt) at 2^16 / 2^17 / 2^18:
-  // 880 / 1055 / 1209 us with c = 12 / 13 / 13 against 610 / 769 / 1129 with c = 15; 15 is also the measured optimum at 2^15 and 2^19.
-  if (!shared_bucket_set && terms < ((size_t)1 << 20) && cmax >= 15) return make_shape(15);
-  double best = 1e300; int bc = 7;
-  // cmax: one sort block keeps all 2^(c-1) counters of a problem in LDS; beyond that every block re-reads its digits once
-  // per counter range (measured at 2^26, c = 20: sort 82 ms vs accumulate 74 ms), which costs more than the 13 -> 16 windows;
-  // the two-level sort (sort2_kernels.cuh) has no such cap and lets large single MSMs take c up to 22.
-  for (int c = 7; c <= cmax; c++) {
-    MsmShape s = make_shape(c);
-    double sets = shared_bucket_set ? 1.0 : (double)s.W;
-    // per bucket: ~56 products in the one-level regime (measured at 2^20), ~40 once the reduction runs on millions of buckets
-    // (many rows over one bucket set each are the same throughput regime: the derefs matrix, 4096 rows x 2814 merged columns, c = 11 / 12 / 13 ->
-    //  19.6 / 18.2 / 19.0 ms — with 56 the model ties 11 and 12 and takes 11; tools/sweep_hyrax_bucket.sh)
-    const double per_bucket = (chard > MSM_C_MAX || (shared_bucket_set && problems >= 256)) ? 40.0 : 56.0;
-    double cost = (double)terms * s.W * 10.0 + sets * s.nb * per_bucket;
-    // a top window narrower than c - 1 bits fills only 2^tb of its buckets, each 2^(c-1-tb) times over: those go through the
-    // segment work list (k_acc_extra / k_acc_merge), measured at about half a window's worth of additions on top
-    if (!shared_bucket_set && 254 - (s.W - 1) * c < c - 1) cost += (double)terms * 5.0;
-    if (cost < best) { best = cost; bc = c; }
-  }
-  return make_shape(bc);
-}
-
 // ---- two-level sort of a large single MSM (sort2_kernels.cuh) ----
 #define S2_FOR_EACH_C(X) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) X(22)
 #define S2_GLV_FOR_EACH_C(X) X(13) X(14) X(15) X(16) X(17)        // window bits the GLV half-scalars (16-byte records) are instantiated for
+// the level-1 kernels of every instantiated (record, window bits, scalars per thread): plain (8 words) and GLV (4 words), each at both SPT values
+struct S2Variant {
+  bool glv; int c, spt;
+  void (*count)(const uint32_t*, S2Geom, uint32_t*, uint32_t*);
+  void (*scatter)(const uint32_t*, S2Geom, const uint32_t*, const uint32_t*, uint32_t*, uint16_t*);
+};
+#define S2_ROW(C, SPT, SW) {SW == 4, C, SPT, k_s2_count<C, SPT, SW>, k_s2_scatter<C, SPT, SW>},
+#define S2_PLAIN(C) S2_ROW(C, S2_SPT, 8) S2_ROW(C, S2_SPT_SMALL, 8)
+#define S2_GLV(C) S2_ROW(C, S2_SPT, 4) S2_ROW(C, S2_SPT_SMALL, 4)
+static const S2Variant s2_variants[] = { S2_FOR_EACH_C(S2_PLAIN) S2_GLV_FOR_EACH_C(S2_GLV) };
+#undef S2_GLV
+#undef S2_PLAIN
+#undef S2_ROW
+static const S2Variant* sort2_variant(bool glv, int c, int spt) {
+  for (const S2Variant& v : s2_variants) if (v.glv == glv && v.c == c && v.spt == spt) return &v;
+  return nullptr;
+}
 static bool sort2_set_lds() {
   bool ok = true;
-  const int bytes = (int)s2_scatter_lds_bytes(S2_P_MAX);
-  if (hipFuncSetAttribute((const void*)k_s2_place, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2_place_lds_bytes(S2_LO_LOG_MAX)) != hipSuccess) { (void)hipGetLastError(); ok = false; }
-#define X(C) if (hipFuncSetAttribute((const void*)k_s2_scatter<C, S2_SPT>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } \
-             if (hipFuncSetAttribute((const void*)k_s2_scatter<C, S2_SPT_SMALL>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; }
-  S2_FOR_EACH_C(X)
-#undef X
-  // k_s2_count keeps W * P counters: up to 24 windows x S2_P_MAX partitions (SBN_SORT2_LO can push P to the maximum with a narrow window)
-  const int cnt_bytes = 24 * S2_P_MAX * 4;
-#define X(C) if (hipFuncSetAttribute((const void*)k_s2_count<C, S2_SPT>, hipFuncAttributeMaxDynamicSharedMemorySize, cnt_bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } \
-             if (hipFuncSetAttribute((const void*)k_s2_count<C, S2_SPT_SMALL>, hipFuncAttributeMaxDynamicSharedMemorySize, cnt_bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; }
-  S2_FOR_EACH_C(X)
-#undef X
-#define X(C) if (hipFuncSetAttribute((const void*)k_s2_count<C, S2_SPT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, cnt_bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } \
-             if (hipFuncSetAttribute((const void*)k_s2_count<C, S2_SPT_SMALL, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, cnt_bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } \
-             if (hipFuncSetAttribute((const void*)k_s2_scatter<C, S2_SPT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } \
-             if (hipFuncSetAttribute((const void*)k_s2_scatter<C, S2_SPT_SMALL, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; }
-  S2_GLV_FOR_EACH_C(X)
-#undef X
+  auto grant = [&](const void* kern, size_t bytes) { if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } };
+  grant((const void*)k_s2_place, s2_place_lds_bytes(S2_LO_LOG_MAX));
+  for (const S2Variant& v : s2_variants) { grant((const void*)v.scatter, s2_scatter_lds_bytes(S2_P_MAX)); grant((const void*)v.count, S2_COUNT_LDS_BYTES); }
   return ok;
 }
 static bool sort2_applies(const sbn_ctx* c, int mode, size_t n, int cbits) {
@@ -97,68 +34,33 @@ static bool sort2_applies(const sbn_ctx* c, int mode, size_t n, int cbits) {
 }
 // scalars -> hist / offs / sorted of all W windows (the arrays the one-level sort leaves behind)
 // glv: the n records are GLV half-scalars (16 B each, glv_kernels.cuh); record t >= n/2 indexes point t + glv_gap
-static int sort2_run(sbn_ctx* c, const uint32_t* scalars, size_t n, const MsmShape& s, size_t estride, uint32_t* hist, uint32_t* offs, uint32_t* sorted, bool glv = false, size_t glv_gap = 0) {
-  S2Geom g; g.n = n; g.c = s.c; g.W = s.W; g.half = n / 2; g.gap = glv ? glv_gap : 0;
+static int sort2_run(sbn_ctx* c, const MsmOverrides& o, const uint32_t* scalars, size_t n, const MsmShape& s, size_t estride, uint32_t* hist, uint32_t* offs, uint32_t* sorted, bool glv = false, size_t glv_gap = 0) {
   if (glv && (s.c < 13 || s.c > 17)) return fail(c, SBN_EINVAL, "two-level sort: no GLV instantiation for windows of %d bits", s.c);
-  // bucket index = hi (level 1, <= 1024 partitions) | lo (level 2, <= 2048 LDS counters): runs of 8192 / P entries leave level 1,
-  // runs of tile / 2^lo_log leave level 2
-  g.lo_log = std::max(s.c - 1 - 8, 8); if (g.lo_log > S2_LO_LOG_MAX) g.lo_log = S2_LO_LOG_MAX;
-  if (const char* e = getenv("SBN_SORT2_LO")) { int v = atoi(e); if (v >= 4 && v <= S2_LO_LOG_MAX) g.lo_log = v; }
-  if (s.c - 1 - g.lo_log < 0) g.lo_log = s.c - 1;
-  while ((s.nb >> g.lo_log) > S2_P_MAX) g.lo_log++;
-  if (g.lo_log > S2_LO_LOG_MAX) return fail(c, SBN_EINVAL, "two-level sort: window of %d bits is too wide", s.c);
-  g.P = s.nb >> g.lo_log;
-  const int LO = 1 << g.lo_log;
-  // scalars per level-1 block: 8192, or 2048 while that still leaves runs of >= 32 entries per partition (P <= 64: windows up to 15 bits) and the
-  // input is small enough for 8192 to mean few blocks: a 2^20 MSM (c = 15) starts 512 blocks of 1024 threads instead of 128 (k_s2_count + k_s2_scatter
-  // 26 + 96 -> 18 + 68 us); at 2^21 / 2^22 (c = 17, P = 256: runs of 8) the small blocks lose (sort 0.42 / 0.83 against 0.33 / 0.64 ms).  SBN_SORT2_SPT = 2 / 8 overrides
-  int spt = (n <= ((size_t)1 << 21) && g.P <= 64) ? S2_SPT_SMALL : S2_SPT;
-  if (const char* e = getenv("SBN_SORT2_SPT")) { const int v = atoi(e); if (v == S2_SPT || v == S2_SPT_SMALL) spt = v; }
-  const size_t ch = (size_t)1024 * spt;
-  g.K = (int)((n + ch - 1) / ch);
-  const size_t WP = (size_t)g.W * g.P;
-  const size_t max_sc = ((size_t)g.W * n) / S2_SUB + WP;          // sum over partitions of ceil(cnt / S2_SUB), cnt summing to <= W n
+  const Sort2Plan p = sort2_plan(n, s, o);
+  if (p.status == S2_PLAN_TOO_WIDE) return fail(c, SBN_EINVAL, "two-level sort: window of %d bits is too wide", s.c);
+  S2Geom g; g.n = n; g.c = s.c; g.W = s.W; g.half = n / 2; g.gap = glv ? glv_gap : 0;
+  g.lo_log = p.lo_log; g.P = p.P; g.K = p.K;
+  const size_t LO = (size_t)1 << g.lo_log, WP = (size_t)g.W * g.P;
   int rc;
-  if ((rc = ensure(c, c->s2_cnt, WP * g.K * 4))) return rc;
-  if ((rc = ensure(c, c->s2_part, (3 * WP + 1) * 4))) return rc;
-  if ((rc = ensure(c, c->s2_idx, (size_t)g.W * n * 4))) return rc;
-  if ((rc = ensure(c, c->s2_lo, (size_t)g.W * n * 2))) return rc;
-  if ((rc = ensure(c, c->blockhist, max_sc * LO * 4))) return rc;
+  if ((rc = ensure(c, c->s2_cnt, WP * g.K * 4)) || (rc = ensure(c, c->s2_part, (3 * WP + 1) * 4))) return rc;
+  if ((rc = ensure(c, c->s2_idx, (size_t)g.W * n * 4)) || (rc = ensure(c, c->s2_lo, (size_t)g.W * n * 2)) || (rc = ensure(c, c->blockhist, p.max_sc * LO * 4))) return rc;
   uint32_t* cntA = (uint32_t*)c->s2_cnt.p; uint32_t* part_cnt = (uint32_t*)c->s2_part.p; uint32_t* part_off = part_cnt + WP; uint32_t* sc_off = part_off + WP;
   uint32_t* tmp_idx = (uint32_t*)c->s2_idx.p; uint16_t* tmp_lo = (uint16_t*)c->s2_lo.p; uint32_t* bh = (uint32_t*)c->blockhist.p;
-  const size_t lds_a = WP * 4, lds_c = s2_scatter_lds_bytes(g.P, spt);
-  if (lds_a > (size_t)24 * S2_P_MAX * 4) return fail(c, SBN_EINVAL, "two-level sort: %zu level-1 counters do not fit the LDS granted to k_s2_count", WP);
+  const size_t lds_a = WP * 4, lds_c = s2_scatter_lds_bytes(g.P, p.spt);
+  if (p.status == S2_PLAN_COUNTERS) return fail(c, SBN_EINVAL, "two-level sort: %zu level-1 counters do not fit the LDS granted to k_s2_count", WP);
+  const S2Variant* v = sort2_variant(glv, s.c, p.spt);
+  if (!v) return fail(c, SBN_EINVAL, "two-level sort: no instantiation for windows of %d bits", s.c);     // not reached: sort2_applies admits S2_C_MIN .. S2_C_MAX only
   {
     ProfScope _ps(c, "k_s2_count");
-    if (glv) switch (s.c) {
-#define X(C) case C: if (spt == S2_SPT) hipLaunchKernelGGL((k_s2_count<C, S2_SPT, 4>), dim3(g.K), dim3(1024), lds_a, c->stream, scalars, g, cntA, c->d_bad); \
-                     else hipLaunchKernelGGL((k_s2_count<C, S2_SPT_SMALL, 4>), dim3(g.K), dim3(1024), lds_a, c->stream, scalars, g, cntA, c->d_bad); break;
-      S2_GLV_FOR_EACH_C(X)
-#undef X
-    } else switch (s.c) {
-#define X(C) case C: if (spt == S2_SPT) hipLaunchKernelGGL((k_s2_count<C, S2_SPT>), dim3(g.K), dim3(1024), lds_a, c->stream, scalars, g, cntA, c->d_bad); \
-                     else hipLaunchKernelGGL((k_s2_count<C, S2_SPT_SMALL>), dim3(g.K), dim3(1024), lds_a, c->stream, scalars, g, cntA, c->d_bad); break;
-      S2_FOR_EACH_C(X)
-#undef X
-    }
+    hipLaunchKernelGGL(v->count, dim3(g.K), dim3(1024), lds_a, c->stream, scalars, g, cntA, c->d_bad);
   }
   LAUNCH(c, "k_s2_prefix", k_s2_prefix_k, (unsigned)WP, 256, cntA, g.K, part_cnt);
   LAUNCH(c, "k_s2_prefix", k_s2_prefix_hi, 1, 1024, (const uint32_t*)part_cnt, g.W, g.P, part_off, sc_off);
   {
     ProfScope _ps(c, "k_s2_scatter");
-    if (glv) switch (s.c) {
-#define X(C) case C: if (spt == S2_SPT) hipLaunchKernelGGL((k_s2_scatter<C, S2_SPT, 4>), dim3(g.K), dim3(1024), lds_c, c->stream, scalars, g, (const uint32_t*)cntA, (const uint32_t*)part_off, tmp_idx, tmp_lo); \
-                     else hipLaunchKernelGGL((k_s2_scatter<C, S2_SPT_SMALL, 4>), dim3(g.K), dim3(1024), lds_c, c->stream, scalars, g, (const uint32_t*)cntA, (const uint32_t*)part_off, tmp_idx, tmp_lo); break;
-      S2_GLV_FOR_EACH_C(X)
-#undef X
-    } else switch (s.c) {
-#define X(C) case C: if (spt == S2_SPT) hipLaunchKernelGGL((k_s2_scatter<C, S2_SPT>), dim3(g.K), dim3(1024), lds_c, c->stream, scalars, g, (const uint32_t*)cntA, (const uint32_t*)part_off, tmp_idx, tmp_lo); \
-                     else hipLaunchKernelGGL((k_s2_scatter<C, S2_SPT_SMALL>), dim3(g.K), dim3(1024), lds_c, c->stream, scalars, g, (const uint32_t*)cntA, (const uint32_t*)part_off, tmp_idx, tmp_lo); break;
-      S2_FOR_EACH_C(X)
-#undef X
-    }
+    hipLaunchKernelGGL(v->scatter, dim3(g.K), dim3(1024), lds_c, c->stream, scalars, g, (const uint32_t*)cntA, (const uint32_t*)part_off, tmp_idx, tmp_lo);
   }
-  const unsigned l2 = s2_level2_blocks(max_sc);
+  const unsigned l2 = s2_level2_blocks(p.max_sc);
   LAUNCH(c, "k_s2_hist", k_s2_hist, l2, 1024, (const uint16_t*)tmp_lo, g, (const uint32_t*)part_off, (const uint32_t*)part_cnt, (const uint32_t*)sc_off, bh);
   LAUNCH(c, "k_s2_prefix", k_s2_prefix2, (unsigned)WP, 1024, bh, g, (const uint32_t*)part_off, (const uint32_t*)sc_off, hist, offs);
   {
@@ -180,137 +82,100 @@ struct BucketJob {
   size_t glv_gap;         // indexes point t + glv_gap
 };
 
+// ---- the accumulate of a bucket job, shared with the derefs key (abi_derefs_key.inc), whose buckets are its result ----
+static const size_t ACC_CTR_BYTES = 64 + (ACC_SEG_MAX + 2) * 4;      // the counters of the accumulate kernels, then the size bins of the bucket ordering: ONE memset clears both
+static_assert(sizeof(AccCounters) <= 64, "the size bins follow the counters at byte 64");
+// everything launch_accumulate touches but the histogram: NB buckets of a.LPB slots, `entries` sorted entries in all
+static int ensure_accumulate(sbn_ctx* c, size_t NB, size_t entries, const AccPlan& a) {
+  int rc;
+  if ((rc = ensure(c, c->offs, NB * 4)) || (rc = ensure(c, c->sorted, entries * 4)) || (rc = ensure(c, c->buckets, NB * 128 * (size_t)a.LPB)) || (rc = ensure(c, c->acc_ctr, ACC_CTR_BYTES))) return rc;
+  if ((rc = ensure(c, c->extra_list, a.max_extra * sizeof(ExtraItem))) || (rc = ensure(c, c->extra_out, a.max_extra * 128)) || (rc = ensure(c, c->big_list, a.max_big * sizeof(BigItem)))) return rc;
+  return ensure(c, c->perm, NB * 4);
+}
+// bucket order by decreasing load (the size bins were cleared with the counters), then the three accumulate kernels: c->buckets holds the sums
+static void launch_accumulate(sbn_ctx* c, const uint32_t* points, size_t NB, int nb, size_t estride, const AccPlan& a, const uint32_t* hist) {
+  const uint32_t* offs = (const uint32_t*)c->offs.p; const uint32_t* sorted = (const uint32_t*)c->sorted.p; uint32_t* buckets = (uint32_t*)c->buckets.p;
+  AccCounters* ctr = (AccCounters*)c->acc_ctr.p;
+  uint32_t* size_bins = (uint32_t*)((uint8_t*)c->acc_ctr.p + 64);
+  const uint32_t SEG = a.SEG;
+  LAUNCH(c, "k_size_sort", k_size_hist, (unsigned)((NB + 1023) / 1024), 1024, hist, NB, SEG, size_bins);
+  LAUNCH(c, "k_size_sort", k_size_scan, 1, 64, size_bins, SEG);
+  LAUNCH(c, "k_size_sort", k_size_scatter, (unsigned)((NB + 1023) / 1024), 1024, hist, NB, SEG, size_bins, (uint32_t*)c->perm.p);
+  const unsigned agrid = (unsigned)((NB * (size_t)a.LPB + 255) / 256);
+  LAUNCH(c, "k_acc_first", (a.LPB == 1 ? k_acc_first<1> : k_acc_first<2>), agrid, 256, points, NB, nb, estride, SEG, hist, offs, sorted, (const uint32_t*)c->perm.p, buckets, ctr,
+         (ExtraItem*)c->extra_list.p, (BigItem*)c->big_list.p);
+  LAUNCH(c, "k_acc_extra", k_acc_extra, 2048, 256, points, nb, estride, SEG, hist, offs, sorted, (const AccCounters*)ctr, (const ExtraItem*)c->extra_list.p, (uint32_t*)c->extra_out.p);
+  LAUNCH(c, "k_acc_merge", k_acc_merge, 4096, 64, (const AccCounters*)ctr, (const BigItem*)c->big_list.p, (const uint32_t*)c->extra_out.p, buckets, a.LPB);
+}
+// weighted sums of the buckets per problem -> c->wsum (P x XYZZ)
+static void launch_reduce(sbn_ctx* c, size_t P, int nb, const AccPlan& a, const uint8_t* skip) {
+  LAUNCH(c, "k_reduce_l1", k_reduce_l1, (unsigned)(P * a.chunks), 64, (const uint32_t*)c->buckets.p, a.L, nb, (uint32_t*)c->red_a.p, skip, a.chunks, a.LPB);
+  uint32_t* in = (uint32_t*)c->red_a.p; uint32_t* outb = (uint32_t*)c->red_b.p;
+  int G = a.chunks;
+  for (int k64 = 1; k64 <= a.levels; k64++) {
+    const int Gout = (G + 63) / 64, final = (k64 == a.levels);
+    if (a.quad) LAUNCH(c, "k_reduce_combine", k_reduce_combine_quad, (unsigned)(P * Gout), 256, in, G, Gout, k64, a.L, final, final ? (uint32_t*)c->wsum.p : outb);
+    else LAUNCH(c, "k_reduce_combine", k_reduce_combine, (unsigned)(P * Gout), 64, in, G, Gout, k64, a.L, final, final ? (uint32_t*)c->wsum.p : outb);
+    std::swap(in, outb); G = Gout;
+  }
+}
+static void store_last_acc(sbn_ctx* c, const AccPlan& a) { const uint64_t v[6] = {a.SEG, (uint64_t)a.LPB, (uint64_t)a.L, (uint64_t)a.chunks, (uint64_t)a.levels, a.quad ? 1u : 0u}; memcpy(c->last_acc, v, sizeof v); }
+
 // digits -> counting sort -> segmented bucket accumulation -> per-problem weighted sums in c->wsum (P x XYZZ)
-static int run_bucket_job(sbn_ctx* c, const BucketJob& J) {
+static int run_bucket_job(sbn_ctx* c, const BucketJob& J, const MsmOverrides& o) {
   const MsmShape& s = J.s;
   const size_t NB = J.P * (size_t)s.nb;
   if (NB > 0xffffffffull) return fail(c, SBN_EINVAL, "bucket space too large");
   const size_t estride = J.da.estride;
   c->last_job[0] = (uint64_t)s.c; c->last_job[1] = (uint64_t)s.W; c->last_job[2] = (uint64_t)(J.P * estride); c->last_job[3] = (uint64_t)NB;
-  // segment length: twice the mean bucket load (power of two, >= 32)
-  size_t mean = estride / (size_t)s.nb + 1;
-  uint32_t SEG = 32; while (SEG < 2 * mean && SEG < ACC_SEG_MAX) SEG <<= 1;
-  // enough segments to fill the chip when a problem has few, heavily loaded buckets (one row, many columns)
-  if (NB < 262144) { const size_t total = J.P * estride; uint32_t cap = 32; while ((size_t)cap * 262144 < total && cap < ACC_SEG_MAX) cap <<= 1; if (SEG > cap) SEG = cap; }
-  if (J.mode == MODE_SINGLE && J.da.n >= 512 && J.da.n <= 4096) SEG = 8;       // small single MSMs: short chains, the partials folded by k_acc_merge (choose_shape)
-  if (const char* es = getenv("SBN_MSM_SEG")) { int v = atoi(es); if (v >= 8 && v <= (int)ACC_SEG_MAX) SEG = (uint32_t)v; }
-  // lanes per bucket (k_acc_first<G>): chains of ~32 mixed additions when the buckets are loaded enough to be split
-  // (only while one lane per bucket would leave the chip short of lanes: at 2^22, c = 17 — 983 k buckets of 64 points — two lanes per bucket accumulate no
-  //  faster (4.74 against 4.77 ms) and make the reduction read two slots per bucket: k_reduce_l1 0.53 against 0.37 ms)
-  int LPB = 1; if (J.mode == MODE_SINGLE && mean >= 48 && NB <= ((size_t)1 << 19)) LPB = 2;
-  const size_t max_extra = J.P * estride / SEG + 1;
-  const size_t max_big = std::min(NB, max_extra);
+  const AccPlan a = acc_plan(J.mode, J.da.n, J.P, estride, s.nb, o);
   int rc;
-  if ((rc = ensure(c, c->hist, NB * 4))) return rc;
-  if ((rc = ensure(c, c->offs, NB * 4))) return rc;
-  if ((rc = ensure(c, c->sorted, J.P * estride * 4))) return rc;
-  if ((rc = ensure(c, c->buckets, NB * 128 * (size_t)LPB))) return rc;
-  if ((rc = ensure(c, c->acc_ctr, 64 + (ACC_SEG_MAX + 2) * 4))) return rc;      // the counters of the accumulate kernels, then the size bins of the bucket ordering: ONE memset clears both
-  if ((rc = ensure(c, c->extra_list, max_extra * sizeof(ExtraItem)))) return rc;
-  if ((rc = ensure(c, c->extra_out, max_extra * 128))) return rc;
-  if ((rc = ensure(c, c->big_list, max_big * sizeof(BigItem)))) return rc;
-  // Buckets per lane (L) of the reduction's first level.  A chunk (one wave, 64 lanes x L buckets) costs a chain of about (2 L - 1) + L (LPB - 1) + 10
-  // additions (running sums, the LPB partial sums of a bucket, the wave's scan and tree) and keeps its SIMD's issue slots busy for all of it, so the
-  // level takes ceil(waves / SIMDs) such chains: L is chosen to minimise that — NOT a power of two in general (2^20 points: 17 windows x 2^14 buckets
-  // with L = 4 are 1 088 waves on 1 024 SIMDs, i.e. 64 SIMDs with two chains, 274 us; L = 5 with a ragged last chunk are 884 waves, one chain each).
-  // Many buckets (millions): the chip holds two waves per SIMD and the level is throughput-bound: the power-of-two rule stays.
-  int L = 1; while ((size_t)L * 64 * 2048 < NB && L < 16) L <<= 1;
-  if (L < 4) L = 4;
-  if (L > s.nb / 64) L = s.nb / 64;
-  if (L < 1) L = 1;
-  if (NB <= (size_t)64 * 16 * 1024) {
-    double best = 1e300; int bl = L;
-    for (int t = 1; t <= 32 && t * 64 <= std::max(s.nb, 64); t++) {
-      const size_t waves = J.P * (size_t)((s.nb + 64 * t - 1) / (64 * t));
-      const double cost = (double)((waves + 1023) / 1024) * (double)((2 * t - 1) + t * (LPB - 1) + 10);
-      if (cost < best) { best = cost; bl = t; }
-    }
-    L = bl;
-  }
-  if (const char* el = getenv("SBN_RED_L")) { int v = atoi(el); if (v >= 1 && v <= 64) L = v; }
-  const int chunks = (s.nb + 64 * L - 1) / (64 * L);      // per problem, >= 1; the last one may be ragged
-  if ((rc = ensure(c, c->red_a, J.P * chunks * 256))) return rc;
-  if ((rc = ensure(c, c->red_b, J.P * ((chunks + 63) / 64) * 256))) return rc;
-  if ((rc = ensure(c, c->wsum, J.P * 128))) return rc;
-
-  uint32_t* hist = (uint32_t*)c->hist.p; uint32_t* offs = (uint32_t*)c->offs.p;
-  uint32_t* sorted = (uint32_t*)c->sorted.p; uint32_t* buckets = (uint32_t*)c->buckets.p;
-  AccCounters* ctr = (AccCounters*)c->acc_ctr.p;
-
-  static_assert(sizeof(AccCounters) <= 64, "the size bins follow the counters at byte 64");
-  HIPCHK(c, hipMemsetAsync(ctr, 0, 64 + (ACC_SEG_MAX + 2) * 4, c->stream));
+  if ((rc = ensure(c, c->hist, NB * 4)) || (rc = ensure_accumulate(c, NB, J.P * estride, a))) return rc;
+  if ((rc = ensure(c, c->red_a, J.P * a.chunks * 256)) || (rc = ensure(c, c->red_b, J.P * ((a.chunks + 63) / 64) * 256)) || (rc = ensure(c, c->wsum, J.P * 128))) return rc;
+  uint32_t* hist = (uint32_t*)c->hist.p; uint32_t* offs = (uint32_t*)c->offs.p; uint32_t* sorted = (uint32_t*)c->sorted.p;
+  HIPCHK(c, hipMemsetAsync(c->acc_ctr.p, 0, ACC_CTR_BYTES, c->stream));
   // digits once, then the LDS counting sort
-  SortGeom g; memset(&g, 0, sizeof g);
-  g.E = estride; g.estride = estride; g.nb = s.nb; g.mode = J.mode; g.ncol = J.da.n; g.tstride = J.da.tstride;
-  g.RS = std::min(s.nb, c->sort_rs_max); g.logRS = 0; while ((1 << g.logRS) < g.RS) g.logRS++;
-  g.R = s.nb / g.RS;
-  { size_t want = (1024 + J.P * g.R - 1) / (J.P * g.R); size_t maxk = std::max<size_t>(1, estride / 4096); g.K = (int)std::max<size_t>(1, std::min(want, maxk)); }
-  g.chunk = (estride + g.K - 1) / g.K;
   const uint8_t* skip = nullptr;
   const bool two_level = sort2_applies(c, J.mode, J.da.n, s.c) && !J.skip;
   if (s.c > MSM_C_MAX && !two_level) return fail(c, SBN_EINVAL, "window of %d bits needs the two-level sort", s.c);
   if (J.glv && !two_level) return fail(c, SBN_EINVAL, "GLV half-scalars need the two-level sort");
   if (two_level) {
-    if ((rc = sort2_run(c, J.da.scalars, J.da.n, s, estride, hist, offs, sorted, J.glv, J.glv_gap))) return rc;
+    if ((rc = sort2_run(c, o, J.da.scalars, J.da.n, s, estride, hist, offs, sorted, J.glv, J.glv_gap))) return rc;
   } else {
-  if (J.P > 65535 || g.R > 65535) return fail(c, SBN_EINVAL, "sort grid too large (P=%zu R=%d)", J.P, g.R);
-  if ((rc = ensure(c, c->digits, J.P * estride * sizeof(dig_t)))) return rc;
-  if ((rc = ensure(c, c->blockhist, J.P * (size_t)g.R * g.K * g.RS * 4))) return rc;
-  dig_t* dig = (dig_t*)c->digits.p; uint32_t* bh = (uint32_t*)c->blockhist.p;
-  const unsigned gd = (unsigned)((J.threads + 255) / 256);
-  const size_t rows_lds = sort_rows_lds_bytes(s.nb);
-  const bool fused_rows = J.mode == MODE_ROWS && c->sort_rows_ok && rows_lds <= 160 * 1024 && estride <= 8 * (size_t)SORT_SL;
-  skip = fused_rows ? J.skip : nullptr;    // the generic sort reads every digit, so nothing may be left unwritten there
-  if (J.mode == MODE_SINGLE) LAUNCH(c, "k_digits_store", (k_digits_store<MODE_SINGLE>), gd, 256, J.da, s, dig, (const uint8_t*)nullptr);
-  else LAUNCH(c, "k_digits_store", (k_digits_store<MODE_ROWS>), gd, 256, J.da, s, dig, skip);
-  if (c->z_consumed && J.mode == MODE_ROWS) HIPCHK(c, hipEventRecord(c->z_consumed, c->stream));   // the scalars are not read again
-  if (fused_rows) {
-    ProfScope _ps(c, "k_sort_rows");
-    hipLaunchKernelGGL(k_sort_rows, dim3((unsigned)J.P), dim3(1024), rows_lds, c->stream, (const dig_t*)dig, g, hist, offs, sorted, skip);
-  } else {
-    {
-      ProfScope _ps(c, "k_hist_lds");
-      hipLaunchKernelGGL(k_hist_lds, dim3(g.K, g.R, (unsigned)J.P), dim3(1024), (size_t)g.RS * 4, c->stream, (const dig_t*)dig, g, bh);
-    }
-    LAUNCH(c, "k_block_prefix", k_block_prefix, (unsigned)((NB + 255) / 256), 256, bh, g, NB, hist);
-    LAUNCH(c, "k_scan", k_scan, (unsigned)J.P, 1024, hist, offs, s.nb);
-    {
-      ProfScope _ps(c, "k_scatter_lds");
-      hipLaunchKernelGGL(k_scatter_lds, dim3(g.K, g.R, (unsigned)J.P), dim3(1024), (size_t)g.RS * 4, c->stream, (const dig_t*)dig, g, (const uint32_t*)bh, (const uint32_t*)offs, sorted);
+    const Sort1Plan sp = sort1_plan(c->sort_rs_max, J.P, estride, s.nb);
+    SortGeom g; memset(&g, 0, sizeof g);
+    g.E = estride; g.estride = estride; g.nb = s.nb; g.mode = J.mode; g.ncol = J.da.n; g.tstride = J.da.tstride;
+    g.RS = sp.RS; g.logRS = sp.logRS; g.R = sp.R; g.K = sp.K; g.chunk = sp.chunk;
+    if (J.P > 65535 || g.R > 65535) return fail(c, SBN_EINVAL, "sort grid too large (P=%zu R=%d)", J.P, g.R);
+    if ((rc = ensure(c, c->digits, J.P * estride * sizeof(dig_t)))) return rc;
+    if ((rc = ensure(c, c->blockhist, J.P * (size_t)g.R * g.K * g.RS * 4))) return rc;
+    dig_t* dig = (dig_t*)c->digits.p; uint32_t* bh = (uint32_t*)c->blockhist.p;
+    const unsigned gd = (unsigned)((J.threads + 255) / 256);
+    const size_t rows_lds = sort_rows_lds_bytes(s.nb);
+    const bool fused_rows = J.mode == MODE_ROWS && c->sort_rows_ok && rows_lds <= 160 * 1024 && estride <= 8 * (size_t)SORT_SL;
+    skip = fused_rows ? J.skip : nullptr;    // the generic sort reads every digit, so nothing may be left unwritten there
+    if (J.mode == MODE_SINGLE) LAUNCH(c, "k_digits_store", (k_digits_store<MODE_SINGLE>), gd, 256, J.da, s, dig, (const uint8_t*)nullptr);
+    else LAUNCH(c, "k_digits_store", (k_digits_store<MODE_ROWS>), gd, 256, J.da, s, dig, skip);
+    if (c->z_consumed && J.mode == MODE_ROWS) HIPCHK(c, hipEventRecord(c->z_consumed, c->stream));   // the scalars are not read again
+    if (fused_rows) {
+      ProfScope _ps(c, "k_sort_rows");
+      hipLaunchKernelGGL(k_sort_rows, dim3((unsigned)J.P), dim3(1024), rows_lds, c->stream, (const dig_t*)dig, g, hist, offs, sorted, skip);
+    } else {
+      {
+        ProfScope _ps(c, "k_hist_lds");
+        hipLaunchKernelGGL(k_hist_lds, dim3(g.K, g.R, (unsigned)J.P), dim3(1024), (size_t)g.RS * 4, c->stream, (const dig_t*)dig, g, bh);
+      }
+      LAUNCH(c, "k_block_prefix", k_block_prefix, (unsigned)((NB + 255) / 256), 256, bh, g, NB, hist);
+      LAUNCH(c, "k_scan", k_scan, (unsigned)J.P, 1024, hist, offs, s.nb);
+      {
+        ProfScope _ps(c, "k_scatter_lds");
+        hipLaunchKernelGGL(k_scatter_lds, dim3(g.K, g.R, (unsigned)J.P), dim3(1024), (size_t)g.RS * 4, c->stream, (const dig_t*)dig, g, (const uint32_t*)bh, (const uint32_t*)offs, sorted);
+      }
     }
   }
-  }   // one-level sort
-  // bucket order by decreasing load
-  if ((rc = ensure(c, c->perm, NB * 4))) return rc;
-  uint32_t* size_bins = (uint32_t*)((uint8_t*)c->acc_ctr.p + 64);           // cleared with the counters at the start of the job
-  LAUNCH(c, "k_size_sort", k_size_hist, (unsigned)((NB + 1023) / 1024), 1024, hist, NB, SEG, size_bins);
-  LAUNCH(c, "k_size_sort", k_size_scan, 1, 64, size_bins, SEG);
-  LAUNCH(c, "k_size_sort", k_size_scatter, (unsigned)((NB + 1023) / 1024), 1024, hist, NB, SEG, size_bins, (uint32_t*)c->perm.p);
-  const unsigned agrid = (unsigned)((NB * (size_t)LPB + 255) / 256);
-#define ACC_FIRST_ARGS J.points, NB, s.nb, estride, SEG, hist, offs, sorted, (const uint32_t*)c->perm.p, buckets, ctr, (ExtraItem*)c->extra_list.p, (BigItem*)c->big_list.p
-  if (LPB == 1) LAUNCH(c, "k_acc_first", k_acc_first<1>, agrid, 256, ACC_FIRST_ARGS);
-  else LAUNCH(c, "k_acc_first", k_acc_first<2>, agrid, 256, ACC_FIRST_ARGS);
-#undef ACC_FIRST_ARGS
-  LAUNCH(c, "k_acc_extra", k_acc_extra, 2048, 256, J.points, s.nb, estride, SEG, hist, offs, sorted, ctr, (const ExtraItem*)c->extra_list.p, (uint32_t*)c->extra_out.p);
-  LAUNCH(c, "k_acc_merge", k_acc_merge, 4096, 64, ctr, (const BigItem*)c->big_list.p, (const uint32_t*)c->extra_out.p, buckets, LPB);
-  // The combine level of a job with few chunks (a single MSM of ~2^20 points, small commits) is a latency chain on a nearly empty chip: the
-  // quad-cooperative kernel (256 threads per group of 64 chunks, 3.5 instead of 7.6 us per dependent addition) runs it in 0.115 instead of
-  // 0.141 ms at 2^20.  Level 1 stays one wave per chunk: measured with quads 0.35 - 0.38 ms against 0.277 at L = 4 / 8 / 16 (level 1 is SIMD-issue
-  // bound, not a latency chain: four times the waves at 2.3x the instructions only make the queues longer; profiles/r04_reduce_quad_sweep.txt).
-  const bool red_quad = J.P * (size_t)chunks <= 2048;
-  LAUNCH(c, "k_reduce_l1", k_reduce_l1, (unsigned)(J.P * chunks), 64, buckets, L, s.nb, (uint32_t*)c->red_a.p, skip, chunks, LPB);
-  uint32_t* in = (uint32_t*)c->red_a.p; uint32_t* outb = (uint32_t*)c->red_b.p;
-  int G = chunks, k64 = 1;
-  c->last_acc[0] = SEG; c->last_acc[1] = (uint64_t)LPB; c->last_acc[2] = (uint64_t)L; c->last_acc[3] = (uint64_t)chunks; c->last_acc[4] = 0; c->last_acc[5] = red_quad ? 1 : 0;
-  for (;;) {
-    c->last_acc[4] += 1;
-    int Gout = (G + 63) / 64;
-    int final = (Gout == 1);
-    if (red_quad) LAUNCH(c, "k_reduce_combine", k_reduce_combine_quad, (unsigned)(J.P * Gout), 256, in, G, Gout, k64, L, final, final ? (uint32_t*)c->wsum.p : outb);
-    else LAUNCH(c, "k_reduce_combine", k_reduce_combine, (unsigned)(J.P * Gout), 64, in, G, Gout, k64, L, final, final ? (uint32_t*)c->wsum.p : outb);
-    if (final) break;
-    std::swap(in, outb); G = Gout; k64 += 1;
-  }
+  launch_accumulate(c, J.points, NB, s.nb, estride, a, hist);
+  store_last_acc(c, a);
+  launch_reduce(c, J.P, s.nb, a, skip);
   LAUNCHCHK(c);
   return SBN_OK;
 }
@@ -319,34 +184,16 @@ static int run_bucket_job(sbn_ctx* c, const BucketJob& J) {
 // one process-wide mutex (taken after the context's own, never the other way round).
 static std::mutex g_bases_tables_mu;
 
-// ---- GLV (glv_kernels.cuh): one MSM of n full-width scalars as an MSM of 2n half-width ones over P_i and phi(P_i) ----
-// Products of the window model above for one MSM in the two-level sort regime (40 per bucket): `terms` x W mixed additions, W x 2^(c-1)
-// buckets, and the half window's worth of additions a short top window costs.
-static double single_msm_cost(size_t terms, const MsmShape& s, int bits) {
-  double cost = (double)terms * s.W * 10.0 + (double)s.W * s.nb * 40.0;
-  if (bits - (s.W - 1) * s.c < s.c - 1) cost += (double)terms * 5.0;
-  return cost;
-}
-// GLV shape for n bases (2n half-scalars of 127 bits): SBN_MSM_C when it is one of the instantiated widths, else the model's best of 13..17
-// (c = 16: 8 windows of 16 bits fill all 2^15 buckets of the top window, 127 = 7 x 16 + 15)
-static MsmShape glv_shape(size_t n) {
-  if (const char* env = getenv("SBN_MSM_C")) { const int v = atoi(env); if (v >= 13 && v <= 17) return make_shape(v, 127); }
-  MsmShape best = make_shape(16, 127);
-  for (int cc = 13; cc <= 17; cc++) { const MsmShape s = make_shape(cc, 127); if (single_msm_cost(2 * n, s, 127) < single_msm_cost(2 * n, best, 127)) best = s; }
-  return best;
-}
-// Whether a single MSM of n terms over the generator set b takes the GLV path.  It needs the two-level sort for its 2n records and a
-// handle (the table of images phi(P) is kept with it).  Automatic rule: the window model's products at least 4 % below the plain shape's
-// (a margin for the split pass and for gathering from a table twice the size) — 2^19 .. 2^20 bases (c = 16 against c = 15: 8 x 2n
-// against 17 x n mixed additions, -5.9 %); at 2^21 the model gains 2 %, at 2^22 and above the plain windows (c = 17, 15 x n) win.
+// Whether a single MSM of n terms over the generator set b takes the GLV path (glv_kernels.cuh).  It needs the two-level sort for its 2n
+// records and a handle (the table of images phi(P) is kept with it).  Automatic rule: glv_pays (msm_plan.hpp).
 // SBN_MSM_GLV=0 / 1 (read when the context is created) switches it off / on wherever it can run; with it unset, an SBN_MSM_C experiment
 // keeps the plain windows it asks for.
-static bool glv_applies(const sbn_ctx* c, const sbn_bases* b, size_t n, const MsmShape& plain) {
-  if (!b || c->msm_glv == 0 || (c->msm_glv < 0 && getenv("SBN_MSM_C"))) return false;
+static bool glv_applies(const sbn_ctx* c, const MsmOverrides& o, const sbn_bases* b, size_t n, const MsmShape& plain) {
+  if (!b || c->msm_glv == 0 || (c->msm_glv < 0 && o.c_set)) return false;
   const size_t npts = b->n + (b->has_h ? 1 : 0);
   if (2 * npts > 0x7fffffffull || !sort2_applies(c, MODE_SINGLE, 2 * n, S2_C_MIN)) return false;
   if (c->msm_glv == 1) return true;
-  return single_msm_cost(2 * n, glv_shape(n), 127) * 1.04 < single_msm_cost(n, plain, 254);
+  return glv_pays(o, n, plain);
 }
 // the GLV table of a generator set: its npts points, then phi of each (2 x npts x 64 B), built on the first GLV MSM and kept with the
 // handle (the contexts that share a handle share one table; derived handles build their own)
@@ -373,27 +220,28 @@ static int msm_device(sbn_ctx* c, const uint32_t* d_scal, const uint32_t* d_base
   if (n > 0x7fffffffull) return fail(c, SBN_EINVAL, "msm: n=%zu exceeds 2^31-1", n);
   BucketJob J; memset(&J, 0, sizeof J);
   J.mode = MODE_SINGLE;
+  const MsmOverrides o = msm_overrides_read();
   {
     int cm = 1; while ((1 << cm) < c->sort_rs_max) cm++;
     const bool s2 = sort2_applies(c, MODE_SINGLE, n, S2_C_MIN);
-    J.s = choose_shape(n, false, s2 ? S2_C_MAX : cm + 1, 1, s2 ? S2_C_MAX : MSM_C_MAX);
+    J.s = choose_shape(o, n, false, s2 ? S2_C_MAX : cm + 1, 1, s2 ? S2_C_MAX : MSM_C_MAX);
   }
   J.P = (size_t)J.s.W; J.threads = n; J.points = d_bases;
   J.da.scalars = d_scal; J.da.n = n; J.da.estride = n; J.da.bad = c->d_bad;
-  const bool glv = glv_applies(c, b, n, J.s);
+  const bool glv = glv_applies(c, o, b, n, J.s);
   int rc;
   if (glv) {
     const uint32_t* tab;
     if ((rc = bases_glv_table(c, b, &tab))) return rc;
     if ((rc = ensure(c, c->glv_scal, 2 * n * 16))) return rc;
-    J.s = glv_shape(n); J.P = (size_t)J.s.W; J.threads = 2 * n; J.points = tab;
+    J.s = glv_shape(o, n); J.P = (size_t)J.s.W; J.threads = 2 * n; J.points = tab;
     J.da.scalars = (const uint32_t*)c->glv_scal.p; J.da.n = 2 * n; J.da.estride = 2 * n;
     J.glv = true; J.glv_gap = b->n + (b->has_h ? 1 : 0) - n;
   }
   if ((rc = ensure_pin(c, std::max<size_t>(4096, J.P * 128)))) return rc;
   if ((rc = input_check_begin(c))) return rc;
   if (glv) LAUNCH(c, "k_glv_split", k_glv_split, (unsigned)((n + 255) / 256), 256, d_scal, n, (uint32_t*)c->glv_scal.p, c->d_bad);
-  if ((rc = run_bucket_job(c, J))) return rc;
+  if ((rc = run_bucket_job(c, J, o))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->pin, c->wsum.p, J.P * 128, hipMemcpyDeviceToHost, c->stream));
   if ((rc = input_check_fetch(c))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -508,6 +356,7 @@ static int commit_rows_launch(sbn_ctx* c, const sbn_bases* b, const uint32_t* dZ
     return commit_rows_launch(c, b->uniq, m, nullptr, L, U + 1, d_xy, d_inf, info);
   }
   if (ri.mont_scalars) return fail(c, SBN_EINVAL, "commit: internal: Montgomery scalars without merged bases");
+  const MsmOverrides o = msm_overrides_read();
   const size_t ncol = R + (dBl ? 1 : 0);
   if (ncol == 0) {
     if (!d_xy) { int rc0; if ((rc0 = ensure(c, c->wsum, L * 128))) return rc0; HIPCHK(c, hipMemsetAsync(c->wsum.p, 0, L * 128, c->stream)); return SBN_OK; }
@@ -519,14 +368,7 @@ static int commit_rows_launch(sbn_ctx* c, const sbn_bases* b, const uint32_t* dZ
     const MsmShape s = make_shape(b->comb_c);
     DigitArgs da; memset(&da, 0, sizeof da);
     da.scalars = dZ; da.blinds = dBl; da.n = ncol; da.R = R; da.L = L; da.tstride = npts; da.bad = c->d_bad;
-    // few rows (latency-bound regime): spread a row over S blocks so that a lane takes at most two table points — the block
-    // sums are log-depth quad-cooperative additions (3.5 us a level), cheaper than a third chained mixed addition (5.4 us)
-    unsigned S = 1;
-    if ((size_t)L * 64 < 2048 && ncol * (size_t)s.W > 1024) {
-      S = (unsigned)std::min<size_t>(128, (ncol * (size_t)s.W + 511) / 512);
-      while (S > 1 && (size_t)L * S > 4096) S--;
-    }
-    if (const char* es = getenv("SBN_COMB_S")) { int v = atoi(es); if (v >= 1 && v <= 128) S = (unsigned)v; }
+    const unsigned S = comb_split(L, ncol, s.W, o);       // blocks per row
     int rc;
     if ((rc = ensure(c, c->wsum, L * 128))) return rc;
     if ((rc = ensure(c, c->comb_partial, S > 1 ? L * S * 128 : L * 257 * 128))) return rc;
@@ -549,14 +391,14 @@ static int commit_rows_launch(sbn_ctx* c, const sbn_bases* b, const uint32_t* dZ
     return SBN_OK;
   }
   BucketJob J; memset(&J, 0, sizeof J);
-  J.mode = MODE_ROWS; J.s = choose_shape(ncol, true, 16, L); J.P = L; J.threads = L * ncol;
+  J.mode = MODE_ROWS; J.s = choose_shape(o, ncol, true, 16, L); J.P = L; J.threads = L * ncol;
   if ((size_t)J.s.W * npts > 0x7fffffffull) return fail(c, SBN_EINVAL, "commit: table index overflow");
   int rc; const uint32_t* tab;
   if ((rc = bases_window_table(c, b, J.s, &tab))) return rc;
   J.points = tab;
   J.da.scalars = dZ; J.da.blinds = dBl; J.da.n = ncol; J.da.R = R; J.da.L = L; J.da.tstride = npts; J.da.estride = ncol * (size_t)J.s.W; J.da.bad = c->d_bad;
   J.skip = skip_rows;
-  if ((rc = run_bucket_job(c, J))) return rc;
+  if ((rc = run_bucket_job(c, J, o))) return rc;
   if (d_xy) LAUNCH(c, "k_xyzz_to_affine", k_xyzz_to_affine, (unsigned)((L + 63) / 64), 64, (const uint32_t*)c->wsum.p, (uint32_t*)nullptr, d_xy, d_inf, L);
   LAUNCHCHK(c);
   return SBN_OK;

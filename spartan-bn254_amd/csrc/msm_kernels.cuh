@@ -18,14 +18,9 @@
 // which a bucket's points are added (atomics decide it in step 3) cannot change the result bits.
 #pragma once
 #include "g1.cuh"
+#include "msm_plan.hpp"      // MsmShape, MODE_*, MSM_C_MAX, ACC_SEG_MAX, MERGE_LANE_MAX: the host's rules and the constants they share with the kernels
 
 namespace sbn {
-
-struct MsmShape {
-  int c;        // window bits
-  int W;        // number of windows
-  int nb;       // buckets per window = 2^(c-1)
-};
 
 // signed digit of window w; carry in/out.  digit in [-2^(c-1), 2^(c-1)) (ark-ec's recentring)
 __device__ __forceinline__ int window_digit(const uint32_t* __restrict__ k /* 8 limbs, global */, int w, int c, uint32_t& carry) {
@@ -92,7 +87,6 @@ __global__ void __launch_bounds__(256) k_points_from_ark(const uint32_t* in, uin
 //   MODE_ROWS    Hyrax row commits over shared bases (hyrax.rs:253-267): problem = matrix row (L problems); all W
 //                windows of a row share ONE bucket set because the table holds 2^(c*w)*G_j for every window w
 //                (entry = w*tstride + column), so no doublings are needed after the bucket sum.
-enum { MODE_SINGLE = 0, MODE_ROWS = 1 };
 struct DigitArgs {
   const uint32_t* scalars;   // SINGLE: n x 8 limbs.  ROWS: L x R x 8, row-major
   const uint32_t* blinds;    // ROWS: L x 8 or null (null = zero blinds, hyrax.rs:301-305)
@@ -107,7 +101,6 @@ struct DigitArgs {
 // signed digits of every scalar, stored once: dig[p*E + e].  Window bits never exceed 16 (LDS counter capacity), so a
 // digit in [-2^15, 2^15) fits 16 bits: half the bytes of the three passes that stream the digit array.
 typedef int16_t dig_t;
-constexpr int MSM_C_MAX = 16;
 //   SINGLE: p = window w, e = scalar index          ROWS: p = row, e = w*ncol + col
 template <int MODE>
 __global__ void __launch_bounds__(256) k_digits_store(DigitArgs a, MsmShape s, dig_t* __restrict__ dig, const uint8_t* __restrict__ skip) {
@@ -319,7 +312,6 @@ __global__ void __launch_bounds__(1024) k_scan(const uint32_t* __restrict__ hist
 // more (skewed scalars, or the short top window of a single MSM whose few buckets hold n/2^tb points each) posts its
 // other segments to a work list that k_acc_extra spreads over the whole chip, and k_acc_merge folds the partials
 // with one wave per oversized bucket.  No lane ever runs a chain longer than SEG mixed adds (+ a short merge).
-constexpr uint32_t ACC_SEG_MAX = 8192;   // longest chain one lane runs before a bucket is cut into segments
 struct AccCounters { uint32_t extra_count, big_count; };
 struct ExtraItem { uint32_t bucket, seg; };
 struct BigItem { uint32_t bucket, base, k; };
@@ -478,7 +470,6 @@ __device__ __forceinline__ XYZZ xyzz_mul_small(const XYZZ& v, uint32_t k) {
 
 // folding the extra partials back into their bucket: a bucket with few of them is finished by one lane (64 buckets per
 // wave), a bucket with many by one whole wave (lane-strided chains, then a wave tree)
-constexpr uint32_t MERGE_LANE_MAX = 12;
 // (`G` = slots per bucket: the extras are folded into the bucket's first slot)
 __global__ void __launch_bounds__(64) k_acc_merge(const AccCounters* __restrict__ ctr, const BigItem* __restrict__ big, const uint32_t* __restrict__ extra_out, uint32_t* __restrict__ buckets, int G) {
   const int lane = threadIdx.x;

@@ -18,11 +18,7 @@
 
 namespace sbn {
 
-constexpr int S2_LO_LOG_MAX = 11, S2_LO_MAX = 1 << S2_LO_LOG_MAX;      // most buckets per partition (LDS counters of level 2)
-constexpr int S2_P_MAX = 1024;                                        // most partitions per window (one scan lane each in level 1)
-constexpr int S2_SPT = 8, S2_CH = 1024 * S2_SPT;          // scalars per thread / per block in level 1 (large inputs)
-constexpr int S2_SPT_SMALL = 2;                           // ... up to 2^21 scalars: 8192 per block would be 128 - 256 blocks, half the chip or less (k_s2_scatter at 2^20: 95 us)
-constexpr int S2_C_MIN = 13, S2_C_MAX = 22;               // window bits this path is built for (P = 2^(c-12) partitions: 2 .. 1024)
+// (S2_LO_LOG_MAX, S2_P_MAX, S2_SPT, S2_SPT_SMALL, S2_C_MIN / S2_C_MAX, S2_SUB: msm_plan.hpp, with the host's rules that use them)
 struct S2Geom {
   size_t n;        // scalars
   int c, W, P;     // window bits, windows, partitions per window
@@ -123,7 +119,6 @@ __global__ void __launch_bounds__(256) k_s2_prefix_k(uint32_t* __restrict__ cntA
 // the index of each partition's first level-2 sub-chunk (sc_off[q], sc_off[W*P] = their number): a partition of cnt entries is
 // cut into ceil(cnt / S2_SUB) sub-chunks, so level-2 blocks carry equal loads whatever the partition sizes are (the short top
 // window puts all its entries into a few partitions; skewed scalars do the same anywhere).
-constexpr uint32_t S2_SUB = 16384;
 __global__ void __launch_bounds__(1024) k_s2_prefix_hi(const uint32_t* __restrict__ part_cnt, int W, int P, uint32_t* __restrict__ part_off, uint32_t* __restrict__ sc_off) {
   // ONE scan over the flat (window, partition) array instead of W scans one after the other (26 us on the critical path of a single
   // MSM): every thread owns a run of consecutive entries; part_off first receives the GLOBAL exclusive prefix (mod 2^32: only

@@ -1,6 +1,7 @@
 """CPU: the model of the accumulate geometry (tests/acc_model.py) is consistent with itself, its builders land on the loads they are
 asked for, and the geometry it gives at the shipped sizes is the one DESIGN.md states.  tests/test_gpu_acc_geometry.py holds the
-model against the host's run_bucket_job and the device's counters."""
+model against the host's run_bucket_job and the device's counters through a real job; tests/test_msm_plan_cpu.py is where the model meets the
+host's rules (csrc/msm_plan.hpp) without a device, over their whole range."""
 import os
 import random
 import re
