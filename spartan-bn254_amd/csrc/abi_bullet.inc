@@ -9,10 +9,9 @@
 //   MSM(a_L, G^(j)_R) = MSM over the original G_t of  w_t = a_L[(t mod m) - m/2] * s_t  for (t mod m) >= m/2, else 0,
 // one elementwise kernel + an MSM, and g_hat = MSM(s, G).  L, R and g_hat are the same group elements.
 // Because the bases never change, both MSMs of a round run as ONE two-row shared-base commit (the Hyrax kernel path with its
-// cached window table and merged duplicate generators) over the derived set G ‖ Q with h = H: row = [w ‖ c], blind = blind.
+// cached window table and merged duplicate generators) over the derived set G ‖ Q with h = H (derived_set, abi_msm.inc): row = [w ‖ c], blind = blind.
 // Included by sbn254.hip.
 
-static std::mutex g_bullet_ext_mu;
 static const size_t BULLET_COMB_BYTES = (size_t)3 << 30;
 struct sbn_bullet {
   size_t n = 0, m = 0;          // original / current length
@@ -105,14 +104,6 @@ __global__ void __launch_bounds__(256) k_bullet_prep(BulletPrep A, size_t n, siz
   if (threadIdx.x >= 128 && threadIdx.x < 136) { const int k = threadIdx.x - 128; A.blinds[k] = bl.v[k]; A.blinds[8 + k] = br.v[k]; }
   if (threadIdx.x == 0) __hip_atomic_store(A.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// the round's results to the host mailbox: the two XYZZ sums of the commit (2 x 32 words), c_L, c_R (2 x 8 words), flag behind them
-__global__ void __launch_bounds__(128) k_bullet_to_host(const uint32_t* __restrict__ sums, const uint32_t* __restrict__ dots, uint32_t* __restrict__ host_out, uint32_t* __restrict__ flag, uint32_t seq) {
-  const uint32_t t = threadIdx.x;
-  if (t < 64) host_out[t] = sums[t]; else if (t < 80) host_out[t] = dots[t - 64];
-  sc_drain_stores();
-  __syncthreads();
-  if (t == 0) sc_flag_store(flag, seq);
-}
 __global__ void __launch_bounds__(256) k_fr_fill_one(uint32_t* __restrict__ out, size_t n) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t < n) fe_store_packed<FrP>(out + 8 * t, fe_one<FrP>());
@@ -147,31 +138,25 @@ static int bullet_begin_impl(sbn_ctx* c, const sbn_bases* G, const uint8_t* Q_xy
   auto chk = [&](hipError_t x) { if (x != hipSuccess && rc == SBN_OK) rc = fail(c, SBN_EHIP, "bullet begin: %s", hipGetErrorString(x)); };
   auto drop = [&]() { pool_put(c, st->slab, st->slab_bytes); delete st; };
   if ((rc = ensure_pin(c, 4096))) { drop(); return rc; }
-  {
-    // the derived generator set for this Q: built once per (G, Q) and kept by G
-    const std::string key = Q_xy ? std::string((const char*)Q_xy, 64) : std::string();
-    std::lock_guard<std::mutex> tg(g_bullet_ext_mu);
-    for (auto& kv : G->bullet_ext) if (kv.first == key) st->ext = kv.second;
-    if (!st->ext) {
-      if ((rc = ensure(c, c->stage_pts, (n + 2) * 64))) { drop(); return rc; }
-      uint8_t* P = (uint8_t*)c->stage_pts.p;
-      chk(hipMemcpyAsync(P, G->d_pts, n * 64, hipMemcpyDeviceToDevice, c->stream));
-      chk(hipMemsetAsync(P + 64 * n, 0, 64, c->stream));
-      if (Q_xy) {
-        memcpy(c->pin, Q_xy, 64);
-        chk(hipMemcpyAsync(P + 64 * n, c->pin, 64, hipMemcpyHostToDevice, c->stream));
-        LAUNCH(c, "k_points_to_mont", k_points_to_mont, 1, 256, (const uint32_t*)(P + 64 * n), (uint32_t*)(P + 64 * n), (size_t)1);
-      }
-      sbn_bases* ext = nullptr;
-      if (rc == SBN_OK) rc = bases_from_device(c, P, n + 1, G->has_h ? (const uint8_t*)G->d_pts + 64 * n : nullptr, &ext);
-      if (rc != SBN_OK) { drop(); return rc; }
-      // a small lookup table (comb_kernels.cuh) for the derived set: a round's two-row commit is latency-bound, and the lookup
-      // path has no sort / bucket-reduction stages to wait for.  Best effort: without the memory the bucket path serves.
-      if (bases_build_comb(c, ext->uniq ? ext->uniq : ext, BULLET_COMB_BYTES) != SBN_OK) (void)hipGetLastError();
-      G->bullet_ext.emplace_back(key, ext);
-      st->ext = ext;
+  // the derived generator set for this Q: built once per (G, Q) and kept by G
+  rc = derived_set(G, DERIVED_BULLET, Q_xy ? std::string((const char*)Q_xy, 64) : std::string(), [&](sbn_bases** ext) -> int {
+    if ((rc = ensure(c, c->stage_pts, (n + 2) * 64))) return rc;
+    uint8_t* P = (uint8_t*)c->stage_pts.p;
+    chk(hipMemcpyAsync(P, G->d_pts, n * 64, hipMemcpyDeviceToDevice, c->stream));
+    chk(hipMemsetAsync(P + 64 * n, 0, 64, c->stream));
+    if (Q_xy) {
+      memcpy(c->pin, Q_xy, 64);
+      chk(hipMemcpyAsync(P + 64 * n, c->pin, 64, hipMemcpyHostToDevice, c->stream));
+      LAUNCH(c, "k_points_to_mont", k_points_to_mont, 1, 256, (const uint32_t*)(P + 64 * n), (uint32_t*)(P + 64 * n), (size_t)1);
     }
-  }
+    if (rc == SBN_OK) rc = bases_from_device(c, P, n + 1, G->has_h ? (const uint8_t*)G->d_pts + 64 * n : nullptr, ext);
+    if (rc != SBN_OK) return rc;
+    // a small lookup table (comb_kernels.cuh) for the derived set: a round's two-row commit is latency-bound, and the lookup
+    // path has no sort / bucket-reduction stages to wait for.  Best effort: without the memory the bucket path serves.
+    if (bases_build_comb(c, (*ext)->uniq ? (*ext)->uniq : *ext, BULLET_COMB_BYTES) != SBN_OK) (void)hipGetLastError();
+    return SBN_OK;
+  }, &st->ext);
+  if (rc != SBN_OK) { drop(); return rc; }
   hipError_t e = pool_get(c, (5 * n + 2 * (n + 2) + 2) * 32, &st->slab, &st->slab_bytes);     // from the context's buffer cache: no hipMalloc per proof
   if (e != hipSuccess) { st->slab = nullptr; rc = fail(c, SBN_ENOMEM, "hipMalloc bullet state: %s", hipGetErrorString(e)); }
   else {
@@ -192,7 +177,7 @@ static int bullet_begin_impl(sbn_ctx* c, const sbn_bases* G, const uint8_t* Q_xy
       LAUNCH(c, "k_scalars_from_mont", k_scalars_from_internal, (unsigned)((n + 255) / 256), 256, (const uint32_t*)st->d_a, (uint32_t*)W, n);
       uint8_t* hp = (uint8_t*)c->pin + 1024; memset(hp, 0, 64);
       if (Q_xy) {
-        if (q_scale) { using namespace sbn_host::fr; const El x = mmul(to_m(el_from(ab)), el_from(q_scale)); memcpy(hp, x.v, 32); }     // <a, b> * q_scale: the scalar on Q_base
+        if (q_scale) { const sbn_host::fr::El x = sbn_host::fr::fmul(el_from(ab), el_from(q_scale)); memcpy(hp, x.v, 32); }     // <a, b> * q_scale: the scalar on Q_base
         else memcpy(hp, ab, 32);
       }
       if (blind) memcpy(hp + 32, blind, 32);
@@ -223,31 +208,21 @@ int sbn_bullet_begin_scaled(sbn_ctx* c, const sbn_bases* G, const uint8_t* Q_bas
 }
 
 }  // extern "C"
-// The two rows in st->d_w (n + 1 canonical scalars each, the two blinds behind them) as ONE two-row commit over the derived set, the two XYZZ
-// sums and the 2 x 8 words of st->d_dots to the host mailbox behind it — launches only; *seq is what bullet_rows_collect waits for.
+// A bullet round's hand-over (rows_to_host_launch / _collect; the first words of the mailbox's final-claims area and its flag): the two rows in st->d_w
+// (n + 1 canonical scalars each, the two blinds behind them) as ONE two-row commit, the 2 x 8 words of st->d_dots behind its sums — launches only
+static const uint32_t BULLET_SLOT_WORD = SC_MBOX_FINALS, BULLET_FLAG_WORD = SC_MBOX_FLAGS + SC_PACK_MAX;
 static int bullet_rows_launch(sbn_ctx* c, sbn_bullet* st, uint32_t* seq) {
-  const size_t n = st->n; int rc;
-  uint8_t* WL = (uint8_t*)st->d_w; uint8_t* BL = WL + 64 * (n + 1);
-  if ((rc = ensure(c, c->wsum, 4096))) return rc;                       // (the commit asks for 2 x 128 B: sized here so that it never reallocates mid-round)
-  if ((rc = sc_tickets(c))) return rc;
-  { RowInfo ri; ri.internal_rows = true;
-    if ((rc = commit_rows_launch(c, st->ext, (const uint32_t*)WL, st->has_h ? (const uint32_t*)BL : nullptr, 2, n + 1, nullptr, nullptr, ri))) return rc; }   // sums stay XYZZ in c->wsum
-  *seq = ++c->mbox_seq;
-  LAUNCH(c, "k_points_to_host", k_bullet_to_host, 1, 128, (const uint32_t*)c->wsum.p, (const uint32_t*)st->d_dots, c->mbox + SC_MBOX_FINALS, c->mbox + SC_MBOX_FLAGS + SC_PACK_MAX, *seq);
-  LAUNCHCHK(c);
-  return SBN_OK;
+  const uint32_t* W = (const uint32_t*)st->d_w;
+  return rows_to_host_launch(c, st->ext, W, st->has_h ? W + 16 * (st->n + 1) : nullptr, 2, st->n + 1, (const uint32_t*)st->d_dots, 16, BULLET_SLOT_WORD, BULLET_FLAG_WORD, seq);
 }
 // the one host wait of such a commit: the two points as canonical affine bytes, the two scalars that travelled with them
 static int bullet_rows_collect(sbn_ctx* c, uint32_t seq, uint8_t P0_xy[64], int* P0_inf, uint8_t P1_xy[64], int* P1_inf, uint8_t s0[32], uint8_t s1[32]) {
-  int rc;
-  uint32_t* hfin = c->mbox + SC_MBOX_FINALS;
-  if ((rc = sc_flag_wait(c, c->mbox + SC_MBOX_FLAGS + SC_PACK_MAX, seq))) return rc;
-  sbn_host::Pt S[2]; memcpy(S, hfin, 256);
-  int il = 0, ir = 0;
-  sbn_host::to_affine_bytes2(sbn_host::pt_from_device(S[0]), sbn_host::pt_from_device(S[1]), P0_xy, &il, P1_xy, &ir);   // one binary-Euclid inversion (2-3 us on a host core) for both points
-  if (P0_inf) *P0_inf = il;
-  if (P1_inf) *P1_inf = ir;
-  memcpy(s0, (const uint8_t*)hfin + 256, 32); memcpy(s1, (const uint8_t*)hfin + 288, 32);
+  uint8_t xy[128], s[64]; int inf[2];
+  const int rc = rows_to_host_collect(c, BULLET_SLOT_WORD, BULLET_FLAG_WORD, seq, 2, xy, inf, s, 64);
+  if (rc) return rc;
+  memcpy(P0_xy, xy, 64); memcpy(P1_xy, xy + 64, 64); memcpy(s0, s, 32); memcpy(s1, s + 32, 32);
+  if (P0_inf) *P0_inf = inf[0];
+  if (P1_inf) *P1_inf = inf[1];
   return SBN_OK;
 }
 // One round's device work and its one host wait: [FOLD: the folds with the previous challenge] + the cross dot products + the two commit
@@ -260,7 +235,7 @@ static int bullet_round_locked(sbn_ctx* c, sbn_bullet* st, bool fold, const uint
   uint8_t* WL = (uint8_t*)st->d_w; uint8_t* WR = WL + 32 * (n + 1); uint8_t* BL = WR + 32 * (n + 1);
   const uint32_t nbd = (uint32_t)std::max<size_t>(1, (h + 255) / 256);
   if ((rc = ensure(c, c->sc_partial, std::max<size_t>(4096, (size_t)nbd * 96)))) return rc;
-  if ((rc = ensure(c, c->wsum, 4096))) return rc;                       // (sized ahead of the launches below, as bullet_rows_launch does)
+  if ((rc = ensure(c, c->wsum, 4096))) return rc;                       // (sized ahead of the launches below, so that rows_to_host_launch never reallocates mid-round)
   if ((rc = sc_tickets(c))) return rc;
   ScScalar su, si, sl, sr; memset(&su, 0, sizeof su); memset(&si, 0, sizeof si); memset(&sl, 0, sizeof sl); memset(&sr, 0, sizeof sr);
   if (fold) { su = scs_from(sbn_host::fr::to_dev_mont(el_from(u))); si = scs_from(sbn_host::fr::to_dev_mont(el_from(u_inv))); }

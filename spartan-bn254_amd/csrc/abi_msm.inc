@@ -92,8 +92,8 @@ void sbn_bases_free(sbn_ctx* c, sbn_bases* b) {
   if (!b) return;
   if (c) { hipSetDevice(c->device); hipStreamSynchronize(c->stream); }     // nothing may still be reading the tables
   if (b->uniq) { sbn_bases_free(c, b->uniq); b->uniq = nullptr; }
-  for (auto& kv : b->bullet_ext) sbn_bases_free(c, kv.second);
-  b->bullet_ext.clear();
+  for (auto& kv : b->derived) sbn_bases_free(c, kv.second);
+  b->derived.clear();
   for (void* p : {b->d_comb, b->d_csr_off, b->d_csr_cols, b->d_big, b->d_glv, b->d_pts}) if (p) hipFree(p);
   for (auto& kv : b->tables) hipFree(kv.second);
   delete b;
@@ -258,18 +258,7 @@ int sbn_commit_rows(sbn_ctx* c, const sbn_bases* b, const uint8_t* Z, const uint
 
 int sbn_g1_compress(const uint8_t* xy, size_t n, uint8_t* out32) {
   if ((!xy || !out32) && n) return SBN_EINVAL;
-  for (size_t i = 0; i < n; i++) {
-    const uint8_t* p = xy + 64 * i; uint8_t* o = out32 + 32 * i;
-    bool inf = true; for (int k = 0; k < 64; k++) if (p[k]) { inf = false; break; }
-    if (inf) { memset(o, 0, 32); o[31] = 0x40; continue; }
-    memcpy(o, p, 32);
-    // y > p - y  <=>  2y > p
-    uint64_t y[4], t[4]; memcpy(y, p + 32, 32);
-    uint64_t cy = 0; for (int k = 0; k < 4; k++) { t[k] = (y[k] << 1) | cy; cy = y[k] >> 63; }
-    bool gt = cy != 0;
-    if (!gt) { gt = false; for (int k = 3; k >= 0; k--) { if (t[k] > sbn_host::QP[k]) { gt = true; break; } if (t[k] < sbn_host::QP[k]) break; } }
-    if (gt) o[31] |= 0x80;
-  }
+  for (size_t i = 0; i < n; i++) sbn_host::g1_compress(xy + 64 * i, out32 + 32 * i);
   return SBN_OK;
 }
 int sbn_g1_sum(const uint8_t* xy, size_t n, uint8_t out_xy[64], int* out_is_inf) {
@@ -401,6 +390,25 @@ static int bases_from_device(sbn_ctx* c, const void* d_G, size_t n, const void* 
   *out = b;
   return SBN_OK;
 }
+}  // extern "C"
+// The generator sets the provers derive from a caller's handle, each built once and kept by that handle (sbn_bases::derived, released with it).
+// A key is the kind byte, then what tells two sets of a kind apart (a bullet set's Q or nothing, a ZK set's gens_1 points): kinds never collide.
+enum DerivedKind : char { DERIVED_BULLET = 1, DERIVED_POLYEVAL, DERIVED_ZK, DERIVED_R1CS_GENS_N, DERIVED_R1CS_GENS_1 };
+static std::mutex g_derived_mu;      // guards every handle's `derived`; taken with the context's mutex held, never the other way round
+// the set `owner` keeps under (kind, rest), built by build(&set) on the first call
+template <class Build>
+static int derived_set(const sbn_bases* owner, DerivedKind kind, const std::string& rest, Build build, const sbn_bases** out) {
+  const std::string key = std::string(1, (char)kind) + rest;
+  std::lock_guard<std::mutex> tg(g_derived_mu);
+  for (auto& kv : owner->derived) if (kv.first == key) { *out = kv.second; return SBN_OK; }
+  sbn_bases* set = nullptr;
+  const int rc = build(&set);
+  if (rc != SBN_OK) return rc;
+  owner->derived.emplace_back(key, set);
+  *out = set;
+  return SBN_OK;
+}
+extern "C" {
 int sbn_bases_split_at(sbn_ctx* c, const sbn_bases* b, size_t mid, sbn_bases** left, sbn_bases** right) {
   if (!c || !b || !left || !right || mid > b->n) return SBN_EINVAL;
   std::lock_guard<std::mutex> g(c->mu);

@@ -30,29 +30,14 @@ static void polyeval_host_eq(const uint8_t* r, size_t m, std::vector<uint8_t>& o
   out.resize(32 * N);
   for (size_t i = 0; i < N; i++) memcpy(&out[32 * i], e[i].v, 32);
 }
-static inline sbn_host::fr::El polyeval_mul(const sbn_host::fr::El& a, const sbn_host::fr::El& b) { return sbn_host::fr::mmul(sbn_host::fr::to_m(a), b); }
-static void polyeval_append_point(sbn_host::MerlinTranscript& t, const char* label, const uint8_t xy[64], uint8_t out32[32]) {
-  sbn_g1_compress(xy, 1, out32);                                  // serialize_compressed (transcript.rs:102-108)
-  t.append_message((const uint8_t*)label, strlen(label), out32, 32);
-}
-static void polyeval_challenge(sbn_host::MerlinTranscript& t, const char* label, uint8_t out[32]) {
-  uint8_t b[64];
-  t.challenge_bytes((const uint8_t*)label, strlen(label), b, 64);
-  transcript_wide_reduce(b, out);
-}
-
 // the copy of the caller's R_size + 1 generators (+ h) that the commits run over, with its lookup table: built on the first opening, owned by `gens`
 static int polyeval_ext(sbn_ctx* c, const sbn_bases* gens, const sbn_bases** out) {
-  static const std::string key("\x01polyeval");                  // (the bullet states' keys are empty or the 64 bytes of Q)
-  std::lock_guard<std::mutex> tg(g_bullet_ext_mu);
-  for (auto& kv : gens->bullet_ext) if (kv.first == key) { *out = kv.second; return SBN_OK; }
-  sbn_bases* ext = nullptr;
-  int rc = bases_from_device(c, gens->d_pts, gens->n, (const uint8_t*)gens->d_pts + 64 * gens->n, &ext);
-  if (rc != SBN_OK) return rc;
-  if (bases_build_comb(c, ext->uniq ? ext->uniq : ext, BULLET_COMB_BYTES) != SBN_OK) (void)hipGetLastError();     // best effort, as in bullet_begin_impl
-  gens->bullet_ext.emplace_back(key, ext);
-  *out = ext;
-  return SBN_OK;
+  return derived_set(gens, DERIVED_POLYEVAL, std::string(), [&](sbn_bases** ext) -> int {
+    const int rc = bases_from_device(c, gens->d_pts, gens->n, (const uint8_t*)gens->d_pts + 64 * gens->n, ext);
+    if (rc != SBN_OK) return rc;
+    if (bases_build_comb(c, (*ext)->uniq ? (*ext)->uniq : *ext, BULLET_COMB_BYTES) != SBN_OK) (void)hipGetLastError();     // best effort, as in bullet_begin_impl
+    return SBN_OK;
+  }, out);
 }
 
 static int polyeval_check(sbn_ctx* c, const sbn_bases* gens, const sbn_table* Z, const uint8_t* blinds, const uint8_t* r, size_t ell, const uint8_t* Zr,
@@ -75,6 +60,7 @@ static int polyeval_prove_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_ta
   using namespace sbn_host::fr;
   typedef std::chrono::steady_clock clk;
   const size_t ml = ell / 2, mr = ell - ml, L_size = (size_t)1 << ml, n = (size_t)1 << mr, lg = mr;
+  sbn_host::Script ts{t};
   int rc;
   sbn_bullet st; st.n = st.m = n; st.has_q = true; st.has_h = true; st.q_scaled = true; memset(&st.qs, 0, sizeof st.qs);
   if ((rc = polyeval_ext(c, gens, &st.ext))) return rc;
@@ -93,8 +79,8 @@ static int polyeval_prove_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_ta
   uint32_t* W0 = (uint32_t*)st.d_w; uint32_t* W1 = W0 + 8 * (n + 1); uint32_t* BL = W1 + 8 * (n + 1);
   uint32_t* d_L = (uint32_t*)st.d_a2; uint32_t* d_blinds = (uint32_t*)st.d_b2;       // free until the first fold writes the ping-pong halves
 
-  t.append_message((const uint8_t*)"protocol-name", 13, (const uint8_t*)"polynomial evaluation proof", 27);      // hyrax.rs:75
-  t.append_message((const uint8_t*)"protocol-name", 13, (const uint8_t*)"dot product proof (log)", 23);          // nizk/mod.rs:451
+  ts.protocol("polynomial evaluation proof");                     // hyrax.rs:75
+  ts.protocol("dot product proof (log)");                         // nizk/mod.rs:451
   const uint8_t* d = rnd; const uint8_t* r_delta = rnd + 32; const uint8_t* r_beta = rnd + 64; const uint8_t* blinds_vec = rnd + 96;
 
   // ---- front: L, R, L*Z, <blinds, L>, the Cx / Cy rows; one two-row commit ----
@@ -125,18 +111,18 @@ static int polyeval_prove_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_ta
   if ((rc = bullet_rows_collect(c, seq, out_Cx_xy, Cx_is_inf, out_Cy_xy, Cy_is_inf, bx, zero32))) return rc;
   const clk::time_point h2 = clk::now();
   uint8_t comp[32];
-  polyeval_append_point(t, "Cx", out_Cx_xy, comp);                // nizk/mod.rs:470-474
-  polyeval_append_point(t, "Cy", out_Cy_xy, comp);
-  for (size_t i = 0; i < n; i++) t.append_message((const uint8_t*)"a", 1, &Rv[32 * i], 32);      // nizk/mod.rs:476 -> transcript.rs:46-50
+  ts.point_xy("Cx", out_Cx_xy, comp);                             // nizk/mod.rs:470-474
+  ts.point_xy("Cy", out_Cy_xy, comp);
+  ts.scalars("a", Rv.data(), n);                                  // nizk/mod.rs:476
   const clk::time_point h3 = clk::now();
   c->polyeval_us[0] = std::chrono::duration<double, std::micro>(h1 - h0).count();
   c->polyeval_us[1] = std::chrono::duration<double, std::micro>(h2 - h1).count();
   c->polyeval_us[2] = std::chrono::duration<double, std::micro>(h3 - h2).count();
   uint8_t rq[32];
-  polyeval_challenge(t, "r", rq);                                 // nizk/mod.rs:480: Q = r * Q_base
+  ts.challenge("r", rq);                                          // nizk/mod.rs:480: Q = r * Q_base
   st.qs = scs_from(to_dev_mont(el_from(rq)));
   El blind_G = el_from(bx);                                       // blind_Gamma = blind_x + r * blind_y (nizk/mod.rs:483)
-  if (blind_Zr) blind_G = add(blind_G, polyeval_mul(el_from(rq), el_from(blind_Zr)));
+  if (blind_Zr) blind_G = add(blind_G, fmul(el_from(rq), el_from(blind_Zr)));
 
   // ---- the rounds (bullet.rs:63-108): one launch + one two-row commit + one wait each ----
   uint8_t u[32] = {0}, ui[32] = {0};
@@ -144,20 +130,20 @@ static int polyeval_prove_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_ta
     const uint8_t* bL = blinds_vec + 64 * j; const uint8_t* bR = bL + 32;
     uint8_t Lxy[64], Rxy[64], cl[32], cr[32]; int li = 0, ri = 0;
     if ((rc = bullet_round_locked(c, &st, j > 0, u, ui, bL, bR, Lxy, &li, Rxy, &ri, cl, cr))) return rc;
-    polyeval_append_point(t, "L", Lxy, out_proof + 32 * j);
-    polyeval_append_point(t, "R", Rxy, out_proof + 32 * (lg + j));
-    polyeval_challenge(t, "u", u);
+    ts.point_xy("L", Lxy, out_proof + 32 * j);
+    ts.point_xy("R", Rxy, out_proof + 32 * (lg + j));
+    ts.challenge("u", u);
     const El eu = el_from(u);
     if (is_zero(eu)) return fail(c, SBN_EINVAL, "polyeval: the challenge u of round %zu is zero  [bullet.rs:82 unwrap]", j);
     const El eui = inv(eu);
     memcpy(ui, eui.v, 32);
-    blind_G = add(add(polyeval_mul(polyeval_mul(eu, eu), el_from(bL)), blind_G), polyeval_mul(polyeval_mul(eui, eui), el_from(bR)));     // bullet.rs:104
+    blind_G = add(add(fmul(fmul(eu, eu), el_from(bL)), blind_G), fmul(fmul(eui, eui), el_from(bR)));     // bullet.rs:104
   }
 
   // ---- close: the last fold, the delta / beta rows; one two-row commit ----
   {
     const ScScalar su = scs_from(to_dev_mont(el_from(u))), si = scs_from(to_dev_mont(el_from(ui))), sd = scs_from(to_dev_mont(el_from(d)));
-    const ScScalar sdr = scs_from(polyeval_mul(el_from(d), el_from(rq)));
+    const ScScalar sdr = scs_from(fmul(el_from(d), el_from(rq)));
     ScScalar s1, s2; memcpy(s1.v, r_delta, 32); memcpy(s2.v, r_beta, 32);
     LAUNCH(c, "k_polyeval_close", k_polyeval_close, (unsigned)((n + 255) / 256), 256, (const uint32_t*)st.d_a, (const uint32_t*)st.d_b, (const uint32_t*)st.d_s,
            W0, W1, BL, (uint32_t*)st.d_dots, n, su, si, sd, sdr, s1, s2);
@@ -166,14 +152,14 @@ static int polyeval_prove_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_ta
   if ((rc = bullet_rows_launch(c, &st, &seq))) return rc;
   uint8_t dxy[64], bxy[64], ah[32], bh[32]; int di = 0, bi = 0;
   if ((rc = bullet_rows_collect(c, seq, dxy, &di, bxy, &bi, ah, bh))) return rc;
-  polyeval_append_point(t, "delta", dxy, out_proof + 64 * lg);    // nizk/mod.rs:501-504
-  polyeval_append_point(t, "beta", bxy, out_proof + 64 * lg + 32);
+  ts.point_xy("delta", dxy, out_proof + 64 * lg);     // nizk/mod.rs:501-504
+  ts.point_xy("beta", bxy, out_proof + 64 * lg + 32);
   uint8_t cc[32];
-  polyeval_challenge(t, "c", cc);
+  ts.challenge("c", cc);
   // x_hat = a_hat of the reduction (the fold of x_vec = L*Z), a_hat = its b_hat (the fold of a_vec = R)   (nizk/mod.rs:484, :495, :508-509)
   const El ec = el_from(cc), x_hat = el_from(ah), a_hat = el_from(bh);
-  const El z1 = add(el_from(d), polyeval_mul(ec, polyeval_mul(x_hat, a_hat)));
-  const El z2 = add(polyeval_mul(a_hat, add(polyeval_mul(ec, blind_G), el_from(r_beta))), el_from(r_delta));
+  const El z1 = add(el_from(d), fmul(ec, fmul(x_hat, a_hat)));
+  const El z2 = add(fmul(a_hat, add(fmul(ec, blind_G), el_from(r_beta))), el_from(r_delta));
   memcpy(out_proof + 64 * lg + 64, z1.v, 32); memcpy(out_proof + 64 * lg + 96, z2.v, 32);
   return SBN_OK;
 }
@@ -187,23 +173,22 @@ int sbn_polyeval_prove(sbn_ctx* c, const sbn_bases* gens, const sbn_table* Z, co
   int rc;
   if ((rc = polyeval_check(c, gens, Z, blinds, r, ell, Zr, blind_Zr, rnd))) return rc;
   std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
-  sbn_host::MerlinTranscript t = tr->t;
-  if ((rc = polyeval_prove_locked(c, gens, Z, blinds, r, ell, Zr, blind_Zr, rnd, t, out_proof, out_Cx_xy, Cx_is_inf, out_Cy_xy, Cy_is_inf))) return rc;
-  tr->t = t;
-  return SBN_OK;
+  return prove_on_copy(c, tr, [&](sbn_host::MerlinTranscript& t) {
+    return polyeval_prove_locked(c, gens, Z, blinds, r, ell, Zr, blind_Zr, rnd, t, out_proof, out_Cx_xy, Cx_is_inf, out_Cy_xy, Cy_is_inf);
+  });
 }
 
 }  // extern "C"
 // the reduction both builds' joint openings start with (sparse_mlpoly_full.rs:384-397, :514-535): the evals under `label_evals`, lc challenges, the fold
 // of the evals from the last challenge down, the joint claim under `label_claim`.  rj: the lc challenges, then r; claim: canonical
-static void joint_reduce(const uint8_t* evals, size_t count, size_t lc, const uint8_t* label_evals, size_t label_evals_len, const uint8_t* label_chal, size_t label_chal_len,
-                         const uint8_t* label_claim, size_t label_claim_len, const uint8_t* r, size_t ell_r, sbn_host::MerlinTranscript& t,
-                         std::vector<uint8_t>& rj, uint8_t claim[32]) {
+static void joint_reduce(const uint8_t* evals, size_t count, size_t lc, sbn_host::Label label_evals, sbn_host::Label label_chal, sbn_host::Label label_claim,
+                         const uint8_t* r, size_t ell_r, sbn_host::MerlinTranscript& t, std::vector<uint8_t>& rj, uint8_t claim[32]) {
   using namespace sbn_host::fr;
   const size_t ell = lc + ell_r;
-  for (size_t i = 0; i < count; i++) t.append_message(label_evals, label_evals_len, evals + 32 * i, 32);      // sparse_mlpoly_full.rs:384
+  sbn_host::Script ts{t};
+  ts.scalars(label_evals, evals, count);                           // sparse_mlpoly_full.rs:384
   rj.assign(32 * ell, 0);
-  for (size_t j = 0; j < lc; j++) { uint8_t b[64]; t.challenge_bytes(label_chal, label_chal_len, b, 64); transcript_wide_reduce(b, &rj[32 * j]); }     // :387
+  ts.challenges(label_chal, rj.data(), lc);                        // :387
   if (ell_r) memcpy(&rj[32 * lc], r, 32 * ell_r);
   std::vector<El> pe(count);
   for (size_t i = 0; i < count; i++) pe[i] = el_from(evals + 32 * i);
@@ -214,19 +199,19 @@ static void joint_reduce(const uint8_t* evals, size_t count, size_t lc, const ui
     for (size_t i = 0; i < len; i++) pe[i] = add(pe[2 * i], mmul(cj, sub(pe[2 * i + 1], pe[2 * i])));
   }
   memcpy(claim, pe[0].v, 32);
-  t.append_message(label_claim, label_claim_len, claim, 32);       // :397
+  ts.scalar(label_claim, claim);                                   // :397
 }
 
 // the reduction and the opening on the transcript `t` (a copy of the caller's); count = 2^lc evals, canonical as r is; the caller holds the
 // context's mutex.  out_challenges: lc x 32 or NULL
 static int joint_opening_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_table* Z, const uint8_t* evals, size_t count, size_t lc,
-                                const uint8_t* label_evals, size_t label_evals_len, const uint8_t* label_chal, size_t label_chal_len,
-                                const uint8_t* label_claim, size_t label_claim_len, const uint8_t* r, size_t ell_r, const uint8_t* rnd, sbn_host::MerlinTranscript& t,
+                                sbn_host::Label label_evals, sbn_host::Label label_chal, sbn_host::Label label_claim,
+                                const uint8_t* r, size_t ell_r, const uint8_t* rnd, sbn_host::MerlinTranscript& t,
                                 uint8_t* out_challenges, uint8_t out_joint_claim[32], uint8_t* out_proof,
                                 uint8_t out_Cx_xy[64], int* Cx_is_inf, uint8_t out_Cy_xy[64], int* Cy_is_inf) {
   const size_t ell = lc + ell_r;
   std::vector<uint8_t> rj; uint8_t claim[32];
-  joint_reduce(evals, count, lc, label_evals, label_evals_len, label_chal, label_chal_len, label_claim, label_claim_len, r, ell_r, t, rj, claim);
+  joint_reduce(evals, count, lc, label_evals, label_chal, label_claim, r, ell_r, t, rj, claim);
   int rc;
   if ((rc = polyeval_check(c, gens, Z, nullptr, rj.data(), ell, claim, nullptr, rnd))) return rc;
   if ((rc = polyeval_prove_locked(c, gens, Z, nullptr, rj.data(), ell, claim, nullptr, rnd, t, out_proof, out_Cx_xy, Cx_is_inf, out_Cy_xy, Cy_is_inf))) return rc;
@@ -251,12 +236,11 @@ int sbn_joint_opening_prove(sbn_ctx* c, const sbn_bases* gens, const sbn_table* 
   if (ell > 2 * (size_t)PE_SIDE_MAX) return fail(c, SBN_EINVAL, "joint opening: %zu variables", ell);
   for (size_t j = 0; j < ell_r; j++) if (!fr_canonical(r + 32 * j)) return fail(c, SBN_EINVAL, "joint opening: r[%zu] is not canonical", j);
   std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
-  sbn_host::MerlinTranscript t = tr->t;
-  const int rc = joint_opening_locked(c, gens, Z, evals, count, lc, label_evals, label_evals_len, label_chal, label_chal_len, label_claim, label_claim_len, r, ell_r, rnd, t,
-                                      out_challenges, out_joint_claim, out_proof, out_Cx_xy, Cx_is_inf, out_Cy_xy, Cy_is_inf);
-  if (rc) return rc;
-  tr->t = t;
-  return SBN_OK;
+  using sbn_host::Label;
+  return prove_on_copy(c, tr, [&](sbn_host::MerlinTranscript& t) {
+    return joint_opening_locked(c, gens, Z, evals, count, lc, Label(label_evals, label_evals_len), Label(label_chal, label_chal_len), Label(label_claim, label_claim_len),
+                                r, ell_r, rnd, t, out_challenges, out_joint_claim, out_proof, out_Cx_xy, Cx_is_inf, out_Cy_xy, Cy_is_inf);
+  });
 }
 
 // host microseconds of the context's most recent opening: {R = a_vec computed on the host, the wait for the Cx / Cy commit behind it,

@@ -27,15 +27,10 @@ static bool r1cs_proof_shape(size_t num_cons, size_t num_vars, R1csProofShape* s
 // gens_n (the first R generators of gens_pc, with h) and gens_1 = (G[R], h) (DotProductProofGens::new, nizk/mod.rs:412-415) as handles of their
 // own: sbn_bases_split_at's copies, made on the first call and owned by gens_pc
 static int r1cs_proof_gens(sbn_ctx* c, const sbn_bases* pc, size_t R, const sbn_bases** gn, const sbn_bases** g1) {
-  static const std::string kn("\x03r1cs_gens_n"), k1("\x03r1cs_gens_1");
-  std::lock_guard<std::mutex> tg(g_bullet_ext_mu);
-  *gn = *g1 = nullptr;
-  for (auto& kv : pc->bullet_ext) { if (kv.first == kn) *gn = kv.second; if (kv.first == k1) *g1 = kv.second; }
   const uint8_t* p = (const uint8_t*)pc->d_pts; const void* h = p + 64 * pc->n;
   int rc;
-  if (!*gn) { sbn_bases* b = nullptr; if ((rc = bases_from_device(c, p, R, h, &b))) return rc; pc->bullet_ext.emplace_back(kn, b); *gn = b; }
-  if (!*g1) { sbn_bases* b = nullptr; if ((rc = bases_from_device(c, p + 64 * R, 1, h, &b))) return rc; pc->bullet_ext.emplace_back(k1, b); *g1 = b; }
-  return SBN_OK;
+  if ((rc = derived_set(pc, DERIVED_R1CS_GENS_N, std::string(), [&](sbn_bases** b) { return bases_from_device(c, p, R, h, b); }, gn))) return rc;
+  return derived_set(pc, DERIVED_R1CS_GENS_1, std::string(), [&](sbn_bases** b) { return bases_from_device(c, p + 64 * R, 1, h, b); }, g1);
 }
 
 // nrows <= 11 elements v * G + b * h over gens_1 as ONE commit over the (gens_1, gens_4) set and ONE host wait; vb: v, b per row, canonical.
@@ -44,26 +39,17 @@ static int r1cs_proof_sigma_rows(sbn_ctx* c, const sbn_bases* ext, const sbn_hos
   int rc;
   const size_t R = ext->n;                                          // gens_4's 4 + its h + gens_1's two points, no blind column
   if ((rc = ensure(c, c->sc_prove, (size_t)R1CS_SIGMA_ROWS_MAX * R * 32))) return rc;
-  if ((rc = ensure(c, c->wsum, 4096))) return rc;
   R1csSigmaRows A; memset(&A, 0, sizeof A);
   for (uint32_t i = 0; i < nrows; i++) { memcpy(A.vb[i], vb[i][0].v, 32); memcpy(A.vb[i] + 8, vb[i][1].v, 32); }
   uint32_t* rows = (uint32_t*)c->sc_prove.p;
   LAUNCH(c, "k_r1cs_sigma_rows", k_r1cs_sigma_rows, 1, 256, rows, (uint32_t)R, nrows, A);
-  { RowInfo ri; ri.internal_rows = true;
-    if ((rc = commit_rows_launch(c, ext, rows, nullptr, nrows, R, nullptr, nullptr, ri))) return rc; }     // sums stay XYZZ in c->wsum
-  const uint32_t seq = ++c->mbox_seq;
-  LAUNCH(c, "k_points_to_host", k_r1cs_points_to_host, 1, 256, (const uint32_t*)c->wsum.p, nrows, zk_slot(c, 0), zk_flag(c, 0), seq);
-  LAUNCHCHK(c);
-  if ((rc = sc_flag_wait(c, zk_flag(c, 0), seq))) return rc;
-  sbn_host::Pt S[R1CS_SIGMA_ROWS_MAX]; memcpy(S, zk_slot(c, 0), (size_t)nrows * 128);
-  for (uint32_t i = 0; i < nrows; i++) S[i] = sbn_host::pt_from_device(S[i]);
+  uint32_t seq = 0;
   uint8_t xy[R1CS_SIGMA_ROWS_MAX * 64];
-  sbn_host::to_affine_bytes_n(S, nrows, xy, nullptr);
+  if ((rc = rows_to_host_launch(c, ext, rows, nullptr, nrows, R, nullptr, 0u, zk_slot_word(0), zk_flag_word(0), &seq))) return rc;
+  if ((rc = rows_to_host_collect(c, zk_slot_word(0), zk_flag_word(0), seq, nrows, xy, nullptr, nullptr, 0))) return rc;
   sbn_g1_compress(xy, nrows, out);
   return SBN_OK;
 }
-
-static void r1cs_proof_name(sbn_host::MerlinTranscript& t, const char* name) { t.append_message((const uint8_t*)"protocol-name", 13, (const uint8_t*)name, strlen(name)); }
 
 // the proof on the transcript `t` (a copy of the caller's); arguments already checked
 static int r1cs_proof_locked(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* vars, const uint8_t* input, size_t num_inputs, const sbn_bases* gens_pc,
@@ -72,7 +58,7 @@ static int r1cs_proof_locked(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* var
   using namespace sbn_host::fr;
   TableScope T(c);                                                 // every intermediate table of the call
   sbn_table *eq = nullptr, *z = nullptr, *in = nullptr, *Az = nullptr, *Bz = nullptr, *Cz = nullptr, *abc = nullptr, *chi = nullptr;
-  auto fmul = [](const El& a, const El& b) { return mmul(to_m(a), b); };
+  sbn_host::Script ts{t};
   auto put = [](uint8_t* o, const El& e) { memcpy(o, e.v, 32); };
   int rc;
   // rnd: the RandomTape draws in the reference's order
@@ -102,8 +88,8 @@ static int r1cs_proof_locked(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* var
   if ((rc = ensure_pin(c, 8192 + 32 * s.rnd_scalars + 65 * s.L))) return rc;      // (sized once: no call below grows it mid-flight)
 
   // ---- 1. the statement (r1csproof.rs:250-255; a slice of scalars is one message per scalar, transcript.rs:46-50) ----
-  r1cs_proof_name(t, "R1CS proof");
-  for (size_t i = 0; i < num_inputs; i++) t.append_message((const uint8_t*)"input", 5, input + 32 * i, 32);
+  ts.protocol("R1CS proof");
+  ts.scalars("input", input, num_inputs);
 
   // ---- 2. the witness commitment (commit_poly, r1csproof.rs:210-237): one L x R commit, absorbed as PolyCommitment (:28-36) ----
   {
@@ -124,14 +110,14 @@ static int r1cs_proof_locked(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* var
     std::vector<uint8_t> xy(64 * s.L);
     if ((rc = commit_rows_device(c, gens_n, dZ, dB, s.L, s.R, xy.data(), nullptr, ri))) return rc;
     sbn_g1_compress(xy.data(), s.L, o_comm);
-    t.append_message((const uint8_t*)"poly_commitment", 15, (const uint8_t*)"poly_commitment_begin", 21);
-    for (size_t i = 0; i < s.L; i++) zk_append_point(t, "poly_commitment_share", o_comm + 32 * i);
-    t.append_message((const uint8_t*)"poly_commitment", 15, (const uint8_t*)"poly_commitment_end", 19);
+    ts.message("poly_commitment", "poly_commitment_begin", 21);
+    for (size_t i = 0; i < s.L; i++) ts.point("poly_commitment_share", o_comm + 32 * i);
+    ts.message("poly_commitment", "poly_commitment_end", 19);
   }
 
   // ---- 3. phase 1 (r1csproof.rs:268-313) ----
   std::vector<uint8_t> tau(32 * s.nx);
-  for (size_t j = 0; j < s.nx; j++) polyeval_challenge(t, "challenge_tau", &tau[32 * j]);     // challenge_vector, transcript.rs:66-70
+  ts.challenges("challenge_tau", tau.data(), s.nx);               // challenge_vector
   if ((rc = eq_evals_locked(c, tau.data(), s.nx, &eq))) return rc;
   T.keep(eq);
   if ((rc = T.alloc(2 * m->nv, "r1cs table", &z))) return rc;
@@ -171,33 +157,33 @@ static int r1cs_proof_locked(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* var
     if ((rc = r1cs_proof_sigma_rows(c, ext, vb, 11, P))) return rc;
     const uint8_t *pC = P, *pKa = P + 32, *pX = P + 64, *pY = P + 96, *pZ = P + 128, *pPa = P + 160, *pPb = P + 192, *pPd = P + 224, *pC1 = P + 256, *pC2 = P + 288, *pEa = P + 320;
     uint8_t cb[32];
-    r1cs_proof_name(t, "knowledge proof");                          // nizk/mod.rs:41
-    zk_append_point(t, "C", pC); zk_append_point(t, "alpha", pKa);
-    polyeval_challenge(t, "c", cb);
+    ts.protocol("knowledge proof");                                 // nizk/mod.rs:41
+    ts.point("C", pC); ts.point("alpha", pKa);
+    ts.challenge("c", cb);
     El cc = el_from(cb);
     memcpy(o_pok, pKa, 32); put(o_pok + 32, add(fmul(Cz_c, cc), t1)); put(o_pok + 64, add(fmul(Cz_b, cc), t2));      // :55-56
-    r1cs_proof_name(t, "product proof");                            // :178
-    zk_append_point(t, "X", pX); zk_append_point(t, "Y", pY); zk_append_point(t, "Z", pZ);
-    zk_append_point(t, "alpha", pPa); zk_append_point(t, "beta", pPb); zk_append_point(t, "delta", pPd);
-    polyeval_challenge(t, "c", cb);
+    ts.protocol("product proof");                                   // :178
+    ts.point("X", pX); ts.point("Y", pY); ts.point("Z", pZ);
+    ts.point("alpha", pPa); ts.point("beta", pPb); ts.point("delta", pPd);
+    ts.challenge("c", cb);
     cc = el_from(cb);
     uint8_t* pp = o_pok + 96;
     memcpy(pp, pPa, 32); memcpy(pp + 32, pPb, 32); memcpy(pp + 64, pPd, 32);
     put(pp + 96, add(b1, fmul(cc, Az_c))); put(pp + 128, add(b2, fmul(cc, Az_b))); put(pp + 160, add(b3, fmul(cc, Bz_c))); put(pp + 192, add(b4, fmul(cc, Bz_b)));
     put(pp + 224, add(b5, fmul(cc, sub(prod_b, fmul(Az_b, Bz_c)))));                                                  // :210-214
     memcpy(o_claims, pX, 32); memcpy(o_claims + 32, pY, 32); memcpy(o_claims + 64, pC, 32); memcpy(o_claims + 96, pZ, 32);
-    zk_append_point(t, "comm_Az_claim", pX); zk_append_point(t, "comm_Bz_claim", pY);                                 // r1csproof.rs:349-352
-    zk_append_point(t, "comm_Cz_claim", pC); zk_append_point(t, "comm_prod_Az_Bz_claims", pZ);
-    r1cs_proof_name(t, "equality proof");                           // nizk/mod.rs:105
-    zk_append_point(t, "C1", pC1); zk_append_point(t, "C2", pC2); zk_append_point(t, "alpha", pEa);
-    polyeval_challenge(t, "c", cb);
+    ts.point("comm_Az_claim", pX); ts.point("comm_Bz_claim", pY);                                                     // r1csproof.rs:349-352
+    ts.point("comm_Cz_claim", pC); ts.point("comm_prod_Az_Bz_claims", pZ);
+    ts.protocol("equality proof");                                  // nizk/mod.rs:105
+    ts.point("C1", pC1); ts.point("C2", pC2); ts.point("alpha", pEa);
+    ts.challenge("c", cb);
     cc = el_from(cb);
     memcpy(o_eq1, pEa, 32); put(o_eq1 + 32, add(fmul(cc, sub(blind_expected, el_from(blind_post1))), r1));            // :121
   }
 
   // ---- 5. phase 2 (r1csproof.rs:368-406) ----
   uint8_t rA[32], rB[32], rC[32];
-  polyeval_challenge(t, "challenge_Az", rA); polyeval_challenge(t, "challenge_Bz", rB); polyeval_challenge(t, "challenge_Cz", rC);
+  ts.challenge("challenge_Az", rA); ts.challenge("challenge_Bz", rB); ts.challenge("challenge_Cz", rC);
   const El claim2 = add(add(fmul(el_from(rA), Az_c), fmul(el_from(rB), Bz_c)), fmul(el_from(rC), Cz_c));              // :373
   const El blind2 = add(add(fmul(el_from(rA), Az_b), fmul(el_from(rB), Bz_b)), fmul(el_from(rC), Cz_b));              // :374
   if ((rc = r1cs_eval_table_locked(c, m, out_rx, s.nx, rA, rB, rC, &abc))) return rc;
@@ -229,9 +215,9 @@ static int r1cs_proof_locked(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* var
     const El vb[3][2] = {{claim_post, blind_expected}, {claim_post, el_from(blind_post2)}, {from_u64(0), r2}};
     uint8_t P[3 * 32], cb[32];
     if ((rc = r1cs_proof_sigma_rows(c, ext, vb, 3, P))) return rc;
-    r1cs_proof_name(t, "equality proof");
-    zk_append_point(t, "C1", P); zk_append_point(t, "C2", P + 32); zk_append_point(t, "alpha", P + 64);
-    polyeval_challenge(t, "c", cb);
+    ts.protocol("equality proof");
+    ts.point("C1", P); ts.point("C2", P + 32); ts.point("alpha", P + 64);
+    ts.challenge("c", cb);
     memcpy(o_eq2, P + 64, 32); put(o_eq2 + 32, add(fmul(el_from(cb), sub(blind_expected, el_from(blind_post2))), r2));
   }
   if (c->prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); prof_drain(c); }
@@ -265,11 +251,7 @@ int sbn_r1cs_proof_prove(sbn_ctx* c, const sbn_r1cs* inst, const sbn_table* vars
   if (gens_4->n != 4 || !gens_4->has_h) return fail(c, SBN_EINVAL, "r1cs proof: gens_4 has %zu points%s, 4 generators with h are needed  [nizk/mod.rs:322 assert_eq]", gens_4->n, gens_4->has_h ? "" : " and no h");
   for (size_t i = 0; i < num_inputs; i++) if (!fr_canonical(input + 32 * i)) return fail(c, SBN_EINVAL, "r1cs proof: input[%zu] is not canonical  [scalar.rs:87-95]", i);
   for (size_t i = 0; i < s.rnd_scalars; i++) if (!fr_canonical(rnd + 32 * i)) return fail(c, SBN_EINVAL, "r1cs proof: rnd[%zu] is not canonical  [scalar.rs:87-95]", i);
-  sbn_host::MerlinTranscript t = tr->t;
-  const int rc = r1cs_proof_locked(c, inst, vars, input, num_inputs, gens_pc, gens_3, gens_4, s, rnd, t, out_proof, out_rx, out_ry);
-  if (rc) return rc;
-  tr->t = t;
-  return SBN_OK;
+  return prove_on_copy(c, tr, [&](sbn_host::MerlinTranscript& t) { return r1cs_proof_locked(c, inst, vars, input, num_inputs, gens_pc, gens_3, gens_4, s, rnd, t, out_proof, out_rx, out_ry); });
 }
 
 }  // extern "C"

@@ -50,8 +50,6 @@ static bool sparse_eval_shape(size_t nx, size_t ny, size_t N, size_t batch, Spar
   return true;
 }
 
-static void sparse_eval_scalar(sbn_host::MerlinTranscript& t, const char* label, const uint8_t* s) { t.append_message((const uint8_t*)label, strlen(label), s, 32); }
-
 // DensePolynomial::commit of a device table with no blinds (hyrax.rs:283-308), as sbn_commit_table's launches; the caller holds the mutex
 static int sparse_eval_commit(sbn_ctx* c, const sbn_bases* gn, const sbn_table* t, size_t L, size_t R, uint8_t* out_xy) {
   const uint32_t* dZ = (const uint32_t*)t->d;
@@ -71,7 +69,7 @@ static int sparse_eval_locked(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx
   // every intermediate of the call: the two eq tables, the derefs table, the 4 batch + 4 hashed sets and their layers, and the views (slices of
   // derefs, comb_ops, comb_mem), which own nothing
   TableScope T(c);
-  auto fmul = [](const El& a, const El& b) { return mmul(to_m(a), b); };
+  sbn_host::Script ts{t};
   int rc;
   const size_t b = s.batch, N = s.N;
   // rnd: the three openings' draws in the reference's order (HashLayerProof::prove: derefs, ops, mem)
@@ -94,7 +92,7 @@ static int sparse_eval_locked(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx
   uint8_t* o_open_m = o_open_o + 64 * s.lg_o + 128;
   uint8_t* o_open_d = o_open_m + 64 * s.lg_m + 128;
 
-  r1cs_proof_name(t, "Sparse polynomial evaluation proof");        // :1709
+  ts.protocol("Sparse polynomial evaluation proof");               // :1709
 
   // ---- 1. equalize, the two eq tables, derefs (:1713-1720) ----
   sbn_table *mem_rx = nullptr, *mem_ry = nullptr, *derefs = nullptr;
@@ -114,6 +112,7 @@ static int sparse_eval_locked(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx
   }
 
   // ---- 2. the derefs commitment (:1723-1727, :341-347; PolyCommitment's lines hyrax.rs:44-51) ----
+  ts.message("derefs_commitment", "begin_derefs_commitment", 23);
   if (kzg) {                                                       // :1781-1785, :349-356, kzg.rs:386-404
     uint8_t xy[64]; int inf = 0;
     const size_t m = std::min(s.n_prefix, srs->n);                 // KZGPolyCommitment::commit truncates to the SRS (kzg.rs:388); the padding behind n' is zero
@@ -122,23 +121,20 @@ static int sparse_eval_locked(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx
     if (rc) return rc;
     if (inf) memset(xy, 0, 64);
     sbn_g1_compress(xy, 1, o_comm);                                // the identity as serialize_compressed writes it
-    t.append_message((const uint8_t*)"derefs_commitment", 17, (const uint8_t*)"begin_derefs_commitment", 23);
-    t.append_message((const uint8_t*)"comm_poly_row_col_ops_val", 25, o_comm, 32);
-    t.append_message((const uint8_t*)"derefs_commitment", 17, (const uint8_t*)"end_derefs_commitment", 21);
+    ts.point("comm_poly_row_col_ops_val", o_comm);
   } else {
     const sbn_bases *gn = nullptr, *g1 = nullptr;
     if ((rc = r1cs_proof_gens(c, gens_derefs, s.Rd, &gn, &g1))) return rc;
     std::vector<uint8_t> xy(64 * s.Ld);
     if ((rc = sparse_eval_commit(c, gn, derefs, s.Ld, s.Rd, xy.data()))) return rc;
     sbn_g1_compress(xy.data(), s.Ld, o_comm);
-    t.append_message((const uint8_t*)"derefs_commitment", 17, (const uint8_t*)"begin_derefs_commitment", 23);
-    t.append_message((const uint8_t*)"comm_poly_row_col_ops_val", 25, (const uint8_t*)"poly_commitment_begin", 21);
-    for (size_t i = 0; i < s.Ld; i++) zk_append_point(t, "poly_commitment_share", o_comm + 32 * i);
-    t.append_message((const uint8_t*)"comm_poly_row_col_ops_val", 25, (const uint8_t*)"poly_commitment_end", 19);
-    t.append_message((const uint8_t*)"derefs_commitment", 17, (const uint8_t*)"end_derefs_commitment", 21);
+    ts.message("comm_poly_row_col_ops_val", "poly_commitment_begin", 21);
+    for (size_t i = 0; i < s.Ld; i++) ts.point("poly_commitment_share", o_comm + 32 * i);
+    ts.message("comm_poly_row_col_ops_val", "poly_commitment_end", 19);
   }
-  uint8_t r_hash[32], r_multiset[32];
-  polyeval_challenge(t, "challenge_r_hash", r_hash); polyeval_challenge(t, "challenge_r_hash", r_multiset);      // :1730
+  ts.message("derefs_commitment", "end_derefs_commitment", 21);
+  uint8_t r_hm[64]; const uint8_t* r_hash = r_hm; const uint8_t* r_multiset = r_hm + 32;
+  ts.challenges("challenge_r_hash", r_hm, 2);                                                                    // :1730
 
   // ---- 3. PolyEvalNetwork::new (:853-866): the hashed sets and their product circuits ----
   // ops circuits in proof_ops' order: row read, row write, col read, col write (:1380-1392); mem circuits: row init, row audit, col init, col audit (:1404-1409)
@@ -179,8 +175,8 @@ static int sparse_eval_locked(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx
   }
 
   // ---- 4. PolyEvalNetworkProof::prove opens with the same protocol name again (:1555); ProductLayerProof::prove: every claim in one wait (:1314-1373) ----
-  r1cs_proof_name(t, "Sparse polynomial evaluation proof");
-  r1cs_proof_name(t, "Sparse polynomial product layer proof");
+  ts.protocol("Sparse polynomial evaluation proof");
+  ts.protocol("Sparse polynomial product layer proof");
   // the split dot-product circuits, interleaved left_i, right_i (:1354-1373; DotProductCircuit::split, product_tree.rs:87-105)
   const size_t n_dotp = 2 * b, half = N / 2;
   std::vector<const sbn_table*> dl(n_dotp), dr(n_dotp), dw(n_dotp);
@@ -219,16 +215,16 @@ static int sparse_eval_locked(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx
       return fail(c, SBN_EHIP, "sparse eval: the %s memory's subset check init * writes == reads * audit failed  [sparse_mlpoly_full.rs:%d assert_eq]", side ? "column" : "row", side ? 1339 : 1324);
     uint8_t* o = side ? o_pl_col : o_pl_row;
     memcpy(o, cl, 32 * (2 * b + 2));
-    sparse_eval_scalar(t, side ? "claim_col_eval_init" : "claim_row_eval_init", o);
-    for (size_t k = 0; k < b; k++) sparse_eval_scalar(t, side ? "claim_col_eval_read" : "claim_row_eval_read", o + 32 * (1 + k));
-    for (size_t k = 0; k < b; k++) sparse_eval_scalar(t, side ? "claim_col_eval_write" : "claim_row_eval_write", o + 32 * (1 + b + k));
-    sparse_eval_scalar(t, side ? "claim_col_eval_audit" : "claim_row_eval_audit", o + 32 * (2 * b + 1));
+    ts.scalar(side ? "claim_col_eval_init" : "claim_row_eval_init", o);
+    ts.scalars(side ? "claim_col_eval_read" : "claim_row_eval_read", o + 32, b);
+    ts.scalars(side ? "claim_col_eval_write" : "claim_row_eval_write", o + 32 * (1 + b), b);
+    ts.scalar(side ? "claim_col_eval_audit" : "claim_row_eval_audit", o + 32 * (2 * b + 1));
   }
   for (size_t k = 0; k < b; k++) {
     const El& l = claim[4 * b + 4 + 2 * k]; const El& r = claim[4 * b + 4 + 2 * k + 1];
     memcpy(o_pl_val + 32 * k, l.v, 32); memcpy(o_pl_val + 32 * (b + k), r.v, 32);
-    sparse_eval_scalar(t, "claim_eval_dotp_left", o_pl_val + 32 * k);
-    sparse_eval_scalar(t, "claim_eval_dotp_right", o_pl_val + 32 * (b + k));
+    ts.scalar("claim_eval_dotp_left", o_pl_val + 32 * k);
+    ts.scalar("claim_eval_dotp_right", o_pl_val + 32 * (b + k));
     if (memcmp(add(l, r).v, evals + 32 * k, 32))
       return fail(c, SBN_EINVAL, "sparse eval: eval_dotp_left + eval_dotp_right != evals[%zu]  [sparse_mlpoly_full.rs:1366 assert_eq]", k);
   }
@@ -249,7 +245,7 @@ static int sparse_eval_locked(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx
   }
 
   // ---- 6. HashLayerProof::prove (:922-1046) ----
-  r1cs_proof_name(t, "Sparse polynomial hash layer proof");
+  ts.protocol("Sparse polynomial hash layer proof");
   {
     // 2 batch derefs polynomials and the 5 batch of comb_ops (row addr, row read_ts, col addr, col read_ts, val: its own order) at rand_ops, ONE eq table
     std::vector<const sbn_table*> Z(7 * b);
@@ -270,12 +266,11 @@ static int sparse_eval_locked(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx
     memcpy(pad.data(), ev.data(), 32 * 2 * b);
     if (kzg) {
       // DerefsEvalProof::prove, KZG (:503-550): the reduction's claim is absorbed, then KZGProof::prove on the derefs table at kzg_eval_point
-      r1cs_proof_name(t, "Derefs evaluation proof (KZG)");
+      ts.protocol("Derefs evaluation proof (KZG)");
       std::vector<uint8_t> rj;
-      joint_reduce(pad.data(), s.cnt_d, s.lc_d, (const uint8_t*)"evals_ops_val", 13, (const uint8_t*)"challenge_combine_n_to_one", 26, (const uint8_t*)"joint_claim_eval", 16,
-                   rand_ops.data(), L_ops, t, rj, jc);
+      joint_reduce(pad.data(), s.cnt_d, s.lc_d, "evals_ops_val", "challenge_combine_n_to_one", "joint_claim_eval", rand_ops.data(), L_ops, t, rj, jc);
       uint8_t z[32], pxy[64]; int pinf = 0;
-      polyeval_challenge(t, "kzg_eval_point", z);
+      ts.challenge("kzg_eval_point", z);
       const size_t n = s.n_prefix;                                 // >= 4
       if ((rc = ensure(c, c->kzg_ws, 64 + kzg_levels_bytes(n)))) return rc;
       uint32_t* evd = (uint32_t*)c->kzg_ws.p;
@@ -291,18 +286,18 @@ static int sparse_eval_locked(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx
       sbn_g1_compress(pxy, 1, o_open_d);
     } else {
     // DerefsEvalProof::prove (:412-432)
-    r1cs_proof_name(t, "Derefs evaluation proof");
-    if ((rc = joint_opening_locked(c, gens_derefs, derefs, pad.data(), s.cnt_d, s.lc_d, (const uint8_t*)"evals_ops_val", 13, (const uint8_t*)"challenge_combine_n_to_one", 26,
-                                   (const uint8_t*)"joint_claim_eval", 16, rand_ops.data(), L_ops, rnd_d, t, nullptr, jc, o_open_d, cx, &xi, cy, &yi))) return rc;
+    ts.protocol("Derefs evaluation proof");
+    if ((rc = joint_opening_locked(c, gens_derefs, derefs, pad.data(), s.cnt_d, s.lc_d, "evals_ops_val", "challenge_combine_n_to_one", "joint_claim_eval",
+                                   rand_ops.data(), L_ops, rnd_d, t, nullptr, jc, o_open_d, cx, &xi, cy, &yi))) return rc;
     }
     // comb_ops (:978-1009)
     std::fill(pad.begin(), pad.end(), 0);
     memcpy(pad.data(), e_ops, 32 * 5 * b);
-    if ((rc = joint_opening_locked(c, gens_ops, &dn->ops, pad.data(), s.cnt_o, s.lc_o, (const uint8_t*)"claim_evals_ops", 15, (const uint8_t*)"challenge_combine_n_to_one", 26,
-                                   (const uint8_t*)"joint_claim_eval_ops", 20, rand_ops.data(), L_ops, rnd_o, t, nullptr, jc, o_open_o, cx, &xi, cy, &yi))) return rc;
+    if ((rc = joint_opening_locked(c, gens_ops, &dn->ops, pad.data(), s.cnt_o, s.lc_o, "claim_evals_ops", "challenge_combine_n_to_one", "joint_claim_eval_ops",
+                                   rand_ops.data(), L_ops, rnd_o, t, nullptr, jc, o_open_o, cx, &xi, cy, &yi))) return rc;
     // comb_mem (:1011-1035)
-    if ((rc = joint_opening_locked(c, gens_mem, &dn->mem, evm, 2, 1, (const uint8_t*)"claim_evals_mem", 15, (const uint8_t*)"challenge_combine_two_to_one", 28,
-                                   (const uint8_t*)"joint_claim_eval_mem", 20, rand_mem.data(), L_mem, rnd_m, t, nullptr, jc, o_open_m, cx, &xi, cy, &yi))) return rc;
+    if ((rc = joint_opening_locked(c, gens_mem, &dn->mem, evm, 2, 1, "claim_evals_mem", "challenge_combine_two_to_one", "joint_claim_eval_mem",
+                                   rand_mem.data(), L_mem, rnd_m, t, nullptr, jc, o_open_m, cx, &xi, cy, &yi))) return rc;
   }
   if (c->prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); prof_drain(c); }
   return T.done();
@@ -335,6 +330,20 @@ static int sparse_eval_check(sbn_ctx* c, const char* pfx, const sbn_dense* dn, c
   return SBN_OK;
 }
 
+// both builds' entry: the checks under the build's name `pfx`, then the proof on a copy of the transcript, into a buffer of the call's own
+static int sparse_eval_entry(sbn_ctx* c, const char* pfx, const sbn_dense* dn, const uint8_t* rx, size_t nx, const uint8_t* ry, size_t ny, const uint8_t* evals,
+                             const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_bases* gens_derefs, const sbn_bases* srs, const sbn_derefs_key* key,
+                             const uint8_t* rnd, sbn_transcript* tr, uint8_t* out_proof) {
+  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+  SparseEvalShape s;
+  int rc;
+  if ((rc = sparse_eval_check(c, pfx, dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, gens_derefs, srs, key, rnd, &s))) return rc;
+  std::vector<uint8_t> proof(srs ? s.proof_bytes_kzg : s.proof_bytes);      // the caller's buffer is written only by a call that succeeded
+  if ((rc = prove_on_copy(c, tr, [&](sbn_host::MerlinTranscript& t) { return sparse_eval_locked(c, dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, gens_derefs, srs, key, s, rnd, t, proof.data()); }))) return rc;
+  memcpy(out_proof, proof.data(), proof.size());
+  return SBN_OK;
+}
+
 extern "C" {
 
 int sbn_sparse_eval_sizes(size_t num_vars_x, size_t num_vars_y, size_t num_ops, size_t batch, size_t* rnd_scalars, size_t* proof_bytes) {
@@ -348,16 +357,7 @@ int sbn_sparse_eval_sizes(size_t num_vars_x, size_t num_vars_y, size_t num_ops, 
 int sbn_sparse_eval_prove(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx, size_t nx, const uint8_t* ry, size_t ny, const uint8_t* evals,
                           const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_bases* gens_derefs, const uint8_t* rnd, sbn_transcript* tr, uint8_t* out_proof) {
   if (!c || !dn || (!rx && nx) || (!ry && ny) || !evals || !gens_ops || !gens_mem || !gens_derefs || !rnd || !tr || !out_proof) return SBN_EINVAL;
-  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
-  SparseEvalShape s;
-  int rc;
-  if ((rc = sparse_eval_check(c, "sparse eval", dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, gens_derefs, nullptr, nullptr, rnd, &s))) return rc;
-  sbn_host::MerlinTranscript t = tr->t;
-  std::vector<uint8_t> proof(s.proof_bytes);                       // the caller's buffer is written only by a call that succeeded
-  if ((rc = sparse_eval_locked(c, dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, gens_derefs, nullptr, nullptr, s, rnd, t, proof.data()))) return rc;
-  memcpy(out_proof, proof.data(), s.proof_bytes);
-  tr->t = t;
-  return SBN_OK;
+  return sparse_eval_entry(c, "sparse eval", dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, gens_derefs, nullptr, nullptr, rnd, tr, out_proof);
 }
 
 int sbn_sparse_eval_kzg_sizes(size_t num_vars_x, size_t num_vars_y, size_t num_ops, size_t batch, size_t* rnd_scalars, size_t* proof_bytes) {
@@ -372,16 +372,7 @@ int sbn_sparse_eval_prove_kzg(sbn_ctx* c, const sbn_dense* dn, const uint8_t* rx
                               const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_bases* srs, const sbn_derefs_key* key,
                               const uint8_t* rnd, sbn_transcript* tr, uint8_t* out_proof) {
   if (!c || !dn || (!rx && nx) || (!ry && ny) || !evals || !gens_ops || !gens_mem || !srs || !rnd || !tr || !out_proof) return SBN_EINVAL;
-  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
-  SparseEvalShape s;
-  int rc;
-  if ((rc = sparse_eval_check(c, "sparse eval (KZG)", dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, nullptr, srs, key, rnd, &s))) return rc;
-  sbn_host::MerlinTranscript t = tr->t;
-  std::vector<uint8_t> proof(s.proof_bytes_kzg);                   // the caller's buffer is written only by a call that succeeded
-  if ((rc = sparse_eval_locked(c, dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, nullptr, srs, key, s, rnd, t, proof.data()))) return rc;
-  memcpy(out_proof, proof.data(), s.proof_bytes_kzg);
-  tr->t = t;
-  return SBN_OK;
+  return sparse_eval_entry(c, "sparse eval (KZG)", dn, rx, nx, ry, ny, evals, gens_ops, gens_mem, nullptr, srs, key, rnd, tr, out_proof);
 }
 
 }  // extern "C"

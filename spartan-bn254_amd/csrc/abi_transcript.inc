@@ -3,17 +3,6 @@
 
 struct sbn_transcript { sbn_host::MerlinTranscript t; };
 
-// 64 little-endian bytes mod r (Fr::from_le_bytes_mod_order, transcript.rs:56-67): lo + hi * 2^256, canonical
-static void transcript_wide_reduce(const uint8_t b[64], uint8_t out[32]) {
-  using namespace sbn_host::fr;
-  El lo, hi; memcpy(lo.v, b, 32); memcpy(hi.v, b + 32, 32);
-  const El zero = {{0, 0, 0, 0}};
-  auto fold = [&](El x) { while (geq(x.v)) { uint64_t br = 0; for (int i = 0; i < 4; i++) { sbn_host::u128 d = (sbn_host::u128)x.v[i] - P[i] - br; x.v[i] = (uint64_t)d; br = (uint64_t)(d >> 127); } } return x; };   // < 2^256 < 6 r
-  El r2; memcpy(r2.v, R2, 32);
-  const El res = add(add(fold(lo), zero), mmul(fold(hi), r2));                  // hi * 2^512 / 2^256
-  memcpy(out, res.v, 32);
-}
-
 // One sumcheck round's seven transcript operations (unipoly.rs:117-122 + challenge_scalar("challenge_nextround")) from the phase
 // (pos, pos_begin): the XOR mask of every block the round completes (200 bytes each; labels, lengths, operation headers, padding),
 // coefficient bytes left zero.  The round ends behind the PRF's 64 bytes: pos = 64, pos_begin = 0, cur_flags = I|A|C.
@@ -61,14 +50,12 @@ int sbn_transcript_challenge_bytes(sbn_transcript* t, const uint8_t* label, size
 }
 int sbn_transcript_challenge_scalar(sbn_transcript* t, const uint8_t* label, size_t label_len, uint8_t out[32]) {
   if (!t || (!label && label_len) || !out) return SBN_EINVAL;
-  uint8_t b[64];
-  t->t.challenge_bytes(label, label_len, b, 64);
-  transcript_wide_reduce(b, out);
+  sbn_host::Script{t->t}.challenge(sbn_host::Label(label, label_len), out);
   return SBN_OK;
 }
 int sbn_fr_from_wide(const uint8_t in[64], uint8_t out[32]) {
   if (!in || !out) return SBN_EINVAL;
-  transcript_wide_reduce(in, out);
+  sbn_host::transcript_wide_reduce(in, out);
   return SBN_OK;
 }
 int sbn_transcript_state(const sbn_transcript* t, uint8_t out[203]) {

@@ -12,8 +12,8 @@
 // (Cx of the dot product proof IS comm_poly_j: it is absorbed twice and computed once.)  B and C need only scalars the host holds; A_{j+1}
 // needs the tables bound with r_j.  Queue order once r_j is drawn:  B_j, bind+eval(r_j), tail, A_{j+1}, then (w known) C_j — so the streaming
 // round kernel runs under the host's transcript work, and the chain sums -> polynomial -> comm_poly has no host wait inside it.  The host
-// waits three times a round: for B_j, for C_j, for A_{j+1}.  Each commit in flight has its own mailbox slot and sequence number (the bullet
-// rounds' bullet_rows_launch / _collect keep theirs: slot 0's words are the ones they use, under the same context mutex).
+// waits three times a round: for B_j, for C_j, for A_{j+1}.  Each commit in flight has its own mailbox slot and sequence number (rows_to_host_launch /
+// _collect, abi_proof_common.inc; the bullet rounds keep their words, which are slot 0's, under the same context mutex).
 // Included by sbn254.hip.
 
 // the derived set has 7 (r1cs) or 6 (quad) points: a lookup table of at most 64 MiB.  bases_build_comb takes the widest window that fits:
@@ -23,55 +23,37 @@
 static const size_t ZK_COMB_BYTES = (size_t)64 << 20;
 template <int KIND> struct ZkShape { static constexpr int NT = KIND == KIND_QUAD ? 2 : 4, N = KIND == KIND_QUAD ? 3 : 4; };
 
-// the derived set of a (gens_1, gens_n) pair, built on the first call and owned by gens_n; the key holds gens_1's two points, which are read
-// back on gens_1's first call only and kept on its handle — a later call finds its set without a copy or a wait
+// the derived set of a (gens_1, gens_n) pair, built on the first call and owned by gens_n; what tells it apart is gens_1's two points, which are
+// read back on gens_1's first call only and kept on its handle — a later call finds its set without a copy or a wait
 static int zk_ext(sbn_ctx* c, const sbn_bases* g1, const sbn_bases* gn, const sbn_bases** out) {
   int rc;
-  std::lock_guard<std::mutex> tg(g_bullet_ext_mu);
-  if (g1->zk_key.empty()) {
-    if ((rc = ensure_pin(c, 4096))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->pin, g1->d_pts, 128, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    g1->zk_key = std::string("\x02zk") + std::string((const char*)c->pin, 128);      // (the bullet states' keys are empty or 64 bytes, the opening's is "\x01polyeval")
+  {
+    // (gens_1's handle is shared between contexts as the sets are: the sets' mutex; written once, so derived_set below may read it unlocked)
+    std::lock_guard<std::mutex> tg(g_derived_mu);
+    if (g1->zk_key.empty()) {
+      if ((rc = ensure_pin(c, 4096))) return rc;
+      HIPCHK(c, hipMemcpyAsync(c->pin, g1->d_pts, 128, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      g1->zk_key.assign((const char*)c->pin, 128);
+    }
   }
-  const std::string& key = g1->zk_key;
-  for (auto& kv : gn->bullet_ext) if (kv.first == key) { *out = kv.second; return SBN_OK; }
-  const size_t n = gn->n;
-  if ((rc = ensure(c, c->stage_pts, (n + 3) * 64))) return rc;
-  uint8_t* P = (uint8_t*)c->stage_pts.p;
-  HIPCHK(c, hipMemcpyAsync(P, gn->d_pts, (n + 1) * 64, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(P + 64 * (n + 1), g1->d_pts, 128, hipMemcpyDeviceToDevice, c->stream));
-  sbn_bases* ext = nullptr;
-  if ((rc = bases_from_device(c, P, n + 3, nullptr, &ext))) return rc;
-  if (bases_build_comb(c, ext->uniq ? ext->uniq : ext, ZK_COMB_BYTES) != SBN_OK) (void)hipGetLastError();     // best effort, as in bullet_begin_impl
-  gn->bullet_ext.emplace_back(key, ext);
-  *out = ext;
-  return SBN_OK;
+  return derived_set(gn, DERIVED_ZK, g1->zk_key, [&](sbn_bases** ext) -> int {
+    const size_t n = gn->n;
+    if ((rc = ensure(c, c->stage_pts, (n + 3) * 64))) return rc;
+    uint8_t* P = (uint8_t*)c->stage_pts.p;
+    HIPCHK(c, hipMemcpyAsync(P, gn->d_pts, (n + 1) * 64, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(P + 64 * (n + 1), g1->d_pts, 128, hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = bases_from_device(c, P, n + 3, nullptr, ext))) return rc;
+    if (bases_build_comb(c, (*ext)->uniq ? (*ext)->uniq : *ext, ZK_COMB_BYTES) != SBN_OK) (void)hipGetLastError();     // best effort, as in bullet_begin_impl
+    return SBN_OK;
+  }, out);
 }
 
-static inline uint32_t* zk_slot(sbn_ctx* c, int slot) { return c->mbox + SC_MBOX_FINALS + ZK_MBOX_SLOT_WORDS * slot; }
-static inline uint32_t* zk_flag(sbn_ctx* c, int slot) { return c->mbox + SC_MBOX_FLAGS + SC_PACK_MAX + 1 + slot; }
-// two rows of R canonical scalars as ONE commit over the derived set, the two XYZZ sums and `nextra` words behind them to mailbox slot `slot` — launches only
-static int zk_rows_launch(sbn_ctx* c, const sbn_bases* ext, const uint32_t* rows, size_t R, const uint32_t* extra, uint32_t nextra, int slot, uint32_t* seq) {
-  int rc;
-  { RowInfo ri; ri.internal_rows = true;
-    if ((rc = commit_rows_launch(c, ext, rows, nullptr, 2, R, nullptr, nullptr, ri))) return rc; }     // sums stay XYZZ in c->wsum: read by the next launch of the stream
-  *seq = ++c->mbox_seq;
-  LAUNCH(c, "k_points_to_host", k_zk_to_host, 1, 128, (const uint32_t*)c->wsum.p, extra, nextra, zk_slot(c, slot), zk_flag(c, slot), *seq);
-  LAUNCHCHK(c);
-  return SBN_OK;
-}
-static int zk_rows_collect(sbn_ctx* c, int slot, uint32_t seq, uint8_t P0_xy[64], uint8_t P1_xy[64], uint8_t* extra, size_t nextra_bytes) {
-  int rc;
-  if ((rc = sc_flag_wait(c, zk_flag(c, slot), seq))) return rc;
-  const uint32_t* h = zk_slot(c, slot);
-  sbn_host::Pt S[2]; memcpy(S, h, 256);
-  int i0 = 0, i1 = 0;
-  sbn_host::to_affine_bytes2(sbn_host::pt_from_device(S[0]), sbn_host::pt_from_device(S[1]), P0_xy, &i0, P1_xy, &i1);
-  if (nextra_bytes) memcpy(extra, (const uint8_t*)h + 256, nextra_bytes);
-  return SBN_OK;
-}
-static void zk_append_point(sbn_host::MerlinTranscript& t, const char* label, const uint8_t comp[32]) { t.append_message((const uint8_t*)label, strlen(label), comp, 32); }
+// a commit in flight has its own words of the host mailbox: result slot `slot` and the flag word that belongs to it
+static inline uint32_t zk_slot_word(int slot) { return (uint32_t)(SC_MBOX_FINALS + ZK_MBOX_SLOT_WORDS * slot); }
+static inline uint32_t zk_flag_word(int slot) { return (uint32_t)(SC_MBOX_FLAGS + SC_PACK_MAX + 1 + slot); }
+static inline uint32_t* zk_slot(sbn_ctx* c, int slot) { return c->mbox + zk_slot_word(slot); }
+static inline uint32_t* zk_flag(sbn_ctx* c, int slot) { return c->mbox + zk_flag_word(slot); }
 
 // the round kernel on the tables' current buffers: round 0's sums (bind == false) or the bind with rs fused with the next round's sums — the
 // launches of sbn_sc_eval_* / sbn_sc_bind_eval_* for one instance (abi_tables.inc: sc_eval_launch / sc_fused_launch), results to `dmbox` (device memory)
@@ -123,7 +105,7 @@ static int zk_prove_locked(sbn_ctx* c, sbn_table* const* T, const sbn_bases* g1,
   const size_t stride = (size_t)(6 + N) * 32;                    // bytes of one round in out_proof
   const uint8_t* blinds_poly = rnd; const uint8_t* blinds_evals = rnd + 32 * rounds;
   auto dp_rnd = [&](size_t j) { return rnd + 32 * (2 * rounds + j * (size_t)(N + 2)); };     // d_vec_j[N], r_delta_j, r_beta_j
-  auto fmul = [](const El& a, const El& b) { return mmul(to_m(a), b); };
+  sbn_host::Script ts{t};
   int rc;
   const sbn_bases* ext = nullptr;
   if ((rc = zk_ext(c, g1, gn, &ext))) return rc;
@@ -144,13 +126,14 @@ static int zk_prove_locked(sbn_ctx* c, sbn_table* const* T, const sbn_bases* g1,
   auto tail_and_A = [&](size_t j, const El& claim, uint32_t* seq) -> int {
     ZkTailArgs a; a.sums = dmbox; a.rnd = d_rnd; a.rows = rowsA; a.coeffs = d_co; a.blind_idx = (uint32_t)j; a.d_idx = (uint32_t)(2 * rounds + j * (size_t)(N + 2));
     LAUNCH(c, "k_zk_round_tail", k_zk_round_tail<KIND>, 1, 64, a, scs_from(to_dev_mont(claim)));
-    return zk_rows_launch(c, ext, rowsA, R, d_co, 8 * N, 0, seq);
+    return rows_to_host_launch(c, ext, rowsA, nullptr, 2, R, d_co, 8 * N, zk_slot_word(0), zk_flag_word(0), seq);
   };
+  auto collect = [&](int slot, uint32_t seq, uint8_t xy[128], uint8_t* extra, size_t nextra) { return rows_to_host_collect(c, zk_slot_word(slot), zk_flag_word(slot), seq, 2, xy, nullptr, extra, nextra); };
   auto host_rows = [&](uint32_t* rows, const El& v0, const uint8_t* b0, const El* v1, const uint8_t* b1, int slot, uint32_t* seq) -> int {
     ScScalar s0 = scs_from(v0), s1, s2, s3; memcpy(s1.v, b0, 32); memset(&s2, 0, sizeof s2); memset(&s3, 0, sizeof s3);
     if (v1) { s2 = scs_from(*v1); memcpy(s3.v, b1, 32); }
     LAUNCH(c, "k_zk_host_rows", k_zk_host_rows, 1, 64, rows, (uint32_t)N, s0, s1, s2, s3);
-    return zk_rows_launch(c, ext, rows, R, nullptr, 0u, slot, seq);
+    return rows_to_host_launch(c, ext, rows, nullptr, 2, R, nullptr, 0u, zk_slot_word(slot), zk_flag_word(slot), seq);
   };
 
   El claim = el_from(claim0);
@@ -163,12 +146,12 @@ static int zk_prove_locked(sbn_ctx* c, sbn_table* const* T, const sbn_bases* g1,
   for (size_t j = 0; j < rounds; j++) {
     uint8_t* pr = out_proof + stride * j;
     uint8_t* comm_poly = pr; uint8_t* comm_eval = pr + 32; uint8_t* delta = pr + 64; uint8_t* beta = pr + 96;
-    uint8_t Pxy[64], Qxy[64], co[32 * N];
-    if ((rc = zk_rows_collect(c, 0, seqA, Pxy, Qxy, co, 32 * N))) return rc;
-    sbn_g1_compress(Pxy, 1, comm_poly); sbn_g1_compress(Qxy, 1, delta);
-    zk_append_point(t, "comm_poly", comm_poly);                   // sumcheck.rs:544
+    uint8_t xy[128], co[32 * N];
+    if ((rc = collect(0, seqA, xy, co, 32 * N))) return rc;
+    sbn_host::g1_compress(xy + 64, delta);
+    ts.point_xy("comm_poly", xy, comm_poly);                      // sumcheck.rs:544
     uint8_t rj[32];
-    polyeval_challenge(t, "challenge_nextround", rj);             // :548
+    ts.challenge("challenge_nextround", rj);                      // :548
     memcpy(out_r + 32 * j, rj, 32);
     const El r = el_from(rj);
     El x[N], pw[N];                                               // the coefficients; 1, r, r^2 ..
@@ -189,14 +172,12 @@ static int zk_prove_locked(sbn_ctx* c, sbn_table* const* T, const sbn_bases* g1,
       LAUNCHCHK(c);
       for (int k = 0; k < NT; k++) T[k]->len = 1;
     }
-    uint8_t Exy[64], Cxy[64];
-    if ((rc = zk_rows_collect(c, 1, seqB, Exy, Cxy, nullptr, 0))) return rc;
-    sbn_g1_compress(Exy, 1, comm_eval);
-    if (j == 0) sbn_g1_compress(Cxy, 1, comm_claim);              // claim.commit(blind_claim, gens_1), sumcheck.rs:487
-    zk_append_point(t, "comm_claim_per_round", comm_claim);       // :571-572
-    zk_append_point(t, "comm_eval", comm_eval);
+    if ((rc = collect(1, seqB, xy, nullptr, 0))) return rc;
+    if (j == 0) sbn_host::g1_compress(xy + 64, comm_claim);       // claim.commit(blind_claim, gens_1), sumcheck.rs:487
+    ts.point("comm_claim_per_round", comm_claim);                 // :571-572
+    ts.point_xy("comm_eval", xy, comm_eval);
     uint8_t wb[64];
-    polyeval_challenge(t, "combine_two_claims_to_one", wb); polyeval_challenge(t, "combine_two_claims_to_one", wb + 32);      // :575
+    ts.challenges("combine_two_claims_to_one", wb, 2);            // :575
     const El w0 = el_from(wb), w1 = el_from(wb + 32);
     const El target = add(fmul(w0, claim), fmul(w1, eval));       // :578
     const El blind = add(fmul(w0, el_from(blind_sc)), fmul(w1, el_from(blinds_evals + 32 * j)));      // :586-594
@@ -208,17 +189,16 @@ static int zk_prove_locked(sbn_ctx* c, sbn_table* const* T, const sbn_bases* g1,
     }
     uint8_t blind_b[32]; memcpy(blind_b, blind.v, 32);
     if ((rc = host_rows(rowsC, target, blind_b, &ad, r_beta, 2, &seqC))) return rc;
-    t.append_message((const uint8_t*)"protocol-name", 13, (const uint8_t*)"dot product proof", 17);      // nizk/mod.rs:318
-    zk_append_point(t, "Cx", comm_poly);                          // :330-331: x_vec.commit(blind_x, gens_n) is comm_poly_j
-    uint8_t Yxy[64], Bxy[64], cy[32];
-    if ((rc = zk_rows_collect(c, 2, seqC, Yxy, Bxy, nullptr, 0))) return rc;
-    sbn_g1_compress(Yxy, 1, cy); sbn_g1_compress(Bxy, 1, beta);
-    zk_append_point(t, "Cy", cy);
-    for (int k = 0; k < N; k++) t.append_message((const uint8_t*)"a", 1, (const uint8_t*)a[k].v, 32);      // :336 -> transcript.rs:46-50
-    zk_append_point(t, "delta", delta);
-    zk_append_point(t, "beta", beta);
+    ts.protocol("dot product proof");                             // nizk/mod.rs:318
+    ts.point("Cx", comm_poly);                                    // :330-331: x_vec.commit(blind_x, gens_n) is comm_poly_j
+    uint8_t cy[32];
+    if ((rc = collect(2, seqC, xy, nullptr, 0))) return rc;
+    ts.point_xy("Cy", xy, cy);
+    ts.scalars("a", a, N);                                        // :336
+    ts.point("delta", delta);
+    ts.point_xy("beta", xy + 64, beta);
     uint8_t cb[32];
-    polyeval_challenge(t, "c", cb);
+    ts.challenge("c", cb);
     const El cc = el_from(cb);
     uint8_t* z = pr + 128;
     for (int k = 0; k < N; k++) { const El zk = add(fmul(cc, x[k]), el_from(dv + 32 * k)); memcpy(z + 32 * k, zk.v, 32); }      // :348-350
@@ -242,13 +222,7 @@ static int zk_prove_entry(sbn_ctx* c, sbn_table* const* T, const sbn_bases* g1, 
   std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
   int rc; size_t rounds = 0;
   if ((rc = zk_check(c, T, ZkShape<KIND>::NT, ZkShape<KIND>::N, g1, gn, claim, blind_claim, rnd, &rounds))) return rc;
-  sbn_host::MerlinTranscript t = tr->t;
-  if ((rc = zk_prove_locked<KIND>(c, T, g1, gn, rounds, claim, blind_claim, rnd, t, out_proof, out_r, out_finals, out_blind))) {
-    hipStreamSynchronize(c->stream);                              // nothing of this call stays queued behind a failure
-    return rc;
-  }
-  tr->t = t;
-  return SBN_OK;
+  return prove_on_copy(c, tr, [&](sbn_host::MerlinTranscript& t) { return zk_prove_locked<KIND>(c, T, g1, gn, rounds, claim, blind_claim, rnd, t, out_proof, out_r, out_finals, out_blind); });
 }
 
 extern "C" {

@@ -76,12 +76,13 @@ struct sbn_bases {
   void* d_csr_off = nullptr; void* d_csr_cols = nullptr; void* d_big = nullptr;
   // fixed-base direct-lookup table (comb_kernels.cuh): W x npts x 2^(c-1) affine points, built by sbn_bases_precompute
   void* d_comb = nullptr; int comb_c = 0; size_t comb_bytes = 0;
-  // bullet reduction (abi_bullet.inc): derived sets G ‖ Q (+ h), one per distinct Q, built on first use and owned by this handle
-  mutable std::vector<std::pair<std::string, sbn_bases*>> bullet_ext;
+  // derived generator sets (abi_msm.inc: derived_set): handles made from this one's points, one per key (DerivedKind ‖ what tells the sets of
+  // a kind apart), built on first use and owned by this handle
+  mutable std::vector<std::pair<std::string, sbn_bases*>> derived;
   // GLV table (glv_kernels.cuh): the n + has_h points, then their images phi(P) = (beta x, y); built by the first single MSM that takes the
   // GLV path and owned by this handle (a derived handle never shares it)
   mutable void* d_glv = nullptr;
-  // ZK sumchecks (abi_zk_sumcheck.inc): this handle's first two points (G[0], h) as bytes, the key of the derived sets it is the gens_1 of;
+  // ZK sumchecks (abi_zk_sumcheck.inc): this handle's first two points (G[0], h) as bytes, which tell apart the derived sets it is the gens_1 of;
   // read back once, on the first such call (the points of a handle never change)
   mutable std::string zk_key;
 };

@@ -3,8 +3,7 @@
 //   k_r1cs_build_z        z = vars ‖ 1 ‖ input ‖ 0 ...  (r1csproof.rs:268-277) as a table of 2 num_vars entries
 //   k_r1cs_sigma_rows     the n-row form of k_zk_host_rows: rows [0 ... 0 ‖ v ‖ b] over a derived set that ends in gens_1's two points — every
 //                         group element of KnowledgeProof / ProductProof / EqualityProof::prove (nizk/mod.rs:34-59, :167-227, :96-124) is one
-//   k_r1cs_points_to_host the n-point form of k_zk_to_host: the rows' XYZZ sums to the four ZK mailbox slots, which are contiguous and idle
-//                         between the two sumchecks
+// The rows' XYZZ sums go to the host (k_points_to_host) in the four ZK mailbox slots, which are contiguous and idle between the two sumchecks.
 #pragma once
 #include "zk_sumcheck_kernels.cuh"
 
@@ -49,15 +48,6 @@ __global__ void __launch_bounds__(256) k_r1cs_sigma_rows(uint32_t* __restrict__ 
     sbn_g_u32x4* o = (sbn_g_u32x4*)(rows + 8 * t);
     o[0] = lo; o[1] = hi;
   }
-}
-
-// npoints XYZZ sums (32 words each) to the host mailbox from `host_out` on, the flag behind them
-__global__ void __launch_bounds__(256) k_r1cs_points_to_host(const uint32_t* __restrict__ sums, uint32_t npoints, uint32_t* __restrict__ host_out, uint32_t* __restrict__ flag,
-                                                             uint32_t seq) {
-  for (uint32_t t = threadIdx.x; t < npoints * 32; t += blockDim.x) host_out[t] = sums[t];
-  sc_drain_stores();
-  __syncthreads();
-  if (threadIdx.x == 0) sc_flag_store(flag, seq);
 }
 
 }  // namespace sbn

@@ -32,6 +32,7 @@
 #include "derefs_key_kernels.cuh"
 #include "host_keccak.hpp"
 #include "host_strobe.hpp"
+#include "proof_host.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -60,6 +61,7 @@ using namespace sbn;
 #include "abi_transcript.inc"
 #include "abi_sumcheck.inc"
 #include "abi_product_proof.inc"
+#include "abi_proof_common.inc"
 #include "abi_bullet.inc"
 #include "abi_polyeval.inc"
 #include "abi_zk_sumcheck.inc"

@@ -76,14 +76,15 @@ __global__ void __launch_bounds__(64) k_zk_host_rows(uint32_t* __restrict__ rows
   }
 }
 
-// a two-row commit's XYZZ sums (2 x 32 words) and `nextra` words that travel with them, to one slot of the host mailbox, flag behind them
-__global__ void __launch_bounds__(128) k_zk_to_host(const uint32_t* __restrict__ sums, const uint32_t* __restrict__ extra, uint32_t nextra, uint32_t* __restrict__ host_out,
-                                                    uint32_t* __restrict__ flag, uint32_t seq) {
-  const uint32_t t = threadIdx.x;
-  if (t < 64) host_out[t] = sums[t]; else if (t - 64 < nextra) host_out[t] = extra[t - 64];
+// The hand-over of a row commit (abi_proof_common.inc: rows_to_host_launch): the npoints XYZZ sums (32 words each) and the `nextra` words that
+// travel with them, to the host mailbox from `host_out` on, the flag behind them.  One block; a caller with at most 128 words launches 128 threads.
+__global__ void __launch_bounds__(256) k_points_to_host(const uint32_t* __restrict__ sums, uint32_t npoints, const uint32_t* __restrict__ extra, uint32_t nextra,
+                                                        uint32_t* __restrict__ host_out, uint32_t* __restrict__ flag, uint32_t seq) {
+  const uint32_t ns = 32 * npoints;
+  for (uint32_t t = threadIdx.x; t < ns + nextra; t += blockDim.x) host_out[t] = t < ns ? sums[t] : extra[t - ns];
   sc_drain_stores();
   __syncthreads();
-  if (t == 0) sc_flag_store(flag, seq);
+  if (threadIdx.x == 0) sc_flag_store(flag, seq);
 }
 
 // the last bind (two entries per table left), in place as k_bind_top leaves it, and the final claims to the host: one lane per table
