@@ -8,7 +8,7 @@
 // So a carry capture costs as much as a multiply.  The round-1 layer (8 x 32-bit limbs, tools/micro/legacy/fp32.cuh) spends
 // 128 multiplies + 8 quotient digits but also 105 carry captures and 50 carry-chained adds per product, and 24 carry-chained
 // instructions per addition.  With 29-bit limbs a 64-bit column holds 18 limb products with room to spare: no capture exists,
-// a product is 162 multiplies + 9 quotient digits + 27 shifts/adds (measured 1.61e11 /s against 1.29e11 /s, squaring 1.97e11 /s:
+// a product is 162 multiplies + 9 quotient digits + 17 shifts (and 17 64-bit adds in the word-serial form) (measured 1.61e11 /s against 1.29e11 /s, squaring 1.97e11 /s:
 // tools/micro/fp29test.hip), and an addition is 9 plain v_add_u32 with no carry chain at all.
 //
 // Representation.  value = sum_k (int32)v[k] * 2^(29 k).  Limbs are SIGNED and values are LAZY:
@@ -119,11 +119,90 @@ template <class M> __device__ __forceinline__ Fe<M> fe_neg(const Fe<M>& a) { ret
 template <class M> __device__ __forceinline__ Fe<M> fe_dbl(const Fe<M>& a) { return fe_norm(fe_dbl_lazy(a)); }
 
 // ---- the multiplier -------------------------------------------------------------------------------------------------
-// Word-serial Montgomery product a*b*2^-261 over a sliding window of nine signed 64-bit columns.  Round i: column k += a[k]*b[i];
-// m = the 29-bit digit that clears the lowest column; column k += m*p[k]; the cleared column's upper part moves up and the
-// window slides.  Written in C on purpose: hipcc turns every line into the one instruction it should be (v_mad_i64_i32 /
-// v_mad_u64_u32 with the column as the 64-bit addend, v_mul_lo_u32 + v_and_b32 for m, v_ashrrev_i64 + v_lshl_add_u64 for the
-// carry) — checked in the ISA (tools/isa_stats.py) — and can schedule freely around it.
+// The UNSIGNED Montgomery product a*b*2^-261 (fe_mulu, fe_squ and their kin: the hot paths) goes BY COLUMNS: the 17 columns of the
+// schoolbook product are visited in order with ONE 64-bit accumulator per product.  For column k the accumulator starts as the carry out of column k - 1 and takes every a_i b_j with i + j = k and every
+// m_i p_j with i + j = k, i < k; then for k <= 8 the 29-bit digit m_k that clears the column is read from its low word and m_k p_0
+// is added, for k >= 9 its low 29 bits are result limb k - 9; then it is shifted down by 29 and is the next column's carry.
+// Written in C on purpose: hipcc turns every line into the one instruction it should be (v_mad_u64_u32 with the
+// accumulator as the 64-bit addend, v_mul_lo_u32 + v_and_b32 for m, v_lshrrev_b64 for the carry) — checked in the
+// ISA (tools/isa_stats.py, tests/test_isa_column_products.py).
+// The carry rides in the next multiply-add: no 64-bit add is left.  The word-serial form (fe_mul_impl below; round i: column k += a_k b_i,
+// then the digit, column k += m p_k, and the cleared column's upper part ADDED into the next column, which already held a partial sum)
+// pays a shift and a v_lshl_add_u64 per column: 17 adds per product that no formula asks for.  Every column total and every digit
+// is the same integer as there (the same terms and the same carry-in, added in another order), so results are limb for limb what
+// they were: tests/fe_model.py still states the word-serial form.
+// Capacity: a column total is what it was (9 * 2^60.6 + 9 * 2^58; with NT = 2, 2 * 9 * 2^59.6 + 9 * 2^58) plus a carry-in below
+// 2^35: it stays below 2^64.
+// Left to itself LLVM reassociates the sums back into per-column partial sums plus carry adds (the ISA is then the word-serial
+// form's, instruction for instruction).  fe_pin64 after every step keeps each sum as written: an empty asm that only READS the
+// accumulator, which gives every partial sum a second use, and a sum with two uses is not reassociated.  It must not have the
+// accumulator as an OUTPUT ("+v"): the compiler then pads every instruction that reads it with an s_nop (it assumes a forwarding
+// hazard behind any asm that writes a VGPR: 3 099 s_nop in k_acc_first<2>, and the latency-bound reduction kernels lost up to 25 %).
+// An asm without outputs is volatile, so the pins keep their source order among themselves: NP products given to one call run in
+// LOCKSTEP as written (NP accumulators, the column scans alternating term by term), which leaves a multiply-add's addend one
+// instruction of distance; products of separate calls follow each other.  Each product sums NT operand pairs before the digit of
+// a column is taken (NT = 2: a0 b0 + a1 b1 with ONE reduction, what cols_zero / cols_mac x 2 / cols_reduce compute, without the 17
+// columns in registers).  Operand pair t of product q is a[q * NT + t], b[q * NT + t].
+__device__ __forceinline__ void fe_pin64(const uint64_t& x) { asm volatile("" ::"v"(x)); }
+template <class M, bool SQR, int NP, int NT> __device__ __forceinline__ void fe_mulu_cols(const Fe<M> (&a)[NP * NT], const Fe<M> (&b)[NP * NT], Fe<M> (&r)[NP]) {
+  uint64_t acc[NP];
+  uint32_t m[NP][NL];
+  uint32_t a2[NP * NT][NL];
+#pragma unroll
+  for (int q = 0; q < NP; q++) acc[q] = 0;
+  if (SQR) {
+#pragma unroll
+    for (int q = 0; q < NP * NT; q++) {
+#pragma unroll
+      for (int k = 0; k < NL; k++) a2[q][k] = a[q].v[k] << 1;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 2 * NL - 1; k++) {
+    const int lo = k < NL ? 0 : k - (NL - 1), hi = k < NL ? k : NL - 1;
+#pragma unroll
+    for (int i = lo; i <= hi; i++) {                                   // a_i b_(k-i); squaring: a_i^2 and 2 a_(k-i) a_i for i < k - i
+      if (SQR && 2 * i > k) continue;
+#pragma unroll
+      for (int t = 0; t < NT; t++) {
+#pragma unroll
+        for (int q = 0; q < NP; q++) {
+          const int e = q * NT + t;
+          if (!SQR) acc[q] += (uint64_t)a[e].v[i] * (uint64_t)b[e].v[k - i];
+          else if (2 * i == k) acc[q] += (uint64_t)a[e].v[i] * (uint64_t)a[e].v[i];
+          else acc[q] += (uint64_t)a2[e][k - i] * (uint64_t)a[e].v[i];
+          fe_pin64(acc[q]);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = lo; i <= hi; i++) {                                   // m_i p_(k-i), i < k
+      if (i == k) continue;
+#pragma unroll
+      for (int q = 0; q < NP; q++) { acc[q] += (uint64_t)m[q][i] * (uint64_t)p29<M>(k - i); fe_pin64(acc[q]); }
+    }
+#pragma unroll
+    for (int q = 0; q < NP; q++) {
+      if (k < NL) {
+        m[q][k] = ((uint32_t)acc[q] * M::NINV29) & LMASK;
+        acc[q] += (uint64_t)m[q][k] * (uint64_t)p29<M>(0); fe_pin64(acc[q]);
+      } else r[q].v[k - NL] = (uint32_t)acc[q] & LMASK;
+    }
+#pragma unroll
+    for (int q = 0; q < NP; q++) { acc[q] >>= 29; fe_pin64(acc[q]); }  // exact for k <= 8: the low 29 bits are zero
+  }
+#pragma unroll
+  for (int q = 0; q < NP; q++) r[q].v[NL - 1] = (uint32_t)acc[q];
+}
+// The general signed product stays WORD-SERIAL (a sliding window of nine signed columns; round i: column k += a_k b_i, the digit,
+// column k += m p_k, the cleared column's upper part added into the next column).  By columns it has 1 64-bit add instead of 17 too,
+// but the pinned order costs registers where many signed products are in flight: k_comb_build, k_scale_points and k_mul_generator
+// went from 132 - 185 VGPRs to 512 with 6 - 7 KB of scratch, k_eq_level2 from 103 to 436 VGPRs, k_sc_round_mixed<true> gained a
+// scratch segment (profiles/r18_isa_column_products.txt).  The one cause that was found: a pinned product of LOOP-INVARIANT operands
+// inside a loop.  The arithmetic is hoisted out of the loop, the volatile pins are not, and each pin wants its partial sum as an
+// input, so every partial sum stays live across the loop.  A caller that multiplies invariant operands by columns inside a loop takes
+// them through fe_pin32 first (g1.cuh: xyzz_dbl_affine).  The signed product runs on rare paths and in latency-bound helpers only;
+// what it leaves in the accumulate kernels is the 64-bit adds of 2 x 3 rare-path products.
 template <class M, bool SQR> __device__ __forceinline__ Fe<M> fe_mul_impl(const Fe<M>& a, const Fe<M>& b) {
   int64_t c[NL];
   int32_t a2[NL];
@@ -195,40 +274,35 @@ template <class M> __device__ __forceinline__ Fe<M> fe_normu(Fe<M> a) {
   for (int i = 0; i < NL - 1; i++) { const uint32_t c = a.v[i] >> 29; a.v[i] &= LMASK; a.v[i + 1] += c; }
   return a;
 }
+// the unsigned product: by columns (fe_mulu_cols above), unsigned 64-bit accumulator
 template <class M, bool SQR> __device__ __forceinline__ Fe<M> fe_mulu_impl(const Fe<M>& a, const Fe<M>& b) {
-  uint64_t c[NL];
-  uint32_t a2[NL];
-  if (SQR) {
-#pragma unroll
-    for (int k = 0; k < NL; k++) a2[k] = a.v[k] << 1;
-  }
-#pragma unroll
-  for (int i = 0; i < NL; i++) {
-#pragma unroll
-    for (int k = 0; k < NL; k++) {
-      uint64_t t = 0; bool has = true;
-      if (!SQR) t = (uint64_t)a.v[k] * (uint64_t)b.v[i];
-      else if (k == i) t = (uint64_t)a.v[k] * (uint64_t)a.v[i];
-      else if (k > i) t = (uint64_t)a2[k] * (uint64_t)a.v[i];
-      else has = false;
-      if (i == 0 || k == NL - 1) c[k] = has ? t : 0;
-      else if (has) c[k] += t;
-    }
-    const uint32_t m = ((uint32_t)c[0] * M::NINV29) & LMASK;
-#pragma unroll
-    for (int k = 0; k < NL; k++) c[k] += (uint64_t)m * (uint64_t)p29<M>(k);
-    c[1] += c[0] >> 29;
-#pragma unroll
-    for (int k = 0; k < NL - 1; k++) c[k] = c[k + 1];
-  }
-  Fe<M> r;
-#pragma unroll
-  for (int k = 0; k < NL - 1; k++) {
-    r.v[k] = (uint32_t)c[k] & LMASK;
-    const uint64_t carry = c[k] >> 29;
-    if (k < NL - 2) c[k + 1] += carry; else r.v[NL - 1] = (uint32_t)carry;
-  }
-  return r;
+  const Fe<M> x[1] = {a}, y[1] = {b};
+  Fe<M> r[1];
+  fe_mulu_cols<M, SQR, 1, 1>(x, y, r);
+  return r[0];
+}
+// two independent products / squarings in lockstep
+template <class M> __device__ __forceinline__ void fe_mulu2(const Fe<M>& a0, const Fe<M>& b0, const Fe<M>& a1, const Fe<M>& b1, Fe<M>& r0, Fe<M>& r1) {
+  const Fe<M> x[2] = {a0, a1}, y[2] = {b0, b1};
+  Fe<M> r[2];
+  fe_mulu_cols<M, false, 2, 1>(x, y, r);
+  r0 = r[0]; r1 = r[1];
+}
+template <class M> __device__ __forceinline__ void fe_squ2(const Fe<M>& a0, const Fe<M>& a1, Fe<M>& r0, Fe<M>& r1) {
+  const Fe<M> x[2] = {a0, a1};
+  Fe<M> r[2];
+  fe_mulu_cols<M, true, 2, 1>(x, x, r);
+  r0 = r[0]; r1 = r[1];
+}
+// (a0 b0 + a1 b1) * 2^-261 with ONE reduction: the digit of a column is taken after both products' terms.  Operand ranges are
+// cols_mac_lazy's: per pair one operand normalised (limbs below 2^29), the other non-negative with limbs below 2^30.6, so a column
+// holds at most 2 * 9 * 2^59.6 + 9 * 2^58 + the carry-in (< 2^35) < 2^64.  Returns the limbs cols_reduce returns for that sum: a
+// normalised value in [0, sum / 2^261 + p).
+template <class M> __device__ __forceinline__ Fe<M> fe_mac2u(const Fe<M>& a0, const Fe<M>& b0, const Fe<M>& a1, const Fe<M>& b1) {
+  const Fe<M> x[2] = {a0, a1}, y[2] = {b0, b1};
+  Fe<M> r[1];
+  fe_mulu_cols<M, false, 1, 2>(x, y, r);
+  return r[0];
 }
 // 32-bit value barrier (no instruction: an empty asm per limb).  A product widens its limbs to 64 bits where it multiplies, and
 // hipcc selects v_mad_u64_u32 only when it sees that widening in the multiply's own basic block.  When an element also feeds a

@@ -69,13 +69,24 @@ __device__ __forceinline__ void xyzz_store(void* p, const XYZZ& a) {
 // 2*P for an affine P != infinity (y != 0 always holds on this curve: no 2-torsion in G1).  Rare path: the safe (signed,
 // normalising) operations, then the coordinates are brought back to the non-negative form the hot formulas expect.
 // Inlined on purpose: an out-of-line callee takes its operand by reference, which forces the caller to keep a copy in scratch memory.
-__device__ __forceinline__ XYZZ xyzz_dbl_affine(const Affine& p) {
-  const Fq U = fe_dbl(p.y), V = fe_sqr(U), W = fe_mul(U, V), S = fe_mul(p.x, V);
-  const Fq xx = fe_sqr(p.x), M3 = fe_add(fe_dbl(xx), xx);
+// p.x, p.y: normalised and NON-NEGATIVE (a table point; the mixed addition passes y or 2p - y, normalised).  Six of the seven products
+// then have two normalised non-negative operands (a product of such operands is non-negative again, and so are their normalised
+// sums), and for those fe_mulu / fe_squ return exactly the limbs of fe_mul / fe_sqr: the columns are the same non-negative integers,
+// below 2^63 either way, so digits and carries agree.  They are taken as the unsigned, column-wise products (no sign patches, 1
+// 64-bit add instead of 17: this path is inlined twice into the accumulate kernels); only M3 (S - X) has an operand that may be negative.
+// The point is taken through fe_pin32 first.  Where a caller's point does not change inside a loop (double-and-add over one base:
+// k_scale_points, k_mul_generator, k_comb_build), this whole function is loop-invariant arithmetic; the compiler hoists it out of the
+// loop, but the products' pins (fp.cuh: fe_pin64, volatile) stay behind in the loop and each wants its partial sum as an input, so
+// every partial sum of six products stayed live across the loop: 512 VGPRs and 5 - 6 KB of scratch.  Behind the barrier nothing here is
+// invariant, and the work stays on the rare path where it is written.
+__device__ __forceinline__ XYZZ xyzz_dbl_affine(const Affine& p_in) {
+  Affine p = p_in; fe_pin32(p.x); fe_pin32(p.y);
+  const Fq U = fe_dbl(p.y), V = fe_squ(U), W = fe_mulu(U, V), S = fe_mulu(p.x, V);
+  const Fq xx = fe_squ(p.x), M3 = fe_add(fe_dbl(xx), xx);
   XYZZ r;
-  const Fq X = fe_sub(fe_sub(fe_sqr(M3), S), S);                                  // (-2.2p, 1.1p)
+  const Fq X = fe_sub(fe_sub(fe_squ(M3), S), S);                                  // (-2.2p, 1.1p)
   r.X = fe_fix_nonneg<FqP, 4>(X);
-  r.Y = fe_fix_nonneg<FqP, 2>(fe_sub(fe_mul(M3, fe_sub(S, X)), fe_mul(W, p.y)));  // (-1.2p, 1.2p)
+  r.Y = fe_fix_nonneg<FqP, 2>(fe_sub(fe_mul(M3, fe_sub(S, X)), fe_mulu(W, p.y))); // (-1.2p, 1.2p)
   r.ZZ = fe_fix_nonneg<FqP, 1>(V); r.ZZZ = fe_fix_nonneg<FqP, 1>(W);
   return r;
 }
@@ -102,7 +113,7 @@ __device__ __forceinline__ void xyzz_madd(XYZZ& acc, const Affine& q_in, bool ne
   if ((q_in.x.v[0] | q_in.y.v[0]) == 0) { if (aff_is_inf(q_in)) return; }
   const Fq qy = neg ? fe_negb<FqP, 2>(q_in.y) : q_in.y;                    // 2p - y: limbs below 2^30
   if (acc.ZZ.v[0] == 0) { if (xyzz_is_inf(acc)) { acc.X = q_in.x; acc.Y = fe_normu(qy); acc.ZZ = fe_one<FqP>(); acc.ZZZ = acc.ZZ; return; } }
-  const Fq U2 = fe_mulu(q_in.x, acc.ZZ), S2 = fe_mulu(qy, acc.ZZZ);        // [0, 1.2p)
+  Fq U2, S2; fe_mulu2(q_in.x, acc.ZZ, qy, acc.ZZZ, U2, S2);                // [0, 1.2p)
   Fq P = fe_normu(fe_subb<FqP, 6, 1>(U2, acc.X));                          // U2 - X + 6p in (0.8p, 7.2p)
   const Fq R = fe_normu(fe_subb<FqP, 4, 1>(S2, acc.Y));                    // S2 - Y + 4p in (0.8p, 5.2p)
   if (fe_maybe_zero(P) && fe_is_zero(P)) {                                 // same x: doubling or cancellation
@@ -110,14 +121,14 @@ __device__ __forceinline__ void xyzz_madd(XYZZ& acc, const Affine& q_in, bool ne
     return;
   }
   fe_pin32(P);                                                             // P fed the exact test: widen it afresh for the products below (fp.cuh)
-  const Fq PP = fe_squ(P), PPP = fe_mulu(P, PP), Q = fe_mulu(acc.X, PP);
+  const Fq PP = fe_squ(P);
+  Fq PPP, Q; fe_mulu2(P, PP, acc.X, PP, PPP, Q);
   const Fq X3 = fe_normu(fe_subb<FqP, 4, 3>(fe_squ(R), fe_add_lazy(fe_add_lazy(PPP, Q), Q)));        // R^2 - PPP - 2Q + 4p in (0.4p, 5.2p)
-  // Y3 = R (Q - X3) - Y PPP as ONE sum of two products with ONE Montgomery reduction (fp.cuh: Cols): R (Q - X3 + 6p) + (4p - Y) PPP.
+  // Y3 = R (Q - X3) - Y PPP as ONE sum of two products with ONE Montgomery reduction (fp.cuh: fe_mac2u): R (Q - X3 + 6p) + (4p - Y) PPP.
   // Limb products: 2^29 x 2^30.6 and 2^30 x 2^29, nine per column each: 1.3e19 + the reduction's 2.6e18 < 2^64.  Value: at most
   // (5.2 * 7.2 + 4 * 1.2) p^2 / 2^261 + p < 1.3 p, normalised by the reduction itself (no carry pass, no second reduction).
-  Cols cy; cols_zero(cy);
-  cols_mac_lazy<FqP>(cy, R, fe_subb<FqP, 6, 1>(Q, X3)); cols_mac_lazy<FqP>(cy, PPP, fe_negb<FqP, 4>(acc.Y));
-  acc.X = X3; acc.Y = cols_reduce<FqP>(cy); acc.ZZ = fe_mulu(acc.ZZ, PP); acc.ZZZ = fe_mulu(acc.ZZZ, PPP);
+  const Fq Y3 = fe_mac2u(R, fe_subb<FqP, 6, 1>(Q, X3), PPP, fe_negb<FqP, 4>(acc.Y));
+  acc.X = X3; acc.Y = Y3; fe_mulu2(acc.ZZ, PP, acc.ZZZ, PPP, acc.ZZ, acc.ZZZ);
 }
 
 // a + b, both XYZZ (normalised, non-negative, ranges as above).  12M + 2S on the common path.  The inlined form is for the
@@ -125,21 +136,21 @@ __device__ __forceinline__ void xyzz_madd(XYZZ& acc, const Affine& q_in, bool ne
 __device__ __forceinline__ XYZZ xyzz_add_inl(const XYZZ& a, const XYZZ& b) {
   if (xyzz_is_inf(a)) return b;
   if (xyzz_is_inf(b)) return a;
-  const Fq U1 = fe_mulu(a.X, b.ZZ), U2 = fe_mulu(b.X, a.ZZ), S1 = fe_mulu(a.Y, b.ZZZ), S2 = fe_mulu(b.Y, a.ZZZ);   // [0, 1.2p)
+  Fq U1, U2, S1, S2;                                                                                              // [0, 1.2p)
+  fe_mulu2(a.X, b.ZZ, b.X, a.ZZ, U1, U2); fe_mulu2(a.Y, b.ZZZ, b.Y, a.ZZZ, S1, S2);
   Fq P = fe_normu(fe_subb<FqP, 2, 1>(U2, U1)); const Fq R = fe_normu(fe_subb<FqP, 2, 1>(S2, S1));               // (0.8p, 3.2p)
   if (fe_maybe_zero(P) && fe_is_zero(P)) {
     if (fe_is_zero(R)) return xyzz_dbl(a);
     return xyzz_inf();
   }
   fe_pin32(P);                                       // (see xyzz_madd)
-  const Fq PP = fe_squ(P), PPP = fe_mulu(P, PP), Q = fe_mulu(U1, PP);
+  const Fq PP = fe_squ(P);
+  Fq PPP, Q, Z12, Z123;
+  fe_mulu2(P, PP, U1, PP, PPP, Q); fe_mulu2(a.ZZ, b.ZZ, a.ZZZ, b.ZZZ, Z12, Z123);
   XYZZ r;
   r.X = fe_normu(fe_subb<FqP, 4, 3>(fe_squ(R), fe_add_lazy(fe_add_lazy(PPP, Q), Q)));
-  Cols cy; cols_zero(cy);                                                            // R (Q - X3 + 6p) + (2p - S1) PPP, one reduction (see xyzz_madd); S1 < 1.2p
-  cols_mac_lazy<FqP>(cy, R, fe_subb<FqP, 6, 1>(Q, r.X)); cols_mac_lazy<FqP>(cy, PPP, fe_negb<FqP, 2>(S1));
-  r.Y = cols_reduce<FqP>(cy);
-  r.ZZ = fe_mulu(fe_mulu(a.ZZ, b.ZZ), PP);
-  r.ZZZ = fe_mulu(fe_mulu(a.ZZZ, b.ZZZ), PPP);
+  r.Y = fe_mac2u(R, fe_subb<FqP, 6, 1>(Q, r.X), PPP, fe_negb<FqP, 2>(S1));           // R (Q - X3 + 6p) + (2p - S1) PPP, one reduction (see xyzz_madd); S1 < 1.2p
+  fe_mulu2(Z12, PP, Z123, PPP, r.ZZ, r.ZZZ);
   return r;
 }
 __device__ __noinline__ XYZZ xyzz_add(const XYZZ& a, const XYZZ& b) { return xyzz_add_inl(a, b); }

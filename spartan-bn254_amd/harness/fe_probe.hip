@@ -4,7 +4,8 @@
 // one 64-lane wave per case for the wave sum).  Elements cross the boundary as 9 raw signed 32-bit limbs, so a test can feed any
 // lazy representation and read back the exact limbs a primitive returned.  Layout of `in` / `out`: [case][lane][element][9 limbs].
 // Memory-format ops (is_canonical, unpack, pack, store_tab) carry 8 little-endian 32-bit words in limbs 0..7 of an element.
-// Not linked with the product library and not part of include/sbn254.h: tests/test_gpu_fe_bounds.py is its only user.
+// Not linked with the product library and not part of include/sbn254.h: tests/test_gpu_fe_bounds.py and
+// tests/test_gpu_column_products.py (ops mulu2, squ2, mac2u) are its only users.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -39,6 +40,7 @@ const OpInfo OPS[] = {
     {"madd", 6, 4, 1, GG, FQ},          {"madd_neg", 6, 4, 1, GG, FQ},      {"add_inl", 8, 4, 1, GG, FQ},
     {"dbl_xyzz", 4, 4, 1, GG, FQ},      {"dbl_affine", 2, 4, 1, GG, FQ},    {"to_affine", 4, 2, 1, GG, FQ},
     {"store_load", 4, 4, 1, GG, FQ},    {"add_quad", 8, 4, 4, GQ, FQ},      {"wave_sum", 4, 4, 64, GW, FQ},
+    {"mulu2", 4, 2, 1, GF, BOTH},       {"squ2", 2, 2, 1, GF, BOTH},        {"mac2u", 4, 1, 1, GF, BOTH},
 };
 constexpr int NOPS = (int)(sizeof(OPS) / sizeof(OPS[0]));
 
@@ -58,7 +60,7 @@ enum : int {
   O_MAYBE_ZERO, O_SUBB_3_1, O_SUBB_4_2, O_SUBB_9_1, O_SUBB_14_1, O_SUBB_2_1, O_SUBB_4_1, O_SUBB_4_3, O_SUBB_6_1, O_NEGB_2, O_NEGB_4,
   O_FIX1, O_FIX2, O_FIX4, O_FIX_TAB, O_COLS12, O_COLS_LAZY2, O_TO_MONT, O_FROM_MONT, O_FROM_ARK, O_ARK_TO_PLAIN, O_FROM_U64, O_INV,
   O_IS_CANON, O_UNPACK, O_PACK, O_STORE_TAB, O_MADD, O_MADD_NEG, O_ADD_INL, O_DBL_XYZZ, O_DBL_AFF, O_TO_AFF, O_STORE_LOAD, O_ADD_QUAD,
-  O_WAVE_SUM, O_COUNT
+  O_WAVE_SUM, O_MULU2, O_SQU2, O_MAC2U, O_COUNT
 };
 static_assert(O_COUNT == NOPS, "op enum and table differ");
 
@@ -126,6 +128,9 @@ __global__ void field_kernel(int op, const int32_t* __restrict__ in, int32_t* __
       const uint32_t w[8] = {buf[0].x, buf[0].y, buf[0].z, buf[0].w, buf[1].x, buf[1].y, buf[1].z, buf[1].w};
       st_words(d, w);
     } break;
+    case O_MULU2: { Fe<M> r0, r1; fe_mulu2(a, ld<M>(s, 1), ld<M>(s, 2), ld<M>(s, 3), r0, r1); st(d, 0, r0); st(d, 1, r1); } break;      // (a0, b0, a1, b1)
+    case O_SQU2: { Fe<M> r0, r1; fe_squ2(a, ld<M>(s, 1), r0, r1); st(d, 0, r0); st(d, 1, r1); } break;
+    case O_MAC2U: st(d, 0, fe_mac2u(a, ld<M>(s, 1), ld<M>(s, 2), ld<M>(s, 3))); break;                                                   // a0 b0 + a1 b1, one reduction
     default: break;
   }
 }

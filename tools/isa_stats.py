@@ -8,12 +8,16 @@ Extracts the gfx950 code object from the .so (llvm-objdump --offloading), reads 
   v_mad_u64_u32   (+ v_mad_i64_i32) the only wide multiplier of the CDNA4 VALU: 4.2 cycles per wave-instruction (tools/micro/ibench.hip)
   v_mul_lo_u32    the Montgomery quotient digits (4.2)
   other VALU      shifts, masks, limb additions, selects, moves: 2.3 cycles for plain VOP2 forms, 4.2 for VOP3 / 64-bit / carry forms
+  add64           64-bit additions among them: v_lshl_add_u64, plus the carry-chained pairs v_add_co_u32 + v_addc_co_u32 (counted once, at the
+                  v_addc_co_u32).  The word-serial field product has 17 per 162 multiply-adds (a column's carry is added into a partial
+                  sum); the column-wise product (fp.cuh: fe_mulu_cols) has 1, because the carry rides as the next multiply-add's addend
   v_mov           the v_mov_b32 among them (register-to-register copies and constants: work no formula asks for)
   mov>mad         v_mov_b32 straight into the destination pair of the v_mad_u64_u32 that follows it: a 64-bit column whose halves
                   the register allocator did not keep adjacent is shuffled into the multiply-add's tied operand and out again
   zero*           multiplies (v_mad_u64_u32 / v_mad_i64_i32 / v_mul_lo_u32) with a factor register that only ever holds the constant 0
                   (every write to it is `v_mov_b32 r, 0` or a copy of such a register): a 64 x 64 product of a zero-extended limb
-  s_nop, SALU, VMEM (global/buffer/scratch), LDS, waitcnt
+  s_nop           padding the compiler inserts for a hazard (e.g. before a VALU instruction that reads a register an inline asm has as an output)
+  SALU, VMEM (global/buffer/scratch), LDS, waitcnt
 and prices them roughly: cycles ~ 4.2 * (mad + mul_lo) + 3 * other VALU; `mult_share` = the multiplier's part of that (1.0 = nothing
 but products).  Needs no GPU (runs on the build machine)."""
 import argparse
@@ -129,7 +133,7 @@ def disasm_counts(co):
         m = re.match(r"^[0-9a-f]+ <([^>]+)>:", line)
         if m:
             cur = m.group(1)
-            counts[cur] = {"total": 0, "v_mad_u64_u32": 0, "v_mul_lo_u32": 0, "other_valu": 0, "v_mov": 0, "mov_mad": 0, "zero_mul": 0, "s_nop": 0, "salu": 0, "vmem": 0, "scratch": 0, "lds": 0, "waitcnt": 0}
+            counts[cur] = {"total": 0, "v_mad_u64_u32": 0, "v_mul_lo_u32": 0, "other_valu": 0, "add64": 0, "v_mov": 0, "mov_mad": 0, "zero_mul": 0, "s_nop": 0, "salu": 0, "vmem": 0, "scratch": 0, "lds": 0, "waitcnt": 0}
             code[cur] = []
             continue
         if cur is None:
@@ -152,6 +156,8 @@ def disasm_counts(co):
             c["other_valu"] += 1
             if op == "v_mov_b32":
                 c["v_mov"] += 1
+            elif op in ("v_lshl_add_u64", "v_addc_co_u32"):
+                c["add64"] += 1
         elif op == "s_nop":
             c["s_nop"] += 1
         elif op == "s_waitcnt":
@@ -219,10 +225,10 @@ def main():
                      "lds_B": m.get("group_segment_fixed_size"), "waves_per_simd": waves_per_simd((m.get("vgpr_count") or 0) + (m.get("agpr_count") or 0)),
                      **c, "mult_share": round(cyc_mult / (cyc_mult + cyc_other), 3) if (cyc_mult + cyc_other) else None,
                      "products_equiv": round(c["v_mad_u64_u32"] / 162.0, 1)})
-    hdr = f"{'kernel':44s} {'vgpr':>4s} {'w/S':>3s} {'scr':>4s} {'instr':>6s} {'mad64':>6s} {'mullo':>5s} {'oVALU':>6s} {'v_mov':>5s} {'mov>mad':>7s} {'zero*':>5s} {'s_nop':>5s} {'vmem':>4s} {'lds':>4s} {'mult%':>6s}"
+    hdr = f"{'kernel':44s} {'vgpr':>4s} {'w/S':>3s} {'scr':>4s} {'instr':>6s} {'mad64':>6s} {'mullo':>5s} {'oVALU':>6s} {'add64':>5s} {'v_mov':>5s} {'mov>mad':>7s} {'zero*':>5s} {'s_nop':>5s} {'vmem':>4s} {'lds':>4s} {'mult%':>6s}"
     print(hdr)
     for r in rows:
-        print(f"{r['kernel'][:44]:44s} {r['vgpr']:4d} {r['waves_per_simd']:3d} {r['scratch_B']:4d} {r['total']:6d} {r['v_mad_u64_u32']:6d} {r['v_mul_lo_u32']:5d} {r['other_valu']:6d} {r['v_mov']:5d} {r['mov_mad']:7d} {r['zero_mul']:5d} {r['s_nop']:5d} {r['vmem'] + r['scratch']:4d} {r['lds']:4d} {100 * (r['mult_share'] or 0):6.1f}")
+        print(f"{r['kernel'][:44]:44s} {r['vgpr']:4d} {r['waves_per_simd']:3d} {r['scratch_B']:4d} {r['total']:6d} {r['v_mad_u64_u32']:6d} {r['v_mul_lo_u32']:5d} {r['other_valu']:6d} {r['add64']:5d} {r['v_mov']:5d} {r['mov_mad']:7d} {r['zero_mul']:5d} {r['s_nop']:5d} {r['vmem'] + r['scratch']:4d} {r['lds']:4d} {100 * (r['mult_share'] or 0):6.1f}")
     if args.json:
         json.dump(rows, open(args.json, "w"), indent=1)
     return 0
