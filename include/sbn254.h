@@ -306,6 +306,39 @@ int sbn_joint_opening_prove(sbn_ctx* ctx, const sbn_bases* gens, const sbn_table
                             uint8_t* out_challenges, uint8_t out_joint_claim[32], uint8_t* out_proof,
                             uint8_t out_Cx_xy[64], int* Cx_is_inf, uint8_t out_Cy_xy[64], int* Cy_is_inf);
 
+/* ---- the Hyrax opening CHECK in one call: PolyEvalProof::verify / verify_plain (hyrax.rs:118-151) with DotProductProofLog::verify
+ *      (nizk/mod.rs:525-567) and BulletReductionProof::verify (nizk/bullet.rs:130-173, compute_s :183-200) inside, the transcript included ---- */
+/* arkworks deserialize_compressed of n points (group.rs:323-329) on the device, one point per lane; the inverse of sbn_g1_compress.
+ * in32: n x 32 (x little-endian; bit 7 of byte 31: y is the larger root, bit 6: the identity).  out_xy: n x 64 canonical affine, the identity
+ * all-zero.  out_ok[i] = 0: x >= p, or x^3 + 3 is not a square; out_xy[i] is then all-zero. */
+int sbn_g1_decompress(sbn_ctx* ctx, const uint8_t* in32, size_t n, uint8_t* out_xy, uint8_t* out_ok);
+/* the same into a resident point set (no h), for a commitment that arrives as bytes (comm_vars, r1csproof.rs:187; comm_derefs,
+ * sparse_mlpoly_full.rs:301-304).  A point that does not decompress: SBN_EINVAL, *bad_index (may be NULL) = the first such i, no handle. */
+int sbn_bases_from_compressed(sbn_ctx* ctx, const uint8_t* in32, size_t n, sbn_bases** out, size_t* bad_index);
+/* (L_size, R_size) = 2^sbn_factored_lens(ell), n = R_size.
+ *   gens:    R_size + 1 generators with h, the handle sbn_polyeval_prove takes.   comm: the L_size row commitments of the polynomial
+ *            (PolyCommitment.C, hyrax.rs:283-308), no h: sbn_bases_upload or sbn_bases_from_compressed; identity rows are ordinary.
+ *   r:       ell x 32.   Exactly one of C_Zr_xy (64 B canonical affine: verify, hyrax.rs:118-137) and Zr (32 B: verify_plain, :139-151) is non-NULL.
+ *   proof:   64 lg n + 128 bytes, the out_proof of sbn_polyeval_prove.
+ * The return code reports misuse only — SBN_EINVAL before any launch, `tr` unchanged: a NULL pointer, ell == 0 or > 40, sbn_bases_len(comm) !=
+ * L_size, gens of another size or without h, both or neither of C_Zr_xy and Zr, a non-canonical r or Zr, a C_Zr_xy that is no point of the curve.
+ * What an adversary controls gives SBN_OK with *accepted = 0: a proof point that does not decompress, z1 or z2 >= r, a challenge u = 0, the
+ * failed check.  `tr` is advanced exactly as the reference's verifier advances it (protocol-name x 2, Cx, Cy, every entry of R = eq(r_right)
+ * as its own "a" message, challenge r, per round L, R, challenge u, then delta, beta, challenge c), and only when *accepted == 1.
+ * Two host waits: C_LZ = sum L_i C_i (and Zr * gens_1.G[0]) for the transcript, then the reference's final equation (nizk/mod.rs:560-565)
+ * moved to one side — an MSM over the 2 lg n + 4 device points of the proof and ONE one-row commit of -z1 s over the prover's derived set —
+ * whose sum must be the identity.  The same group equation, no random batching; no scalar multiplication on the CPU. */
+int sbn_polyeval_verify(sbn_ctx* ctx, const sbn_bases* gens, const sbn_bases* comm, const uint8_t* r, size_t ell, const uint8_t* C_Zr_xy, const uint8_t* Zr,
+                        const uint8_t* proof, sbn_transcript* tr, int* accepted);
+/* The n-to-1 reduction in front of it, the mirror of sbn_joint_opening_prove: DerefsEvalProof::verify_single (sparse_mlpoly_full.rs:434-457) and its
+ * two siblings in HashLayerProof::verify.  Append `evals`, challenge_vector, joint_claim = evals bound from the last challenge down, append it,
+ * then verify_plain at challenges || r with Zr = joint_claim.  out_challenges: log2 count x 32, written whenever the call returns SBN_OK (may be
+ * NULL).  Misuse as above, and a count that is no power of two or non-canonical evals. */
+int sbn_joint_opening_verify(sbn_ctx* ctx, const sbn_bases* gens, const sbn_bases* comm, const uint8_t* evals, size_t count,
+                             const uint8_t* label_evals, size_t label_evals_len, const uint8_t* label_chal, size_t label_chal_len,
+                             const uint8_t* label_claim, size_t label_claim_len, const uint8_t* r, size_t ell_r,
+                             const uint8_t* proof, sbn_transcript* tr, uint8_t* out_challenges, int* accepted);
+
 /* ---- the two ZK sumchecks of R1CSProof::prove (r1csproof.rs:295, :394) in ONE call each: ZKSumcheckInstanceProof::
  *      prove_cubic_with_additive_term (sumcheck.rs:465-649) and ::prove_quad (sumcheck.rs:657-811), with UniPoly::from_evals, the four
  *      commitments of a round and DotProductProof::prove (nizk/mod.rs:306-366) inside, the Merlin transcript included ----

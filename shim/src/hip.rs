@@ -38,7 +38,9 @@ use crate::r1cs::R1CSShape;
 use crate::r1csproof::{R1CSGens, R1CSProof};
 use crate::sparse_mlpoly_full::{SparseMatPolyCommitmentGens, SparseMatPolyEvalProof};
 use crate::sumcheck::{SumcheckInstanceProof, ZKSumcheckInstanceProof};
-use ark_serialize::CanonicalDeserialize;
+use ark_serialize::{CanonicalDeserialize, CanonicalSerialize};
+use crate::errors::ProofVerifyError;
+use crate::hyrax::{PolyCommitment, PolyCommitmentGens, PolyEvalProof};
 use crate::transcript::{AppendToTranscript, ProofTranscript};
 use crate::unipoly::{CompressedUniPoly, UniPoly};
 
@@ -145,6 +147,10 @@ extern "C" {
     pub fn sbn_bullet_finish(ctx: *mut sbn_ctx, st: *mut sbn_bullet, a_hat: *mut u8, b_hat: *mut u8, g_hat_xy: *mut u8, g_hat_is_inf: *mut c_int) -> c_int;
     pub fn sbn_polyeval_prove(ctx: *mut sbn_ctx, gens: *const sbn_bases, z: *const sbn_table, blinds: *const u8, r: *const u8, ell: usize, zr: *const u8, blind_zr: *const u8, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8, out_cx_xy: *mut u8, cx_is_inf: *mut c_int, out_cy_xy: *mut u8, cy_is_inf: *mut c_int) -> c_int;
     pub fn sbn_joint_opening_prove(ctx: *mut sbn_ctx, gens: *const sbn_bases, z: *const sbn_table, evals: *const u8, count: usize, label_evals: *const u8, label_evals_len: usize, label_chal: *const u8, label_chal_len: usize, label_claim: *const u8, label_claim_len: usize, r: *const u8, ell_r: usize, rnd: *const u8, tr: *mut sbn_transcript, out_challenges: *mut u8, out_joint_claim: *mut u8, out_proof: *mut u8, out_cx_xy: *mut u8, cx_is_inf: *mut c_int, out_cy_xy: *mut u8, cy_is_inf: *mut c_int) -> c_int;
+    pub fn sbn_g1_decompress(ctx: *mut sbn_ctx, in32: *const u8, n: usize, out_xy: *mut u8, out_ok: *mut u8) -> c_int;
+    pub fn sbn_bases_from_compressed(ctx: *mut sbn_ctx, in32: *const u8, n: usize, out: *mut *mut sbn_bases, bad_index: *mut usize) -> c_int;
+    pub fn sbn_polyeval_verify(ctx: *mut sbn_ctx, gens: *const sbn_bases, comm: *const sbn_bases, r: *const u8, ell: usize, c_zr_xy: *const u8, zr: *const u8, proof: *const u8, tr: *mut sbn_transcript, accepted: *mut c_int) -> c_int;
+    pub fn sbn_joint_opening_verify(ctx: *mut sbn_ctx, gens: *const sbn_bases, comm: *const sbn_bases, evals: *const u8, count: usize, label_evals: *const u8, label_evals_len: usize, label_chal: *const u8, label_chal_len: usize, label_claim: *const u8, label_claim_len: usize, r: *const u8, ell_r: usize, proof: *const u8, tr: *mut sbn_transcript, out_challenges: *mut u8, accepted: *mut c_int) -> c_int;
     pub fn sbn_zk_sumcheck_prove_r1cs(ctx: *mut sbn_ctx, tau: *mut sbn_table, az: *mut sbn_table, bz: *mut sbn_table, cz: *mut sbn_table, gens_1: *const sbn_bases, gens_4: *const sbn_bases, claim: *const u8, blind_claim: *const u8, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8, out_r: *mut u8, out_finals: *mut u8, out_blind: *mut u8) -> c_int;
     pub fn sbn_zk_sumcheck_prove_quad(ctx: *mut sbn_ctx, z: *mut sbn_table, abc: *mut sbn_table, gens_1: *const sbn_bases, gens_3: *const sbn_bases, claim: *const u8, blind_claim: *const u8, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8, out_r: *mut u8, out_finals: *mut u8, out_blind: *mut u8) -> c_int;
     pub fn sbn_hash_layer(ctx: *mut sbn_ctx, addr_dev: *const c_void, val: *const sbn_table, ts_dev: *const c_void, ts_add: u32, r_hash: *const u8, r_multiset: *const u8, out: *mut *mut sbn_table) -> c_int;
@@ -1251,6 +1257,97 @@ pub fn sparse_eval_prove(
     let l_d = n_proof - (32 * (13 * b + 6) + 64 * (m * (m - 1) + n * (n - 1)) + 256 * (m + b * n) + 192 * b + 64 * (lg_o + lg_m + lg_d) + 384);
     let ser = sparse_eval_stream(&proof, b, m, n, lg_o, lg_m, Some((l_d, lg_d)));
     SparseMatPolyEvalProof::deserialize_compressed(&ser[..]).expect("SparseMatPolyEvalProof from the library's bytes")
+}
+
+// ---- the opening check: PolyEvalProof::verify / verify_plain (hyrax.rs:118-151) and the n-to-1 reduction in front of it
+//      (DerefsEvalProof::verify_single, sparse_mlpoly_full.rs:434-457) in ONE foreign call each ------------------------------------------
+/// PolyCommitment.C (or any commitment that arrives as compressed points: comm_vars, comm_derefs) as a resident point set without h
+/// (sbn_bases_from_compressed).  Err(i): point i does not decompress — what GroupElement's deserialize_compressed reports (group.rs:323-329).
+pub fn bases_from_compressed(compressed: &[u8]) -> Result<Bases, usize> {
+    assert_eq!(compressed.len() % 32, 0);
+    let (mut b, mut bad) = (null_mut(), usize::MAX);
+    let rc = unsafe { sbn_bases_from_compressed(ctx(), compressed.as_ptr(), compressed.len() / 32, &mut b, &mut bad) };
+    if rc != 0 && bad != usize::MAX { return Err(bad); }
+    check(rc);
+    Ok(Bases(b))
+}
+/// the points of a PolyCommitment as the bytes `bases_from_compressed` takes: ark-serialize's stream of the Vec without its u64 length
+pub fn commitment_bytes(comm: &PolyCommitment) -> Vec<u8> {
+    let mut ser = Vec::with_capacity(8 + 32 * comm.C.len());
+    comm.C.serialize_compressed(&mut ser).expect("PolyCommitment to bytes");
+    ser.split_off(8)
+}
+/// PolyEvalProof as the library lays it out (out_proof of sbn_polyeval_prove): L_vec, R_vec, delta, beta, z1, z2 without the two u64 lengths
+fn open_bytes(proof: &PolyEvalProof) -> Vec<u8> {
+    let mut ser = Vec::new();
+    proof.serialize_compressed(&mut ser).expect("PolyEvalProof to bytes");
+    let lg = (ser.len() - 16 - 128) / 64;
+    let mut out = Vec::with_capacity(64 * lg + 128);
+    out.extend_from_slice(&ser[8..8 + 32 * lg]);
+    out.extend_from_slice(&ser[16 + 32 * lg..]);
+    out
+}
+fn verdict(accepted: c_int) -> Result<(), ProofVerifyError> {
+    if accepted == 1 { Ok(()) } else { Err(ProofVerifyError::InternalError) }         // what DotProductProofLog::verify returns (nizk/mod.rs:565)
+}
+/// PolyEvalProof::verify with a `DevTranscript`; `comm` is the commitment on the device (`bases_from_compressed`).  The transcript moves on
+/// only behind Ok(()).
+#[allow(non_snake_case)]
+pub fn polyeval_verify(
+    proof: &PolyEvalProof,
+    gens: &PolyCommitmentGens,
+    transcript: &mut DevTranscript,
+    r: &[Scalar],
+    C_Zr: &GroupElement,
+    comm: &Bases,
+) -> Result<(), ProofVerifyError> {
+    let g = pc_bases(&gens.gens.gens_n, &gens.gens.gens_1);
+    let (rb, pb) = (scalars_canonical(r), open_bytes(proof));
+    let a = affine_of(C_Zr);
+    let mut xy = [0u8; 64];
+    if !a.is_zero() {
+        xy[..32].copy_from_slice(&limbs_le(&a.x.into_bigint().0));
+        xy[32..].copy_from_slice(&limbs_le(&a.y.into_bigint().0));
+    }
+    let mut accepted: c_int = 0;
+    check(unsafe { sbn_polyeval_verify(ctx(), g.0, comm.0, rb.as_ptr(), r.len(), xy.as_ptr(), null(), pb.as_ptr(), transcript.0, &mut accepted) });
+    verdict(accepted)
+}
+/// PolyEvalProof::verify_plain (hyrax.rs:139-151): C_Zr = Zr.commit(0, gens_1) is formed on the device
+#[allow(non_snake_case)]
+pub fn polyeval_verify_plain(
+    proof: &PolyEvalProof,
+    gens: &PolyCommitmentGens,
+    transcript: &mut DevTranscript,
+    r: &[Scalar],
+    Zr: &Scalar,
+    comm: &Bases,
+) -> Result<(), ProofVerifyError> {
+    let g = pc_bases(&gens.gens.gens_n, &gens.gens.gens_1);
+    let (rb, pb, zb) = (scalars_canonical(r), open_bytes(proof), Zr.to_bytes());
+    let mut accepted: c_int = 0;
+    check(unsafe { sbn_polyeval_verify(ctx(), g.0, comm.0, rb.as_ptr(), r.len(), null(), zb.as_ptr(), pb.as_ptr(), transcript.0, &mut accepted) });
+    verdict(accepted)
+}
+/// DerefsEvalProof::verify_single (sparse_mlpoly_full.rs:434-457) and its two siblings in HashLayerProof::verify, which differ in `labels`
+/// = (evals, challenge, claim); `evals` padded to a power of two by the caller, as the reference pads them
+pub fn joint_opening_verify(
+    proof: &PolyEvalProof,
+    comm: &Bases,
+    r: &[Scalar],
+    evals: Vec<Scalar>,
+    gens: &PolyCommitmentGens,
+    transcript: &mut DevTranscript,
+    labels: (&'static [u8], &'static [u8], &'static [u8]),
+) -> Result<(), ProofVerifyError> {
+    let g = pc_bases(&gens.gens.gens_n, &gens.gens.gens_1);
+    let (rb, pb, eb) = (scalars_canonical(r), open_bytes(proof), scalars_canonical(&evals));
+    let mut accepted: c_int = 0;
+    check(unsafe {
+        sbn_joint_opening_verify(ctx(), g.0, comm.0, eb.as_ptr(), evals.len(), labels.0.as_ptr(), labels.0.len(), labels.1.as_ptr(), labels.1.len(),
+                                 labels.2.as_ptr(), labels.2.len(), rb.as_ptr(), r.len(), pb.as_ptr(), transcript.0, null_mut(), &mut accepted)
+    });
+    verdict(accepted)
 }
 
 // ---- the KZG build (--features hip,kzg): SparseMatPolyEvalProof::prove (sparse_mlpoly_full.rs:1757-1813) in ONE foreign call ---------------

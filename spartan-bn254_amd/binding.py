@@ -18,7 +18,8 @@ EXPORTED_SYMBOLS = [
     "sbn_sumcheck_begin", "sbn_sumcheck_begin_eq", "sbn_sumcheck_round", "sbn_sumcheck_len", "sbn_sumcheck_finish", "sbn_sumcheck_free",
     "sbn_transcript_new", "sbn_transcript_clone", "sbn_transcript_free", "sbn_transcript_append_message", "sbn_transcript_challenge_bytes", "sbn_transcript_challenge_scalar",
     "sbn_transcript_state", "sbn_transcript_from_state", "sbn_fr_from_wide", "sbn_sumcheck_prove", "sbn_product_proof_prove",
-    "sbn_polyeval_prove", "sbn_joint_opening_prove", "sbn_prof_last_polyeval", "sbn_zk_sumcheck_prove_r1cs", "sbn_zk_sumcheck_prove_quad",
+    "sbn_polyeval_prove", "sbn_joint_opening_prove", "sbn_prof_last_polyeval",
+    "sbn_g1_decompress", "sbn_bases_from_compressed", "sbn_polyeval_verify", "sbn_joint_opening_verify", "sbn_zk_sumcheck_prove_r1cs", "sbn_zk_sumcheck_prove_quad",
     "sbn_group_create", "sbn_group_destroy", "sbn_group_size", "sbn_group_ctx", "sbn_group_last_error", "sbn_group_bases_upload", "sbn_group_gens_new", "sbn_group_bases_precompute",
     "sbn_group_bases_free", "sbn_group_commit_rows", "sbn_group_commit_rows_dev", "sbn_group_gather_commit", "sbn_group_msm", "sbn_group_bases_upload_ranges", "sbn_group_bases_synthetic_ranges", "sbn_group_range", "sbn_group_msm_bases", "sbn_group_msm_bases_dev",
     "sbn_eq_evals", "sbn_hash_layer", "sbn_hash_layer_pair", "sbn_hash_layer_pair_product", "sbn_product_layer", "sbn_product_circuit", "sbn_product_circuit_many", "sbn_table_halves", "sbn_table_slice", "sbn_table_dot", "sbn_table_evaluate", "sbn_table_evaluate_many", "sbn_table_bound", "sbn_gather_merge", "sbn_gather_merge_rows", "sbn_commit_table", "sbn_bullet_begin", "sbn_bullet_begin_scaled", "sbn_bullet_free", "sbn_bullet_len", "sbn_bullet_cross", "sbn_bullet_fold_cross", "sbn_bullet_fold", "sbn_bullet_finish", "sbn_prof_enable", "sbn_prof_reset", "sbn_prof_count", "sbn_prof_get", "sbn_prof_last_job", "sbn_prof_last_acc",
@@ -87,6 +88,10 @@ def lib():
         L.sbn_product_proof_prove.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
         L.sbn_polyeval_prove.argtypes = [C.c_void_p] * 5 + [C.c_size_t] + [C.c_void_p] * 9
         L.sbn_joint_opening_prove.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p, C.c_size_t] * 3 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 9
+        L.sbn_g1_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.sbn_bases_from_compressed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.sbn_polyeval_verify.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 5
+        L.sbn_joint_opening_verify.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p, C.c_size_t] * 3 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 4
         L.sbn_zk_sumcheck_prove_r1cs.argtypes = [C.c_void_p] * 15
         L.sbn_zk_sumcheck_prove_quad.argtypes = [C.c_void_p] * 13
         L.sbn_r1cs_proof_sizes.argtypes = [C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
@@ -895,6 +900,46 @@ class Context:
                                                 _ptr(lcl), C.c_size_t(len(lcl)), _ptr(r), C.c_size_t(len(r) // 32), _ptr(rnd), tr.h, ch, claim, proof,
                                                 cx, C.byref(xi), cy, C.byref(yi)), "sbn_joint_opening_prove")
         return bytes(ch[:32 * lc]), bytes(claim), bytes(proof), bytes(cx), bytes(cy)
+
+    # ---- the Hyrax opening check in one call (hyrax.rs:118-151, nizk/mod.rs:525-567, nizk/bullet.rs:130-173)
+    def g1_decompress(self, comp32):
+        """deserialize_compressed of n points on the device (sbn_g1_decompress) -> (n x 64 canonical affine bytes, n flags: 0 = does not decompress)"""
+        n = len(comp32) // 32
+        xy, ok = (C.c_uint8 * max(64 * n, 1))(), (C.c_uint8 * max(n, 1))()
+        self._chk(lib().sbn_g1_decompress(self.h, _ptr(comp32), C.c_size_t(n), xy, ok), "sbn_g1_decompress")
+        return bytes(xy[:64 * n]), bytes(ok[:n])
+
+    def bases_from_compressed(self, comp32):
+        """a resident point set (no h) from compressed bytes (sbn_bases_from_compressed); a point that does not decompress raises SbnError
+        with its index in `.bad_index`"""
+        n = len(comp32) // 32
+        hb = C.c_void_p(); bad = C.c_size_t(n)
+        rc = lib().sbn_bases_from_compressed(self.h, _ptr(comp32), C.c_size_t(n), C.byref(hb), C.byref(bad))
+        if rc:
+            err = SbnError(f"sbn_bases_from_compressed: rc={rc}: {lib().sbn_last_error(self.h).decode()}")
+            err.bad_index = bad.value if bad.value < n else None
+            raise err
+        return Bases(self, hb)
+
+    def polyeval_verify(self, gens, comm, r, proof, tr, C_Zr_xy=None, Zr=None):
+        """PolyEvalProof::verify (C_Zr_xy) / verify_plain (Zr) in one call (sbn_polyeval_verify) -> accepted; comm: the L_size row commitments as a
+        Bases without h; `tr` moves on only when the proof is accepted.  Misuse raises SbnError"""
+        acc = C.c_int(0)
+        self._chk(lib().sbn_polyeval_verify(self.h, gens.h, comm.h, _ptr(r), C.c_size_t(len(r) // 32), _ptr(C_Zr_xy), _ptr(Zr), _ptr(proof), tr.h, C.byref(acc)),
+                  "sbn_polyeval_verify")
+        return bool(acc.value)
+
+    def joint_opening_verify(self, gens, comm, evals, labels, r, proof, tr):
+        """the n-to-1 reduction + verify_plain of sparse_mlpoly_full.rs:434-457 (sbn_joint_opening_verify); labels = (evals, challenge, claim)
+        -> (accepted, challenges)"""
+        count = len(evals) // 32
+        lc = count.bit_length() - 1
+        ch = (C.c_uint8 * max(32 * lc, 1))(); acc = C.c_int(0)
+        le, lch, lcl = labels
+        self._chk(lib().sbn_joint_opening_verify(self.h, gens.h, comm.h, _ptr(evals), C.c_size_t(count), _ptr(le), C.c_size_t(len(le)), _ptr(lch), C.c_size_t(len(lch)),
+                                                 _ptr(lcl), C.c_size_t(len(lcl)), _ptr(r), C.c_size_t(len(r) // 32), _ptr(proof), tr.h, ch, C.byref(acc)),
+                  "sbn_joint_opening_verify")
+        return bool(acc.value), bytes(ch[:32 * lc])
 
     def prof_last_polyeval(self):
         """host microseconds of the most recent opening: (R on the host, wait for the first commit, Cx + Cy + a_vec absorbed)"""

@@ -9,6 +9,7 @@
 //   R1CSShape multiply_vec / evaluate, compute_eval_table_sparse  src/r1cs.rs:126-163  -> sbn_r1cs_*
 //   multi_sparse_to_dense_rep, AddrTimestamps::new      src/sparse_mlpoly_full.rs:120-174, 211-243  -> sbn_dense_*
 //   PolyEvalProof::prove, DotProductProofLog::prove     src/hyrax.rs:65-116, src/nizk/mod.rs:439-522 -> sbn_polyeval_prove / sbn_joint_opening_prove
+//   PolyEvalProof::verify / verify_plain, DotProductProofLog::verify  src/hyrax.rs:118-151, src/nizk/mod.rs:525-567 -> sbn_polyeval_verify / sbn_joint_opening_verify
 //   SparseMatPolyEvalProof::prove                        src/sparse_mlpoly_full.rs:1700-1755 -> sbn_sparse_eval_prove
 //   SparseMatPolyEvalProof::prove (--features kzg), Derefs::commit_kzg  src/sparse_mlpoly_full.rs:1757-1813, 307-312 -> sbn_sparse_eval_prove_kzg / sbn_derefs_key_*
 //   ZKSumcheckInstanceProof::prove_cubic_with_additive_term, ::prove_quad, DotProductProof::prove  src/sumcheck.rs:465-811, src/nizk/mod.rs:306-366 -> sbn_zk_sumcheck_prove_r1cs / _quad
@@ -26,6 +27,7 @@
 #include "dense_kernels.cuh"
 #include "transcript_kernels.cuh"
 #include "polyeval_kernels.cuh"
+#include "decompress_kernels.cuh"
 #include "zk_sumcheck_kernels.cuh"
 #include "r1cs_proof_kernels.cuh"
 #include "sparse_eval_kernels.cuh"
@@ -64,6 +66,7 @@ using namespace sbn;
 #include "abi_proof_common.inc"
 #include "abi_bullet.inc"
 #include "abi_polyeval.inc"
+#include "abi_polyeval_verify.inc"
 #include "abi_zk_sumcheck.inc"
 #include "abi_group.inc"
 #include "abi_kzg.inc"
