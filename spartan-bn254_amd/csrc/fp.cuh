@@ -33,6 +33,15 @@ namespace sbn {
 constexpr int NL = 9;                         // limbs per element
 constexpr uint32_t LMASK = (1u << 29) - 1;
 
+// Wave priority of the kernels on a single MSM's critical path OTHER than the accumulate (split, sort, bucket ordering, merge, combine levels): the first
+// statement of each.  A SIMD issues VALU by priority, then age; beside another MSM's k_acc_first waves (priority 0, ~370 us old, VALU 93 % of the time) a
+// younger helper wave got the leftover slots.  Raised, it outranks them one for one and gives the slots back when it ends: the total VALU work is
+// unchanged.  Rule: k_acc_first / k_acc_extra never call this; where the helpers fill the chip themselves all waves are equal and nothing changes.
+// k_reduce_l1 does not call it either: one wave per SIMD that issues VALU all the time gains nothing from it (msm_kernels.cuh).  Priority 3 measured no better than 1.
+// (s_setprio is scalar and ignores EXEC: one unconditional instruction per wave.)
+constexpr int WAVE_PRIO_HELPER = 1;
+__device__ __forceinline__ void wave_prio_helper() { __builtin_amdgcn_s_setprio(WAVE_PRIO_HELPER); }
+
 struct FqP {
   // the modulus as 8 x 32-bit words (memory format, canonical test)
   static constexpr uint32_t P0 = 0xd87cfd47u, P1 = 0x3c208c16u, P2 = 0x6871ca8du, P3 = 0x97816a91u,

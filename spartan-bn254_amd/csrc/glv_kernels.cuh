@@ -118,6 +118,7 @@ __device__ __forceinline__ void glv_split(const uint64_t (&k)[4], uint64_t (&k1)
 // sort read 16-byte records: k_s2_count / k_s2_scatter<C, SPT, 4>).  Scalars >= r are counted in *bad (SBN_EINVAL, as on the plain
 // path) and split as zero.
 __global__ void __launch_bounds__(256) k_glv_split(const uint32_t* __restrict__ scalars, size_t n, uint32_t* __restrict__ out, uint32_t* __restrict__ bad) {
+  wave_prio_helper();
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
   const uint4 a = reinterpret_cast<const uint4*>(scalars + 8 * t)[0], b = reinterpret_cast<const uint4*>(scalars + 8 * t)[1];

@@ -104,7 +104,9 @@ static void launch_accumulate(sbn_ctx* c, const uint32_t* points, size_t NB, int
   const unsigned agrid = (unsigned)((NB * (size_t)a.LPB + 255) / 256);
   LAUNCH(c, "k_acc_first", (a.LPB == 1 ? k_acc_first<1> : k_acc_first<2>), agrid, 256, points, NB, nb, estride, SEG, hist, offs, sorted, (const uint32_t*)c->perm.p, buckets, ctr,
          (ExtraItem*)c->extra_list.p, (BigItem*)c->big_list.p);
-  LAUNCH(c, "k_acc_extra", k_acc_extra, 2048, 256, points, nb, estride, SEG, hist, offs, sorted, (const AccCounters*)ctr, (const ExtraItem*)c->extra_list.p, (uint32_t*)c->extra_out.p);
+  // grid-stride over at most max_extra items (the work list's capacity): no more blocks than that many lanes, 2048 at the most
+  const unsigned egrid = (unsigned)std::max<size_t>(1, std::min<size_t>(2048, (a.max_extra + 255) / 256));
+  LAUNCH(c, "k_acc_extra", k_acc_extra, egrid, 256, points, nb, estride, SEG, hist, offs, sorted, (const AccCounters*)ctr, (const ExtraItem*)c->extra_list.p, (uint32_t*)c->extra_out.p);
   LAUNCH(c, "k_acc_merge", k_acc_merge, 4096, 64, (const AccCounters*)ctr, (const BigItem*)c->big_list.p, (const uint32_t*)c->extra_out.p, buckets, a.LPB);
 }
 // weighted sums of the buckets per problem -> c->wsum (P x XYZZ)

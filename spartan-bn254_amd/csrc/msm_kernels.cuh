@@ -352,6 +352,7 @@ __device__ __forceinline__ XYZZ acc_segment(const uint32_t* __restrict__ points,
 // then run chains of equal length instead of waiting for the longest of 64 Poisson draws, and the heaviest waves are
 // dispatched first so the tail of the launch is made of the lightest ones.
 __global__ void __launch_bounds__(1024) k_size_hist(const uint32_t* __restrict__ hist, size_t nbuckets, uint32_t SEG, uint32_t* __restrict__ gbins) {
+  wave_prio_helper();
   __shared__ uint32_t bins[ACC_SEG_MAX + 2];
   for (uint32_t j = threadIdx.x; j <= SEG; j += blockDim.x) bins[j] = 0;
   __syncthreads();
@@ -363,6 +364,7 @@ __global__ void __launch_bounds__(1024) k_size_hist(const uint32_t* __restrict__
 // exclusive scan of the SEG + 1 bins by one wave: lane l owns a contiguous run of bins, the runs' totals are scanned with shuffles
 // (one lane walking all bins was a 27 us dependent chain on the critical path of a single MSM)
 __global__ void __launch_bounds__(64) k_size_scan(uint32_t* __restrict__ gbins, uint32_t SEG) {
+  wave_prio_helper();
   const uint32_t n = SEG + 1, per = (n + 63) / 64, lane = threadIdx.x;
   const uint32_t j0 = lane * per, j1 = (j0 + per < n) ? j0 + per : n;
   uint32_t sum = 0;
@@ -374,6 +376,7 @@ __global__ void __launch_bounds__(64) k_size_scan(uint32_t* __restrict__ gbins, 
   for (uint32_t j = j0; j < j1; j++) { const uint32_t v = gbins[j]; gbins[j] = run; run += v; }
 }
 __global__ void __launch_bounds__(1024) k_size_scatter(const uint32_t* __restrict__ hist, size_t nbuckets, uint32_t SEG, uint32_t* __restrict__ gcur, uint32_t* __restrict__ perm) {
+  wave_prio_helper();
   __shared__ uint32_t bins[ACC_SEG_MAX + 2];
   __shared__ uint32_t base[ACC_SEG_MAX + 2];
   for (uint32_t j = threadIdx.x; j <= SEG; j += blockDim.x) bins[j] = 0;
@@ -472,6 +475,7 @@ __device__ __forceinline__ XYZZ xyzz_mul_small(const XYZZ& v, uint32_t k) {
 // wave), a bucket with many by one whole wave (lane-strided chains, then a wave tree)
 // (`G` = slots per bucket: the extras are folded into the bucket's first slot)
 __global__ void __launch_bounds__(64) k_acc_merge(const AccCounters* __restrict__ ctr, const BigItem* __restrict__ big, const uint32_t* __restrict__ extra_out, uint32_t* __restrict__ buckets, int G) {
+  wave_prio_helper();
   const int lane = threadIdx.x;
   const uint32_t total = ctr->big_count;
   if (total == 0) return;                                  // uniform scalars: no oversized bucket — the launch is a no-op (one launch, not two, since round 4)
@@ -505,6 +509,8 @@ __device__ __forceinline__ XYZZ bucket_load(const uint32_t* __restrict__ p, int 
 }
 // L: buckets per lane (any value >= 1: the host picks it so that the chunks spread evenly over the SIMDs); nb: buckets per problem; the last chunk of a
 // problem may be ragged (buckets past nb count as the identity).
+// (No wave_prio_helper() here, alone among the helpers: measured, the raise leaves this kernel's time beside other MSMs where it was, 283 - 303 us, and costs
+//  it 2.5 us alone, 0.1762 -> 0.1790 ms; profiles/r20_helper_priority_bench_ab.txt, call 5.)
 __global__ void __launch_bounds__(64) k_reduce_l1(const uint32_t* __restrict__ X, int L, int nb, uint32_t* __restrict__ out, const uint8_t* __restrict__ skip, int chunks_per_problem, int G) {
   const int lane = threadIdx.x;
   const size_t chunk = blockIdx.x;
@@ -538,6 +544,7 @@ __global__ void __launch_bounds__(64) k_reduce_l1(const uint32_t* __restrict__ X
 // G = chunks per problem at the input level (lanes past G contribute the identity); Gout = ceil(G/64).
 // When `final` is set (Gout == 1) the wave writes sum_b (b+1) X_b = Wt' + S' as a single point instead.
 __global__ void __launch_bounds__(64) k_reduce_combine(const uint32_t* __restrict__ in, int G, int Gout, int k64, int Lb, int final, uint32_t* __restrict__ out) {
+  wave_prio_helper();
   const int lane = threadIdx.x;
   const size_t prob = blockIdx.x / Gout;
   const int grp = blockIdx.x % Gout;
@@ -594,6 +601,7 @@ __device__ __forceinline__ XYZZ quad_tree_sum(XYZZ v, int q, int role, uint32_t*
   return v;
 }
 __global__ void __launch_bounds__(256) k_reduce_combine_quad(const uint32_t* __restrict__ in, int G, int Gout, int k64, int Lb, int final, uint32_t* __restrict__ out) {
+  wave_prio_helper();
   __shared__ __align__(16) uint32_t sm[64 * 32];
   const int q = threadIdx.x >> 2, role = threadIdx.x & 3;
   const size_t prob = blockIdx.x / Gout;

@@ -74,6 +74,7 @@ __device__ __forceinline__ void s2_count_scalar(const s2_u32x8 kk, int P, int lo
 }
 template <int C, int SPT, int SW = 8>
 __global__ void __launch_bounds__(1024) k_s2_count(const uint32_t* __restrict__ scalars, S2Geom g, uint32_t* __restrict__ cntA, uint32_t* __restrict__ bad) {
+  wave_prio_helper();
   constexpr int W = S2Shape<C, SW>::W; constexpr int CH = 1024 * SPT;
   const int k = blockIdx.x, P = g.P;
   for (int j = threadIdx.x; j < W * P; j += 1024) s2_lds[j] = 0;
@@ -106,6 +107,7 @@ __device__ __forceinline__ uint32_t s2_block_scan(uint32_t v, uint32_t* tmp /* 1
 }
 // pass B1: row j = (w, hi): exclusive prefix over the K chunks in place, total -> part_cnt[j]
 __global__ void __launch_bounds__(256) k_s2_prefix_k(uint32_t* __restrict__ cntA, int K, uint32_t* __restrict__ part_cnt) {
+  wave_prio_helper();
   __shared__ uint32_t tmp[17];
   uint32_t* row = cntA + (size_t)blockIdx.x * K;
   const int per = (K + 255) / 256, b0 = threadIdx.x * per;
@@ -120,6 +122,7 @@ __global__ void __launch_bounds__(256) k_s2_prefix_k(uint32_t* __restrict__ cntA
 // cut into ceil(cnt / S2_SUB) sub-chunks, so level-2 blocks carry equal loads whatever the partition sizes are (the short top
 // window puts all its entries into a few partitions; skewed scalars do the same anywhere).
 __global__ void __launch_bounds__(1024) k_s2_prefix_hi(const uint32_t* __restrict__ part_cnt, int W, int P, uint32_t* __restrict__ part_off, uint32_t* __restrict__ sc_off) {
+  wave_prio_helper();
   // ONE scan over the flat (window, partition) array instead of W scans one after the other (26 us on the critical path of a single
   // MSM): every thread owns a run of consecutive entries; part_off first receives the GLOBAL exclusive prefix (mod 2^32: only
   // differences are used) and then loses its window's start.
@@ -195,6 +198,7 @@ __device__ __forceinline__ void s2_scatter_windows(const s2_u32x8 (&kk)[SPT], ui
 template <int C, int SPT, int SW = 8>
 __global__ void __launch_bounds__(1024) k_s2_scatter(const uint32_t* __restrict__ scalars, S2Geom g, const uint32_t* __restrict__ cntA /* prefixed over k */,
                                                      const uint32_t* __restrict__ part_off, uint32_t* __restrict__ tmp_idx, uint16_t* __restrict__ tmp_lo) {
+  wave_prio_helper();
   S2ScatterArgs a; a.cntA = cntA; a.part_off = part_off; a.tmp_idx = tmp_idx; a.tmp_lo = tmp_lo; a.n = g.n; a.P = g.P; a.K = g.K; a.k = blockIdx.x; a.lo_log = g.lo_log;
   a.half = g.half; a.gap = SW == 8 ? 0 : g.gap;
   s2_u32x8 kk[SPT]; uint32_t carry[SPT];
@@ -229,6 +233,7 @@ __device__ __forceinline__ void s2_range(const S2Geom& g, const uint32_t* __rest
 }
 // blockhist[sidx * LO + lo]
 __global__ void __launch_bounds__(1024) k_s2_hist(const uint16_t* __restrict__ tmp_lo, S2Geom g, const uint32_t* __restrict__ part_off, const uint32_t* __restrict__ part_cnt, const uint32_t* __restrict__ sc_off, uint32_t* __restrict__ blockhist) {
+  wave_prio_helper();
   __shared__ uint32_t h[S2_LO_MAX];
   int q; uint32_t sidx, k2; if (!s2_decode(g, sc_off, q, sidx, k2)) return;
   const int LO = 1 << g.lo_log;
@@ -243,6 +248,7 @@ __global__ void __launch_bounds__(1024) k_s2_hist(const uint16_t* __restrict__ t
 // one block per partition: exclusive prefix over its sub-chunks for every bucket (in place), the bucket sizes (hist) and the
 // bucket start offsets inside the window (offs = partition start + exclusive prefix over the partition's buckets)
 __global__ void __launch_bounds__(1024) k_s2_prefix2(uint32_t* __restrict__ blockhist, S2Geom g, const uint32_t* __restrict__ part_off, const uint32_t* __restrict__ sc_off, uint32_t* __restrict__ hist, uint32_t* __restrict__ offs) {
+  wave_prio_helper();
   __shared__ uint32_t tmp[17];
   const int q = blockIdx.x, LO = 1 << g.lo_log, w = q / g.P, hi = q - w * g.P;
   const uint32_t s0 = sc_off[q], nk = sc_off[q + 1] - s0;
@@ -269,6 +275,7 @@ __host__ __device__ inline size_t s2_place_lds_bytes(int lo_log) { return ((size
 __global__ void __launch_bounds__(1024) k_s2_place(const uint16_t* __restrict__ tmp_lo, const uint32_t* __restrict__ tmp_idx, S2Geom g, const uint32_t* __restrict__ part_off, const uint32_t* __restrict__ part_cnt,
                                                    const uint32_t* __restrict__ sc_off, const uint32_t* __restrict__ blockhist /* prefixed over the partition's sub-chunks */,
                                                    const uint32_t* __restrict__ offs, uint32_t* __restrict__ sorted, size_t estride) {
+  wave_prio_helper();
   constexpr uint32_t T = 1024 * S2_EPT;
   int q; uint32_t sidx, k2; if (!s2_decode(g, sc_off, q, sidx, k2)) return;
   const int LO = 1 << g.lo_log, tid = threadIdx.x;
