@@ -543,6 +543,39 @@ int sbn_r1cs_proof_prove(sbn_ctx* ctx, const sbn_r1cs* inst, const sbn_table* va
                          const sbn_bases* gens_pc, const sbn_bases* gens_3, const sbn_bases* gens_4, const uint8_t* rnd, sbn_transcript* tr,
                          uint8_t* out_proof, uint8_t* out_rx, uint8_t* out_ry);
 
+/* ---- the CHECK of that proof in one call: R1CSProof::verify (r1csproof.rs:463-619) and, on its own, ZKSumcheckInstanceProof::verify
+ *      (sumcheck.rs:366-457) with DotProductProof::verify (nizk/mod.rs:368-400) inside, the Merlin transcript included ----
+ * No fresh point is multiplied: every point of a check is a point of the proof or a generator and every coefficient a scalar the host derives
+ * from the transcript (c * Cy_i = (c w0) P_{i-1} + (c w1) comm_eval_i), so every check is a sum of entries of one table T[p][k] = 2^k P_p,
+ * selected by scalar bits.  Per call: ONE decompress launch over all the proof's points, ONE table launch over them and the generators, one
+ * sum launch and one host wait for each point whose bytes the transcript needs, and ONE last launch for every equation, each moved to one
+ * side, answered as packed "the sum is the identity" bits.  The same group equations, no random batching; no scalar multiplication and no
+ * point addition on the CPU.
+ * Both calls follow the contract of sbn_polyeval_verify.  The return code reports misuse only — SBN_EINVAL before any launch, `tr` unchanged.
+ * What an adversary controls gives SBN_OK with *accepted = 0: a point that does not decompress, a scalar of the proof >= r, any failed
+ * check.  `tr` is advanced exactly as the reference's verifier advances it, and only when *accepted == 1; the out_ arrays are written only then.
+ *
+ * sbn_zk_sumcheck_verify:  gens_1: one generator with h; gens_n: degree_bound + 1 generators with h; comm_claim_xy: canonical affine (all-zero:
+ *   the identity); proof: num_rounds x (6 + n) x 32 with n = degree_bound + 1, the out_proof of sbn_zk_sumcheck_prove_r1cs (3) / _quad (2).
+ *   out_r: num_rounds x 32; out_comm_eval_xy: comm_evals[num_rounds - 1] (sumcheck.rs:456), canonical affine.  num_rounds + 1 sum launches.
+ *   Misuse: a NULL pointer, num_rounds == 0 or > 64, degree_bound outside {2, 3}, a generator handle of the wrong size or without h, a
+ *   comm_claim_xy that is no canonical point of the curve. */
+int sbn_zk_sumcheck_verify(sbn_ctx* ctx, const sbn_bases* gens_1, const sbn_bases* gens_n, const uint8_t comm_claim_xy[64],
+                           size_t num_rounds, size_t degree_bound, const uint8_t* proof, sbn_transcript* tr,
+                           uint8_t* out_r, uint8_t out_comm_eval_xy[64], int* accepted);
+/* sbn_r1cs_proof_verify:  shape, input, gens_pc, gens_3, gens_4 as sbn_r1cs_proof_prove takes them; proof: its out_proof (sbn_r1cs_proof_sizes).
+ *   evals = A(rx, ry) || B(rx, ry) || C(rx, ry), canonical: the caller's, as in the reference (r1csproof.rs:469) — sbn_r1cs_evaluate after a
+ *   first pass, or the proof's inst_evals; it enters the last equality check only (:603-605).
+ *   In the reference's order: both sumcheck checks, KnowledgeProof / ProductProof / EqualityProof::verify (nizk/mod.rs:61-81, :243-283, :126-149),
+ *   the opening of comm_vars at ry[1..] (the body of sbn_polyeval_verify on a handle made of the proof's bytes, as sbn_bases_from_compressed
+ *   makes one: its own two waits), poly_input_eval (:580-594).  nx + ny + 3 sum launches with a wait each (Cy of every round, phase 2's
+ *   comm_claim, the two `expected` points) and one for the 2 (nx + ny) + 6 equations.
+ *   Misuse: a NULL pointer (input may be NULL with num_inputs == 0), a shape below 2 or no power of two, num_inputs >= num_vars, a generator
+ *   handle of the wrong size or without h, a non-canonical input or evals. */
+int sbn_r1cs_proof_verify(sbn_ctx* ctx, size_t num_cons, size_t num_vars, const uint8_t* input, size_t num_inputs, const uint8_t evals[96],
+                          const sbn_bases* gens_pc, const sbn_bases* gens_3, const sbn_bases* gens_4, const uint8_t* proof,
+                          sbn_transcript* tr, uint8_t* out_rx, uint8_t* out_ry, int* accepted);
+
 /* ---- MultiSparseMatPolynomialAsDense on the device: what SNARK::encode -> R1CSShape::commit (r1cs.rs:375-400) builds once per circuit ----
  * SparseMatPolynomial::multi_sparse_to_dense_rep -> AddrTimestamps::new (sparse_mlpoly_full.rs:89-101, 120-174, 211-243), from the same
  * (row, col, val) triplets sbn_r1cs_upload takes, in the caller's entry order.  `batch` matrices (1 .. 8; the reference uses 3), nnz[k] entries each.

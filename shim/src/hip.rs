@@ -195,6 +195,8 @@ extern "C" {
     pub fn sbn_r1cs_evaluate(ctx: *mut sbn_ctx, m: *const sbn_r1cs, rx: *const u8, ell_x: usize, ry: *const u8, ell_y: usize, out: *mut u8) -> c_int;
     pub fn sbn_r1cs_proof_sizes(num_cons: usize, num_vars: usize, rnd_scalars: *mut usize, proof_bytes: *mut usize) -> c_int;
     pub fn sbn_r1cs_proof_prove(ctx: *mut sbn_ctx, inst: *const sbn_r1cs, vars: *const sbn_table, input: *const u8, num_inputs: usize, gens_pc: *const sbn_bases, gens_3: *const sbn_bases, gens_4: *const sbn_bases, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8, out_rx: *mut u8, out_ry: *mut u8) -> c_int;
+    pub fn sbn_zk_sumcheck_verify(ctx: *mut sbn_ctx, gens_1: *const sbn_bases, gens_n: *const sbn_bases, comm_claim_xy: *const u8, num_rounds: usize, degree_bound: usize, proof: *const u8, tr: *mut sbn_transcript, out_r: *mut u8, out_comm_eval_xy: *mut u8, accepted: *mut c_int) -> c_int;
+    pub fn sbn_r1cs_proof_verify(ctx: *mut sbn_ctx, num_cons: usize, num_vars: usize, input: *const u8, num_inputs: usize, evals: *const u8, gens_pc: *const sbn_bases, gens_3: *const sbn_bases, gens_4: *const sbn_bases, proof: *const u8, tr: *mut sbn_transcript, out_rx: *mut u8, out_ry: *mut u8, accepted: *mut c_int) -> c_int;
     pub fn sbn_dense_build(ctx: *mut sbn_ctx, num_vars_x: usize, num_vars_y: usize, rows: *const *const u32, cols: *const *const u32, vals: *const *const u8, nnz: *const usize, batch: usize, flags: u32, out: *mut *mut sbn_dense) -> c_int;
     pub fn sbn_dense_free(ctx: *mut sbn_ctx, d: *mut sbn_dense);
     pub fn sbn_dense_num_ops(d: *const sbn_dense) -> usize;

@@ -25,7 +25,7 @@ EXPORTED_SYMBOLS = [
     "sbn_eq_evals", "sbn_hash_layer", "sbn_hash_layer_pair", "sbn_hash_layer_pair_product", "sbn_product_layer", "sbn_product_circuit", "sbn_product_circuit_many", "sbn_table_halves", "sbn_table_slice", "sbn_table_dot", "sbn_table_evaluate", "sbn_table_evaluate_many", "sbn_table_bound", "sbn_gather_merge", "sbn_gather_merge_rows", "sbn_commit_table", "sbn_bullet_begin", "sbn_bullet_begin_scaled", "sbn_bullet_free", "sbn_bullet_len", "sbn_bullet_cross", "sbn_bullet_fold_cross", "sbn_bullet_fold", "sbn_bullet_finish", "sbn_prof_enable", "sbn_prof_reset", "sbn_prof_count", "sbn_prof_get", "sbn_prof_last_job", "sbn_prof_last_acc",
     "sbn_kzg_srs_upload", "sbn_kzg_srs_from_tau", "sbn_kzg_commit", "sbn_poly_div_linear", "sbn_kzg_open", "sbn_kzg_open_batched",
     "sbn_r1cs_upload", "sbn_r1cs_free", "sbn_r1cs_multiply", "sbn_r1cs_eval_table", "sbn_r1cs_evaluate",
-    "sbn_r1cs_proof_sizes", "sbn_r1cs_proof_prove", "sbn_sparse_eval_sizes", "sbn_sparse_eval_prove",
+    "sbn_r1cs_proof_sizes", "sbn_r1cs_proof_prove", "sbn_zk_sumcheck_verify", "sbn_r1cs_proof_verify", "sbn_sparse_eval_sizes", "sbn_sparse_eval_prove",
     "sbn_derefs_key_build", "sbn_derefs_key_free", "sbn_derefs_key_len", "sbn_derefs_key_download", "sbn_derefs_key_commit",
     "sbn_sparse_eval_kzg_sizes", "sbn_sparse_eval_prove_kzg",
     "sbn_dense_build", "sbn_dense_free", "sbn_dense_num_ops", "sbn_dense_num_cells", "sbn_dense_batch", "sbn_dense_addr_dev", "sbn_dense_read_ts_dev",
@@ -96,6 +96,8 @@ def lib():
         L.sbn_zk_sumcheck_prove_quad.argtypes = [C.c_void_p] * 13
         L.sbn_r1cs_proof_sizes.argtypes = [C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
         L.sbn_r1cs_proof_prove.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 8
+        L.sbn_zk_sumcheck_verify.argtypes = [C.c_void_p] * 4 + [C.c_size_t] * 2 + [C.c_void_p] * 5
+        L.sbn_r1cs_proof_verify.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_void_p] * 9
         L.sbn_sparse_eval_sizes.argtypes = [C.c_size_t] * 4 + [C.c_void_p] * 2
         L.sbn_sparse_eval_prove.argtypes = [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_void_p] * 7
         L.sbn_sparse_eval_kzg_sizes.argtypes = [C.c_size_t] * 4 + [C.c_void_p] * 2
@@ -976,6 +978,34 @@ class Context:
         self._chk(lib().sbn_r1cs_proof_prove(self.h, inst.h, vars.h, _ptr(inputs) if inputs else None, C.c_size_t(len(inputs) // 32 if inputs else 0),
                                              gens_pc.h, gens_3.h, gens_4.h, _ptr(rnd), tr.h, proof, rx, ry), "sbn_r1cs_proof_prove")
         return bytes(proof), bytes(rx), bytes(ry)
+
+    # ---- R1CSProof::verify and ZKSumcheckInstanceProof::verify in one call each (r1csproof.rs:463-619, sumcheck.rs:366-457)
+    def zk_sumcheck_verify(self, gens_1, gens_n, comm_claim_xy, num_rounds, degree_bound, proof, tr):
+        """ZKSumcheckInstanceProof::verify (sbn_zk_sumcheck_verify) -> (comm_evals[-1] as 64 canonical affine bytes, challenges), or None when the
+        proof is refused; proof: the out_proof of zk_sumcheck_prove_r1cs (degree_bound 3) / _quad (2); `tr` moves on only when the proof is accepted.
+        Misuse raises SbnError"""
+        n = degree_bound + 1
+        if len(proof) != (6 + n) * 32 * num_rounds:
+            raise ValueError(f"zk_sumcheck_verify: the proof holds {len(proof)} bytes, {num_rounds} rounds of degree {degree_bound} need {(6 + n) * 32 * num_rounds}")
+        rs = (C.c_uint8 * max(32 * num_rounds, 1))(); xy = (C.c_uint8 * 64)(); acc = C.c_int(0)
+        self._chk(lib().sbn_zk_sumcheck_verify(self.h, gens_1.h, gens_n.h, _ptr(comm_claim_xy), C.c_size_t(num_rounds), C.c_size_t(degree_bound), _ptr(proof), tr.h,
+                                               rs, xy, C.byref(acc)), "sbn_zk_sumcheck_verify")
+        return (bytes(xy), bytes(rs[:32 * num_rounds])) if acc.value else None
+
+    def r1cs_proof_verify(self, num_cons, num_vars, inputs, evals, gens_pc, gens_3, gens_4, proof, tr):
+        """R1CSProof::verify (sbn_r1cs_proof_verify) -> (rx, ry), or None when the proof is refused; inputs: canonical scalars, 32 bytes each (b"" for
+        none); evals: A, B, C(rx, ry), 96 bytes; proof: the out_proof of r1cs_proof_prove; `tr` moves on only when the proof is accepted.  Misuse raises
+        SbnError"""
+        n_proof = r1cs_proof_sizes(num_cons, num_vars)[1]
+        if len(proof) != n_proof:
+            raise ValueError(f"r1cs_proof_verify: the proof holds {len(proof)} bytes, the shape needs {n_proof}")
+        if len(evals) != 96:
+            raise ValueError(f"r1cs_proof_verify: evals holds {len(evals)} bytes, A, B, C(rx, ry) are 96")
+        nx, ny = num_cons.bit_length() - 1, num_vars.bit_length()
+        rx = (C.c_uint8 * (32 * nx))(); ry = (C.c_uint8 * (32 * ny))(); acc = C.c_int(0)
+        self._chk(lib().sbn_r1cs_proof_verify(self.h, C.c_size_t(num_cons), C.c_size_t(num_vars), _ptr(inputs) if inputs else None, C.c_size_t(len(inputs) // 32 if inputs else 0),
+                                              _ptr(evals), gens_pc.h, gens_3.h, gens_4.h, _ptr(proof), tr.h, rx, ry, C.byref(acc)), "sbn_r1cs_proof_verify")
+        return (bytes(rx), bytes(ry)) if acc.value else None
 
     # ---- SparseMatPolyEvalProof::prove in one call (sparse_mlpoly_full.rs:1700-1755)
     def sparse_eval_prove(self, dense, rx, ry, evals, gens_ops, gens_mem, gens_derefs, rnd, tr):

@@ -43,18 +43,22 @@ static int msm_windows_launch(sbn_ctx* c, const uint32_t* d_scal, const uint32_t
 
 static const int VERIFY_STAGE_POINTS = 64;      // window sums of one MSM (<= 37 at c = 7, the narrowest window) and two commit sums
 static const uint32_t VBOX_EXTRA_WORDS = 16, VBOX_FLAG_WORD = 32 * VERIFY_STAGE_POINTS + VBOX_EXTRA_WORDS, VBOX_WORDS = VBOX_FLAG_WORD + 16;
-// `npoints` XYZZ sums at d_pts and the `nextra` words at d_extra to the host in ONE launch and ONE wait: the hand-over of a bullet round
-// (k_points_to_host, sc_flag_wait) into an area of its own — the window sums of an MSM do not fit the mailbox's final-claims words
-static int verify_handover(sbn_ctx* c, const uint32_t* d_pts, size_t npoints, const uint32_t* d_extra, uint32_t nextra, sbn_host::Pt* out, uint32_t* extra_out) {
-  int rc;
-  if (npoints > (size_t)VERIFY_STAGE_POINTS || nextra > VBOX_EXTRA_WORDS) return fail(c, SBN_EINVAL, "polyeval verify: %zu points and %u words do not fit the hand-over area", npoints, nextra);
+// the hand-over area, allocated on first use
+static int vbox_ensure(sbn_ctx* c) {
   if (!c->vbox) {
     uint32_t* vb = nullptr;
     HIPCHK(c, hipHostMalloc((void**)&vb, VBOX_WORDS * 4, hipHostMallocMapped | hipHostMallocCoherent));
     memset(vb, 0, VBOX_WORDS * 4);
     c->vbox = vb;
   }
-  if ((rc = sc_tickets(c))) return rc;                                  // (the mailbox whose sequence numbers the flag takes)
+  return sc_tickets(c);                                                 // (the mailbox whose sequence numbers the flag takes)
+}
+// `npoints` XYZZ sums at d_pts and the `nextra` words at d_extra to the host in ONE launch and ONE wait: the hand-over of a bullet round
+// (k_points_to_host, sc_flag_wait) into an area of its own — the window sums of an MSM do not fit the mailbox's final-claims words
+static int verify_handover(sbn_ctx* c, const uint32_t* d_pts, size_t npoints, const uint32_t* d_extra, uint32_t nextra, sbn_host::Pt* out, uint32_t* extra_out) {
+  int rc;
+  if (npoints > (size_t)VERIFY_STAGE_POINTS || nextra > VBOX_EXTRA_WORDS) return fail(c, SBN_EINVAL, "polyeval verify: %zu points and %u words do not fit the hand-over area", npoints, nextra);
+  if ((rc = vbox_ensure(c))) return rc;
   const uint32_t seq = ++c->mbox_seq;
   LAUNCH(c, "k_points_to_host", k_points_to_host, 1, 256, d_pts, (uint32_t)npoints, d_extra, nextra, c->vbox, c->vbox + VBOX_FLAG_WORD, seq);
   LAUNCHCHK(c);
@@ -237,30 +241,9 @@ static int verify_on_copy(sbn_ctx* c, sbn_transcript* tr, int* accepted, Body bo
   return SBN_OK;
 }
 
-extern "C" {
-
-int sbn_g1_decompress(sbn_ctx* c, const uint8_t* in32, size_t n, uint8_t* out_xy, uint8_t* out_ok) {
-  if (!c || ((!in32 || !out_xy || !out_ok) && n)) return SBN_EINVAL;
-  if (n == 0) return SBN_OK;
-  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
-  int rc;
-  const size_t o_xy = 32 * n, o_ok = o_xy + 64 * n;
-  if ((rc = ensure(c, c->stage_pts, o_ok + n))) return rc;
-  uint8_t* p = (uint8_t*)c->stage_pts.p;
-  HIPCHK(c, hipMemcpyAsync(p, in32, 32 * n, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "k_g1_decompress", k_g1_decompress, (unsigned)((n + 63) / 64), 64, (const uint32_t*)p, n, (uint32_t*)(p + o_xy), (uint32_t*)nullptr, p + o_ok);
-  LAUNCHCHK(c);
-  HIPCHK(c, hipMemcpyAsync(out_xy, p + o_xy, 64 * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(out_ok, p + o_ok, n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->prof) prof_drain(c);
-  return SBN_OK;
-}
-
-int sbn_bases_from_compressed(sbn_ctx* c, const uint8_t* in32, size_t n, sbn_bases** out, size_t* bad_index) {
-  if (!c || !out || (!in32 && n)) return SBN_EINVAL;
-  *out = nullptr;
-  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+// sbn_bases_from_compressed with the context's mutex held: a handle over n decompressed points.  A point that does not decompress is SBN_EINVAL
+// with its index in *bad_index (which the caller set to SIZE_MAX to tell it from other misuse)
+static int bases_from_compressed_locked(sbn_ctx* c, const uint8_t* in32, size_t n, sbn_bases** out, size_t* bad_index) {
   int rc;
   const size_t o_xy = 32 * n, o_ok = o_xy + 64 * n;
   if ((rc = ensure(c, c->stage_pts, o_ok + n + 64))) return rc;
@@ -292,6 +275,33 @@ int sbn_bases_from_compressed(sbn_ctx* c, const uint8_t* in32, size_t n, sbn_bas
   if (n && (rc = bases_build_dedupe(c, b, keys))) { sbn_bases_free(c, b); return rc; }
   *out = b;
   return SBN_OK;
+}
+
+extern "C" {
+
+int sbn_g1_decompress(sbn_ctx* c, const uint8_t* in32, size_t n, uint8_t* out_xy, uint8_t* out_ok) {
+  if (!c || ((!in32 || !out_xy || !out_ok) && n)) return SBN_EINVAL;
+  if (n == 0) return SBN_OK;
+  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+  int rc;
+  const size_t o_xy = 32 * n, o_ok = o_xy + 64 * n;
+  if ((rc = ensure(c, c->stage_pts, o_ok + n))) return rc;
+  uint8_t* p = (uint8_t*)c->stage_pts.p;
+  HIPCHK(c, hipMemcpyAsync(p, in32, 32 * n, hipMemcpyHostToDevice, c->stream));
+  LAUNCH(c, "k_g1_decompress", k_g1_decompress, (unsigned)((n + 63) / 64), 64, (const uint32_t*)p, n, (uint32_t*)(p + o_xy), (uint32_t*)nullptr, p + o_ok);
+  LAUNCHCHK(c);
+  HIPCHK(c, hipMemcpyAsync(out_xy, p + o_xy, 64 * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out_ok, p + o_ok, n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->prof) prof_drain(c);
+  return SBN_OK;
+}
+
+int sbn_bases_from_compressed(sbn_ctx* c, const uint8_t* in32, size_t n, sbn_bases** out, size_t* bad_index) {
+  if (!c || !out || (!in32 && n)) return SBN_EINVAL;
+  *out = nullptr;
+  std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+  return bases_from_compressed_locked(c, in32, n, out, bad_index);
 }
 
 int sbn_polyeval_verify(sbn_ctx* c, const sbn_bases* gens, const sbn_bases* comm, const uint8_t* r, size_t ell, const uint8_t* C_Zr_xy, const uint8_t* Zr,
