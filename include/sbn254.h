@@ -576,6 +576,50 @@ int sbn_r1cs_proof_verify(sbn_ctx* ctx, size_t num_cons, size_t num_vars, const 
                           const sbn_bases* gens_pc, const sbn_bases* gens_3, const sbn_bases* gens_4, const uint8_t* proof,
                           sbn_transcript* tr, uint8_t* out_rx, uint8_t* out_ry, int* accepted);
 
+/* ---- many short sums of fresh points in ONE launch: what a verifier's equations over a handful of proof points are in the reference,
+ *      GroupElement::vartime_multiscalar_mul (group.rs:143-158) over 2 lg n + 4 points in DotProductProofLog::verify (nizk/mod.rs:560-565) and
+ *      over 2 .. 8 in DotProductProof / EqualityProof::verify (nizk/mod.rs:389-394, :141-146) ----
+ * Sum i = sum_j scalars[j] * points[j] over the next counts[i] entries of the two arrays (counts[i] <= 64, nsums <= 256; a count of 0: the
+ * identity).  points_xy: canonical affine x || y as sbn_msm takes them, all-zero = the identity.  scalars: canonical.  out_xy: nsums x 64 canonical
+ * affine, all-zero for the identity; out_is_inf: nsums flags, may be NULL.
+ * No table of multiples and no bucket pipeline: the scalars are cut into 64 windows of 4 bits, one block per (sum, window) adds digit * P over
+ * the sum's terms (each lane one bit of one digit: at most three doublings), whatever nsums in ONE launch; one upload in front of it, one
+ * hand-over behind it, and the host folds each sum's 64 window sums (252 doublings), as it folds the bucket pipeline's.  Repeated points, P and
+ * -P and identity inputs take the degenerate branches of the ordinary addition.
+ * Host work, on the calling thread and outside the context's mutex (other threads' calls on the context run meanwhile): per term the curve check and
+ * two Montgomery conversions, per sum the fold and one inversion, about 70 us a sum of 64 terms: 18 of the 20 ms of a call
+ * at the cap.  A caller with hundreds of sums spreads them over threads, a few dozen sums a call.
+ * SBN_EINVAL before any launch: a NULL pointer with nsums > 0, counts[i] > 64, nsums > 256, a scalar >= r, a point that is not on the curve or
+ * not canonical.  nsums == 0 is SBN_OK and touches nothing. */
+int sbn_g1_small_sums(sbn_ctx* ctx, const uint8_t* points_xy, const uint8_t* scalars, const uint32_t* counts, size_t nsums,
+                      uint8_t* out_xy, uint8_t* out_is_inf);
+
+/* ---- the sparse polynomial evaluation proof's CHECK in one call, the Hyrax build: SparseMatPolyEvalProof::verify (sparse_mlpoly_full.rs:1815-1845; what
+ *      R1CSEvalProof::verify wraps, r1cs.rs:465-490) with PolyEvalNetworkProof::verify (:1581-1650), ProductLayerProof::verify (:1436-1520), both
+ *      ProductCircuitEvalProofBatched::verify (product_tree.rs:394-537), HashLayerProof::verify (:1048-1265), the three joint openings and the
+ *      Merlin transcript inside.  With sbn_r1cs_proof_verify it is the whole of SNARK::verify.  The KZG build's derefs opening is a pairing check
+ *      and stays with the caller. ----
+ *   shape:   num_vars_x, num_vars_y, num_ops (N), batch as sbn_sparse_eval_prove's dense handle has them; num_cells = 2^max(num_vars_x, num_vars_y).
+ *   proof:   exactly the out_proof of sbn_sparse_eval_prove (sbn_sparse_eval_sizes gives its length).
+ *   comm_ops / comm_mem: the row commitments of comb_ops / comb_mem (the computation commitment, :176-193) as point sets without h, 2^(ell/2) points
+ *            each with ell = log2 N + log2 next_pow2(5 batch) and log2 num_cells + 1: sbn_bases_upload or sbn_bases_from_compressed; resident across proofs.
+ *   gens_*:  the handles the prover's call takes.   rx, ry, evals: num_vars_x, num_vars_y, batch x 32, canonical.
+ * Work: ONE k_g1_decompress launch over every point of the proof before any hashing (comm_derefs lands in table layout and is read where it lies: no
+ * handle is built); the field checks and the transcript on the host; per opening (derefs, ops, mem) the n-to-1 reduction on the host, eq(r), C_LZ as
+ * an MSM over the commitment's device points and Zr * G as a one-term k_window_sums launch, one hand-over and one wait, then the opening's transcript
+ * lines.  The three final equations (nizk/mod.rs:560-565, each moved to one side) feed no transcript: their row commits are queued behind the next
+ * opening's hand-over, their sums over the 2 lg n + 4 proof points go through ONE k_window_sums launch, and one last hand-over brings everything.
+ * Four host waits a call; each equation is tested for the identity on its own, no random batching.
+ * The return code reports misuse only — SBN_EINVAL before any launch, `tr` unchanged: a NULL pointer, batch outside 1 .. 4, N below 2 or no power of
+ * two, num_cells != 2^max(num_vars_x, num_vars_y), a commitment or generator handle of the wrong size (or generators without h), a non-canonical rx,
+ * ry or evals.  What the prover controls gives SBN_OK with *accepted = 0: a scalar of the proof >= r, a point that does not decompress, a failed
+ * sumcheck round, layer check, subset or hash check, eval_dotp_left + eval_dotp_right != evals[i], a challenge u = 0, a failed equation.  `tr`
+ * moves on only behind *accepted == 1 and then ends where the prover's transcript ended; behind a refusal nothing stays queued. */
+int sbn_sparse_eval_verify(sbn_ctx* ctx, size_t num_vars_x, size_t num_vars_y, size_t num_ops, size_t num_cells, size_t batch,
+                           const sbn_bases* comm_ops, const sbn_bases* comm_mem, const uint8_t* rx, const uint8_t* ry, const uint8_t* evals,
+                           const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_bases* gens_derefs,
+                           const uint8_t* proof, sbn_transcript* tr, int* accepted);
+
 /* ---- MultiSparseMatPolynomialAsDense on the device: what SNARK::encode -> R1CSShape::commit (r1cs.rs:375-400) builds once per circuit ----
  * SparseMatPolynomial::multi_sparse_to_dense_rep -> AddrTimestamps::new (sparse_mlpoly_full.rs:89-101, 120-174, 211-243), from the same
  * (row, col, val) triplets sbn_r1cs_upload takes, in the caller's entry order.  `batch` matrices (1 .. 8; the reference uses 3), nnz[k] entries each.

@@ -197,6 +197,8 @@ extern "C" {
     pub fn sbn_r1cs_proof_prove(ctx: *mut sbn_ctx, inst: *const sbn_r1cs, vars: *const sbn_table, input: *const u8, num_inputs: usize, gens_pc: *const sbn_bases, gens_3: *const sbn_bases, gens_4: *const sbn_bases, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8, out_rx: *mut u8, out_ry: *mut u8) -> c_int;
     pub fn sbn_zk_sumcheck_verify(ctx: *mut sbn_ctx, gens_1: *const sbn_bases, gens_n: *const sbn_bases, comm_claim_xy: *const u8, num_rounds: usize, degree_bound: usize, proof: *const u8, tr: *mut sbn_transcript, out_r: *mut u8, out_comm_eval_xy: *mut u8, accepted: *mut c_int) -> c_int;
     pub fn sbn_r1cs_proof_verify(ctx: *mut sbn_ctx, num_cons: usize, num_vars: usize, input: *const u8, num_inputs: usize, evals: *const u8, gens_pc: *const sbn_bases, gens_3: *const sbn_bases, gens_4: *const sbn_bases, proof: *const u8, tr: *mut sbn_transcript, out_rx: *mut u8, out_ry: *mut u8, accepted: *mut c_int) -> c_int;
+    pub fn sbn_g1_small_sums(ctx: *mut sbn_ctx, points_xy: *const u8, scalars: *const u8, counts: *const u32, nsums: usize, out_xy: *mut u8, out_is_inf: *mut u8) -> c_int;
+    pub fn sbn_sparse_eval_verify(ctx: *mut sbn_ctx, num_vars_x: usize, num_vars_y: usize, num_ops: usize, num_cells: usize, batch: usize, comm_ops: *const sbn_bases, comm_mem: *const sbn_bases, rx: *const u8, ry: *const u8, evals: *const u8, gens_ops: *const sbn_bases, gens_mem: *const sbn_bases, gens_derefs: *const sbn_bases, proof: *const u8, tr: *mut sbn_transcript, accepted: *mut c_int) -> c_int;
     pub fn sbn_dense_build(ctx: *mut sbn_ctx, num_vars_x: usize, num_vars_y: usize, rows: *const *const u32, cols: *const *const u32, vals: *const *const u8, nnz: *const usize, batch: usize, flags: u32, out: *mut *mut sbn_dense) -> c_int;
     pub fn sbn_dense_free(ctx: *mut sbn_ctx, d: *mut sbn_dense);
     pub fn sbn_dense_num_ops(d: *const sbn_dense) -> usize;

@@ -25,7 +25,7 @@ EXPORTED_SYMBOLS = [
     "sbn_eq_evals", "sbn_hash_layer", "sbn_hash_layer_pair", "sbn_hash_layer_pair_product", "sbn_product_layer", "sbn_product_circuit", "sbn_product_circuit_many", "sbn_table_halves", "sbn_table_slice", "sbn_table_dot", "sbn_table_evaluate", "sbn_table_evaluate_many", "sbn_table_bound", "sbn_gather_merge", "sbn_gather_merge_rows", "sbn_commit_table", "sbn_bullet_begin", "sbn_bullet_begin_scaled", "sbn_bullet_free", "sbn_bullet_len", "sbn_bullet_cross", "sbn_bullet_fold_cross", "sbn_bullet_fold", "sbn_bullet_finish", "sbn_prof_enable", "sbn_prof_reset", "sbn_prof_count", "sbn_prof_get", "sbn_prof_last_job", "sbn_prof_last_acc",
     "sbn_kzg_srs_upload", "sbn_kzg_srs_from_tau", "sbn_kzg_commit", "sbn_poly_div_linear", "sbn_kzg_open", "sbn_kzg_open_batched",
     "sbn_r1cs_upload", "sbn_r1cs_free", "sbn_r1cs_multiply", "sbn_r1cs_eval_table", "sbn_r1cs_evaluate",
-    "sbn_r1cs_proof_sizes", "sbn_r1cs_proof_prove", "sbn_zk_sumcheck_verify", "sbn_r1cs_proof_verify", "sbn_sparse_eval_sizes", "sbn_sparse_eval_prove",
+    "sbn_r1cs_proof_sizes", "sbn_r1cs_proof_prove", "sbn_zk_sumcheck_verify", "sbn_r1cs_proof_verify", "sbn_g1_small_sums", "sbn_sparse_eval_verify", "sbn_sparse_eval_sizes", "sbn_sparse_eval_prove",
     "sbn_derefs_key_build", "sbn_derefs_key_free", "sbn_derefs_key_len", "sbn_derefs_key_download", "sbn_derefs_key_commit",
     "sbn_sparse_eval_kzg_sizes", "sbn_sparse_eval_prove_kzg",
     "sbn_dense_build", "sbn_dense_free", "sbn_dense_num_ops", "sbn_dense_num_cells", "sbn_dense_batch", "sbn_dense_addr_dev", "sbn_dense_read_ts_dev",
@@ -98,6 +98,8 @@ def lib():
         L.sbn_r1cs_proof_prove.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 8
         L.sbn_zk_sumcheck_verify.argtypes = [C.c_void_p] * 4 + [C.c_size_t] * 2 + [C.c_void_p] * 5
         L.sbn_r1cs_proof_verify.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_void_p] * 9
+        L.sbn_g1_small_sums.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 2
+        L.sbn_sparse_eval_verify.argtypes = [C.c_void_p] + [C.c_size_t] * 5 + [C.c_void_p] * 11
         L.sbn_sparse_eval_sizes.argtypes = [C.c_size_t] * 4 + [C.c_void_p] * 2
         L.sbn_sparse_eval_prove.argtypes = [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_void_p] * 7
         L.sbn_sparse_eval_kzg_sizes.argtypes = [C.c_size_t] * 4 + [C.c_void_p] * 2
@@ -1006,6 +1008,35 @@ class Context:
         self._chk(lib().sbn_r1cs_proof_verify(self.h, C.c_size_t(num_cons), C.c_size_t(num_vars), _ptr(inputs) if inputs else None, C.c_size_t(len(inputs) // 32 if inputs else 0),
                                               _ptr(evals), gens_pc.h, gens_3.h, gens_4.h, _ptr(proof), tr.h, rx, ry, C.byref(acc)), "sbn_r1cs_proof_verify")
         return (bytes(rx), bytes(ry)) if acc.value else None
+
+    # ---- many short sums of fresh points in one launch (the verifier's vartime_multiscalar_mul over a handful of proof points)
+    def g1_small_sums(self, points_xy, scalars, counts):
+        """sbn_g1_small_sums: sum i = sum of scalars[j] * points[j] over the next counts[i] entries -> (len(counts) x 64 canonical affine bytes, flags:
+        1 = the identity).  points_xy: 64 bytes each, all-zero = the identity; scalars: canonical, 32 bytes each; at most 64 terms a sum and 256 sums.
+        Misuse raises SbnError"""
+        total = sum(counts)
+        if len(points_xy) != 64 * total or len(scalars) != 32 * total:
+            raise ValueError(f"g1_small_sums: {len(points_xy)} point bytes and {len(scalars)} scalar bytes, the counts need {64 * total} and {32 * total}")
+        n = len(counts)
+        cn = (C.c_uint32 * max(n, 1))(*counts)
+        xy, inf = (C.c_uint8 * max(64 * n, 1))(), (C.c_uint8 * max(n, 1))()
+        self._chk(lib().sbn_g1_small_sums(self.h, _ptr(points_xy), _ptr(scalars), cn, C.c_size_t(n), xy, inf), "sbn_g1_small_sums")
+        return bytes(xy[:64 * n]), bytes(inf[:n])
+
+    # ---- SparseMatPolyEvalProof::verify in one call (sparse_mlpoly_full.rs:1815-1845)
+    def sparse_eval_verify(self, nx, ny, num_ops, num_cells, batch, comm_ops, comm_mem, rx, ry, evals, gens_ops, gens_mem, gens_derefs, proof, tr):
+        """SparseMatPolyEvalProof::verify (sbn_sparse_eval_verify) -> True, or False when the proof is refused.  comm_ops / comm_mem: Bases of the row
+        commitments of comb_ops / comb_mem; rx, ry, evals: canonical scalars, 32 bytes each; proof: the out_proof of sparse_eval_prove; `tr` moves on only
+        when the proof is accepted.  Misuse raises SbnError"""
+        n_proof = sparse_eval_sizes(nx, ny, num_ops, batch)[1]
+        if len(proof) != n_proof:
+            raise ValueError(f"sparse_eval_verify: the proof holds {len(proof)} bytes, the shape needs {n_proof}")
+        if len(rx) != 32 * nx or len(ry) != 32 * ny or len(evals) != 32 * batch:
+            raise ValueError("sparse_eval_verify: rx, ry or evals does not have the shape's length")
+        acc = C.c_int(0)
+        self._chk(lib().sbn_sparse_eval_verify(self.h, C.c_size_t(nx), C.c_size_t(ny), C.c_size_t(num_ops), C.c_size_t(num_cells), C.c_size_t(batch), comm_ops.h, comm_mem.h,
+                                               _ptr(rx), _ptr(ry), _ptr(evals), gens_ops.h, gens_mem.h, gens_derefs.h, _ptr(proof), tr.h, C.byref(acc)), "sbn_sparse_eval_verify")
+        return bool(acc.value)
 
     # ---- SparseMatPolyEvalProof::prove in one call (sparse_mlpoly_full.rs:1700-1755)
     def sparse_eval_prove(self, dense, rx, ry, evals, gens_ops, gens_mem, gens_derefs, rnd, tr):

@@ -47,6 +47,7 @@ void sbn_ctx_destroy(sbn_ctx* c) {
   if (c->h_bad) hipHostFree(c->h_bad);
   if (c->mbox) hipHostFree(c->mbox);
   if (c->vbox) hipHostFree(c->vbox);
+  if (c->sbox) hipHostFree(c->sbox);
   for (hipEvent_t e : c->evt_pool) hipEventDestroy(e);
   if (c->copy_stream) hipStreamDestroy(c->copy_stream);
   if (c->pp_stream) hipStreamDestroy(c->pp_stream);

@@ -99,6 +99,57 @@ static int polyeval_verify_check(sbn_ctx* c, const sbn_bases* gens, const sbn_ba
   return SBN_OK;
 }
 
+// the transcript lines of PolyEvalProof::verify_plain / verify with DotProductProofLog::verify and BulletReductionProof::verify inside (hyrax.rs:127,
+// nizk/mod.rs:538-556, bullet.rs:147-153), as every opening check writes them.  Cxy: Cx ‖ Cy; Rv: a_vec = R, n scalars; comp: the proof's 2 lg + 2
+// normalised points.  Out: the challenges r and c, u and their inverses.  false: a challenge u = 0 has no inverse (bullet.rs:161-165)
+static bool polyeval_verify_script(sbn_host::Script& ts, const uint8_t Cxy[128], const uint8_t* Rv, size_t n, const uint8_t* comp, size_t lg,
+                                   uint8_t rq[32], uint8_t cc[32], std::vector<sbn_host::fr::El>& u, std::vector<sbn_host::fr::El>& ui) {
+  using namespace sbn_host::fr;
+  uint8_t c32[32];
+  ts.protocol("polynomial evaluation proof");                     // hyrax.rs:127
+  ts.protocol("dot product proof (log)");                         // nizk/mod.rs:538
+  ts.point_xy("Cx", Cxy, c32);                                    // :543-545
+  ts.point_xy("Cy", Cxy + 64, c32);
+  ts.scalars("a", Rv, n);
+  ts.challenge("r", rq);                                          // :548
+  u.assign(lg, from_u64(0)); ui.assign(lg, from_u64(0));
+  for (size_t j = 0; j < lg; j++) {                               // bullet.rs:147-153
+    ts.point("L", comp + 32 * j);
+    ts.point("R", comp + 32 * (lg + j));
+    uint8_t ub[32];
+    ts.challenge("u", ub);
+    u[j] = el_from(ub);
+    if (is_zero(u[j])) return false;                              // no inverse (bullet.rs:161-165)
+    ui[j] = inv(u[j]);
+  }
+  ts.point("delta", comp + 64 * lg);                              // nizk/mod.rs:555-556
+  ts.point("beta", comp + 64 * lg + 32);
+  ts.challenge("c", cc);
+  return true;
+}
+// b_hat = <s, R> in closed form over the right-hand coordinates r_right, the scalars of the final equation's 2 lg + 4 points (L, R, delta, beta, Cx,
+// Cy) into hs, and the constants of the row -z1 s ‖ -z1 a r with blind -z2
+struct PolyevalFinal { sbn_host::fr::El a_hat, nz1, nz2, tail; };
+static PolyevalFinal polyeval_verify_scalars(const uint8_t* r_right, size_t lg, const std::vector<sbn_host::fr::El>& u, const std::vector<sbn_host::fr::El>& ui,
+                                             const uint8_t rq[32], const uint8_t cc[32], const uint8_t* z1b, const uint8_t* z2b, uint8_t* hs) {
+  using namespace sbn_host::fr;
+  const El one = from_u64(1), zero = from_u64(0);
+  El a_hat = one;
+  for (size_t k = 0; k < lg; k++) {
+    const El rk = el_from(r_right + 32 * k);
+    a_hat = fmul(a_hat, add(fmul(ui[k], sub(one, rk)), fmul(u[k], rk)));
+  }
+  const El ec = el_from(cc), er = el_from(rq), ac = fmul(a_hat, ec), z1 = el_from(z1b), z2 = el_from(z2b);
+  for (size_t j = 0; j < lg; j++) {
+    const El sl = fmul(ac, fmul(u[j], u[j])), sr = fmul(ac, fmul(ui[j], ui[j]));
+    memcpy(hs + 32 * j, sl.v, 32); memcpy(hs + 32 * (lg + j), sr.v, 32);
+  }
+  memcpy(hs + 64 * lg, one.v, 32); memcpy(hs + 64 * lg + 32, a_hat.v, 32);               // delta, beta
+  { const El sy = fmul(ac, er); memcpy(hs + 64 * lg + 64, ac.v, 32); memcpy(hs + 64 * lg + 96, sy.v, 32); }   // Cx, Cy
+  PolyevalFinal f; f.a_hat = a_hat; f.nz1 = sub(zero, z1); f.nz2 = sub(zero, z2); f.tail = fmul(f.nz1, fmul(a_hat, er));
+  return f;
+}
+
 // the check on the transcript `t` (a copy of the caller's); arguments already checked.  SBN_OK with *accepted = 0: the proof is refused
 static int polyeval_verify_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_bases* comm, const uint8_t* r, size_t ell, const uint8_t* C_Zr_xy, const uint8_t* Zr,
                                   const uint8_t* proof, sbn_host::MerlinTranscript& t, int* accepted) {
@@ -169,44 +220,15 @@ static int polyeval_verify_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_b
   if (Zr) sbn_host::to_affine_bytes(sbn_host::pt_from_device(S[s1.W]), Cxy + 64, nullptr); else memcpy(Cxy + 64, C_Zr_xy, 64);
 
   // ---- the transcript, as the reference's verifier writes it ----
-  uint8_t c32[32], rq[32], cc[32];
-  ts.protocol("polynomial evaluation proof");                     // hyrax.rs:127
-  ts.protocol("dot product proof (log)");                         // nizk/mod.rs:538
-  ts.point_xy("Cx", Cxy, c32);                                    // :543-545
-  ts.point_xy("Cy", Cxy + 64, c32);
-  ts.scalars("a", Rv.data(), n);
-  ts.challenge("r", rq);                                          // :548
-  std::vector<El> u(lg), ui(lg);
-  for (size_t j = 0; j < lg; j++) {                               // bullet.rs:147-153
-    ts.point("L", comp + 32 * j);
-    ts.point("R", comp + 32 * (lg + j));
-    uint8_t ub[32];
-    ts.challenge("u", ub);
-    u[j] = el_from(ub);
-    if (is_zero(u[j])) return SBN_OK;                             // no inverse (bullet.rs:161-165)
-    ui[j] = inv(u[j]);
-  }
-  ts.point("delta", comp + 64 * lg);                              // nizk/mod.rs:555-556
-  ts.point("beta", comp + 64 * lg + 32);
-  ts.challenge("c", cc);
+  uint8_t rq[32], cc[32];
+  std::vector<El> u, ui;
+  if (!polyeval_verify_script(ts, Cxy, Rv.data(), n, comp, lg, rq, cc, u, ui)) return SBN_OK;      // a challenge u = 0
 
   // ---- O(lg n) field work: b_hat in closed form, the scalars of the proof's points, the row's constants ----
-  const El one = from_u64(1), zero = from_u64(0);
-  El a_hat = one;
-  for (size_t k = 0; k < lg; k++) {
-    const El rk = el_from(r + 32 * (ml + k));
-    a_hat = fmul(a_hat, add(fmul(ui[k], sub(one, rk)), fmul(u[k], rk)));
-  }
-  const El ec = el_from(cc), er = el_from(rq), ac = fmul(a_hat, ec), z1 = el_from(z1b), z2 = el_from(z2b);
   uint8_t* hs = pin + 4096;                                       // (np + 2) scalars, then Cx ‖ Cy
-  for (size_t j = 0; j < lg; j++) {
-    const El sl = fmul(ac, fmul(u[j], u[j])), sr = fmul(ac, fmul(ui[j], ui[j]));
-    memcpy(hs + 32 * j, sl.v, 32); memcpy(hs + 32 * (lg + j), sr.v, 32);
-  }
-  memcpy(hs + 64 * lg, one.v, 32); memcpy(hs + 64 * lg + 32, a_hat.v, 32);               // delta, beta
-  { const El sy = fmul(ac, er); memcpy(hs + 64 * lg + 64, ac.v, 32); memcpy(hs + 64 * lg + 96, sy.v, 32); }   // Cx, Cy
+  const PolyevalFinal fin = polyeval_verify_scalars(r + 32 * ml, lg, u, ui, rq, cc, z1b, z2b, hs);
   memcpy(hs + 32 * (np + 2), Cxy, 128);
-  const El nz1 = sub(zero, z1), nz2 = sub(zero, z2), tail = fmul(nz1, fmul(a_hat, er));
+  const El nz1 = fin.nz1, nz2 = fin.nz2, tail = fin.tail;
 
   // ---- second launch: the folded equation ----
   HIPCHK(c, hipMemcpyAsync(d_scal, hs, 32 * (np + 2), hipMemcpyHostToDevice, c->stream));

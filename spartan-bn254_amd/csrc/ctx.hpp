@@ -55,6 +55,7 @@ struct sbn_ctx {
   uint32_t* h_bad = nullptr;                 // its pinned host copy
   uint32_t* mbox = nullptr; uint32_t mbox_seq = 0;   // coherent pinned mailbox of the single-launch sumcheck rounds (results + per-instance flags)
   uint32_t* vbox = nullptr;                  // coherent pinned hand-over area of the opening check (abi_polyeval_verify.inc): staged sums, flags, the sequence word
+  uint32_t* sbox = nullptr; size_t sbox_words = 0;   // coherent pinned hand-over area of the window sums (abi_small_sums.inc): one flag per block, then the sums
   std::vector<std::pair<void*, size_t>> pool; size_t pool_bytes = 0;   // cached table buffers (see pool_get)
   uint64_t last_job[4] = {0, 0, 0, 0};      // window bits, windows, (digit, point) slots, buckets of the most recent bucket job
   uint64_t last_acc[6] = {0, 0, 0, 0, 0, 0};   // SEG, LPB, L, chunks, combine launches, quad combine of the most recent bucket job (sbn_prof_last_acc)

@@ -14,6 +14,8 @@
 //   SparseMatPolyEvalProof::prove (--features kzg), Derefs::commit_kzg  src/sparse_mlpoly_full.rs:1757-1813, 307-312 -> sbn_sparse_eval_prove_kzg / sbn_derefs_key_*
 //   ZKSumcheckInstanceProof::prove_cubic_with_additive_term, ::prove_quad, DotProductProof::prove  src/sumcheck.rs:465-811, src/nizk/mod.rs:306-366 -> sbn_zk_sumcheck_prove_r1cs / _quad
 //   R1CSProof::verify, ZKSumcheckInstanceProof::verify, DotProductProof::verify  src/r1csproof.rs:463-619, src/sumcheck.rs:366-457, src/nizk/mod.rs:368-400 -> sbn_r1cs_proof_verify / sbn_zk_sumcheck_verify
+//   SparseMatPolyEvalProof::verify, PolyEvalNetworkProof::verify, ProductLayerProof / HashLayerProof::verify  src/sparse_mlpoly_full.rs:1815-1845, :1581-1650, :1436-1520, :1048-1265 -> sbn_sparse_eval_verify
+//   the verifier's short sums of proof points (nizk/mod.rs:560-565, :389-394 as GroupElement::vartime_multiscalar_mul)          -> sbn_g1_small_sums
 // There is no CPU fallback in this file: every entry point needs the gfx950 device.
 #include "../../include/sbn254.h"
 #include "host_field.hpp"
@@ -32,11 +34,13 @@
 #include "zk_sumcheck_kernels.cuh"
 #include "r1cs_proof_kernels.cuh"
 #include "r1cs_verify_kernels.cuh"
+#include "small_sum_kernels.cuh"
 #include "sparse_eval_kernels.cuh"
 #include "derefs_key_kernels.cuh"
 #include "host_keccak.hpp"
 #include "host_strobe.hpp"
 #include "proof_host.hpp"
+#include "sparse_verify_host.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -75,9 +79,11 @@ using namespace sbn;
 #include "abi_r1cs.inc"
 #include "abi_r1cs_proof.inc"
 #include "abi_r1cs_verify.inc"
+#include "abi_small_sums.inc"
 #include "abi_dense.inc"
 #include "abi_derefs_key.inc"
 #include "abi_sparse_eval.inc"
+#include "abi_sparse_verify.inc"
 
 extern "C" {
 
