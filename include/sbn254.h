@@ -472,7 +472,7 @@ int sbn_group_msm_bases_dev(sbn_group* g, const sbn_group_bases* gb, const void*
 /* ---- KZG mode (--features kzg): commitments and openings over a resident SRS (kzg.rs) ----
  * The SRS is an sbn_bases handle (no h; sbn_bases_free / _len / _download work on it).  A polynomial is the first n entries of a
  * table, coefficients low to high; n <= the table's length, entries from n on are never read.  z, gamma, tau: canonical (< r).
- * Pairings, G2 and the transcript stay with the caller. */
+ * The transcript stays with the caller; the pairing checks of these openings are sbn_kzg_verify / sbn_kzg_verify_batched below. */
 /* KZGSrs.powers_g1 (kzg.rs:25-31): n canonical affine points (SBN_POINTS_MONT: ark-ff limbs); no duplicate detection */
 int sbn_kzg_srs_upload(sbn_ctx* ctx, const uint8_t* powers_xy, size_t n, uint32_t flags, sbn_bases** out);
 /* [tau^i]G1 for i < n (kzg.rs:37-56 with tau supplied), built on the device; tau non-zero, n >= 1 */
@@ -597,8 +597,8 @@ int sbn_g1_small_sums(sbn_ctx* ctx, const uint8_t* points_xy, const uint8_t* sca
 /* ---- the sparse polynomial evaluation proof's CHECK in one call, the Hyrax build: SparseMatPolyEvalProof::verify (sparse_mlpoly_full.rs:1815-1845; what
  *      R1CSEvalProof::verify wraps, r1cs.rs:465-490) with PolyEvalNetworkProof::verify (:1581-1650), ProductLayerProof::verify (:1436-1520), both
  *      ProductCircuitEvalProofBatched::verify (product_tree.rs:394-537), HashLayerProof::verify (:1048-1265), the three joint openings and the
- *      Merlin transcript inside.  With sbn_r1cs_proof_verify it is the whole of SNARK::verify.  The KZG build's derefs opening is a pairing check
- *      and stays with the caller. ----
+ *      Merlin transcript inside.  With sbn_r1cs_proof_verify it is the whole of SNARK::verify.  The KZG build's derefs opening is a pairing check:
+ *      sbn_sparse_eval_verify_kzg below is the KZG build's whole check. ----
  *   shape:   num_vars_x, num_vars_y, num_ops (N), batch as sbn_sparse_eval_prove's dense handle has them; num_cells = 2^max(num_vars_x, num_vars_y).
  *   proof:   exactly the out_proof of sbn_sparse_eval_prove (sbn_sparse_eval_sizes gives its length).
  *   comm_ops / comm_mem: the row commitments of comb_ops / comb_mem (the computation commitment, :176-193) as point sets without h, 2^(ell/2) points
@@ -731,11 +731,65 @@ int sbn_derefs_key_commit(sbn_ctx* ctx, const sbn_derefs_key* key, const sbn_tab
  *   out_proof  the Hyrax layout with  comm_derefs [32]  and  proof_hash_layer.proof_derefs [proof 32 | eval 32]  (the identity as sbn_g1_compress writes it).
  *              proof_bytes = 32 (13 b + 6) + 64 (m (m - 1) + n (n - 1)) + 256 (m + b n) + 192 b + 64 (lg_ops + lg_mem) + 352.
  * SBN_EINVAL before any launch: the Hyrax call's refusals (without gens_derefs), an SRS with h, srs->n < n_d - 1, a key whose recorded shape, SRS length or
- * handles are not this call's.  Pairings and verification stay with the caller. */
+ * handles are not this call's.  sbn_sparse_eval_verify_kzg checks this proof in one call. */
 int sbn_sparse_eval_kzg_sizes(size_t num_vars_x, size_t num_vars_y, size_t num_ops /* N */, size_t batch, size_t* rnd_scalars, size_t* proof_bytes);
 int sbn_sparse_eval_prove_kzg(sbn_ctx* ctx, const sbn_dense* dense, const uint8_t* rx, size_t nx, const uint8_t* ry, size_t ny, const uint8_t* evals /* batch x 32 */,
                               const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_bases* srs, const sbn_derefs_key* key /* or NULL */,
                               const uint8_t* rnd, sbn_transcript* tr, uint8_t* out_proof);
+
+/* ---- pairings and KZG verification: Bn254::pairing at the reference's verifier call sites (kzg.rs:196-217, :315-352) ----
+ * Tower: Fq2 = Fq[u]/(u^2 + 1), xi = 9 + u, Fq6 = Fq2[v]/(v^3 - xi), Fq12 = Fq6[w]/(w^2 - v) (arkworks').  A GT value is 384 bytes: the twelve Fq
+ * coefficients c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1, each 32 bytes little-endian canonical.  The pairing is the optimal ate pairing with the
+ * EXACT final exponent (q^12 - 1)/r, so GT bytes are comparable with any implementation that takes that exponent (tests/pairing_model.py).
+ * A G2 point is 128 bytes  x.c0 | x.c1 | y.c0 | y.c1  of the twist E': y^2 = x^3 + 3/xi, each part canonical (< q) little-endian; with SBN_POINTS_MONT
+ * the parts are ark-ff's Montgomery limbs (G2Affine's in-memory x, y).  A G1 point is 64 bytes x | y as everywhere; 64 zero bytes: the identity. */
+typedef struct sbn_g2_lines sbn_g2_lines;
+/* G2Prepared::from (what Bn254::pairing builds from srs.g2 / srs.tau_g2 on every call, kzg.rs:212-214), ONCE per point: parsed, checked, the 88 lines of
+ * its Miller loop computed on the host (most of the time is the literal subgroup test [r]Q == O; DESIGN 4.20 has the figure) and uploaded (11 KiB).  The handle belongs to `ctx`.
+ * SBN_EINVAL: a NULL pointer, unknown flags, a coordinate >= q, the identity (128 zero bytes), a point off E', a point of E' outside the r-torsion
+ * (#E'(Fq2) = r (2q - r): most points of E' are). */
+int sbn_g2_prepare(sbn_ctx* ctx, const uint8_t q_xy[128], uint32_t flags, sbn_g2_lines** out);
+/* releases the handle to the context that made it (`ctx` is not consulted: a handle knows its context); before that context is destroyed */
+void sbn_g2_lines_free(sbn_ctx* ctx, sbn_g2_lines* l);
+/* Bn254::multi_pairing (kzg.rs:212-216 compares two of them): nchecks independent products  prod_t e(P_t, Q_t)  in ONE launch of k_pairing_products,
+ * one wave a check.  counts[i] in 0 .. 4: the terms of check i, laid out one check after the other in p_xy (64 B each) and q; 0 terms is the empty
+ * product (is_one = 1), a term whose P is the identity contributes 1.  The same handle may stand in any number of terms.
+ * out_is_one: nchecks bytes, 1 where the product is the unit of GT;  out_gt: nchecks x 384 bytes, or NULL.  One upload, one launch, one wait.
+ * SBN_EINVAL before any launch, outputs untouched: a NULL pointer, nchecks > 65536, counts[i] > 4, a NULL handle or one of another context, a P that is not a canonical
+ * point of the curve.  nchecks == 0 is SBN_OK and touches nothing. */
+int sbn_pairing_products(sbn_ctx* ctx, const uint8_t* p_xy, const sbn_g2_lines* const* q, const uint32_t* counts, size_t nchecks,
+                         uint8_t* out_is_one, uint8_t* out_gt);
+/* KZGProof::verify (kzg.rs:196-217) / KZGPolyEvalProof::verify (:428-437):  e(C - y G, g2) == e(pi, tau_g2 - z g2)  tested as
+ *     e(C - y G + z pi, g2) * e(-pi, tau_g2) == 1
+ * which is the same statement by bilinearity alone (no relation between g2 and tau_g2 is assumed) and multiplies no G2 point.  G = (1, 2).
+ * Work: the three-term G1 sum through sbn_g1_small_sums' launch and fold, then one two-term k_pairing_products launch: two host waits.
+ * pi = O reduces the check to C == y G.  The return code reports misuse only — SBN_EINVAL before any launch, *accepted untouched: a NULL pointer,
+ * a handle of another context, z or eval >= r, a commitment that is not a canonical point of the curve.  A proof point that is not on the curve
+ * is the prover's doing: SBN_OK with *accepted = 0, as for a failed product. */
+int sbn_kzg_verify(sbn_ctx* ctx, const sbn_g2_lines* g2, const sbn_g2_lines* tau_g2, const uint8_t comm_xy[64], const uint8_t z[32],
+                   const uint8_t eval[32], const uint8_t proof_xy[64], int* accepted);
+/* KZGBatchProof::batch_verify (kzg.rs:315-352): the check above on  sum_k gamma^k C_k  and  sum_k gamma^k evals[k]; gamma from the caller's
+ * transcript as in sbn_kzg_open_batched (any canonical value, zero included).  The combination is part of the same G1 sum (count + 2 terms):
+ * count <= 62.  count = 0 tests pi against the identity commitment.  SBN_EINVAL as above, and for count > 62 or an eval >= r. */
+int sbn_kzg_verify_batched(sbn_ctx* ctx, const sbn_g2_lines* g2, const sbn_g2_lines* tau_g2, const uint8_t* comms_xy, size_t count,
+                           const uint8_t z[32], const uint8_t gamma[32], const uint8_t* evals, const uint8_t proof_xy[64], int* accepted);
+
+/* SparseMatPolyEvalProof::verify, the KZG build (--features kzg; sparse_mlpoly_full.rs:1815-1845 with DerefsEvalProof::verify, :552-595) in ONE call:
+ * sbn_sparse_eval_verify above with (g2, tau_g2) in place of gens_derefs and the proof layout of sbn_sparse_eval_prove_kzg (sbn_sparse_eval_kzg_sizes):
+ * comm_derefs [32], proof_hash_layer.proof_derefs [proof 32 | eval 32].  With sbn_r1cs_proof_verify the KZG build's SNARK::verify is two foreign calls.
+ * The commitment is absorbed as :349-356 does; derefs_reduce (:561-584) runs on the host: as in the reference the joint claim is absorbed and NOT
+ * compared, and the opening is checked at kzg_eval_point against the proof's own eval.  The field half, the transcript and the two joint openings of
+ * comb_ops and comb_mem are the Hyrax call's (one decompress launch over their points, one wait an opening, one for the two final equations: three
+ * host waits); behind them comm_derefs and pi are decompressed (sbn_g1_decompress: one wait) and the opening is checked as sbn_kzg_verify checks it (two
+ * waits): SIX host waits a call.  The pairing check is not yet queued under the host's hashing of the openings; it costs its 2 ms behind them.
+ * Rules as for sbn_sparse_eval_verify: SBN_EINVAL before any launch with `tr` and *accepted untouched for a NULL pointer, a G2 handle of another
+ * context, a bad shape, handle size or non-canonical rx, ry, evals.  SBN_OK with *accepted = 0 for what the prover controls, among it an eval >= r inside
+ * the proof, comm_derefs or pi that does not decompress, a failed pairing product.  `tr` moves on only behind *accepted == 1 and then ends where
+ * sbn_sparse_eval_prove_kzg's transcript ended. */
+int sbn_sparse_eval_verify_kzg(sbn_ctx* ctx, size_t num_vars_x, size_t num_vars_y, size_t num_ops, size_t num_cells, size_t batch,
+                               const sbn_bases* comm_ops, const sbn_bases* comm_mem, const uint8_t* rx, const uint8_t* ry, const uint8_t* evals,
+                               const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_g2_lines* g2, const sbn_g2_lines* tau_g2,
+                               const uint8_t* proof, sbn_transcript* tr, int* accepted);
 
 /* ---- per-kernel timing (HIP events on the context's stream), for bench.py's roofline line ---- */
 int sbn_prof_enable(sbn_ctx* ctx, int on);

@@ -55,6 +55,7 @@ use crate::unipoly::{CompressedUniPoly, UniPoly};
 #[repr(C)] pub struct sbn_r1cs { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_dense { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_derefs_key { _p: [u8; 0] }
+#[repr(C)] pub struct sbn_g2_lines { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_transcript { _p: [u8; 0] }
 
 pub const SBN_OK: c_int = 0;
@@ -218,6 +219,12 @@ extern "C" {
     pub fn sbn_derefs_key_commit(ctx: *mut sbn_ctx, key: *const sbn_derefs_key, mem_rx: *const sbn_table, mem_ry: *const sbn_table, out_xy: *mut u8, out_is_inf: *mut c_int) -> c_int;
     pub fn sbn_sparse_eval_kzg_sizes(num_vars_x: usize, num_vars_y: usize, num_ops: usize, batch: usize, rnd_scalars: *mut usize, proof_bytes: *mut usize) -> c_int;
     pub fn sbn_sparse_eval_prove_kzg(ctx: *mut sbn_ctx, dense: *const sbn_dense, rx: *const u8, nx: usize, ry: *const u8, ny: usize, evals: *const u8, gens_ops: *const sbn_bases, gens_mem: *const sbn_bases, srs: *const sbn_bases, key: *const sbn_derefs_key, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8) -> c_int;
+    pub fn sbn_g2_prepare(ctx: *mut sbn_ctx, q_xy: *const u8, flags: u32, out: *mut *mut sbn_g2_lines) -> c_int;
+    pub fn sbn_g2_lines_free(ctx: *mut sbn_ctx, l: *mut sbn_g2_lines);
+    pub fn sbn_pairing_products(ctx: *mut sbn_ctx, p_xy: *const u8, q: *const *const sbn_g2_lines, counts: *const u32, nchecks: usize, out_is_one: *mut u8, out_gt: *mut u8) -> c_int;
+    pub fn sbn_kzg_verify(ctx: *mut sbn_ctx, g2: *const sbn_g2_lines, tau_g2: *const sbn_g2_lines, comm_xy: *const u8, z: *const u8, eval: *const u8, proof_xy: *const u8, accepted: *mut c_int) -> c_int;
+    pub fn sbn_kzg_verify_batched(ctx: *mut sbn_ctx, g2: *const sbn_g2_lines, tau_g2: *const sbn_g2_lines, comms_xy: *const u8, count: usize, z: *const u8, gamma: *const u8, evals: *const u8, proof_xy: *const u8, accepted: *mut c_int) -> c_int;
+    pub fn sbn_sparse_eval_verify_kzg(ctx: *mut sbn_ctx, num_vars_x: usize, num_vars_y: usize, num_ops: usize, num_cells: usize, batch: usize, comm_ops: *const sbn_bases, comm_mem: *const sbn_bases, rx: *const u8, ry: *const u8, evals: *const u8, gens_ops: *const sbn_bases, gens_mem: *const sbn_bases, g2: *const sbn_g2_lines, tau_g2: *const sbn_g2_lines, proof: *const u8, tr: *mut sbn_transcript, accepted: *mut c_int) -> c_int;
     pub fn sbn_prof_enable(ctx: *mut sbn_ctx, on: c_int) -> c_int;
     pub fn sbn_prof_reset(ctx: *mut sbn_ctx) -> c_int;
     pub fn sbn_prof_count(ctx: *mut sbn_ctx) -> c_int;
@@ -971,6 +978,55 @@ pub fn kzg_open_batched(polys: &[(&Table, usize)], point: &Scalar, gamma: &Scala
     });
     (group_from_xy(&xy, inf != 0), ev.chunks(32).map(sc).collect())
 }
+/// srs.g2 / srs.tau_g2 made ready for pairings (sbn_g2_prepare: what Bn254::pairing's G2Prepared::from does on every call, once per SRS).
+/// `xy`: G2Affine's in-memory x.c0, x.c1, y.c0, y.c1 (ark-ff Montgomery limbs, 4 x 32 bytes)
+pub struct G2Lines(pub *mut sbn_g2_lines);
+unsafe impl Send for G2Lines {}
+unsafe impl Sync for G2Lines {}
+impl Drop for G2Lines { fn drop(&mut self) { if !self.0.is_null() { unsafe { sbn_g2_lines_free(ctx(), self.0) } } } }
+impl G2Lines {
+    pub fn from_mont_limbs(x_c0: &[u64; 4], x_c1: &[u64; 4], y_c0: &[u64; 4], y_c1: &[u64; 4]) -> G2Lines {
+        let mut xy = [0u8; 128];
+        for (i, l) in [x_c0, x_c1, y_c0, y_c1].iter().enumerate() { xy[32 * i..32 * i + 32].copy_from_slice(&limbs_le(l)); }
+        let mut h = null_mut();
+        check(unsafe { sbn_g2_prepare(ctx(), xy.as_ptr(), SBN_POINTS_MONT, &mut h) });
+        G2Lines(h)
+    }
+}
+/// canonical x || y of an affine point (64 zero bytes: the identity): what the verifier entry points take
+pub fn point_xy_canonical(p: &G1Affine) -> [u8; 64] {
+    let mut o = [0u8; 64];
+    if !p.is_zero() {
+        o[..32].copy_from_slice(&limbs_le(&ark_ff::PrimeField::into_bigint(p.x).0));
+        o[32..].copy_from_slice(&limbs_le(&ark_ff::PrimeField::into_bigint(p.y).0));
+    }
+    o
+}
+/// KZGProof::verify (kzg.rs:196-217): e(C - y G + z pi, g2) * e(-pi, tau_g2) == 1 on the device
+pub fn kzg_verify(g2: &G2Lines, tau_g2: &G2Lines, commitment: &G1Affine, point: &Scalar, eval: &Scalar, proof: &G1Affine) -> bool {
+    let (c, p) = (point_xy_canonical(commitment), point_xy_canonical(proof));
+    let mut accepted: c_int = 0;
+    check(unsafe { sbn_kzg_verify(ctx(), g2.0, tau_g2.0, c.as_ptr(), point.to_bytes().as_ptr(), eval.to_bytes().as_ptr(), p.as_ptr(), &mut accepted) });
+    accepted != 0
+}
+/// SparseMatPolyEvalProof::verify of the KZG build (sparse_mlpoly_full.rs:1815-1845) in ONE foreign call.  `proof`: the bytes in the library's layout
+/// (what `sbn_sparse_eval_prove_kzg` wrote: include/sbn254.h); `comm_ops` / `comm_mem`: the computation commitment's row commitments, resident;
+/// `transcript` moves on only when the proof is accepted.  With `sbn_r1cs_proof_verify` this is the whole of the KZG build's `SNARK::verify`.
+#[cfg(feature = "kzg")]
+pub fn sparse_eval_verify_kzg(
+    num_vars_x: usize, num_vars_y: usize, num_ops: usize, num_cells: usize, comm_ops: &Bases, comm_mem: &Bases, rx: &[Scalar], ry: &[Scalar], evals: &[Scalar],
+    gens: &SparseMatPolyCommitmentGens, g2: &G2Lines, tau_g2: &G2Lines, proof: &[u8], transcript: &mut DevTranscript,
+) -> bool {
+    let (rxb, ryb, evb) = (scalars_canonical(rx), scalars_canonical(ry), scalars_canonical(evals));
+    let g_ops = pc_bases(&gens.gens_ops.gens.gens_n, &gens.gens_ops.gens.gens_1);
+    let g_mem = pc_bases(&gens.gens_mem.gens.gens_n, &gens.gens_mem.gens.gens_1);
+    let mut accepted: c_int = 0;
+    check(unsafe {
+        sbn_sparse_eval_verify_kzg(ctx(), num_vars_x, num_vars_y, num_ops, num_cells, evals.len(), comm_ops.0, comm_mem.0, rxb.as_ptr(), ryb.as_ptr(), evb.as_ptr(),
+                                   g_ops.0, g_mem.0, g2.0, tau_g2.0, proof.as_ptr(), transcript.0, &mut accepted)
+    });
+    accepted != 0
+}
 
 // ---- the R1CS matrices on the device (r1cs.rs): uploaded once per circuit, next to the instance --------------------------------
 /// R1CSShape (r1cs.rs:22-82) on the device: the field `dev` an R1CSInstance carries next to its shape, filled at encode time the way
@@ -1376,8 +1432,8 @@ impl DerefsKey {
     pub fn is_empty(&self) -> bool { self.len() == 0 }
 }
 /// SparseMatPolyEvalProof::prove of the KZG build with a `DevTranscript`.  `srs` is gens.gens_derefs_kzg.srs.powers_g1 on the device; `key` is
-/// optional (the bytes are the same with and without it).  The derefs opening draws nothing from the RandomTape (:510); pairings and
-/// verification stay in the reference's code.
+/// optional (the bytes are the same with and without it).  The derefs opening draws nothing from the RandomTape (:510); the whole
+/// check of this proof is `sparse_eval_verify_kzg` above.
 #[cfg(feature = "kzg")]
 pub fn sparse_eval_prove_kzg(
     dense_dev: *const sbn_dense,

@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = [
     "sbn_r1cs_proof_sizes", "sbn_r1cs_proof_prove", "sbn_zk_sumcheck_verify", "sbn_r1cs_proof_verify", "sbn_g1_small_sums", "sbn_sparse_eval_verify", "sbn_sparse_eval_sizes", "sbn_sparse_eval_prove",
     "sbn_derefs_key_build", "sbn_derefs_key_free", "sbn_derefs_key_len", "sbn_derefs_key_download", "sbn_derefs_key_commit",
     "sbn_sparse_eval_kzg_sizes", "sbn_sparse_eval_prove_kzg",
+    "sbn_g2_prepare", "sbn_g2_lines_free", "sbn_pairing_products", "sbn_kzg_verify", "sbn_kzg_verify_batched", "sbn_sparse_eval_verify_kzg",
     "sbn_dense_build", "sbn_dense_free", "sbn_dense_num_ops", "sbn_dense_num_cells", "sbn_dense_batch", "sbn_dense_addr_dev", "sbn_dense_read_ts_dev",
     "sbn_dense_audit_ts_dev", "sbn_dense_comb_ops", "sbn_dense_comb_mem",
 ]
@@ -109,6 +110,12 @@ def lib():
         L.sbn_derefs_key_len.restype = C.c_size_t; L.sbn_derefs_key_len.argtypes = [C.c_void_p]
         L.sbn_derefs_key_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
         L.sbn_derefs_key_commit.argtypes = [C.c_void_p] * 6
+        L.sbn_g2_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.sbn_g2_lines_free.restype = None; L.sbn_g2_lines_free.argtypes = [C.c_void_p] * 2
+        L.sbn_pairing_products.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 2
+        L.sbn_kzg_verify.argtypes = [C.c_void_p] * 8
+        L.sbn_sparse_eval_verify_kzg.argtypes = [C.c_void_p] + [C.c_size_t] * 5 + [C.c_void_p] * 12
+        L.sbn_kzg_verify_batched.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 5
         L.sbn_dense_audit_ts_dev.restype = C.c_void_p; L.sbn_dense_audit_ts_dev.argtypes = [C.c_void_p, C.c_int]
         for name in ("sbn_dense_comb_ops", "sbn_dense_comb_mem"):
             getattr(L, name).restype = C.c_void_p; getattr(L, name).argtypes = [C.c_void_p]
@@ -390,6 +397,18 @@ def sparse_eval_kzg_sizes(num_vars_x, num_vars_y, num_ops, batch):
     if rc:
         raise SbnError(f"sbn_sparse_eval_kzg_sizes: ({num_vars_x}, {num_vars_y}, N = {num_ops}, batch = {batch}) is a shape the call refuses (rc={rc})")
     return a.value, b.value
+
+
+class G2Lines:
+    """a fixed G2 point made ready for pairings (sbn_g2_prepare): srs.g2 or srs.tau_g2.  Belongs to its Context."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    def free(self):
+        if self.h:
+            lib().sbn_g2_lines_free(self.ctx.h, self.h)
+            self.h = None
 
 
 class DerefsKey:
@@ -1117,6 +1136,61 @@ class Context:
         ev = (C.c_uint8 * (32 * max(k, 1)))(); out = (C.c_uint8 * 64)(); inf = C.c_int()
         self._chk(lib().sbn_kzg_open_batched(self.h, srs.h, arr, nn, C.c_size_t(k), _ptr(z), _ptr(gamma), ev, out, C.byref(inf)), "sbn_kzg_open_batched")
         return [bytes(ev[32 * i:32 * i + 32]) for i in range(k)], bytes(out), bool(inf.value)
+
+    # ---- pairings and KZG verification (kzg.rs:196-217, :315-352)
+    def g2_prepare(self, q_xy, flags=0):
+        """sbn_g2_prepare: 128 bytes x.c0 | x.c1 | y.c0 | y.c1 -> G2Lines.  A point that is not canonical, the identity, off E' or outside the
+        r-torsion raises SbnError"""
+        if len(q_xy) != 128:
+            raise ValueError(f"g2_prepare: a G2 point is 128 bytes, got {len(q_xy)}")
+        h = C.c_void_p()
+        self._chk(lib().sbn_g2_prepare(self.h, _ptr(q_xy), C.c_uint32(flags), C.byref(h)), "sbn_g2_prepare")
+        return G2Lines(self, h)
+
+    def pairing_products(self, p_xy, qs, counts, want_gt=True):
+        """sbn_pairing_products: check i = the product of e(P, Q) over the next counts[i] entries of p_xy (64 bytes each) and qs (G2Lines)
+        -> (is_one bytes, [384 GT bytes a check] or None).  One launch, one wave a check; at most 4 terms a check.  Misuse raises SbnError"""
+        total, n = sum(counts), len(counts)
+        if len(p_xy) != 64 * total or len(qs) != total:
+            raise ValueError(f"pairing_products: {len(p_xy)} point bytes and {len(qs)} handles, the counts need {64 * total} and {total}")
+        cn = (C.c_uint32 * max(n, 1))(*counts)
+        arr = (C.c_void_p * max(total, 1))(*[q.h for q in qs])
+        one = (C.c_uint8 * max(n, 1))(); gt = (C.c_uint8 * max(384 * n, 1))() if want_gt else None
+        self._chk(lib().sbn_pairing_products(self.h, _ptr(p_xy) if total else None, arr, cn, C.c_size_t(n), one, gt), "sbn_pairing_products")
+        raw = bytes(gt) if want_gt else None
+        return bytes(one[:n]), ([raw[384 * i:384 * i + 384] for i in range(n)] if want_gt else None)
+
+    def kzg_verify(self, g2, tau_g2, comm_xy, z, eval_, proof_xy):
+        """KZGProof::verify (sbn_kzg_verify) -> True / False.  comm_xy, proof_xy: 64 canonical affine bytes (all-zero: the identity)"""
+        acc = C.c_int(0)
+        self._chk(lib().sbn_kzg_verify(self.h, g2.h, tau_g2.h, _ptr(comm_xy), _ptr(z), _ptr(eval_), _ptr(proof_xy), C.byref(acc)), "sbn_kzg_verify")
+        return bool(acc.value)
+
+    def kzg_verify_batched(self, g2, tau_g2, comms_xy, z, gamma, evals, proof_xy):
+        """KZGBatchProof::batch_verify (sbn_kzg_verify_batched) -> True / False.  comms_xy: count x 64 bytes, evals: count x 32 bytes (or a list)"""
+        if isinstance(evals, (list, tuple)):
+            evals = b"".join(evals)
+        k = len(comms_xy) // 64
+        if len(comms_xy) != 64 * k or len(evals) != 32 * k:
+            raise ValueError(f"kzg_verify_batched: {len(comms_xy)} commitment bytes and {len(evals)} eval bytes")
+        acc = C.c_int(0)
+        self._chk(lib().sbn_kzg_verify_batched(self.h, g2.h, tau_g2.h, _ptr(comms_xy) if k else None, C.c_size_t(k), _ptr(z), _ptr(gamma),
+                                               _ptr(evals) if k else None, _ptr(proof_xy), C.byref(acc)), "sbn_kzg_verify_batched")
+        return bool(acc.value)
+
+    def sparse_eval_verify_kzg(self, nx, ny, num_ops, num_cells, batch, comm_ops, comm_mem, rx, ry, evals, gens_ops, gens_mem, g2, tau_g2, proof, tr):
+        """SparseMatPolyEvalProof::verify of the KZG build (sbn_sparse_eval_verify_kzg) -> True, or False when the proof is refused.  As
+        sparse_eval_verify with G2Lines of srs.g2 / srs.tau_g2 in place of gens_derefs; proof: the out_proof of sparse_eval_prove_kzg; `tr` moves on
+        only when the proof is accepted.  Misuse raises SbnError"""
+        n_proof = sparse_eval_kzg_sizes(nx, ny, num_ops, batch)[1]
+        if len(proof) != n_proof:
+            raise ValueError(f"sparse_eval_verify_kzg: the proof holds {len(proof)} bytes, the shape needs {n_proof}")
+        if len(rx) != 32 * nx or len(ry) != 32 * ny or len(evals) != 32 * batch:
+            raise ValueError("sparse_eval_verify_kzg: rx, ry or evals does not have the shape's length")
+        acc = C.c_int(0)
+        self._chk(lib().sbn_sparse_eval_verify_kzg(self.h, C.c_size_t(nx), C.c_size_t(ny), C.c_size_t(num_ops), C.c_size_t(num_cells), C.c_size_t(batch), comm_ops.h, comm_mem.h,
+                                                   _ptr(rx), _ptr(ry), _ptr(evals), gens_ops.h, gens_mem.h, g2.h, tau_g2.h, _ptr(proof), tr.h, C.byref(acc)), "sbn_sparse_eval_verify_kzg")
+        return bool(acc.value)
 
     # ---- R1CS matrices on the device (r1cs.rs): multiply_vec, the phase-2 table, evaluate
     def r1cs_upload(self, num_cons, num_vars, mats, flags=0):

@@ -13,9 +13,14 @@
 //                        hand-over of opening k + 1 and runs while the host hashes; behind the mem opening's transcript ONE k_window_sums launch takes
 //                        the three sums over 2 lg + 4 points each (the proof's points, Cx, Cy), ONE hand-over brings them and the three commit sums,
 //                        and the host folds and tests each equation for the identity on its own: the group equations of the reference, no batching.
+// The KZG build (sbn_sparse_eval_verify_kzg) runs the same function with `kz` set: comm_derefs is one compressed point absorbed as :349-356 does, derefs_reduce
+// (:561-584) replaces the derefs opening (the joint claim is absorbed, not compared, and kzg_eval_point is drawn), the two Hyrax openings of comb_ops and
+// comb_mem and their final equations are what they are above, and the pairing check of (comm_derefs, kzg_eval_point, eval, pi) follows behind the mutex'
+// release through sbn_g1_decompress and the KZG check of abi_pairing.inc.
 // Included by sbn254.hip.
 
 static const int SV_OPENINGS = 3;                    // derefs, ops, mem
+struct SvKzg { uint8_t comm[32], pi[32], y[32], z[32]; };      // out: the KZG opening to check: the two points normalised compressed, eval, kzg_eval_point
 static const size_t SV_STAGE_POINTS = 64 + SS_WINDOWS;      // the window sums of C_LZ (at most 64: checked) and of C_Zr
 
 struct SvOpening {
@@ -46,21 +51,23 @@ static int sv_row_commit(sbn_ctx* c, const SvOpening& o, int k, uint32_t* d_row,
 static int sparse_verify_locked(sbn_ctx* c, const SparseEvalShape& s, const sbn_host::spv::Layout& L, const sbn_bases* comm_ops, const sbn_bases* comm_mem,
                                 const uint8_t* rx, size_t nx, const uint8_t* ry, size_t ny, const uint8_t* evals,
                                 const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_bases* gens_derefs, const uint8_t* proof,
-                                sbn_host::MerlinTranscript& t, int* accepted) {
+                                sbn_host::MerlinTranscript& t, int* accepted, SvKzg* kz = nullptr) {
   using namespace sbn_host::fr;
   namespace spv = sbn_host::spv;
   *accepted = 0;
   if (!spv::proof_scalars_canonical(L, proof)) return SBN_OK;      // Scalar::from_bytes fails (scalar.rs:87-95): nothing has been launched
   int rc;
   SvOpening op[SV_OPENINGS];
+  const int k0 = kz ? 1 : 0;                                           // the KZG build has no derefs opening
   {
     const sbn_bases* gs[SV_OPENINGS] = {gens_derefs, gens_ops, gens_mem};
     const sbn_bases* cm[SV_OPENINGS] = {nullptr, comm_ops, comm_mem};
     const size_t ells[SV_OPENINGS] = {s.ell_d, s.ell_o, s.ell_mm};
     const spv::Field fl[SV_OPENINGS] = {spv::HASH_PROOF_DEREFS, spv::HASH_PROOF_OPS, spv::HASH_PROOF_MEM};
-    size_t pt = s.Ld;
+    size_t pt = kz ? 0 : s.Ld;
     for (int k = 0; k < SV_OPENINGS; k++) {
       SvOpening& o = op[k];
+      if (k < k0) { o.gens = o.ext = o.comm = nullptr; o.comm_pts = nullptr; o.ell = o.ml = o.mr = o.L_size = o.n = o.lg = o.np = o.pt0 = 0; o.proof = nullptr; continue; }
       o.gens = gs[k]; o.comm = cm[k]; o.ell = ells[k]; o.ml = o.ell / 2; o.mr = o.ell - o.ml; o.L_size = (size_t)1 << o.ml; o.n = (size_t)1 << o.mr; o.lg = o.mr;
       o.np = 2 * o.lg + 2; o.pt0 = pt; pt += o.np; o.proof = proof + L.off[fl[k]];
       o.comm_pts = cm[k] ? (const uint32_t*)cm[k]->d_pts : nullptr;
@@ -96,7 +103,8 @@ static int sparse_verify_locked(sbn_ctx* c, const SparseEvalShape& s, const sbn_
 
   // ---- before any hashing: every point of the proof, one launch ----
   uint8_t* comp = pin + h_comp;                                       // normalised: the identity in the form sbn_g1_compress writes it
-  for (size_t i = 0; i < s.Ld; i++) rv_normalise(proof + 32 * i, comp + 32 * i);
+  if (!kz) for (size_t i = 0; i < s.Ld; i++) rv_normalise(proof + 32 * i, comp + 32 * i);
+  else { rv_normalise(proof, kz->comm); rv_normalise(proof + L.off[spv::HASH_PROOF_DEREFS], kz->pi); memcpy(kz->y, proof + L.off[spv::HASH_PROOF_DEREFS] + 32, 32); }
   for (const SvOpening& o : op) for (size_t i = 0; i < o.np; i++) rv_normalise(o.proof + 32 * i, comp + 32 * (o.pt0 + i));
   HIPCHK(c, hipMemsetAsync(d_ok, 0, 128 * okp, c->stream));
   HIPCHK(c, hipMemcpyAsync(p0 + o_comp, comp, 32 * NP, hipMemcpyHostToDevice, c->stream));
@@ -108,9 +116,12 @@ static int sparse_verify_locked(sbn_ctx* c, const SparseEvalShape& s, const sbn_
   static const char NAME[] = "Sparse polynomial evaluation proof";
   ts.protocol(NAME);                                                  // sparse_mlpoly_full.rs:1824
   ts.message("derefs_commitment", "begin_derefs_commitment", 23);     // :341-347
-  ts.message("comm_poly_row_col_ops_val", "poly_commitment_begin", 21);      // hyrax.rs:44-51
-  for (size_t i = 0; i < s.Ld; i++) ts.point("poly_commitment_share", comp + 32 * i);
-  ts.message("comm_poly_row_col_ops_val", "poly_commitment_end", 19);
+  if (kz) ts.point("comm_poly_row_col_ops_val", kz->comm);           // :349-356 with kzg.rs:399-403: the 32 compressed bytes
+  else {
+    ts.message("comm_poly_row_col_ops_val", "poly_commitment_begin", 21);      // hyrax.rs:44-51
+    for (size_t i = 0; i < s.Ld; i++) ts.point("poly_commitment_share", comp + 32 * i);
+    ts.message("comm_poly_row_col_ops_val", "poly_commitment_end", 19);
+  }
   ts.message("derefs_commitment", "end_derefs_commitment", 21);
   uint8_t rhb[64];
   ts.challenges("challenge_r_hash", rhb, 2);
@@ -128,12 +139,16 @@ static int sparse_verify_locked(sbn_ctx* c, const SparseEvalShape& s, const sbn_
   if (pc.rand_mem.size() != m || pc.rand_ops.size() != s.L_ops) return SBN_OK;
   if (!spv::hash_layer_field(hf, s.batch, pc, rxe.data(), rye.data(), el_from(rhb), el_from(rhb + 32), &je)) return SBN_OK;
   ts.protocol("Sparse polynomial hash layer proof");                  // :1135
-  ts.protocol("Derefs evaluation proof");                             // :467
+  ts.protocol(kz ? "Derefs evaluation proof (KZG)" : "Derefs evaluation proof");      // :467 / :512
+  if (kz) {                                                           // derefs_reduce (:561-584): the claim is absorbed and not compared; then the opening's point
+    joint_reduce(je.derefs.data(), s.cnt_d, s.lc_d, "evals_ops_val", "challenge_combine_n_to_one", "joint_claim_eval", (const uint8_t*)pc.rand_ops.data(), s.L_ops, t, op[0].rj, op[0].claim);
+    ts.challenges("kzg_eval_point", kz->z, 1);
+  }
 
   // ---- the three openings ----
   std::vector<uint8_t> Rv, Rv_right;                                  // R = eq(r_right) and the coordinates it was made of
   int pending = -1;                                                   // the opening whose row commit waits for the next hand-over to be in front of it
-  for (int k = 0; k < SV_OPENINGS; k++) {
+  for (int k = k0; k < SV_OPENINGS; k++) {
     SvOpening& o = op[k];
     if (k == 0) joint_reduce(je.derefs.data(), s.cnt_d, s.lc_d, "evals_ops_val", "challenge_combine_n_to_one", "joint_claim_eval", (const uint8_t*)pc.rand_ops.data(), s.L_ops, t, o.rj, o.claim);
     else if (k == 1) joint_reduce(je.ops.data(), s.cnt_o, s.lc_o, "claim_evals_ops", "challenge_combine_n_to_one", "joint_claim_eval_ops", (const uint8_t*)pc.rand_ops.data(), s.L_ops, t, o.rj, o.claim);
@@ -149,7 +164,7 @@ static int sparse_verify_locked(sbn_ctx* c, const SparseEvalShape& s, const sbn_
     MsmShape s1;
     if ((rc = msm_windows_launch(c, d_Lc, o.comm_pts, o.L_size, o.comm, &s1))) return rc;
     if (s1.W < 1 || (size_t)s1.W > SV_STAGE_POINTS - SS_WINDOWS) return fail(c, SBN_EINVAL, "sparse verify: %d windows", s1.W);
-    const size_t W = (size_t)s1.W, npts = W + SS_WINDOWS + (k == 0 ? okp : 0);
+    const size_t W = (size_t)s1.W, npts = W + SS_WINDOWS + (k == k0 ? okp : 0);
     HIPCHK(c, hipMemcpyAsync(d_stage, c->wsum.p, W * 128, hipMemcpyDeviceToDevice, c->stream));
     {
       uint32_t* d = (uint32_t*)(pin + h_d1 + desc_bytes * k);
@@ -159,7 +174,7 @@ static int sparse_verify_locked(sbn_ctx* c, const SparseEvalShape& s, const sbn_
       HIPCHK(c, hipMemcpyAsync(p0 + o_d1 + desc_bytes * k, d, desc_bytes, hipMemcpyHostToDevice, c->stream));
       LAUNCH(c, "k_window_sums", k_window_sums, (unsigned)SS_WINDOWS, 256, (const uint32_t*)(p0 + o_d1 + desc_bytes * k), (const uint32_t*)o.ext->d_pts, d_stage + 32 * W);
     }
-    if (k == 0) HIPCHK(c, hipMemcpyAsync(d_stage + 32 * (W + SS_WINDOWS), d_ok, 128 * okp, hipMemcpyDeviceToDevice, c->stream));
+    if (k == k0) HIPCHK(c, hipMemcpyAsync(d_stage + 32 * (W + SS_WINDOWS), d_ok, 128 * okp, hipMemcpyDeviceToDevice, c->stream));
     uint32_t seq = 0;
     if ((rc = sums_handover_begin(c, d_stage, npts, &seq))) return rc;
     // behind the hand-over: the previous opening's row commit, which the device works on while the host hashes
@@ -171,7 +186,7 @@ static int sparse_verify_locked(sbn_ctx* c, const SparseEvalShape& s, const sbn_
     }
     const sbn_host::Pt* S = nullptr;
     if ((rc = sums_handover_wait(c, npts, seq, &S))) return rc;
-    if (k == 0) {
+    if (k == k0) {
       const uint8_t* ok = (const uint8_t*)(S + W + SS_WINDOWS);
       for (size_t i = 0; i < NP; i++) if (!ok[i]) return SBN_OK;      // a point of the proof does not decompress
     }
@@ -187,10 +202,10 @@ static int sparse_verify_locked(sbn_ctx* c, const SparseEvalShape& s, const sbn_
   if ((rc = sv_row_commit(c, op[pending], pending, d_row, d_fin))) return rc;
 
   // ---- the three final equations: one launch over the proof's points, Cx and Cy; one hand-over with the three commit sums ----
-  for (int k = 0; k < SV_OPENINGS; k++) {
+  memset(pin + h_df, 0, (h_total - h_df));                            // (an opening the KZG build does not have: a sum of no terms, not read)
+  for (int k = k0; k < SV_OPENINGS; k++) {
     const SvOpening& o = op[k];
     uint32_t* d = (uint32_t*)(pin + h_df + desc_bytes * k);
-    memset(d, 0, desc_bytes);
     d[0] = (uint32_t)(o.np + 2);                                      // at most 2 * 20 + 4 terms (the shape's check of ell)
     for (size_t i = 0; i < o.np; i++) d[SS_DESC_IDX + i] = (uint32_t)(o.pt0 + i);
     d[SS_DESC_IDX + o.np] = (uint32_t)(NP + 2 * k); d[SS_DESC_IDX + o.np + 1] = (uint32_t)(NP + 2 * k + 1);      // (d_mont holds NP + 6 points)
@@ -203,7 +218,7 @@ static int sparse_verify_locked(sbn_ctx* c, const SparseEvalShape& s, const sbn_
   const sbn_host::Pt* S = nullptr;
   if ((rc = sums_handover(c, d_fin, SV_OPENINGS * SS_WINDOWS + SV_OPENINGS, &S))) return rc;
   bool all = true;
-  for (int k = 0; k < SV_OPENINGS; k++)
+  for (int k = k0; k < SV_OPENINGS; k++)
     if (!sbn_host::is_inf(sbn_host::padd(small_sum_fold(S + (size_t)SS_WINDOWS * k), sbn_host::pt_from_device(S[SV_OPENINGS * SS_WINDOWS + k])))) all = false;
   *accepted = all ? 1 : 0;
   return SBN_OK;
@@ -236,6 +251,54 @@ int sbn_sparse_eval_verify(sbn_ctx* c, size_t num_vars_x, size_t num_vars_y, siz
   return verify_on_copy(c, tr, accepted, [&](sbn_host::MerlinTranscript& t) {
     return sparse_verify_locked(c, s, L, comm_ops, comm_mem, rx, num_vars_x, ry, num_vars_y, evals, gens_ops, gens_mem, gens_derefs, proof, t, accepted);
   });
+}
+
+int sbn_sparse_eval_verify_kzg(sbn_ctx* c, size_t num_vars_x, size_t num_vars_y, size_t num_ops, size_t num_cells, size_t batch,
+                               const sbn_bases* comm_ops, const sbn_bases* comm_mem, const uint8_t* rx, const uint8_t* ry, const uint8_t* evals,
+                               const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_g2_lines* g2, const sbn_g2_lines* tau_g2,
+                               const uint8_t* proof, sbn_transcript* tr, int* accepted) {
+  if (!c || !comm_ops || !comm_mem || (!rx && num_vars_x) || (!ry && num_vars_y) || !evals || !gens_ops || !gens_mem || !g2 || !tau_g2 || !proof || !tr || !accepted) return SBN_EINVAL;
+  const char* pfx = "sparse verify (KZG)";
+  if (g2->ctx != c || tau_g2->ctx != c) return fail(c, SBN_EINVAL, "%s: a G2 handle of another context", pfx);
+  if (batch < 1 || batch > (size_t)SE_BATCH_MAX) return fail(c, SBN_EINVAL, "%s: batch = %zu is outside 1 .. %d", pfx, batch, SE_BATCH_MAX);
+  if (num_ops < 2 || (num_ops & (num_ops - 1))) return fail(c, SBN_EINVAL, "%s: N = %zu (a power of two from 2 on)  [product_tree.rs:89 assert_eq]", pfx, num_ops);
+  SparseEvalShape s;
+  sbn_host::spv::Layout L;
+  if (!sparse_eval_shape(num_vars_x, num_vars_y, num_ops, batch, &s) || !sbn_host::spv::layout_make(num_vars_x, num_vars_y, num_ops, batch, &L, true) || L.off[sbn_host::spv::NFIELDS] != s.proof_bytes_kzg)
+    return fail(c, SBN_EINVAL, "%s: shape (%zu, %zu, N = %zu, batch = %zu) is outside what the openings take", pfx, num_vars_x, num_vars_y, num_ops, batch);
+  if (num_cells != s.cells) return fail(c, SBN_EINVAL, "%s: %zu memory cells, rx and ry have %zu and %zu variables  [sparse_mlpoly_full.rs:1828 assert_eq]", pfx, num_cells, num_vars_x, num_vars_y);
+  if (comm_ops->n != ((size_t)1 << (s.ell_o / 2)) || comm_mem->n != ((size_t)1 << (s.ell_mm / 2)))
+    return fail(c, SBN_EINVAL, "%s: comm_ops has %zu and comm_mem %zu row commitments, the shape has %zu and %zu", pfx, comm_ops->n, comm_mem->n, (size_t)1 << (s.ell_o / 2), (size_t)1 << (s.ell_mm / 2));
+  const struct { const sbn_bases* g; size_t lg; const char* name; } gs[2] = {{gens_ops, s.lg_o, "gens_ops"}, {gens_mem, s.lg_m, "gens_mem"}};
+  for (const auto& x : gs)
+    if (x.g->n != ((size_t)1 << x.lg) + 1 || !x.g->has_h)
+      return fail(c, SBN_EINVAL, "%s: %s has %zu points%s, the opening needs %zu + 1 with h  [nizk/mod.rs:412-415]", pfx, x.name, x.g->n, x.g->has_h ? "" : " and no h", (size_t)1 << x.lg);
+  const struct { const uint8_t* p; size_t n; const char* name; } sc[3] = {{rx, num_vars_x, "rx"}, {ry, num_vars_y, "ry"}, {evals, batch, "evals"}};
+  for (const auto& x : sc)
+    for (size_t i = 0; i < x.n; i++) if (!fr_canonical(x.p + 32 * i)) return fail(c, SBN_EINVAL, "%s: %s[%zu] is not canonical  [scalar.rs:87-95]", pfx, x.name, i);
+  // the field half, the transcript and the two Hyrax openings on a copy of the transcript, under the context's mutex
+  sbn_host::MerlinTranscript t = tr->t;
+  SvKzg kz;
+  int acc = 0;
+  {
+    std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
+    const int rc = sparse_verify_locked(c, s, L, comm_ops, comm_mem, rx, num_vars_x, ry, num_vars_y, evals, gens_ops, gens_mem, nullptr, proof, t, &acc, &kz);
+    if (rc != SBN_OK) { hipStreamSynchronize(c->stream); return rc; }
+  }
+  if (!acc) { *accepted = 0; return SBN_OK; }
+  // DerefsEvalProof::verify's KZGProof::verify (:586-594): the opening of comm_derefs at kzg_eval_point against the proof's own eval
+  uint8_t comp[64], xy[128], ok[2] = {0, 0};
+  memcpy(comp, kz.comm, 32); memcpy(comp + 32, kz.pi, 32);
+  int rc;
+  if ((rc = sbn_g1_decompress(c, comp, 2, xy, ok))) return rc;
+  if (!ok[0] || !ok[1]) { *accepted = 0; return SBN_OK; }                // a point of the proof does not decompress
+  static const uint8_t ONE[32] = {1};
+  std::vector<uint8_t> pts(xy, xy + 64), scal(ONE, ONE + 32);
+  int paired = 0;
+  if ((rc = kzg_check_run(c, g2, tau_g2, pts, scal, kz.y, kz.z, xy + 64, &paired))) return rc;
+  *accepted = paired;
+  if (paired) tr->t = t;
+  return SBN_OK;
 }
 
 }  // extern "C"

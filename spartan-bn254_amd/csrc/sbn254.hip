@@ -15,6 +15,7 @@
 //   ZKSumcheckInstanceProof::prove_cubic_with_additive_term, ::prove_quad, DotProductProof::prove  src/sumcheck.rs:465-811, src/nizk/mod.rs:306-366 -> sbn_zk_sumcheck_prove_r1cs / _quad
 //   R1CSProof::verify, ZKSumcheckInstanceProof::verify, DotProductProof::verify  src/r1csproof.rs:463-619, src/sumcheck.rs:366-457, src/nizk/mod.rs:368-400 -> sbn_r1cs_proof_verify / sbn_zk_sumcheck_verify
 //   SparseMatPolyEvalProof::verify, PolyEvalNetworkProof::verify, ProductLayerProof / HashLayerProof::verify  src/sparse_mlpoly_full.rs:1815-1845, :1581-1650, :1436-1520, :1048-1265 -> sbn_sparse_eval_verify
+//   KZGProof::verify, KZGBatchProof::batch_verify, Bn254::pairing  src/kzg.rs:196-217, :315-352 -> sbn_kzg_verify / _batched / sbn_pairing_products / sbn_g2_prepare
 //   the verifier's short sums of proof points (nizk/mod.rs:560-565, :389-394 as GroupElement::vartime_multiscalar_mul)          -> sbn_g1_small_sums
 // There is no CPU fallback in this file: every entry point needs the gfx950 device.
 #include "../../include/sbn254.h"
@@ -37,10 +38,12 @@
 #include "small_sum_kernels.cuh"
 #include "sparse_eval_kernels.cuh"
 #include "derefs_key_kernels.cuh"
+#include "pairing_kernels.cuh"
 #include "host_keccak.hpp"
 #include "host_strobe.hpp"
 #include "proof_host.hpp"
 #include "sparse_verify_host.hpp"
+#include "pairing_host.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -80,6 +83,7 @@ using namespace sbn;
 #include "abi_r1cs_proof.inc"
 #include "abi_r1cs_verify.inc"
 #include "abi_small_sums.inc"
+#include "abi_pairing.inc"
 #include "abi_dense.inc"
 #include "abi_derefs_key.inc"
 #include "abi_sparse_eval.inc"

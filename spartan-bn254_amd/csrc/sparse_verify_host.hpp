@@ -40,30 +40,33 @@ struct Layout {
   size_t cnt_d, cnt_o;                             // evals of the derefs / ops joint openings, padded to a power of two
   size_t lg_d, lg_o, lg_m, Ld;                     // rounds of the three openings; row commitments in comm_derefs
   size_t off[NFIELDS + 1];                         // field f lies at [off[f], off[f + 1])
+  bool kzg;                                        // the KZG build's layout: comm_derefs one point, proof_derefs [proof 32 | eval 32]
 };
 static inline size_t pcepb_bytes(size_t circuits, size_t layers, size_t dotp) { return 128 * (layers * (layers - 1) / 2) + 32 * (2 * circuits * layers + 3 * dotp); }
 // false where SparseMatPolyCommitmentGens::new or the verifier's first assert would fail: N below 2 or no power of two, no batch, no variable
-static inline bool layout_make(size_t nx, size_t ny, size_t N, size_t batch, Layout* L) {
+static inline bool layout_make(size_t nx, size_t ny, size_t N, size_t batch, Layout* L, bool kzg = false) {
   if (batch < 1 || N < 2 || (N & (N - 1)) || nx > 63 || ny > 63 || (nx < 1 && ny < 1)) return false;
-  L->b = batch; L->n = log2z(N); L->m = nx > ny ? nx : ny;
+  L->kzg = kzg; L->b = batch; L->n = log2z(N); L->m = nx > ny ? nx : ny;
   L->cnt_d = 1; while (L->cnt_d < 2 * batch) L->cnt_d <<= 1;
   L->cnt_o = 1; while (L->cnt_o < 5 * batch) L->cnt_o <<= 1;
   const size_t ell_d = L->n + log2z(L->cnt_d), ell_o = L->n + log2z(L->cnt_o), ell_m = L->m + 1;      // sparse_mlpoly_full.rs:619-623
   L->lg_d = ell_d - ell_d / 2; L->lg_o = ell_o - ell_o / 2; L->lg_m = ell_m - ell_m / 2; L->Ld = (size_t)1 << (ell_d / 2);
   const size_t b = batch;
-  const size_t len[NFIELDS] = {32 * L->Ld, 32 * (2 + 2 * b), 32 * (2 + 2 * b), 64 * b, pcepb_bytes(4, L->m, 0), pcepb_bytes(4 * b, L->n, 2 * b),
-                               32 * (2 * b + 1), 32 * (2 * b + 1), 32 * b, 64 * b, 64 * L->lg_o + 128, 64 * L->lg_m + 128, 64 * L->lg_d + 128};
+  const size_t len[NFIELDS] = {kzg ? 32 : 32 * L->Ld, 32 * (2 + 2 * b), 32 * (2 + 2 * b), 64 * b, pcepb_bytes(4, L->m, 0), pcepb_bytes(4 * b, L->n, 2 * b),
+                               32 * (2 * b + 1), 32 * (2 * b + 1), 32 * b, 64 * b, 64 * L->lg_o + 128, 64 * L->lg_m + 128, kzg ? 64 : 64 * L->lg_d + 128};
   L->off[0] = 0;
   for (int f = 0; f < NFIELDS; f++) L->off[f + 1] = L->off[f] + len[f];
   return true;
 }
 static inline Span field(const Layout& L, const uint8_t* proof, Field f) { return Span{proof + L.off[f], L.off[f + 1] - L.off[f]}; }
-// every scalar of the proof is below r: the nine scalar fields, and z1, z2 at the end of each opening
+// every scalar of the proof is below r: the nine scalar fields, and z1, z2 at the end of each opening (the KZG build: of the two Hyrax openings, and
+// the eval behind the derefs proof point)
 static inline bool proof_scalars_canonical(const Layout& L, const uint8_t* proof) {
   El x;
   for (int f = PROD_EVAL_ROW; f <= HASH_EVAL_DEREFS; f++)
     for (size_t o = L.off[f]; o < L.off[f + 1]; o += 32) if (!el_load(proof + o, &x)) return false;
-  for (int f = HASH_PROOF_OPS; f <= HASH_PROOF_DEREFS; f++)
+  if (L.kzg && !el_load(proof + L.off[HASH_PROOF_DEREFS] + 32, &x)) return false;
+  for (int f = HASH_PROOF_OPS; f <= (L.kzg ? HASH_PROOF_MEM : HASH_PROOF_DEREFS); f++)
     for (size_t o = L.off[f + 1] - 64; o < L.off[f + 1]; o += 32) if (!el_load(proof + o, &x)) return false;
   return true;
 }
