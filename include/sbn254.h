@@ -791,6 +791,88 @@ int sbn_sparse_eval_verify_kzg(sbn_ctx* ctx, size_t num_vars_x, size_t num_vars_
                                const sbn_bases* gens_ops, const sbn_bases* gens_mem, const sbn_g2_lines* g2, const sbn_g2_lines* tau_g2,
                                const uint8_t* proof, sbn_transcript* tr, int* accepted);
 
+/* ---- Instance::is_sat (snark.rs:137-158 -> R1CSShape::is_sat, r1cs.rs:105-123) on the device: does z = vars | 1 | input satisfy Az o Bz = Cz? ----
+ *   vars   a table of at most num_vars entries (a power of two, as every table); a shorter one is zero-padded on the device (Assignment::pad).
+ *   input  num_inputs canonical scalars, num_inputs < num_vars (z has 2 num_vars entries).
+ * Work: k_r1cs_build_z, the launches of sbn_r1cs_multiply into tables of the call's own (released before it returns), then ONE k_r1cs_sat_check pass:
+ * a lane a row, Az[i] Bz[i] - Cz[i] tested on its canonical value, one atomicAdd and one atomicMin a block.  One host wait.
+ *   *sat = 1: every row holds.  Otherwise *num_bad = the violated rows and *first_bad = the lowest of them (meaningful only with *sat == 0).
+ * SBN_EINVAL before any launch, outputs untouched: a NULL pointer, vars longer than num_vars, num_inputs >= num_vars, an input >= r. */
+int sbn_r1cs_is_sat(sbn_ctx* ctx, const sbn_r1cs* inst, const sbn_table* vars, const uint8_t* input, size_t num_inputs,
+                    int* sat, uint64_t* num_bad, uint64_t* first_bad);
+
+/* ---- the reference's public surface in one call each: SNARKGens::new, Instance::new + SNARK::encode, Instance::is_sat, SNARK::prove, SNARK::verify
+ *      (snark.rs:59-158, :290-529), both builds.  NIZK is not here: its transcript absorbs R1CSShape::get_digest, zlib over bincode (r1cs.rs:97-101). ----
+ * Shapes are RAW: num_cons, num_vars, num_inputs as the circuit has them, columns as the circuit numbers them (vars | 1 | inputs).  Instance::new's
+ * rules are applied inside (snark.rs:74-110): num_vars_padded = npo2(max(num_vars, num_inputs + 1)), num_cons_padded = npo2(max(num_cons, 2)), a column
+ * >= num_vars moves to col + num_vars_padded - num_vars; nx = log2 num_cons_padded, ny = log2(2 num_vars_padded).  Entry order is kept.
+ *
+ * sbn_snark_gens: SNARKGens (snark.rs:305-328).  Six sets through sbn_gens_new: under the label "gens_r1cs_sat" gens_pc (R + 1 generators with h,
+ *   (L, R) = 2^sbn_factored_lens(log2 num_vars_padded)), gens_3 and gens_4 (r1csproof.rs:155-182: gens_1 is gens_pc's); under "gens_r1cs_eval"
+ *   gens_ops, gens_mem, gens_derefs (R_k + 1 each, sbn_sparse_eval_prove's notation with b = 3, N = npo2(num_nz_entries), sparse_mlpoly_full.rs:612-630).
+ *   num_nz_entries is the largest of the three nnz, as the reference requires (r1cs.rs:273-274): a bundle made for another N is refused by encode.
+ *   sbn_snark_gens_get(gens, which): which = 0 gens_pc, 1 gens_3, 2 gens_4, 3 gens_ops, 4 gens_mem, 5 gens_derefs; owned by the bundle (e.g. for
+ *   sbn_bases_precompute); NULL for another `which`.  The KZG build ignores gens_derefs.
+ *
+ * sbn_snark_key: what SNARK::encode returns, resident.  The prover's half: the matrices (sbn_r1cs) and their dense representation (sbn_dense); the
+ *   verifier's half: the shape and the two PolyCommitments of R1CSCommitment as point sets.
+ *   sbn_snark_encode      rows / cols / vals / nnz: three matrices as sbn_r1cs_upload takes them, raw.  In order: the conversion on the host, sbn_r1cs_upload,
+ *                         sbn_dense_build(nx, ny), DensePolynomial::commit of comb_ops and comb_mem with no blinds (hyrax.rs:283-308), sbn_g1_compress.
+ *                         SBN_EINVAL: a row >= num_cons, a col >= num_vars + 1 + num_inputs, a value >= r (snark.rs:95-101), num_vars_padded < 2, no matrix
+ *                         with more than one entry (N < 2: product_tree.rs:89), a bundle made for another shape or N, flags other than SBN_SCALARS_MONT.
+ *   sbn_snark_key_comm    R1CSCommitment as bytes: six little-endian u64  num_cons_padded | num_vars_padded | num_inputs | batch (3) | num_ops N |
+ *                         num_mem_cells,  then comm_comb_ops [L_ops x 32] and comm_comb_mem [L_mem x 32] as sbn_g1_compress gives them, L_k = 2^left of
+ *                         sbn_factored_lens(ell_k).  *len <- the length, always; out == NULL asks for the length alone; cap < *len is SBN_EINVAL.
+ *   sbn_snark_key_from_comm  the verifier's half from those bytes (sbn_bases_from_compressed twice).  The bytes are the caller's own data: SBN_EINVAL for a
+ *                         wrong length, a size that is no power of two, N < 2, num_mem_cells != 2^max(nx, ny), num_inputs >= num_vars_padded, batch != 3,
+ *                         a point that does not decompress.  Proving or checking a witness on such a key is SBN_EINVAL.
+ *   sbn_snark_key_dense   the prover's dense handle, owned by the key (NULL on a verifier key): what sbn_derefs_key_build takes for the KZG build.
+ *   sbn_snark_sizes       kzg = 0 / 1: rnd_scalars and proof_bytes of the build.
+ *        rnd   = sbn_r1cs_proof_prove's rnd | sbn_sparse_eval_prove[_kzg]'s rnd: ONE RandomTape (b"snark_proof", snark.rs:438), draws in call order.
+ *        proof = r1cs_sat_proof (sbn_r1cs_proof_prove's out_proof) | inst_evals A, B, C(rx, ry) [96] | r1cs_eval_proof (sbn_sparse_eval_prove[_kzg]'s
+ *                out_proof): the declaration order of snark.rs:405-409.
+ *
+ * sbn_snark_is_sat: sbn_r1cs_is_sat on the key's matrices; num_inputs must be the instance's (snark.rs:145).
+ * sbn_snark_prove: SNARK::prove (snark.rs:428-484).  Transcript: protocol-name "Spartan SNARK proof"; R1CSCommitment::append_to_transcript (r1cs.rs:355-362,
+ *   sparse_mlpoly_full.rs:710-717): append_u64 (Merlin's: eight little-endian bytes) of num_cons, num_vars, num_inputs, batch_size, num_ops,
+ *   num_mem_cells, then the two PolyCommitments under comm_comb_ops / comm_comb_mem (hyrax.rs:44-51); then R1CSProof::prove on the padded vars
+ *   (sbn_r1cs_proof_prove's body), A, B, C(rx, ry) (sbn_r1cs_evaluate's), R1CSEvalProof::prove (sbn_sparse_eval_prove's), all under one hold of the mutex.
+ *   vars: at most num_vars_padded entries; a table at raw and at padded length give the same bytes.  num_inputs must be the instance's.
+ *   flags: SBN_SNARK_CHECK_SAT runs the witness check first; an unsatisfied witness is SBN_EUNSAT before any proving launch (the text names the count and
+ *   the first row).  `tr` moves on and out_proof is written only behind SBN_OK.  SBN_EINVAL before any launch: a NULL pointer, a verifier key, unknown
+ *   flags, a wrong num_inputs, vars too long, a bundle of another shape, a scalar of input or rnd >= r; the KZG build's SRS and derefs-key rules are
+ *   sbn_sparse_eval_prove_kzg's (derefs_key: sbn_derefs_key_build(sbn_snark_key_dense(key), srs), or NULL).
+ * sbn_snark_verify: SNARK::verify (snark.rs:487-528) on either kind of key: proof_len against sbn_snark_sizes, the prefix, R1CSProof::verify with the
+ *   proof's own inst_evals (sbn_r1cs_proof_verify's body), R1CSEvalProof::verify at the (rx, ry) it returned (sbn_sparse_eval_verify[_kzg]'s); a refused
+ *   first half skips the second.  SBN_EINVAL before any launch, `tr` unchanged: a NULL pointer, a wrong proof_len or num_inputs, an input >= r, a
+ *   bundle of another shape, a G2 handle of another context.  What the prover controls is SBN_OK with *accepted = 0, an inst_evals scalar >= r among
+ *   it.  `tr` moves on only behind *accepted == 1 and then ends where sbn_snark_prove's transcript ended. */
+#define SBN_EUNSAT (-5)            /* sbn_snark_prove with SBN_SNARK_CHECK_SAT: the witness does not satisfy the instance */
+#define SBN_SNARK_CHECK_SAT 1u
+typedef struct sbn_snark_gens sbn_snark_gens;
+typedef struct sbn_snark_key sbn_snark_key;
+int sbn_snark_gens_new(sbn_ctx* ctx, size_t num_cons, size_t num_vars, size_t num_inputs, size_t num_nz_entries, sbn_snark_gens** out);
+const sbn_bases* sbn_snark_gens_get(const sbn_snark_gens* gens, int which);
+void sbn_snark_gens_free(sbn_ctx* ctx, sbn_snark_gens* gens);
+int sbn_snark_encode(sbn_ctx* ctx, size_t num_cons, size_t num_vars, size_t num_inputs, const uint32_t* const* rows, const uint32_t* const* cols,
+                     const uint8_t* const* vals, const size_t* nnz, uint32_t flags, const sbn_snark_gens* gens, sbn_snark_key** out);
+int sbn_snark_key_from_comm(sbn_ctx* ctx, const uint8_t* comm, size_t len, sbn_snark_key** out);
+int sbn_snark_key_comm(const sbn_snark_key* key, uint8_t* out, size_t cap, size_t* len);
+const sbn_dense* sbn_snark_key_dense(const sbn_snark_key* key);
+void sbn_snark_key_free(sbn_ctx* ctx, sbn_snark_key* key);
+int sbn_snark_sizes(const sbn_snark_key* key, int kzg, size_t* rnd_scalars, size_t* proof_bytes);
+int sbn_snark_is_sat(sbn_ctx* ctx, const sbn_snark_key* key, const sbn_table* vars, const uint8_t* input, size_t num_inputs,
+                     int* sat, uint64_t* num_bad, uint64_t* first_bad);
+int sbn_snark_prove(sbn_ctx* ctx, const sbn_snark_key* key, const sbn_table* vars, const uint8_t* input, size_t num_inputs, const sbn_snark_gens* gens,
+                    uint32_t flags, const uint8_t* rnd, sbn_transcript* tr, uint8_t* out_proof);
+int sbn_snark_verify(sbn_ctx* ctx, const sbn_snark_key* key, const uint8_t* input, size_t num_inputs, const sbn_snark_gens* gens,
+                     const uint8_t* proof, size_t proof_len, sbn_transcript* tr, int* accepted);
+int sbn_snark_prove_kzg(sbn_ctx* ctx, const sbn_snark_key* key, const sbn_table* vars, const uint8_t* input, size_t num_inputs, const sbn_snark_gens* gens,
+                        const sbn_bases* srs, const sbn_derefs_key* derefs_key /* or NULL */, uint32_t flags, const uint8_t* rnd, sbn_transcript* tr,
+                        uint8_t* out_proof);
+int sbn_snark_verify_kzg(sbn_ctx* ctx, const sbn_snark_key* key, const uint8_t* input, size_t num_inputs, const sbn_snark_gens* gens,
+                         const sbn_g2_lines* g2, const sbn_g2_lines* tau_g2, const uint8_t* proof, size_t proof_len, sbn_transcript* tr, int* accepted);
+
 /* ---- per-kernel timing (HIP events on the context's stream), for bench.py's roofline line ---- */
 int sbn_prof_enable(sbn_ctx* ctx, int on);
 int sbn_prof_reset(sbn_ctx* ctx);

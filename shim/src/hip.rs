@@ -57,6 +57,8 @@ use crate::unipoly::{CompressedUniPoly, UniPoly};
 #[repr(C)] pub struct sbn_derefs_key { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_g2_lines { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_transcript { _p: [u8; 0] }
+#[repr(C)] pub struct sbn_snark_gens { _p: [u8; 0] }
+#[repr(C)] pub struct sbn_snark_key { _p: [u8; 0] }
 
 pub const SBN_OK: c_int = 0;
 pub const SBN_SCALARS_MONT: u32 = 1;
@@ -225,6 +227,21 @@ extern "C" {
     pub fn sbn_kzg_verify(ctx: *mut sbn_ctx, g2: *const sbn_g2_lines, tau_g2: *const sbn_g2_lines, comm_xy: *const u8, z: *const u8, eval: *const u8, proof_xy: *const u8, accepted: *mut c_int) -> c_int;
     pub fn sbn_kzg_verify_batched(ctx: *mut sbn_ctx, g2: *const sbn_g2_lines, tau_g2: *const sbn_g2_lines, comms_xy: *const u8, count: usize, z: *const u8, gamma: *const u8, evals: *const u8, proof_xy: *const u8, accepted: *mut c_int) -> c_int;
     pub fn sbn_sparse_eval_verify_kzg(ctx: *mut sbn_ctx, num_vars_x: usize, num_vars_y: usize, num_ops: usize, num_cells: usize, batch: usize, comm_ops: *const sbn_bases, comm_mem: *const sbn_bases, rx: *const u8, ry: *const u8, evals: *const u8, gens_ops: *const sbn_bases, gens_mem: *const sbn_bases, g2: *const sbn_g2_lines, tau_g2: *const sbn_g2_lines, proof: *const u8, tr: *mut sbn_transcript, accepted: *mut c_int) -> c_int;
+    pub fn sbn_r1cs_is_sat(ctx: *mut sbn_ctx, inst: *const sbn_r1cs, vars: *const sbn_table, input: *const u8, num_inputs: usize, sat: *mut c_int, num_bad: *mut u64, first_bad: *mut u64) -> c_int;
+    pub fn sbn_snark_gens_new(ctx: *mut sbn_ctx, num_cons: usize, num_vars: usize, num_inputs: usize, num_nz_entries: usize, out: *mut *mut sbn_snark_gens) -> c_int;
+    pub fn sbn_snark_gens_get(gens: *const sbn_snark_gens, which: c_int) -> *const sbn_bases;
+    pub fn sbn_snark_gens_free(ctx: *mut sbn_ctx, gens: *mut sbn_snark_gens);
+    pub fn sbn_snark_encode(ctx: *mut sbn_ctx, num_cons: usize, num_vars: usize, num_inputs: usize, rows: *const *const u32, cols: *const *const u32, vals: *const *const u8, nnz: *const usize, flags: u32, gens: *const sbn_snark_gens, out: *mut *mut sbn_snark_key) -> c_int;
+    pub fn sbn_snark_key_from_comm(ctx: *mut sbn_ctx, comm: *const u8, len: usize, out: *mut *mut sbn_snark_key) -> c_int;
+    pub fn sbn_snark_key_comm(key: *const sbn_snark_key, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
+    pub fn sbn_snark_key_dense(key: *const sbn_snark_key) -> *const sbn_dense;
+    pub fn sbn_snark_key_free(ctx: *mut sbn_ctx, key: *mut sbn_snark_key);
+    pub fn sbn_snark_sizes(key: *const sbn_snark_key, kzg: c_int, rnd_scalars: *mut usize, proof_bytes: *mut usize) -> c_int;
+    pub fn sbn_snark_is_sat(ctx: *mut sbn_ctx, key: *const sbn_snark_key, vars: *const sbn_table, input: *const u8, num_inputs: usize, sat: *mut c_int, num_bad: *mut u64, first_bad: *mut u64) -> c_int;
+    pub fn sbn_snark_prove(ctx: *mut sbn_ctx, key: *const sbn_snark_key, vars: *const sbn_table, input: *const u8, num_inputs: usize, gens: *const sbn_snark_gens, flags: u32, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8) -> c_int;
+    pub fn sbn_snark_verify(ctx: *mut sbn_ctx, key: *const sbn_snark_key, input: *const u8, num_inputs: usize, gens: *const sbn_snark_gens, proof: *const u8, proof_len: usize, tr: *mut sbn_transcript, accepted: *mut c_int) -> c_int;
+    pub fn sbn_snark_prove_kzg(ctx: *mut sbn_ctx, key: *const sbn_snark_key, vars: *const sbn_table, input: *const u8, num_inputs: usize, gens: *const sbn_snark_gens, srs: *const sbn_bases, derefs_key: *const sbn_derefs_key, flags: u32, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8) -> c_int;
+    pub fn sbn_snark_verify_kzg(ctx: *mut sbn_ctx, key: *const sbn_snark_key, input: *const u8, num_inputs: usize, gens: *const sbn_snark_gens, g2: *const sbn_g2_lines, tau_g2: *const sbn_g2_lines, proof: *const u8, proof_len: usize, tr: *mut sbn_transcript, accepted: *mut c_int) -> c_int;
     pub fn sbn_prof_enable(ctx: *mut sbn_ctx, on: c_int) -> c_int;
     pub fn sbn_prof_reset(ctx: *mut sbn_ctx) -> c_int;
     pub fn sbn_prof_count(ctx: *mut sbn_ctx) -> c_int;

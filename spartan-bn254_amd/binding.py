@@ -31,11 +31,19 @@ EXPORTED_SYMBOLS = [
     "sbn_g2_prepare", "sbn_g2_lines_free", "sbn_pairing_products", "sbn_kzg_verify", "sbn_kzg_verify_batched", "sbn_sparse_eval_verify_kzg",
     "sbn_dense_build", "sbn_dense_free", "sbn_dense_num_ops", "sbn_dense_num_cells", "sbn_dense_batch", "sbn_dense_addr_dev", "sbn_dense_read_ts_dev",
     "sbn_dense_audit_ts_dev", "sbn_dense_comb_ops", "sbn_dense_comb_mem",
+    "sbn_r1cs_is_sat", "sbn_snark_gens_new", "sbn_snark_gens_get", "sbn_snark_gens_free", "sbn_snark_encode", "sbn_snark_key_from_comm", "sbn_snark_key_comm", "sbn_snark_key_dense",
+    "sbn_snark_key_free", "sbn_snark_sizes", "sbn_snark_is_sat", "sbn_snark_prove", "sbn_snark_verify", "sbn_snark_prove_kzg", "sbn_snark_verify_kzg",
 ]
+SBN_EUNSAT = -5
+SBN_SNARK_CHECK_SAT = 1
 
 
 class SbnError(RuntimeError):
     pass
+
+
+class SbnUnsat(SbnError):
+    """SBN_EUNSAT: snark_prove with check_sat met a witness that does not satisfy the instance"""
 
 
 def lib_path():
@@ -119,6 +127,21 @@ def lib():
         L.sbn_dense_audit_ts_dev.restype = C.c_void_p; L.sbn_dense_audit_ts_dev.argtypes = [C.c_void_p, C.c_int]
         for name in ("sbn_dense_comb_ops", "sbn_dense_comb_mem"):
             getattr(L, name).restype = C.c_void_p; getattr(L, name).argtypes = [C.c_void_p]
+        L.sbn_r1cs_is_sat.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 3
+        L.sbn_snark_gens_new.argtypes = [C.c_void_p] + [C.c_size_t] * 4 + [C.c_void_p]
+        L.sbn_snark_gens_get.restype = C.c_void_p; L.sbn_snark_gens_get.argtypes = [C.c_void_p, C.c_int]
+        L.sbn_snark_gens_free.restype = None; L.sbn_snark_gens_free.argtypes = [C.c_void_p] * 2
+        L.sbn_snark_encode.argtypes = [C.c_void_p] + [C.c_size_t] * 3 + [C.c_void_p] * 4 + [C.c_uint32] + [C.c_void_p] * 2
+        L.sbn_snark_key_from_comm.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sbn_snark_key_comm.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sbn_snark_key_dense.restype = C.c_void_p; L.sbn_snark_key_dense.argtypes = [C.c_void_p]
+        L.sbn_snark_key_free.restype = None; L.sbn_snark_key_free.argtypes = [C.c_void_p] * 2
+        L.sbn_snark_sizes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.sbn_snark_is_sat.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 3
+        L.sbn_snark_prove.argtypes = [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
+        L.sbn_snark_verify.argtypes = [C.c_void_p] * 3 + [C.c_size_t] + [C.c_void_p] * 2 + [C.c_size_t] + [C.c_void_p] * 2
+        L.sbn_snark_prove_kzg.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 3
+        L.sbn_snark_verify_kzg.argtypes = [C.c_void_p] * 3 + [C.c_size_t] + [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 2
         _LIB = L
     return _LIB
 
@@ -461,6 +484,68 @@ class Dense:
         if self.h:
             self.comb_ops.h = self.comb_mem.h = None
             lib().sbn_dense_free(self.ctx.h, self.h)
+            self.h = None
+
+
+class _BorrowedBases(Bases):
+    """a generator set owned by another handle: never passed to sbn_bases_free"""
+
+    def free(self):
+        self.h = None
+
+
+class _BorrowedDense(Dense):
+    """the dense representation a SnarkKey owns: never passed to sbn_dense_free"""
+
+    def free(self):
+        self.comb_ops.h = self.comb_mem.h = None
+        self.h = None
+
+
+class SnarkGens:
+    """SNARKGens (snark.rs:290-328) resident on the device (sbn_snark_gens_new): pc, g3, g4, ops, mem, derefs are Bases that belong to the bundle"""
+    KINDS = ("pc", "g3", "g4", "ops", "mem", "derefs")
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+        for i, k in enumerate(self.KINDS):
+            setattr(self, k, _BorrowedBases(ctx, C.c_void_p(lib().sbn_snark_gens_get(handle, i))))
+
+    def free(self):
+        if self.h:
+            for k in self.KINDS:
+                getattr(self, k).h = None
+            lib().sbn_snark_gens_free(self.ctx.h, self.h)
+            self.h = None
+
+
+class SnarkKey:
+    """what SNARK::encode returns, resident (sbn_snark_encode), or its verifier's half made of the commitment's bytes (sbn_snark_key_from_comm)"""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+        d = lib().sbn_snark_key_dense(handle)
+        self.dense = _BorrowedDense(ctx, C.c_void_p(d)) if d else None
+
+    def comm(self):
+        """R1CSCommitment as bytes (include/sbn254.h has the layout)"""
+        n = C.c_size_t(0)
+        self.ctx._chk(lib().sbn_snark_key_comm(self.h, None, C.c_size_t(0), C.byref(n)), "sbn_snark_key_comm")
+        out = (C.c_uint8 * n.value)()
+        self.ctx._chk(lib().sbn_snark_key_comm(self.h, out, n, C.byref(n)), "sbn_snark_key_comm")
+        return bytes(out)
+
+    def sizes(self, kzg=False):
+        """-> (scalars of rnd, bytes of the proof) of snark_prove / snark_prove_kzg"""
+        a, b = C.c_size_t(0), C.c_size_t(0)
+        self.ctx._chk(lib().sbn_snark_sizes(self.h, int(kzg), C.byref(a), C.byref(b)), "sbn_snark_sizes")
+        return a.value, b.value
+
+    def free(self):
+        if self.h:
+            if self.dense is not None:
+                self.dense.free()
+            lib().sbn_snark_key_free(self.ctx.h, self.h)
             self.h = None
 
 
@@ -1253,6 +1338,81 @@ class Context:
         self._chk(lib().sbn_dense_build(self.h, C.c_size_t(num_vars_x), C.c_size_t(num_vars_y), rows, cols, vals, nnz, C.c_size_t(b), C.c_uint32(flags),
                                         C.byref(h)), "sbn_dense_build")
         return Dense(self, h)
+
+    # ---- the witness check and the reference's public surface in one call each (snark.rs:59-158, :290-529)
+    def r1cs_is_sat(self, m, vars_, input_):
+        """R1CSShape::is_sat (sbn_r1cs_is_sat) -> (sat, violated rows, the lowest of them).  vars_: a Table of at most num_vars entries; input_: bytes"""
+        sat, nb, fb = C.c_int(-1), C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().sbn_r1cs_is_sat(self.h, m.h, vars_.h, _ptr(input_) if input_ else None, C.c_size_t(len(input_) // 32), C.byref(sat), C.byref(nb), C.byref(fb)), "sbn_r1cs_is_sat")
+        return bool(sat.value), nb.value, fb.value
+
+    def snark_gens_new(self, num_cons, num_vars, num_inputs, num_nz_entries):
+        """SNARKGens::new on the raw sizes (sbn_snark_gens_new) -> SnarkGens"""
+        h = C.c_void_p()
+        self._chk(lib().sbn_snark_gens_new(self.h, C.c_size_t(num_cons), C.c_size_t(num_vars), C.c_size_t(num_inputs), C.c_size_t(num_nz_entries), C.byref(h)), "sbn_snark_gens_new")
+        return SnarkGens(self, h)
+
+    def snark_encode(self, num_cons, num_vars, num_inputs, mats, gens, flags=0):
+        """Instance::new + SNARK::encode (sbn_snark_encode) -> SnarkKey.  The shape and the columns are raw; mats: A, B, C as for r1cs_upload"""
+        import numpy as np
+        if len(mats) != 3:
+            raise ValueError("snark_encode: mats must hold A, B and C")
+        keep, rows, cols, vals, nnz = [], (C.c_void_p * 3)(), (C.c_void_p * 3)(), (C.c_void_p * 3)(), (C.c_size_t * 3)()
+        for m, (r, c, v) in enumerate(mats):
+            r = np.ascontiguousarray(r, dtype=np.uint32); c = np.ascontiguousarray(c, dtype=np.uint32)
+            v = np.frombuffer(v, dtype=np.uint8) if isinstance(v, (bytes, bytearray)) else np.ascontiguousarray(v, dtype=np.uint8).reshape(-1)
+            n = len(r)
+            if len(c) != n or len(v) != 32 * n:
+                raise ValueError(f"snark_encode: matrix {m}: {n} rows, {len(c)} cols, {len(v)} value bytes")
+            keep += [r, c, v]
+            nnz[m] = n
+            rows[m] = r.ctypes.data if n else None; cols[m] = c.ctypes.data if n else None; vals[m] = v.ctypes.data if n else None
+        h = C.c_void_p()
+        self._chk(lib().sbn_snark_encode(self.h, C.c_size_t(num_cons), C.c_size_t(num_vars), C.c_size_t(num_inputs), rows, cols, vals, nnz, C.c_uint32(flags), gens.h, C.byref(h)),
+                  "sbn_snark_encode")
+        return SnarkKey(self, h)
+
+    def snark_key_from_comm(self, comm):
+        """the verifier's half of a key from R1CSCommitment's bytes (sbn_snark_key_from_comm); malformed bytes raise SbnError"""
+        h = C.c_void_p()
+        self._chk(lib().sbn_snark_key_from_comm(self.h, _ptr(comm) if comm else None, C.c_size_t(len(comm)), C.byref(h)), "sbn_snark_key_from_comm")
+        return SnarkKey(self, h)
+
+    def snark_is_sat(self, key, vars_, input_):
+        """Instance::is_sat (sbn_snark_is_sat) -> (sat, violated rows, the lowest of them)"""
+        sat, nb, fb = C.c_int(-1), C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().sbn_snark_is_sat(self.h, key.h, vars_.h, _ptr(input_) if input_ else None, C.c_size_t(len(input_) // 32), C.byref(sat), C.byref(nb), C.byref(fb)), "sbn_snark_is_sat")
+        return bool(sat.value), nb.value, fb.value
+
+    def snark_prove(self, key, vars_, input_, gens, rnd, tr, check_sat=False, srs=None, derefs_key=None):
+        """SNARK::prove (sbn_snark_prove; with srs: sbn_snark_prove_kzg) -> proof bytes.  vars_: a Table of at most num_vars_padded entries; rnd:
+        key.sizes(kzg)[0] scalars; `tr` (Transcript) moves on.  check_sat: an unsatisfied witness raises SbnUnsat before any proving launch"""
+        kzg = srs is not None
+        n_rnd, n_proof = key.sizes(kzg)
+        if len(rnd) != 32 * n_rnd:
+            raise ValueError(f"snark_prove: rnd holds {len(rnd)} bytes, the shape needs {32 * n_rnd}")
+        proof = (C.c_uint8 * n_proof)()
+        flags = C.c_uint32(SBN_SNARK_CHECK_SAT if check_sat else 0)
+        inp, ni = (_ptr(input_) if input_ else None), C.c_size_t(len(input_) // 32)
+        if kzg:
+            rc = lib().sbn_snark_prove_kzg(self.h, key.h, vars_.h, inp, ni, gens.h, srs.h, derefs_key.h if derefs_key is not None else None, flags, _ptr(rnd), tr.h, proof)
+        else:
+            rc = lib().sbn_snark_prove(self.h, key.h, vars_.h, inp, ni, gens.h, flags, _ptr(rnd), tr.h, proof)
+        if rc == SBN_EUNSAT:
+            raise SbnUnsat(f"sbn_snark_prove: rc={rc}: {lib().sbn_last_error(self.h).decode()}")
+        self._chk(rc, "sbn_snark_prove_kzg" if kzg else "sbn_snark_prove")
+        return bytes(proof)
+
+    def snark_verify(self, key, input_, gens, proof, tr, g2=None, tau_g2=None):
+        """SNARK::verify (sbn_snark_verify; with g2 and tau_g2: sbn_snark_verify_kzg) -> True, or False when the proof is refused; `tr` moves on only
+        when it is accepted.  Misuse (a wrong proof length among it) raises SbnError"""
+        acc = C.c_int(0)
+        inp, ni = (_ptr(input_) if input_ else None), C.c_size_t(len(input_) // 32)
+        if g2 is not None:
+            self._chk(lib().sbn_snark_verify_kzg(self.h, key.h, inp, ni, gens.h, g2.h, tau_g2.h, _ptr(proof), C.c_size_t(len(proof)), tr.h, C.byref(acc)), "sbn_snark_verify_kzg")
+        else:
+            self._chk(lib().sbn_snark_verify(self.h, key.h, inp, ni, gens.h, _ptr(proof), C.c_size_t(len(proof)), tr.h, C.byref(acc)), "sbn_snark_verify")
+        return bool(acc.value)
 
     # ---- profiling
     def prof_enable(self, on=True):

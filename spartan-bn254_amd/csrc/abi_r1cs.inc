@@ -91,6 +91,88 @@ static int r1cs_eval_table_locked(sbn_ctx* c, const sbn_r1cs* m, const uint8_t* 
   return S.done();                                            // eq and x: recycled in stream order
 }
 
+// the launches of sbn_r1cs_evaluate; arguments checked, the caller holds the context's mutex (sbn_snark_prove runs them between its two halves)
+static int r1cs_evaluate_locked(sbn_ctx* c, const sbn_r1cs* m, const uint8_t* rx, size_t ell_x, const uint8_t* ry, size_t ell_y, uint8_t out[96]) {
+  const R1csCsr& rm = m->rowm;
+  const unsigned nblk = (unsigned)std::max<size_t>(1, std::min<size_t>(R1CS_EVAL_BLOCKS, ((size_t)rm.nchunks + 255) / 256));
+  TableScope S(c); sbn_table *ex = nullptr, *ey = nullptr;
+  int rc = eq_evals_locked(c, rx, ell_x, &ex);
+  S.keep(ex);
+  if (rc == SBN_OK) rc = eq_evals_locked(c, ry, ell_y, &ey);
+  S.keep(ey);
+  if (rc == SBN_OK) rc = ensure(c, c->r1cs_ws, r1cs_align((size_t)nblk * 96) + 256);
+  if (rc == SBN_OK) rc = ensure_pin(c, 4096);
+  if (rc == SBN_OK) {
+    uint32_t* partial = (uint32_t*)c->r1cs_ws.p;
+    uint32_t* res = (uint32_t*)((uint8_t*)c->r1cs_ws.p + r1cs_align((size_t)nblk * 96));
+    R1csOut o; o.p[0] = o.p[1] = o.p[2] = nullptr; o.shift = m->log_nc;
+    // sum over the rows of M(row, .) . eq(ry), times eq(rx)[row], per matrix (sparse_mlpoly.rs:113-143), then the 3 x nblk block sums folded
+    LAUNCH(c, "k_r1cs_spmv_eval", k_r1cs_spmv<true>, nblk, 256, (const uint32_t*)rm.row_end, (const uint32_t*)rm.start_row, (const uint32_t*)rm.idx,
+           (const uint32_t*)rm.val, rm.nrows, rm.nnz, rm.nchunks, (const uint32_t*)ey->d, o, (uint32_t*)nullptr, (uint32_t*)nullptr,
+           (const uint32_t*)ex->d, partial);
+    LAUNCH(c, "k_sc_finish", k_sc_finish, 1, 64, (const uint32_t*)partial, (int)nblk, res);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) rc = fail(c, SBN_EHIP, "r1cs_evaluate: %s", hipGetErrorString(le));
+    else {
+      hipError_t e = hipMemcpyAsync(c->pin, res, 96, hipMemcpyDeviceToHost, c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+      if (c->prof) prof_drain(c);
+      if (e != hipSuccess) rc = fail(c, SBN_EHIP, "r1cs_evaluate: %s", hipGetErrorString(e));
+      else memcpy(out, c->pin, 96);
+    }
+  }
+  return rc ? rc : S.done();
+}
+
+// Assignment::pad (snark.rs:149-156, :445-452): a vars table shorter than num_vars as a table of num_vars entries, zeros behind what the caller gave
+// (zero words are the table's zero); a table of full length is used where it lies.  Enqueue only; the copy belongs to the caller's scope
+static int r1cs_pad_vars(sbn_ctx* c, TableScope& T, const sbn_table* vars, size_t nv, const sbn_table** out) {
+  if (vars->len == nv) { *out = vars; return SBN_OK; }
+  sbn_table* p = nullptr; int rc;
+  if ((rc = T.alloc(nv, "padded vars", &p))) return rc;
+  HIPCHK(c, hipMemcpyAsync(p->d, vars->d, vars->len * 32, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync((uint8_t*)p->d + vars->len * 32, 0, (nv - vars->len) * 32, c->stream));
+  *out = p;
+  return SBN_OK;
+}
+// R1CSShape::is_sat (r1cs.rs:105-123) on the device: z by k_r1cs_build_z, Az / Bz / Cz by the multiply, ONE k_r1cs_sat_check pass over them.  The three
+// tables live in the call's scope and are released before it returns.  Arguments checked; the caller holds the context's mutex
+static int r1cs_is_sat_locked(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* vars, const uint8_t* input, size_t num_inputs, int* sat, uint64_t* num_bad, uint64_t* first_bad) {
+  TableScope T(c);
+  const sbn_table* pv = nullptr; sbn_table *z = nullptr, *in = nullptr, *Az = nullptr, *Bz = nullptr, *Cz = nullptr;
+  int rc;
+  if ((rc = ensure(c, c->sc_out, 4096))) return rc;
+  if ((rc = ensure_pin(c, 4096))) return rc;
+  if ((rc = r1cs_pad_vars(c, T, vars, m->nv, &pv))) return rc;
+  if ((rc = T.alloc(2 * m->nv, "r1cs table", &z))) return rc;
+  if (num_inputs) {                                                 // (canonical bytes, not table entries: k_r1cs_build_z converts them)
+    if ((rc = T.alloc(num_inputs, "r1cs inputs", &in))) return rc;
+    HIPCHK(c, hipMemcpyAsync(in->d, input, num_inputs * 32, hipMemcpyHostToDevice, c->stream));
+  }
+  LAUNCH(c, "k_r1cs_build_z", k_r1cs_build_z, stream_grid(2 * m->nv), 256, (const uint32_t*)pv->d, (const uint32_t*)(in ? in->d : nullptr), m->nv, num_inputs, (uint32_t*)z->d);
+  LAUNCHCHK(c);
+  if ((rc = r1cs_multiply_locked(c, m, z, &Az, &Bz, &Cz))) return rc;
+  T.keep(Az); T.keep(Bz); T.keep(Cz);
+  uint32_t* res = (uint32_t*)c->sc_out.p;                           // {violated rows, the lowest of them}
+  HIPCHK(c, hipMemsetAsync(res, 0, 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(res + 1, 0xff, 4, c->stream));
+  LAUNCH(c, "k_r1cs_sat_check", k_r1cs_sat_check, stream_grid(m->nc), 256, (const uint32_t*)Az->d, (const uint32_t*)Bz->d, (const uint32_t*)Cz->d, (uint32_t)m->nc, res);
+  LAUNCHCHK(c);
+  HIPCHK(c, hipMemcpyAsync(c->pin, res, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->prof) prof_drain(c);
+  const uint32_t* h = (const uint32_t*)c->pin;
+  *sat = h[0] == 0 ? 1 : 0; *num_bad = h[0]; *first_bad = h[0] ? h[1] : 0;
+  return T.done();
+}
+// what both witness checks refuse before any launch
+static int r1cs_is_sat_check(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* vars, const uint8_t* input, size_t num_inputs) {
+  if (vars->len > m->nv) return fail(c, SBN_EINVAL, "r1cs is_sat: vars has %zu entries, the instance has num_vars = %zu  [snark.rs:142-144]", vars->len, m->nv);
+  if (num_inputs >= m->nv) return fail(c, SBN_EINVAL, "r1cs is_sat: %zu inputs, num_vars = %zu: z = vars | 1 | inputs has 2 num_vars entries  [r1csproof.rs:253]", num_inputs, m->nv);
+  for (size_t i = 0; i < num_inputs; i++) if (!fr_canonical(input + 32 * i)) return fail(c, SBN_EINVAL, "r1cs is_sat: input[%zu] is not canonical  [scalar.rs:87-95]", i);
+  return SBN_OK;
+}
+
 extern "C" {
 
 void sbn_r1cs_free(sbn_ctx* c, sbn_r1cs* m) {
@@ -194,35 +276,19 @@ int sbn_r1cs_evaluate(sbn_ctx* c, const sbn_r1cs* m, const uint8_t* rx, size_t e
     return fail(c, SBN_EINVAL, "r1cs_evaluate: ell_x=%zu, ell_y=%zu; the shape needs %u and %u (r1cs.rs:126-129)", ell_x, ell_y, m->log_nc, m->log_z);
   std::lock_guard<std::mutex> g(c->mu);
   hipSetDevice(c->device);
-  const R1csCsr& rm = m->rowm;
-  const unsigned nblk = (unsigned)std::max<size_t>(1, std::min<size_t>(R1CS_EVAL_BLOCKS, ((size_t)rm.nchunks + 255) / 256));
-  TableScope S(c); sbn_table *ex = nullptr, *ey = nullptr;
-  int rc = eq_evals_locked(c, rx, ell_x, &ex);
-  S.keep(ex);
-  if (rc == SBN_OK) rc = eq_evals_locked(c, ry, ell_y, &ey);
-  S.keep(ey);
-  if (rc == SBN_OK) rc = ensure(c, c->r1cs_ws, r1cs_align((size_t)nblk * 96) + 256);
-  if (rc == SBN_OK) rc = ensure_pin(c, 4096);
-  if (rc == SBN_OK) {
-    uint32_t* partial = (uint32_t*)c->r1cs_ws.p;
-    uint32_t* res = (uint32_t*)((uint8_t*)c->r1cs_ws.p + r1cs_align((size_t)nblk * 96));
-    R1csOut o; o.p[0] = o.p[1] = o.p[2] = nullptr; o.shift = m->log_nc;
-    // sum over the rows of M(row, .) . eq(ry), times eq(rx)[row], per matrix (sparse_mlpoly.rs:113-143), then the 3 x nblk block sums folded
-    LAUNCH(c, "k_r1cs_spmv_eval", k_r1cs_spmv<true>, nblk, 256, (const uint32_t*)rm.row_end, (const uint32_t*)rm.start_row, (const uint32_t*)rm.idx,
-           (const uint32_t*)rm.val, rm.nrows, rm.nnz, rm.nchunks, (const uint32_t*)ey->d, o, (uint32_t*)nullptr, (uint32_t*)nullptr,
-           (const uint32_t*)ex->d, partial);
-    LAUNCH(c, "k_sc_finish", k_sc_finish, 1, 64, (const uint32_t*)partial, (int)nblk, res);
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) rc = fail(c, SBN_EHIP, "r1cs_evaluate: %s", hipGetErrorString(le));
-    else {
-      hipError_t e = hipMemcpyAsync(c->pin, res, 96, hipMemcpyDeviceToHost, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (c->prof) prof_drain(c);
-      if (e != hipSuccess) rc = fail(c, SBN_EHIP, "r1cs_evaluate: %s", hipGetErrorString(e));
-      else memcpy(out, c->pin, 96);
-    }
-  }
-  return rc ? rc : S.done();
+  return r1cs_evaluate_locked(c, m, rx, ell_x, ry, ell_y, out);
+}
+
+int sbn_r1cs_is_sat(sbn_ctx* c, const sbn_r1cs* m, const sbn_table* vars, const uint8_t* input, size_t num_inputs, int* sat, uint64_t* num_bad, uint64_t* first_bad) {
+  if (!c || !m || !vars || (!input && num_inputs) || !sat || !num_bad || !first_bad) return SBN_EINVAL;
+  int rc;
+  if ((rc = r1cs_is_sat_check(c, m, vars, input, num_inputs))) return rc;
+  std::lock_guard<std::mutex> g(c->mu);
+  hipSetDevice(c->device);
+  int s = 0; uint64_t nb = 0, fb = 0;
+  if ((rc = r1cs_is_sat_locked(c, m, vars, input, num_inputs, &s, &nb, &fb))) return rc;
+  *sat = s; *num_bad = nb; *first_bad = fb;
+  return SBN_OK;
 }
 
 }  // extern "C"

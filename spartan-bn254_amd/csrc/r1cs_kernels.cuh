@@ -150,4 +150,28 @@ __global__ void __launch_bounds__(256) k_r1cs_fix(const uint32_t* __restrict__ k
   }
 }
 
+// R1CSShape::is_sat's last line (r1cs.rs:121-122) over the three product tables: row i is violated when Az[i] Bz[i] - Cz[i] != 0 (mod r).
+// One streaming pass: a lane takes one row at a time (three 32-byte loads, one Montgomery product), the grid is stream_grid's and the loop strides
+// over the rows.  The test is on the canonical value of the difference (fe_is_zero), never on the stored words: a table entry is whatever
+// representative its producer left.  out[0] += the block's violated rows, out[1] = min(out[1], its lowest violated row): ONE atomicAdd and ONE
+// atomicMin a block; the host sets out = {0, 0xffffffff} in front of the launch.  Row numbers are below 2^29 (sbn_r1cs_upload).
+__global__ void __launch_bounds__(256) k_r1cs_sat_check(const uint32_t* __restrict__ Az, const uint32_t* __restrict__ Bz, const uint32_t* __restrict__ Cz, uint32_t nrows,
+                                                        uint32_t* __restrict__ out) {
+  uint32_t bad = 0, first = 0xffffffffu;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nrows; i += gridDim.x * blockDim.x) {
+    const Fr a = fe_gload<FrP>(Az + 8 * (size_t)i), b = fe_gload<FrP>(Bz + 8 * (size_t)i), cc = fe_gload<FrP>(Cz + 8 * (size_t)i);
+    if (!fe_is_zero<FrP>(fe_sub_lazy<FrP>(fe_mul(a, b), fe_norm(cc)))) { bad++; first = min(first, i); }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) { bad += __shfl_down(bad, d); first = min(first, (uint32_t)__shfl_down(first, d)); }
+  __shared__ uint32_t sm[2][4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) { sm[0][wv] = bad; sm[1][wv] = first; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicAdd(out, sm[0][0] + sm[0][1] + sm[0][2] + sm[0][3]);
+    atomicMin(out + 1, min(min(sm[1][0], sm[1][1]), min(sm[1][2], sm[1][3])));
+  }
+}
+
 }  // namespace sbn

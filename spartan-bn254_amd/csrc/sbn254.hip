@@ -43,6 +43,7 @@
 #include "host_strobe.hpp"
 #include "proof_host.hpp"
 #include "sparse_verify_host.hpp"
+#include "snark_host.hpp"
 #include "pairing_host.hpp"
 
 #include <hip/hip_runtime.h>
@@ -88,6 +89,7 @@ using namespace sbn;
 #include "abi_derefs_key.inc"
 #include "abi_sparse_eval.inc"
 #include "abi_sparse_verify.inc"
+#include "abi_snark.inc"
 
 extern "C" {
 
