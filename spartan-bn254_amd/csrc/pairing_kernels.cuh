@@ -156,6 +156,18 @@ __device__ __forceinline__ void f12_inv_fq(uint32_t* S, int dst, int a, int lane
   if (lane < 12) lds_fe_store(S + dst + lane * NL, res);
   __syncthreads();
 }
+// S[0] = S[0]^((q^12 - 1)/r) for a non-zero S[0]: the program PAIR_FINAL_EXP over the slots 0 .. PAIR_SLOTS - 1 (every slot is written before it is read)
+__device__ __forceinline__ void f12_final_exp(uint32_t* S, int lane) {
+#pragma unroll 1
+  for (int pc = 0; pc < SBN_PAIRING_FINAL_EXP_LEN; pc++) {
+    const uint32_t w = PAIR_FINAL_EXP[pc];
+    const int op = w & 3, dst = ((w >> 2) & 15) * F12_WORDS, a = ((w >> 6) & 15) * F12_WORDS, b = ((w >> 10) & 15) * F12_WORDS;
+    if (op == PAIR_OP_MUL) f12_mul(S, dst, a, b, lane);
+    else if (op == PAIR_OP_FROB) f12_frob(S, dst, a, lane);
+    else if (op == PAIR_OP_CONJ) f12_conj(S, dst, a, lane);
+    else f12_inv_fq(S, dst, a, lane);
+  }
+}
 
 // checks: gridDim.x descriptors; square_first[nlines]: the schedule every table was built over; out_is_one: a byte a check; out_gt: 384 bytes a
 // check (arkworks' coefficient order, canonical little-endian) or null
@@ -187,15 +199,7 @@ __global__ void __launch_bounds__(64) k_pairing_products(const PairCheck* __rest
         f12_mul(S, 0, 0, PAIR_LINE_OFF, lane);
       }
     }
-#pragma unroll 1
-    for (int pc = 0; pc < SBN_PAIRING_FINAL_EXP_LEN; pc++) {
-      const uint32_t w = PAIR_FINAL_EXP[pc];
-      const int op = w & 3, dst = ((w >> 2) & 15) * F12_WORDS, a = ((w >> 6) & 15) * F12_WORDS, b = ((w >> 10) & 15) * F12_WORDS;
-      if (op == PAIR_OP_MUL) f12_mul(S, dst, a, b, lane);
-      else if (op == PAIR_OP_FROB) f12_frob(S, dst, a, lane);
-      else if (op == PAIR_OP_CONJ) f12_conj(S, dst, a, lane);
-      else f12_inv_fq(S, dst, a, lane);
-    }
+    f12_final_exp(S, lane);
   }
   bool ok = true;
   if (lane < 12) {

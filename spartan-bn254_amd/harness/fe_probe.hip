@@ -1,23 +1,34 @@
-// fe_probe.hip — a test-only device probe of the shipped field and G1 layer (csrc/fp.cuh, csrc/g1.cuh, included unmodified).
+// fe_probe.hip — a test-only device probe of the shipped field, G1 and Fq12 layer (csrc/fp.cuh, csrc/g1.cuh, csrc/pairing_kernels.cuh,
+// included unmodified).
 //
 // One host entry point runs one primitive over n cases, one thread per case (4 lanes per case for the quad-cooperative addition,
 // one 64-lane wave per case for the wave sum).  Elements cross the boundary as 9 raw signed 32-bit limbs, so a test can feed any
 // lazy representation and read back the exact limbs a primitive returned.  Layout of `in` / `out`: [case][lane][element][9 limbs].
 // Memory-format ops (is_canonical, unpack, pack, store_tab) carry 8 little-endian 32-bit words in limbs 0..7 of an element.
-// Not linked with the product library and not part of include/sbn254.h: tests/test_gpu_fe_bounds.py and
-// tests/test_gpu_column_products.py (ops mulu2, squ2, mac2u) are its only users.
+// The Fq12 ops (f12_*) run one 64-lane block per case over an LDS image of k_pairing_products' own size; a case is ONE row of elements
+// (lanes = 1): the operands' 12 coefficients each, then one element whose limb 0 selects where the operands and the result lie:
+//   f12_mul  a, b, selector -> result, S[a] and S[b] read back after the call.  Selector: 0 dst, a, b distinct slots; 1 dst == a, b in the
+//            line slot PAIR_LINE_OFF (the Miller step); 2 dst == a == b (the squaring; the case's b is not used); 3 dst == b != a;
+//            4 a == b != dst (the final exponentiation's powers by u; the case's b is not used)
+//   f12_frob, f12_conj, f12_inv_fq  a, selector -> result, S[a] read back.  Selector: 0 dst != a; 1 dst == a
+//   f12_final_exp  a -> f12_final_exp of a in slot 0 (no selector)
+// Not linked with the product library and not part of include/sbn254.h: tests/test_gpu_fe_bounds.py,
+// tests/test_gpu_column_products.py (ops mulu2, squ2, mac2u) and tests/test_gpu_f12_bounds.py (nine, negb_11, f12_*) are its only users.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../csrc/g1.cuh"
+#include "../csrc/pairing_kernels.cuh"
 
 using namespace sbn;
 
 namespace {
 
-enum Group { GF, GG, GQ, GW };       // field op (per field), G1 op (Fq), quad addition (4 lanes), wave sum (64 lanes)
+enum Group { GF, GG, GQ, GW, GP };   // field op (per field), G1 op (Fq), quad addition (4 lanes), wave sum (64 lanes), Fq12 op (one block a case)
 enum Fields { FQ = 1, FR = 2, BOTH = 3 };
 struct OpInfo { const char* name; int nin, nout, lanes, group, fields; };
 
@@ -41,6 +52,9 @@ const OpInfo OPS[] = {
     {"dbl_xyzz", 4, 4, 1, GG, FQ},      {"dbl_affine", 2, 4, 1, GG, FQ},    {"to_affine", 4, 2, 1, GG, FQ},
     {"store_load", 4, 4, 1, GG, FQ},    {"add_quad", 8, 4, 4, GQ, FQ},      {"wave_sum", 4, 4, 64, GW, FQ},
     {"mulu2", 4, 2, 1, GF, BOTH},       {"squ2", 2, 2, 1, GF, BOTH},        {"mac2u", 4, 1, 1, GF, BOTH},
+    {"nine", 1, 1, 1, GF, FQ},          {"negb_11", 1, 1, 1, GF, FQ},       {"f12_mul", 25, 36, 1, GP, FQ},
+    {"f12_frob", 13, 24, 1, GP, FQ},    {"f12_conj", 13, 24, 1, GP, FQ},    {"f12_inv_fq", 13, 24, 1, GP, FQ},
+    {"f12_final_exp", 12, 12, 1, GP, FQ},
 };
 constexpr int NOPS = (int)(sizeof(OPS) / sizeof(OPS[0]));
 
@@ -60,7 +74,7 @@ enum : int {
   O_MAYBE_ZERO, O_SUBB_3_1, O_SUBB_4_2, O_SUBB_9_1, O_SUBB_14_1, O_SUBB_2_1, O_SUBB_4_1, O_SUBB_4_3, O_SUBB_6_1, O_NEGB_2, O_NEGB_4,
   O_FIX1, O_FIX2, O_FIX4, O_FIX_TAB, O_COLS12, O_COLS_LAZY2, O_TO_MONT, O_FROM_MONT, O_FROM_ARK, O_ARK_TO_PLAIN, O_FROM_U64, O_INV,
   O_IS_CANON, O_UNPACK, O_PACK, O_STORE_TAB, O_MADD, O_MADD_NEG, O_ADD_INL, O_DBL_XYZZ, O_DBL_AFF, O_TO_AFF, O_STORE_LOAD, O_ADD_QUAD,
-  O_WAVE_SUM, O_MULU2, O_SQU2, O_MAC2U, O_COUNT
+  O_WAVE_SUM, O_MULU2, O_SQU2, O_MAC2U, O_NINE, O_NEGB_11, O_F12_MUL, O_F12_FROB, O_F12_CONJ, O_F12_INV_FQ, O_F12_FINAL_EXP, O_COUNT
 };
 static_assert(O_COUNT == NOPS, "op enum and table differ");
 
@@ -131,6 +145,8 @@ __global__ void field_kernel(int op, const int32_t* __restrict__ in, int32_t* __
     case O_MULU2: { Fe<M> r0, r1; fe_mulu2(a, ld<M>(s, 1), ld<M>(s, 2), ld<M>(s, 3), r0, r1); st(d, 0, r0); st(d, 1, r1); } break;      // (a0, b0, a1, b1)
     case O_SQU2: { Fe<M> r0, r1; fe_squ2(a, ld<M>(s, 1), r0, r1); st(d, 0, r0); st(d, 1, r1); } break;
     case O_MAC2U: st(d, 0, fe_mac2u(a, ld<M>(s, 1), ld<M>(s, 2), ld<M>(s, 3))); break;                                                   // a0 b0 + a1 b1, one reduction
+    case O_NINE: if constexpr (std::is_same<M, FqP>::value) st(d, 0, fe_nine(a)); break;                                                 // pairing_kernels.cuh, Fq only
+    case O_NEGB_11: st(d, 0, fe_negb<M, 11>(a)); break;
     default: break;
   }
 }
@@ -171,6 +187,42 @@ __global__ void wave_kernel(const int32_t* __restrict__ in, int32_t* __restrict_
   st_xyzz(out + t * 4 * NL, wave_sum_all(ld_xyzz(in + t * 4 * NL, 0)));
 }
 
+// the slots (word offsets into S) of the Fq12 ops' selectors: {dst, a, b}
+constexpr int F12_MUL_SELS = 5, F12_UNARY_SELS = 2;
+__device__ const int F12_MUL_SLOTS[F12_MUL_SELS][3] = {{2 * F12_WORDS, 0, F12_WORDS}, {0, 0, PAIR_LINE_OFF}, {0, 0, 0}, {F12_WORDS, 0, F12_WORDS}, {2 * F12_WORDS, 0, 0}};
+int f12_selectors(int op) { return op == O_F12_MUL ? F12_MUL_SELS : op == O_F12_FINAL_EXP ? 0 : F12_UNARY_SELS; }
+// one 64-lane block per case, S as k_pairing_products declares and clears it; the host has checked every selector
+__global__ void __launch_bounds__(64) f12_kernel(int op, const int32_t* __restrict__ in, int32_t* __restrict__ out, int nin, int nout) {
+  __shared__ uint32_t S[PAIR_LDS_WORDS];
+  const int lane = threadIdx.x;
+  const int32_t* s = in + (size_t)blockIdx.x * nin * NL;
+  int32_t* d = out + (size_t)blockIdx.x * nout * NL;
+  for (int i = lane; i < PAIR_LDS_WORDS; i += 64) S[i] = 0;
+  __syncthreads();
+  int dst = 0, a = 0, b = 0;
+  if (op == O_F12_MUL) {
+    const int sel = min(max(s[24 * NL], 0), F12_MUL_SELS - 1);
+    dst = F12_MUL_SLOTS[sel][0]; a = F12_MUL_SLOTS[sel][1]; b = F12_MUL_SLOTS[sel][2];
+  } else if (op != O_F12_FINAL_EXP) {
+    dst = s[12 * NL] == 1 ? 0 : F12_WORDS;
+  }
+  for (int i = lane; i < F12_WORDS; i += 64) {
+    S[a + i] = (uint32_t)s[i];
+    if (op == O_F12_MUL && b != a) S[b + i] = (uint32_t)s[F12_WORDS + i];
+  }
+  __syncthreads();
+  if (op == O_F12_MUL) f12_mul(S, dst, a, b, lane);
+  else if (op == O_F12_FROB) f12_frob(S, dst, a, lane);
+  else if (op == O_F12_CONJ) f12_conj(S, dst, a, lane);
+  else if (op == O_F12_INV_FQ) f12_inv_fq(S, dst, a, lane);
+  else f12_final_exp(S, lane);
+  for (int i = lane; i < F12_WORDS; i += 64) {
+    d[i] = (int32_t)S[dst + i];
+    if (op != O_F12_FINAL_EXP) d[F12_WORDS + i] = (int32_t)S[a + i];
+    if (op == O_F12_MUL) d[2 * F12_WORDS + i] = (int32_t)S[b + i];
+  }
+}
+
 int fail(char* err, size_t errlen, const char* what, hipError_t e) {
   if (err && errlen) snprintf(err, errlen, "%s: %s", what, hipGetErrorString(e));
   return (int)e;
@@ -194,6 +246,12 @@ int fe_probe_run(int op, int field, const int32_t* in, int32_t* out, size_t n, c
   if (err && errlen) err[0] = 0;
   if (fe_probe_shape(op, field, &nin, &nout, &lanes) != 0) return fail(err, errlen, "no such op for this field", hipErrorInvalidValue);
   if (n == 0) return 0;
+  if (OPS[op].group == GP && f12_selectors(op)) {          // a selector picks LDS offsets: refuse one the kernel does not know
+    for (size_t c = 0; c < n; c++) {
+      const int32_t sel = in[(c * nin + (nin - 1)) * NL];
+      if (sel < 0 || sel >= f12_selectors(op)) return fail(err, errlen, "no such placement selector", hipErrorInvalidValue);
+    }
+  }
   const size_t bin = n * lanes * nin * NL * sizeof(int32_t), bout = n * lanes * nout * NL * sizeof(int32_t);
   int32_t *din = nullptr, *dout = nullptr;
   hipError_t e = hipMalloc((void**)&din, bin);
@@ -210,6 +268,7 @@ int fe_probe_run(int op, int field, const int32_t* in, int32_t* out, size_t n, c
     else if (g == GF) field_kernel<FrP><<<blocks, 64>>>(op, din, dout, n, nin, nout);
     else if (g == GG) g1_kernel<<<blocks, 64>>>(op, din, dout, n, nin, nout);
     else if (g == GQ) quad_kernel<<<blocks, 64>>>(din, dout, n);
+    else if (g == GP) f12_kernel<<<(unsigned)n, 64>>>(op, din, dout, nin, nout);
     else wave_kernel<<<(unsigned)n, 64>>>(din, dout);
     what = "launch";
     e = hipGetLastError();
