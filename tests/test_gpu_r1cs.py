@@ -26,7 +26,8 @@ def _val(rng):
 
 def _instance(nc, nv, seed, empty=None):
     """random triplets in random order with duplicates and 0 / 1 / r-1 / uniform values, empty rows (the top quarter of the rows), one
-    row and one column longer than a chunk (and, at the largest shape, longer than one fix-up pass), matrix `empty` with nnz = 0"""
+    row and one column longer than a chunk (and, at the largest shape, longer than one fix-up pass), matrix `empty` with nnz = 0.
+    The seams a random draw cannot reach (the last rows of A and B, the fix-up pass counts, the carry cadence) are pinned in test_gpu_r1cs_seams.py"""
     rng = random.Random(seed)
     nz = 2 * nv
     live = max(1, (3 * nc) // 4)
