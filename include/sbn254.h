@@ -802,7 +802,8 @@ int sbn_r1cs_is_sat(sbn_ctx* ctx, const sbn_r1cs* inst, const sbn_table* vars, c
                     int* sat, uint64_t* num_bad, uint64_t* first_bad);
 
 /* ---- the reference's public surface in one call each: SNARKGens::new, Instance::new + SNARK::encode, Instance::is_sat, SNARK::prove, SNARK::verify
- *      (snark.rs:59-158, :290-529), both builds.  NIZK is not here: its transcript absorbs R1CSShape::get_digest, zlib over bincode (r1cs.rs:97-101). ----
+ *      (snark.rs:59-158, :290-529), both builds.  NIZK mode (snark.rs:162-287) follows below as sbn_nizk_*: its transcript absorbs R1CSShape::get_digest
+ *      (zlib over bincode, r1cs.rs:97-101), which arrives as bytes — the caller's inst.digest — and is never computed here. ----
  * Shapes are RAW: num_cons, num_vars, num_inputs as the circuit has them, columns as the circuit numbers them (vars | 1 | inputs).  Instance::new's
  * rules are applied inside (snark.rs:74-110): num_vars_padded = npo2(max(num_vars, num_inputs + 1)), num_cons_padded = npo2(max(num_cons, 2)), a column
  * >= num_vars moves to col + num_vars_padded - num_vars; nx = log2 num_cons_padded, ny = log2(2 num_vars_padded).  Entry order is kept.
@@ -872,6 +873,50 @@ int sbn_snark_prove_kzg(sbn_ctx* ctx, const sbn_snark_key* key, const sbn_table*
                         uint8_t* out_proof);
 int sbn_snark_verify_kzg(sbn_ctx* ctx, const sbn_snark_key* key, const uint8_t* input, size_t num_inputs, const sbn_snark_gens* gens,
                          const sbn_g2_lines* g2, const sbn_g2_lines* tau_g2, const uint8_t* proof, size_t proof_len, sbn_transcript* tr, int* accepted);
+
+/* ---- NIZK mode in one call each: NIZKGens::new, Instance::new, Instance::is_sat, NIZK::prove, NIZK::verify (snark.rs:162-287).  No preprocessing: no
+ *      dense representation, no commitment, and the verifier holds the matrices.  A prove is the R1CS proof alone.  Shapes are RAW, as for sbn_snark_*. ----
+ * The digest: NIZK::prove and ::verify append inst.digest under "R1CSShapeDigest" (snark.rs:213, :253) and do nothing else with it.  It is an opaque byte
+ *   string that Instance::new computed once (snark.rs:125-127); the caller passes those bytes to sbn_nizk_instance_new, which keeps a copy.  Any length
+ *   up to 2^32 - 1 is taken, NULL with length 0 too; the library does not compute, check or interpret them.  Prover and verifier must hold the same bytes.
+ *
+ * sbn_nizk_gens_new: NIZKGens::new (snark.rs:169-180) = R1CSGens::new(b"gens_r1cs_sat", num_cons, num_vars_padded): the first three sets of
+ *   sbn_snark_gens_new (gens_pc, gens_3, gens_4) under the same label, as a sbn_snark_gens whose three eval sets are absent: sbn_snark_gens_get(g, 3..5)
+ *   is NULL, sbn_snark_encode / _prove / _verify refuse it (SBN_EINVAL), sbn_snark_gens_free frees it.  A whole SNARK bundle of the right shape is taken
+ *   by the NIZK calls and gives the same bytes.
+ * sbn_nizk_instance_new: Instance::new (snark.rs:66-128) on a raw circuit, as sbn_snark_encode takes one: the conversion on the host with its three errors
+ *   in the reference's order (a row >= num_cons, a col >= num_vars + 1 + num_inputs, a value >= r: SBN_EINVAL, the text names the entry), then
+ *   sbn_r1cs_upload.  No sbn_dense_build, no commitment.  num_vars_padded < 2 is SBN_EINVAL as in encode; an instance whose matrices hold one entry or
+ *   none is valid (encode's N < 2 rule comes from the product circuits, which NIZK does not have).  flags: SBN_SCALARS_MONT only.
+ *   sbn_nizk_instance_r1cs   the matrices, owned by the handle: what sbn_r1cs_evaluate takes.  NULL for NULL.
+ *   sbn_nizk_sizes           rnd_scalars = sbn_r1cs_proof_sizes' count at the padded shape; proof_bytes = its proof length + 32 (nx + ny).
+ *        proof = r1cs_sat_proof (sbn_r1cs_proof_prove's out_proof) | rx [nx x 32] | ry [ny x 32], canonical: the declaration order of snark.rs:191-194.
+ * sbn_nizk_is_sat: sbn_r1cs_is_sat on the handle's matrices; num_inputs must be the instance's (snark.rs:145).
+ * sbn_nizk_prove: NIZK::prove (snark.rs:202-240) under one hold of the mutex: protocol-name "Spartan NIZK proof", "R1CSShapeDigest" <- the digest,
+ *   Assignment::pad on the device, R1CSProof::prove (sbn_r1cs_proof_prove's body); out_proof = its proof | the rx, ry it returned.  rnd: R1CSProof::prove's
+ *   draws (RandomTape b"proof", snark.rs:210), drawn by the caller.  vars: at most num_vars_padded entries; a table at raw and at padded length give the
+ *   same bytes.  flags: SBN_SNARK_CHECK_SAT as in sbn_snark_prove: an unsatisfied witness is SBN_EUNSAT before any proving launch.  `tr` moves on and
+ *   out_proof is written only behind SBN_OK.  SBN_EINVAL before any launch: a NULL pointer, unknown flags, a wrong num_inputs, vars longer than
+ *   num_vars_padded, a bundle of another shape, a scalar of input or rnd >= r.
+ * sbn_nizk_verify: NIZK::verify (snark.rs:243-286): the two prefix lines; A, B, C at the CLAIMED (rx, ry) over the handle's own matrices (sbn_r1cs_evaluate's
+ *   body); R1CSProof::verify with those three values (sbn_r1cs_proof_verify's body); then the (rx, ry) it derived against the claimed ones.  That last
+ *   comparison is assert_eq! in the reference (snark.rs:280-281), a panic; a proof is the prover's data, so here a mismatch is a refusal: SBN_OK with
+ *   *accepted = 0.  So are a claimed scalar >= r and a refused R1CS proof.  SBN_EINVAL reports misuse only, before any launch and with `tr` and
+ *   *accepted unchanged: a NULL pointer, a wrong proof_len or num_inputs, an input >= r, a bundle of another shape.  `tr` moves on only behind
+ *   *accepted == 1 and then ends where sbn_nizk_prove's transcript ended. */
+typedef struct sbn_nizk_inst sbn_nizk_inst;
+int sbn_nizk_gens_new(sbn_ctx* ctx, size_t num_cons, size_t num_vars, size_t num_inputs, sbn_snark_gens** out);
+int sbn_nizk_instance_new(sbn_ctx* ctx, size_t num_cons, size_t num_vars, size_t num_inputs, const uint32_t* const* rows, const uint32_t* const* cols,
+                          const uint8_t* const* vals, const size_t* nnz, uint32_t flags, const uint8_t* digest, size_t digest_len, sbn_nizk_inst** out);
+void sbn_nizk_instance_free(sbn_ctx* ctx, sbn_nizk_inst* inst);
+const sbn_r1cs* sbn_nizk_instance_r1cs(const sbn_nizk_inst* inst);
+int sbn_nizk_sizes(const sbn_nizk_inst* inst, size_t* rnd_scalars, size_t* proof_bytes);
+int sbn_nizk_is_sat(sbn_ctx* ctx, const sbn_nizk_inst* inst, const sbn_table* vars, const uint8_t* input, size_t num_inputs,
+                    int* sat, uint64_t* num_bad, uint64_t* first_bad);
+int sbn_nizk_prove(sbn_ctx* ctx, const sbn_nizk_inst* inst, const sbn_table* vars, const uint8_t* input, size_t num_inputs, const sbn_snark_gens* gens,
+                   uint32_t flags, const uint8_t* rnd, sbn_transcript* tr, uint8_t* out_proof);
+int sbn_nizk_verify(sbn_ctx* ctx, const sbn_nizk_inst* inst, const uint8_t* input, size_t num_inputs, const sbn_snark_gens* gens,
+                    const uint8_t* proof, size_t proof_len, sbn_transcript* tr, int* accepted);
 
 /* ---- per-kernel timing (HIP events on the context's stream), for bench.py's roofline line ---- */
 int sbn_prof_enable(sbn_ctx* ctx, int on);

@@ -59,6 +59,7 @@ use crate::unipoly::{CompressedUniPoly, UniPoly};
 #[repr(C)] pub struct sbn_transcript { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_snark_gens { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_snark_key { _p: [u8; 0] }
+#[repr(C)] pub struct sbn_nizk_inst { _p: [u8; 0] }
 
 pub const SBN_OK: c_int = 0;
 pub const SBN_SCALARS_MONT: u32 = 1;
@@ -242,6 +243,14 @@ extern "C" {
     pub fn sbn_snark_verify(ctx: *mut sbn_ctx, key: *const sbn_snark_key, input: *const u8, num_inputs: usize, gens: *const sbn_snark_gens, proof: *const u8, proof_len: usize, tr: *mut sbn_transcript, accepted: *mut c_int) -> c_int;
     pub fn sbn_snark_prove_kzg(ctx: *mut sbn_ctx, key: *const sbn_snark_key, vars: *const sbn_table, input: *const u8, num_inputs: usize, gens: *const sbn_snark_gens, srs: *const sbn_bases, derefs_key: *const sbn_derefs_key, flags: u32, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8) -> c_int;
     pub fn sbn_snark_verify_kzg(ctx: *mut sbn_ctx, key: *const sbn_snark_key, input: *const u8, num_inputs: usize, gens: *const sbn_snark_gens, g2: *const sbn_g2_lines, tau_g2: *const sbn_g2_lines, proof: *const u8, proof_len: usize, tr: *mut sbn_transcript, accepted: *mut c_int) -> c_int;
+    pub fn sbn_nizk_gens_new(ctx: *mut sbn_ctx, num_cons: usize, num_vars: usize, num_inputs: usize, out: *mut *mut sbn_snark_gens) -> c_int;
+    pub fn sbn_nizk_instance_new(ctx: *mut sbn_ctx, num_cons: usize, num_vars: usize, num_inputs: usize, rows: *const *const u32, cols: *const *const u32, vals: *const *const u8, nnz: *const usize, flags: u32, digest: *const u8, digest_len: usize, out: *mut *mut sbn_nizk_inst) -> c_int;
+    pub fn sbn_nizk_instance_free(ctx: *mut sbn_ctx, inst: *mut sbn_nizk_inst);
+    pub fn sbn_nizk_instance_r1cs(inst: *const sbn_nizk_inst) -> *const sbn_r1cs;
+    pub fn sbn_nizk_sizes(inst: *const sbn_nizk_inst, rnd_scalars: *mut usize, proof_bytes: *mut usize) -> c_int;
+    pub fn sbn_nizk_is_sat(ctx: *mut sbn_ctx, inst: *const sbn_nizk_inst, vars: *const sbn_table, input: *const u8, num_inputs: usize, sat: *mut c_int, num_bad: *mut u64, first_bad: *mut u64) -> c_int;
+    pub fn sbn_nizk_prove(ctx: *mut sbn_ctx, inst: *const sbn_nizk_inst, vars: *const sbn_table, input: *const u8, num_inputs: usize, gens: *const sbn_snark_gens, flags: u32, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8) -> c_int;
+    pub fn sbn_nizk_verify(ctx: *mut sbn_ctx, inst: *const sbn_nizk_inst, input: *const u8, num_inputs: usize, gens: *const sbn_snark_gens, proof: *const u8, proof_len: usize, tr: *mut sbn_transcript, accepted: *mut c_int) -> c_int;
     pub fn sbn_prof_enable(ctx: *mut sbn_ctx, on: c_int) -> c_int;
     pub fn sbn_prof_reset(ctx: *mut sbn_ctx) -> c_int;
     pub fn sbn_prof_count(ctx: *mut sbn_ctx) -> c_int;

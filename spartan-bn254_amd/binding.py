@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "sbn_dense_audit_ts_dev", "sbn_dense_comb_ops", "sbn_dense_comb_mem",
     "sbn_r1cs_is_sat", "sbn_snark_gens_new", "sbn_snark_gens_get", "sbn_snark_gens_free", "sbn_snark_encode", "sbn_snark_key_from_comm", "sbn_snark_key_comm", "sbn_snark_key_dense",
     "sbn_snark_key_free", "sbn_snark_sizes", "sbn_snark_is_sat", "sbn_snark_prove", "sbn_snark_verify", "sbn_snark_prove_kzg", "sbn_snark_verify_kzg",
+    "sbn_nizk_gens_new", "sbn_nizk_instance_new", "sbn_nizk_instance_free", "sbn_nizk_instance_r1cs", "sbn_nizk_sizes", "sbn_nizk_is_sat", "sbn_nizk_prove", "sbn_nizk_verify",
 ]
 SBN_EUNSAT = -5
 SBN_SNARK_CHECK_SAT = 1
@@ -142,6 +143,14 @@ def lib():
         L.sbn_snark_verify.argtypes = [C.c_void_p] * 3 + [C.c_size_t] + [C.c_void_p] * 2 + [C.c_size_t] + [C.c_void_p] * 2
         L.sbn_snark_prove_kzg.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 3
         L.sbn_snark_verify_kzg.argtypes = [C.c_void_p] * 3 + [C.c_size_t] + [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 2
+        L.sbn_nizk_gens_new.argtypes = [C.c_void_p] + [C.c_size_t] * 3 + [C.c_void_p]
+        L.sbn_nizk_instance_new.argtypes = [C.c_void_p] + [C.c_size_t] * 3 + [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sbn_nizk_instance_free.restype = None; L.sbn_nizk_instance_free.argtypes = [C.c_void_p] * 2
+        L.sbn_nizk_instance_r1cs.restype = C.c_void_p; L.sbn_nizk_instance_r1cs.argtypes = [C.c_void_p]
+        L.sbn_nizk_sizes.argtypes = [C.c_void_p] * 3
+        L.sbn_nizk_is_sat.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 3
+        L.sbn_nizk_prove.argtypes = [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
+        L.sbn_nizk_verify.argtypes = [C.c_void_p] * 3 + [C.c_size_t] + [C.c_void_p] * 2 + [C.c_size_t] + [C.c_void_p] * 2
         _LIB = L
     return _LIB
 
@@ -186,6 +195,24 @@ def harness_prove(ctx, log_ops, log_mem, log_cons, stateful=True, lookup_bytes_s
     stages = {n: ms[i] for i, n in enumerate(HARNESS_STAGES)}
     rounds = {"sumcheck_rounds_ops": prm.rounds_out[0], "sumcheck_rounds_mem": prm.rounds_out[1], "bullet_rounds": prm.rounds_out[2], "layers": prm.rounds_out[3]}
     return stages, bytes(dig), (bytes(tr[:tl.value]) if trace_cap else b""), rounds
+
+
+def _three_mats(what, mats):
+    """A, B, C as (rows, cols, vals) triplets -> (the arrays to keep alive, rows[3], cols[3], vals[3], nnz[3]) as the C ABI takes a circuit"""
+    import numpy as np
+    if len(mats) != 3:
+        raise ValueError(f"{what}: mats must hold A, B and C")
+    keep, rows, cols, vals, nnz = [], (C.c_void_p * 3)(), (C.c_void_p * 3)(), (C.c_void_p * 3)(), (C.c_size_t * 3)()
+    for m, (r, c, v) in enumerate(mats):
+        r = np.ascontiguousarray(r, dtype=np.uint32); c = np.ascontiguousarray(c, dtype=np.uint32)
+        v = np.frombuffer(v, dtype=np.uint8) if isinstance(v, (bytes, bytearray)) else np.ascontiguousarray(v, dtype=np.uint8).reshape(-1)
+        n = len(r)
+        if len(c) != n or len(v) != 32 * n:
+            raise ValueError(f"{what}: matrix {m}: {n} rows, {len(c)} cols, {len(v)} value bytes")
+        keep += [r, c, v]
+        nnz[m] = n
+        rows[m] = r.ctypes.data if n else None; cols[m] = c.ctypes.data if n else None; vals[m] = v.ctypes.data if n else None
+    return keep, rows, cols, vals, nnz
 
 
 def _ptr(x):
@@ -503,18 +530,21 @@ class _BorrowedDense(Dense):
 
 
 class SnarkGens:
-    """SNARKGens (snark.rs:290-328) resident on the device (sbn_snark_gens_new): pc, g3, g4, ops, mem, derefs are Bases that belong to the bundle"""
+    """SNARKGens (snark.rs:290-328) resident on the device (sbn_snark_gens_new): pc, g3, g4, ops, mem, derefs are Bases that belong to the bundle.
+    A bundle from nizk_gens_new (NIZKGens, snark.rs:162-181) holds pc, g3 and g4 alone: ops, mem and derefs are None"""
     KINDS = ("pc", "g3", "g4", "ops", "mem", "derefs")
 
     def __init__(self, ctx, handle):
         self.ctx, self.h = ctx, handle
         for i, k in enumerate(self.KINDS):
-            setattr(self, k, _BorrowedBases(ctx, C.c_void_p(lib().sbn_snark_gens_get(handle, i))))
+            b = lib().sbn_snark_gens_get(handle, i)
+            setattr(self, k, _BorrowedBases(ctx, C.c_void_p(b)) if b else None)
 
     def free(self):
         if self.h:
             for k in self.KINDS:
-                getattr(self, k).h = None
+                if getattr(self, k) is not None:
+                    getattr(self, k).h = None
             lib().sbn_snark_gens_free(self.ctx.h, self.h)
             self.h = None
 
@@ -546,6 +576,35 @@ class SnarkKey:
             if self.dense is not None:
                 self.dense.free()
             lib().sbn_snark_key_free(self.ctx.h, self.h)
+            self.h = None
+
+
+class _BorrowedR1cs(R1cs):
+    """the matrices a NizkInst owns: never passed to sbn_r1cs_free"""
+
+    def free(self):
+        self.h = None
+
+
+class NizkInst:
+    """Instance (snark.rs:59-128) for NIZK mode, resident (sbn_nizk_instance_new): the padded matrices and the caller's digest bytes.  r1cs is the
+    R1cs that belongs to the handle (what r1cs_evaluate takes)"""
+
+    def __init__(self, ctx, handle, num_cons, num_vars, num_inputs):
+        self.ctx, self.h, self.raw = ctx, handle, (num_cons, num_vars, num_inputs)
+        npo2 = lambda n: 1 << max(n - 1, 0).bit_length()             # noqa: E731 (snark.rs:74-90)
+        self.r1cs = _BorrowedR1cs(ctx, C.c_void_p(lib().sbn_nizk_instance_r1cs(handle)), npo2(max(num_cons, 2)), npo2(max(num_vars, num_inputs + 1)))
+
+    def sizes(self):
+        """-> (scalars of rnd, bytes of the proof) of nizk_prove"""
+        a, b = C.c_size_t(0), C.c_size_t(0)
+        self.ctx._chk(lib().sbn_nizk_sizes(self.h, C.byref(a), C.byref(b)), "sbn_nizk_sizes")
+        return a.value, b.value
+
+    def free(self):
+        if self.h:
+            self.r1cs.free()
+            lib().sbn_nizk_instance_free(self.ctx.h, self.h)
             self.h = None
 
 
@@ -1354,19 +1413,7 @@ class Context:
 
     def snark_encode(self, num_cons, num_vars, num_inputs, mats, gens, flags=0):
         """Instance::new + SNARK::encode (sbn_snark_encode) -> SnarkKey.  The shape and the columns are raw; mats: A, B, C as for r1cs_upload"""
-        import numpy as np
-        if len(mats) != 3:
-            raise ValueError("snark_encode: mats must hold A, B and C")
-        keep, rows, cols, vals, nnz = [], (C.c_void_p * 3)(), (C.c_void_p * 3)(), (C.c_void_p * 3)(), (C.c_size_t * 3)()
-        for m, (r, c, v) in enumerate(mats):
-            r = np.ascontiguousarray(r, dtype=np.uint32); c = np.ascontiguousarray(c, dtype=np.uint32)
-            v = np.frombuffer(v, dtype=np.uint8) if isinstance(v, (bytes, bytearray)) else np.ascontiguousarray(v, dtype=np.uint8).reshape(-1)
-            n = len(r)
-            if len(c) != n or len(v) != 32 * n:
-                raise ValueError(f"snark_encode: matrix {m}: {n} rows, {len(c)} cols, {len(v)} value bytes")
-            keep += [r, c, v]
-            nnz[m] = n
-            rows[m] = r.ctypes.data if n else None; cols[m] = c.ctypes.data if n else None; vals[m] = v.ctypes.data if n else None
+        keep, rows, cols, vals, nnz = _three_mats("snark_encode", mats)      # noqa: F841 (keep: the arrays live until the call returns)
         h = C.c_void_p()
         self._chk(lib().sbn_snark_encode(self.h, C.c_size_t(num_cons), C.c_size_t(num_vars), C.c_size_t(num_inputs), rows, cols, vals, nnz, C.c_uint32(flags), gens.h, C.byref(h)),
                   "sbn_snark_encode")
@@ -1412,6 +1459,50 @@ class Context:
             self._chk(lib().sbn_snark_verify_kzg(self.h, key.h, inp, ni, gens.h, g2.h, tau_g2.h, _ptr(proof), C.c_size_t(len(proof)), tr.h, C.byref(acc)), "sbn_snark_verify_kzg")
         else:
             self._chk(lib().sbn_snark_verify(self.h, key.h, inp, ni, gens.h, _ptr(proof), C.c_size_t(len(proof)), tr.h, C.byref(acc)), "sbn_snark_verify")
+        return bool(acc.value)
+
+    # ---- NIZK mode in one call each (snark.rs:162-287): no encode, the verifier holds the matrices
+    def nizk_gens_new(self, num_cons, num_vars, num_inputs):
+        """NIZKGens::new on the raw sizes (sbn_nizk_gens_new) -> SnarkGens with pc, g3, g4 alone"""
+        h = C.c_void_p()
+        self._chk(lib().sbn_nizk_gens_new(self.h, C.c_size_t(num_cons), C.c_size_t(num_vars), C.c_size_t(num_inputs), C.byref(h)), "sbn_nizk_gens_new")
+        return SnarkGens(self, h)
+
+    def nizk_instance_new(self, num_cons, num_vars, num_inputs, mats, digest=b"", flags=0):
+        """Instance::new (sbn_nizk_instance_new) -> NizkInst.  The shape and the columns are raw; mats: A, B, C as for r1cs_upload; digest: the bytes of
+        the reference's inst.digest, absorbed as they are"""
+        keep, rows, cols, vals, nnz = _three_mats("nizk_instance_new", mats)      # noqa: F841 (keep: the arrays live until the call returns)
+        h = C.c_void_p()
+        self._chk(lib().sbn_nizk_instance_new(self.h, C.c_size_t(num_cons), C.c_size_t(num_vars), C.c_size_t(num_inputs), rows, cols, vals, nnz, C.c_uint32(flags),
+                                              _ptr(digest) if digest else None, C.c_size_t(len(digest)), C.byref(h)), "sbn_nizk_instance_new")
+        return NizkInst(self, h, num_cons, num_vars, num_inputs)
+
+    def nizk_is_sat(self, inst, vars_, input_):
+        """Instance::is_sat (sbn_nizk_is_sat) -> (sat, violated rows, the lowest of them)"""
+        sat, nb, fb = C.c_int(-1), C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().sbn_nizk_is_sat(self.h, inst.h, vars_.h, _ptr(input_) if input_ else None, C.c_size_t(len(input_) // 32), C.byref(sat), C.byref(nb), C.byref(fb)), "sbn_nizk_is_sat")
+        return bool(sat.value), nb.value, fb.value
+
+    def nizk_prove(self, inst, vars_, input_, gens, rnd, tr, check_sat=False):
+        """NIZK::prove (sbn_nizk_prove) -> proof bytes: the R1CS proof | rx | ry.  vars_: a Table of at most num_vars_padded entries; rnd: inst.sizes()[0]
+        scalars; `tr` (Transcript) moves on.  check_sat: an unsatisfied witness raises SbnUnsat before any proving launch"""
+        n_rnd, n_proof = inst.sizes()
+        if len(rnd) != 32 * n_rnd:
+            raise ValueError(f"nizk_prove: rnd holds {len(rnd)} bytes, the shape needs {32 * n_rnd}")
+        proof = (C.c_uint8 * n_proof)()
+        rc = lib().sbn_nizk_prove(self.h, inst.h, vars_.h, _ptr(input_) if input_ else None, C.c_size_t(len(input_) // 32), gens.h,
+                                  C.c_uint32(SBN_SNARK_CHECK_SAT if check_sat else 0), _ptr(rnd), tr.h, proof)
+        if rc == SBN_EUNSAT:
+            raise SbnUnsat(f"sbn_nizk_prove: rc={rc}: {lib().sbn_last_error(self.h).decode()}")
+        self._chk(rc, "sbn_nizk_prove")
+        return bytes(proof)
+
+    def nizk_verify(self, inst, input_, gens, proof, tr):
+        """NIZK::verify (sbn_nizk_verify) -> True, or False when the proof is refused (a derived (rx, ry) that differs from the claimed one among it); `tr`
+        moves on only when it is accepted.  Misuse (a wrong proof length among it) raises SbnError"""
+        acc = C.c_int(0)
+        self._chk(lib().sbn_nizk_verify(self.h, inst.h, _ptr(input_) if input_ else None, C.c_size_t(len(input_) // 32), gens.h, _ptr(proof), C.c_size_t(len(proof)), tr.h,
+                                        C.byref(acc)), "sbn_nizk_verify")
         return bool(acc.value)
 
     # ---- profiling

@@ -8,7 +8,8 @@
 //            sparse_eval_locked — rnd is ONE tape, the sat half's draws, then the eval half's
 //   verify   the prefix, r1cs_verify_locked with the proof's own inst_evals, sparse_verify_locked at the (rx, ry) it returned (skipped behind a refusal);
 //            the KZG build's pairing check follows behind the mutex' release, as in sbn_sparse_eval_verify_kzg
-// A key from sbn_snark_key_from_comm holds the verifier's half only: the shape and the two commitments.  Included by sbn254.hip.
+// A key from sbn_snark_key_from_comm holds the verifier's half only: the shape and the two commitments.  snark_gens_make and snark_convert serve NIZK mode
+// too (abi_nizk.inc).  Included by sbn254.hip.
 
 struct sbn_snark_gens {
   sbn_bases* g[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // pc, g3, g4, ops, mem, derefs
@@ -55,6 +56,44 @@ static int snark_gens_check(sbn_ctx* c, const char* pfx, const sbn_snark_gens* g
   return SBN_OK;
 }
 
+// the first `nsets` of SNARKGens::new's six sets: 6 is the whole bundle, 3 is R1CSGens::new alone, which is all NIZKGens::new makes (snark.rs:169-180);
+// the eval sets of such a bundle stay null and N is not looked at
+static int snark_gens_make(sbn_ctx* c, const char* pfx, const sbn_host::snark::Shape& sh, size_t N, int nsets, sbn_snark_gens** out) {
+  namespace sn = sbn_host::snark;
+  const size_t ell = sn::log2u(sh.nv), e_o = sn::ell_ops(N), e_m = std::max(sh.nx, sh.ny) + 1, e_d = sn::log2u(N) + sn::log2u(sn::npo2(2 * (size_t)sn::BATCH));
+  if ((nsets == 6 ? std::max(std::max(ell, e_o), std::max(e_m, e_d)) : ell) > 2 * (size_t)PE_SIDE_MAX) return fail(c, SBN_EINVAL, "%s: the shape is outside what the openings take", pfx);
+  auto R = [](size_t e) { return (size_t)1 << (e - e / 2); };                   // 2^right of compute_factored_lens
+  static const char SAT[] = "gens_r1cs_sat", EVAL[] = "gens_r1cs_eval";          // snark.rs:321-322
+  const struct { size_t n; const char* label; } want[6] = {{R(ell) + 1, SAT}, {3, SAT}, {4, SAT},      // R1CSGens::new, r1csproof.rs:177-182 (gens_1 is gens_pc's)
+                                                           {R(e_o) + 1, EVAL}, {R(e_m) + 1, EVAL}, {R(e_d) + 1, EVAL}};      // sparse_mlpoly_full.rs:612-630
+  sbn_snark_gens* g = new sbn_snark_gens();
+  g->nc = sh.nc; g->nv = sh.nv; g->N = nsets == 6 ? N : 0;
+  for (int k = 0; k < nsets; k++) {
+    const int rc = sbn_gens_new(c, want[k].n, (const uint8_t*)want[k].label, strlen(want[k].label), nullptr, &g->g[k]);
+    if (rc) { for (int j = 0; j < k; j++) sbn_bases_free(c, g->g[j]); delete g; return rc; }
+  }
+  *out = g;
+  return SBN_OK;
+}
+
+// Instance::new's convert (snark.rs:92-110) on the three raw matrices: ncols[m] <- the columns of the padded instance, held by store[m]
+static int snark_convert(sbn_ctx* c, const char* pfx, const sbn_host::snark::Shape& sh, const uint32_t* const* rows, const uint32_t* const* cols, const uint8_t* const* vals,
+                         const size_t* nnz, std::vector<uint32_t> store[3], const uint32_t* ncols[3]) {
+  namespace sn = sbn_host::snark;
+  const size_t live = sh.num_vars + 1 + sh.num_inputs;
+  for (int m = 0; m < 3; m++) {
+    if (nnz[m] && (!rows[m] || !cols[m] || !vals[m])) return fail(c, SBN_EINVAL, "%s: matrix %d has %zu entries and a NULL array", pfx, m, nnz[m]);
+    store[m].resize(std::max<size_t>(nnz[m], 1));
+    size_t bad = 0;
+    const int e = sn::convert_cols(sh, rows[m], cols[m], vals[m], nnz[m], store[m].data(), &bad);
+    if (e == sn::CONV_ROW) return fail(c, SBN_EINVAL, "%s: matrix %d entry %zu: row %u >= num_cons %zu  [snark.rs:95 InvalidIndex]", pfx, m, bad, rows[m][bad], sh.num_cons);
+    if (e == sn::CONV_COL) return fail(c, SBN_EINVAL, "%s: matrix %d entry %zu: col %u >= num_vars + 1 + num_inputs = %zu  [snark.rs:98 InvalidIndex]", pfx, m, bad, cols[m][bad], live);
+    if (e == sn::CONV_VAL) return fail(c, SBN_EINVAL, "%s: matrix %d entry %zu: value >= r  [snark.rs:101 InvalidScalar]", pfx, m, bad);
+    ncols[m] = store[m].data();
+  }
+  return SBN_OK;
+}
+
 extern "C" {
 
 int sbn_snark_gens_new(sbn_ctx* c, size_t num_cons, size_t num_vars, size_t num_inputs, size_t num_nz_entries, sbn_snark_gens** out) {
@@ -64,21 +103,7 @@ int sbn_snark_gens_new(sbn_ctx* c, size_t num_cons, size_t num_vars, size_t num_
   sn::Shape sh;
   if (!sn::shape_make(num_cons, num_vars, num_inputs, &sh) || num_nz_entries > ((size_t)1 << 31))
     return fail(c, SBN_EINVAL, "snark gens: shape %zu x %zu, %zu inputs, %zu non-zeros is too large", num_cons, num_vars, num_inputs, num_nz_entries);
-  const size_t N = sn::npo2(num_nz_entries);
-  const size_t ell = sn::log2u(sh.nv), e_o = sn::ell_ops(N), e_m = std::max(sh.nx, sh.ny) + 1, e_d = sn::log2u(N) + sn::log2u(sn::npo2(2 * (size_t)sn::BATCH));
-  if (std::max(std::max(ell, e_o), std::max(e_m, e_d)) > 2 * (size_t)PE_SIDE_MAX) return fail(c, SBN_EINVAL, "snark gens: the shape is outside what the openings take");
-  auto R = [](size_t e) { return (size_t)1 << (e - e / 2); };                   // 2^right of compute_factored_lens
-  static const char SAT[] = "gens_r1cs_sat", EVAL[] = "gens_r1cs_eval";          // snark.rs:321-322
-  const struct { size_t n; const char* label; } want[6] = {{R(ell) + 1, SAT}, {3, SAT}, {4, SAT},      // R1CSGens::new, r1csproof.rs:177-182 (gens_1 is gens_pc's)
-                                                           {R(e_o) + 1, EVAL}, {R(e_m) + 1, EVAL}, {R(e_d) + 1, EVAL}};      // sparse_mlpoly_full.rs:612-630
-  sbn_snark_gens* g = new sbn_snark_gens();
-  g->nc = sh.nc; g->nv = sh.nv; g->N = N;
-  for (int k = 0; k < 6; k++) {
-    const int rc = sbn_gens_new(c, want[k].n, (const uint8_t*)want[k].label, strlen(want[k].label), nullptr, &g->g[k]);
-    if (rc) { for (int j = 0; j < k; j++) sbn_bases_free(c, g->g[j]); delete g; return rc; }
-  }
-  *out = g;
-  return SBN_OK;
+  return snark_gens_make(c, "snark gens", sh, sn::npo2(num_nz_entries), 6, out);
 }
 const sbn_bases* sbn_snark_gens_get(const sbn_snark_gens* g, int which) { return (g && which >= 0 && which < 6) ? g->g[which] : nullptr; }
 void sbn_snark_gens_free(sbn_ctx* c, sbn_snark_gens* g) {
@@ -98,22 +123,13 @@ int sbn_snark_encode(sbn_ctx* c, size_t num_cons, size_t num_vars, size_t num_in
   sn::Shape sh;
   if (!sn::shape_make(num_cons, num_vars, num_inputs, &sh)) return fail(c, SBN_EINVAL, "snark encode: shape %zu x %zu, %zu inputs is too large", num_cons, num_vars, num_inputs);
   if (sh.nv < 2) return fail(c, SBN_EINVAL, "snark encode: num_vars = %zu pads to %zu: the opening of the witness needs at least one variable  [hyrax.rs:77]", num_vars, sh.nv);
-  // Instance::new's convert (snark.rs:92-110)
   std::vector<uint32_t> nc_[3];
   const uint32_t* ncols[3];
-  for (int m = 0; m < 3; m++) {
-    if (nnz[m] && (!rows[m] || !cols[m] || !vals[m])) return fail(c, SBN_EINVAL, "snark encode: matrix %d has %zu entries and a NULL array", m, nnz[m]);
-    nc_[m].resize(std::max<size_t>(nnz[m], 1));
-    size_t bad = 0;
-    const int e = sn::convert_cols(sh, rows[m], cols[m], vals[m], nnz[m], nc_[m].data(), &bad);
-    if (e == sn::CONV_ROW) return fail(c, SBN_EINVAL, "snark encode: matrix %d entry %zu: row %u >= num_cons %zu  [snark.rs:95 InvalidIndex]", m, bad, rows[m][bad], num_cons);
-    if (e == sn::CONV_COL) return fail(c, SBN_EINVAL, "snark encode: matrix %d entry %zu: col %u >= num_vars + 1 + num_inputs = %zu  [snark.rs:98 InvalidIndex]", m, bad, cols[m][bad], num_vars + 1 + num_inputs);
-    if (e == sn::CONV_VAL) return fail(c, SBN_EINVAL, "snark encode: matrix %d entry %zu: value >= r  [snark.rs:101 InvalidScalar]", m, bad);
-    ncols[m] = nc_[m].data();
-  }
+  int rc = snark_convert(c, "snark encode", sh, rows, cols, vals, nnz, nc_, ncols);
+  if (rc) return rc;
   if (gens->nc != sh.nc || gens->nv != sh.nv) return fail(c, SBN_EINVAL, "snark encode: the generator bundle was made for %zu x %zu, the instance pads to %zu x %zu", gens->nc, gens->nv, sh.nc, sh.nv);
   sbn_snark_key* k = new sbn_snark_key();
-  int rc = sbn_r1cs_upload(c, sh.nc, sh.nv, rows, ncols, vals, nnz, flags, &k->inst);
+  rc = sbn_r1cs_upload(c, sh.nc, sh.nv, rows, ncols, vals, nnz, flags, &k->inst);
   if (rc == SBN_OK) rc = sbn_dense_build(c, sh.nx, sh.ny, rows, ncols, vals, nnz, (size_t)sn::BATCH, flags, &k->dense);
   if (rc) { snark_key_release(c, k); return rc; }
   const size_t N = k->dense->N;

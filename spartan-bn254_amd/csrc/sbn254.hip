@@ -16,6 +16,7 @@
 //   R1CSProof::verify, ZKSumcheckInstanceProof::verify, DotProductProof::verify  src/r1csproof.rs:463-619, src/sumcheck.rs:366-457, src/nizk/mod.rs:368-400 -> sbn_r1cs_proof_verify / sbn_zk_sumcheck_verify
 //   SparseMatPolyEvalProof::verify, PolyEvalNetworkProof::verify, ProductLayerProof / HashLayerProof::verify  src/sparse_mlpoly_full.rs:1815-1845, :1581-1650, :1436-1520, :1048-1265 -> sbn_sparse_eval_verify
 //   KZGProof::verify, KZGBatchProof::batch_verify, Bn254::pairing  src/kzg.rs:196-217, :315-352 -> sbn_kzg_verify / _batched / sbn_pairing_products / sbn_g2_prepare
+//   NIZKGens::new, NIZK::prove, NIZK::verify            src/snark.rs:162-287 -> sbn_nizk_*
 //   the verifier's short sums of proof points (nizk/mod.rs:560-565, :389-394 as GroupElement::vartime_multiscalar_mul)          -> sbn_g1_small_sums
 // There is no CPU fallback in this file: every entry point needs the gfx950 device.
 #include "../../include/sbn254.h"
@@ -90,6 +91,7 @@ using namespace sbn;
 #include "abi_sparse_eval.inc"
 #include "abi_sparse_verify.inc"
 #include "abi_snark.inc"
+#include "abi_nizk.inc"
 
 extern "C" {
 

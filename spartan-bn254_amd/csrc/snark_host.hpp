@@ -6,7 +6,8 @@
 //   prefix              the transcript lines in front of R1CSProof: the protocol name and R1CSCommitment::append_to_transcript (r1cs.rs:355-362,
 //                       sparse_mlpoly_full.rs:710-717, hyrax.rs:44-51), through proof_host.hpp's Script
 //   sizes               rnd = r1cs rnd | sparse rnd (ONE RandomTape, draws in call order); proof = r1cs_sat_proof | inst_evals [96] | r1cs_eval_proof
-// tests/snark_host_check.cpp builds this header alone, under ASan + UBSan.
+//   nizk_prefix / nizk_sizes   NIZK mode (snark.rs:162-287): the protocol name and the caller's digest bytes; proof = r1cs_sat_proof | rx | ry
+// tests/snark_host_check.cpp and tests/nizk_host_check.cpp build this header alone, under ASan + UBSan.
 #pragma once
 #include "proof_host.hpp"
 #include <vector>
@@ -114,13 +115,33 @@ static inline void prefix(Script& ts, const Comm& c, const uint8_t* comm, Hook a
   poly("comm_comb_mem", comm_mem(c, comm), c.L_mem);
 }
 
+// ---- NIZK mode (snark.rs:162-287): the two lines in front of R1CSProof::prove / ::verify (:212-213, :252-253).  The digest is the caller's
+//      inst.digest as bytes, of any length: it is absorbed, never computed or read ----
+template <class Hook = NoHook>
+static inline void nizk_prefix(Script& ts, const uint8_t* digest, size_t digest_len, Hook after = Hook()) {
+  ts.protocol("Spartan NIZK proof"); after();
+  ts.message("R1CSShapeDigest", digest, digest_len); after();
+}
+
 // ---- sizes: the layouts the two halves' calls write (include/sbn254.h), laid end to end ----
+// R1CSProof alone at a padded shape: sbn_r1cs_proof_sizes' two numbers
+static inline void sat_sizes(size_t nv, size_t nx, size_t ny, size_t* rnd, size_t* proof) {
+  const size_t ell = log2u(nv), ml = ell / 2, lg = ell - ml, L = (size_t)1 << ml;
+  *rnd = L + 8 * nx + 7 * ny + 2 * lg + 17;
+  *proof = 32 * (L + 10 * nx + 9 * ny + 20) + 64 * lg + 128;
+}
+// NIZK: rnd = R1CSProof::prove's draws; proof = r1cs_sat_proof | rx [nx x 32] | ry [ny x 32], the declaration order of snark.rs:191-194
+struct NizkSizes { size_t r1cs_proof, rnd_scalars, proof_bytes; };
+static inline NizkSizes nizk_sizes(const Shape& s) {
+  NizkSizes z;
+  sat_sizes(s.nv, s.nx, s.ny, &z.rnd_scalars, &z.r1cs_proof);
+  z.proof_bytes = z.r1cs_proof + 32 * (s.nx + s.ny);
+  return z;
+}
 struct Sizes { size_t r1cs_rnd, r1cs_proof, eval_rnd, eval_proof, rnd_scalars, proof_bytes; };
 static inline Sizes sizes(const Comm& c, bool kzg) {
   Sizes z;
-  const size_t ell = log2u((size_t)c.nv), ml = ell / 2, lg = ell - ml, L = (size_t)1 << ml, nx = c.nx, ny = c.ny;
-  z.r1cs_rnd = L + 8 * nx + 7 * ny + 2 * lg + 17;
-  z.r1cs_proof = 32 * (L + 10 * nx + 9 * ny + 20) + 64 * lg + 128;
+  sat_sizes((size_t)c.nv, c.nx, c.ny, &z.r1cs_rnd, &z.r1cs_proof);
   const size_t b = (size_t)BATCH, n = log2u((size_t)c.N), m = log2u((size_t)c.cells);
   const size_t e_o = ell_ops((size_t)c.N), e_m = m + 1, e_d = n + log2u(npo2(2 * b));
   const size_t lg_o = e_o - e_o / 2, lg_m = e_m - e_m / 2, lg_d = e_d - e_d / 2, Ld = (size_t)1 << (e_d / 2);
