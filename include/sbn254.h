@@ -918,6 +918,47 @@ int sbn_nizk_prove(sbn_ctx* ctx, const sbn_nizk_inst* inst, const sbn_table* var
 int sbn_nizk_verify(sbn_ctx* ctx, const sbn_nizk_inst* inst, const uint8_t* input, size_t num_inputs, const sbn_snark_gens* gens,
                     const uint8_t* proof, size_t proof_len, sbn_transcript* tr, int* accepted);
 
+/* ---- circom's .r1cs and .wtns files straight onto the device (reference src/r1cs_reader.rs, examples/keyless_benchmark.rs:38-72) ----
+ * The caller maps or reads the two files; bytes go in, resident handles come out, and the prove and verify calls above take those handles as they are.
+ * The host scans the sections and walks the 3 * nConstraints entry counts (the format's one sequential dependency); the payload goes up in one copy and
+ * everything per entry — the record, the value against r, the column remap, the two compressed copies, the dense representation — is device work.
+ *
+ * sbn_circom_r1cs_load: R1CS::from_reader (r1cs_reader.rs:55-191) and to_sparse_matrices_padded (:213-242) at the padded shape Instance::new gives
+ *   (num_vars = nWires - 1 - num_pub_inputs, num_inputs = num_pub_inputs = nPubOut + nPubIn, num_cons = nConstraints; snark.rs:74-90).  The handle holds,
+ *   per matrix and in file order, (row = constraint, remapped column, canonical value): wire 0 -> num_vars_padded, wires 1..=num_pub_inputs ->
+ *   num_vars_padded + wire, the others -> wire - num_pub_inputs - 1.  An entry whose value is >= r is dropped, as the reader drops it (:156-158), and
+ *   counted in `dropped`.  Refused with SBN_EINVAL and a reason in sbn_last_error: a wrong magic, a version other than 1, field_size other than 32, a
+ *   missing section 1 or 2, any read past `len`, nWires < 1 + num_pub_inputs, more than 2^31 entries, a shape past 2^29; and three things the reference
+ *   would misread without a word: a prime that is not BN254's r, a constraints walk that passes the end of section 2 (the reference reads on into the
+ *   next section), a wire >= nWires (the reference aliases it onto another column; the text names the entry).  One host wait; a second one only where a
+ *   value was dropped.  The file's bytes are free again when the call returns.
+ * sbn_circom_r1cs_info: the stored counts, no device work.  nnz[m] are R1CSStats' nnz_a, _b, _c (kept entries); their maximum is the num_nz_entries
+ *   sbn_snark_gens_new takes.
+ * sbn_circom_r1cs_download: matrix m (0, 1, 2) as to_sparse_matrices_padded(num_vars_padded) returns it: nnz[m] rows, columns and 32-byte values.
+ * sbn_r1cs_from_circom: the handle sbn_r1cs_upload(num_cons_padded, num_vars_padded, ...) makes of those triplets, without the host's sorts.
+ * sbn_nizk_instance_from_circom: sbn_nizk_instance_new on the parsed circuit; the digest stays the caller's bytes.
+ * sbn_snark_encode_circom: sbn_snark_encode on the parsed circuit, with the same refusals (num_vars_padded < 2, N < 2, a bundle of another shape or N).
+ * The handles made from a sbn_circom_r1cs keep nothing of it: it may be freed right after.
+ * sbn_circom_wtns_load: parse_wtns (keyless_benchmark.rs:38-72): input <- witness[1 .. 1 + num_inputs] (canonical bytes), *vars <- witness[1 + num_inputs ..]
+ *   as a table of next_power_of_two(max(its length, num_inputs + 1)) entries, zeros behind the last value; *num_witness <- the file's value count.  Refused
+ *   (SBN_EINVAL, no table) where the example truncates or concatenates without a word: a second section 2, a section past the end of the file, a size
+ *   that is no multiple of 32, fewer than 1 + num_inputs values, and a value >= r (the example takes its low 64 bits; the text names the index). */
+typedef struct sbn_circom_r1cs sbn_circom_r1cs;
+typedef struct {
+  uint64_t num_constraints, num_variables, num_pub_inputs, num_prv_inputs, num_labels;
+  uint64_t nnz[3];       /* kept entries: R1CSStats' nnz_a, _b, _c */
+  uint64_t dropped[3];   /* values >= r the reader skipped */
+  uint64_t num_vars, num_cons_padded, num_vars_padded;
+} sbn_circom_info;
+int sbn_circom_r1cs_load(sbn_ctx* ctx, const uint8_t* file, size_t len, sbn_circom_r1cs** out);
+int sbn_circom_r1cs_info(const sbn_circom_r1cs* f, sbn_circom_info* out);
+int sbn_circom_r1cs_download(sbn_ctx* ctx, const sbn_circom_r1cs* f, int m, uint32_t* rows, uint32_t* cols, uint8_t* vals);
+void sbn_circom_r1cs_free(sbn_ctx* ctx, sbn_circom_r1cs* f);
+int sbn_r1cs_from_circom(sbn_ctx* ctx, const sbn_circom_r1cs* f, sbn_r1cs** out);
+int sbn_nizk_instance_from_circom(sbn_ctx* ctx, const sbn_circom_r1cs* f, const uint8_t* digest, size_t digest_len, sbn_nizk_inst** out);
+int sbn_snark_encode_circom(sbn_ctx* ctx, const sbn_circom_r1cs* f, const sbn_snark_gens* gens, sbn_snark_key** out);
+int sbn_circom_wtns_load(sbn_ctx* ctx, const uint8_t* file, size_t len, size_t num_inputs, sbn_table** vars, uint8_t* input, size_t* num_witness);
+
 /* ---- per-kernel timing (HIP events on the context's stream), for bench.py's roofline line ---- */
 int sbn_prof_enable(sbn_ctx* ctx, int on);
 int sbn_prof_reset(sbn_ctx* ctx);

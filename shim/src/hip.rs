@@ -60,6 +60,14 @@ use crate::unipoly::{CompressedUniPoly, UniPoly};
 #[repr(C)] pub struct sbn_snark_gens { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_snark_key { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_nizk_inst { _p: [u8; 0] }
+#[repr(C)] pub struct sbn_circom_r1cs { _p: [u8; 0] }
+/// what `sbn_circom_r1cs_info` fills: the file's header fields, the kept and dropped entries per matrix, the shape `Instance::new` gives
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct sbn_circom_info {
+    pub num_constraints: u64, pub num_variables: u64, pub num_pub_inputs: u64, pub num_prv_inputs: u64, pub num_labels: u64,
+    pub nnz: [u64; 3], pub dropped: [u64; 3],
+    pub num_vars: u64, pub num_cons_padded: u64, pub num_vars_padded: u64,
+}
 
 pub const SBN_OK: c_int = 0;
 pub const SBN_SCALARS_MONT: u32 = 1;
@@ -251,6 +259,14 @@ extern "C" {
     pub fn sbn_nizk_is_sat(ctx: *mut sbn_ctx, inst: *const sbn_nizk_inst, vars: *const sbn_table, input: *const u8, num_inputs: usize, sat: *mut c_int, num_bad: *mut u64, first_bad: *mut u64) -> c_int;
     pub fn sbn_nizk_prove(ctx: *mut sbn_ctx, inst: *const sbn_nizk_inst, vars: *const sbn_table, input: *const u8, num_inputs: usize, gens: *const sbn_snark_gens, flags: u32, rnd: *const u8, tr: *mut sbn_transcript, out_proof: *mut u8) -> c_int;
     pub fn sbn_nizk_verify(ctx: *mut sbn_ctx, inst: *const sbn_nizk_inst, input: *const u8, num_inputs: usize, gens: *const sbn_snark_gens, proof: *const u8, proof_len: usize, tr: *mut sbn_transcript, accepted: *mut c_int) -> c_int;
+    pub fn sbn_circom_r1cs_load(ctx: *mut sbn_ctx, file: *const u8, len: usize, out: *mut *mut sbn_circom_r1cs) -> c_int;
+    pub fn sbn_circom_r1cs_info(f: *const sbn_circom_r1cs, out: *mut sbn_circom_info) -> c_int;
+    pub fn sbn_circom_r1cs_download(ctx: *mut sbn_ctx, f: *const sbn_circom_r1cs, m: c_int, rows: *mut u32, cols: *mut u32, vals: *mut u8) -> c_int;
+    pub fn sbn_circom_r1cs_free(ctx: *mut sbn_ctx, f: *mut sbn_circom_r1cs);
+    pub fn sbn_r1cs_from_circom(ctx: *mut sbn_ctx, f: *const sbn_circom_r1cs, out: *mut *mut sbn_r1cs) -> c_int;
+    pub fn sbn_nizk_instance_from_circom(ctx: *mut sbn_ctx, f: *const sbn_circom_r1cs, digest: *const u8, digest_len: usize, out: *mut *mut sbn_nizk_inst) -> c_int;
+    pub fn sbn_snark_encode_circom(ctx: *mut sbn_ctx, f: *const sbn_circom_r1cs, gens: *const sbn_snark_gens, out: *mut *mut sbn_snark_key) -> c_int;
+    pub fn sbn_circom_wtns_load(ctx: *mut sbn_ctx, file: *const u8, len: usize, num_inputs: usize, vars: *mut *mut sbn_table, input: *mut u8, num_witness: *mut usize) -> c_int;
     pub fn sbn_prof_enable(ctx: *mut sbn_ctx, on: c_int) -> c_int;
     pub fn sbn_prof_reset(ctx: *mut sbn_ctx) -> c_int;
     pub fn sbn_prof_count(ctx: *mut sbn_ctx) -> c_int;

@@ -34,6 +34,8 @@ EXPORTED_SYMBOLS = [
     "sbn_r1cs_is_sat", "sbn_snark_gens_new", "sbn_snark_gens_get", "sbn_snark_gens_free", "sbn_snark_encode", "sbn_snark_key_from_comm", "sbn_snark_key_comm", "sbn_snark_key_dense",
     "sbn_snark_key_free", "sbn_snark_sizes", "sbn_snark_is_sat", "sbn_snark_prove", "sbn_snark_verify", "sbn_snark_prove_kzg", "sbn_snark_verify_kzg",
     "sbn_nizk_gens_new", "sbn_nizk_instance_new", "sbn_nizk_instance_free", "sbn_nizk_instance_r1cs", "sbn_nizk_sizes", "sbn_nizk_is_sat", "sbn_nizk_prove", "sbn_nizk_verify",
+    "sbn_circom_r1cs_load", "sbn_circom_r1cs_info", "sbn_circom_r1cs_download", "sbn_circom_r1cs_free", "sbn_r1cs_from_circom", "sbn_nizk_instance_from_circom",
+    "sbn_snark_encode_circom", "sbn_circom_wtns_load",
 ]
 SBN_EUNSAT = -5
 SBN_SNARK_CHECK_SAT = 1
@@ -151,6 +153,14 @@ def lib():
         L.sbn_nizk_is_sat.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 3
         L.sbn_nizk_prove.argtypes = [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
         L.sbn_nizk_verify.argtypes = [C.c_void_p] * 3 + [C.c_size_t] + [C.c_void_p] * 2 + [C.c_size_t] + [C.c_void_p] * 2
+        L.sbn_circom_r1cs_load.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sbn_circom_r1cs_info.argtypes = [C.c_void_p] * 2
+        L.sbn_circom_r1cs_download.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        L.sbn_circom_r1cs_free.restype = None; L.sbn_circom_r1cs_free.argtypes = [C.c_void_p] * 2
+        L.sbn_r1cs_from_circom.argtypes = [C.c_void_p] * 3
+        L.sbn_nizk_instance_from_circom.argtypes = [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]
+        L.sbn_snark_encode_circom.argtypes = [C.c_void_p] * 4
+        L.sbn_circom_wtns_load.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t] + [C.c_void_p] * 3
         _LIB = L
     return _LIB
 
@@ -605,6 +615,39 @@ class NizkInst:
         if self.h:
             self.r1cs.free()
             lib().sbn_nizk_instance_free(self.ctx.h, self.h)
+            self.h = None
+
+
+class CircomInfo(C.Structure):
+    """sbn_circom_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("num_constraints", "num_variables", "num_pub_inputs", "num_prv_inputs", "num_labels")] + \
+               [("nnz", C.c_uint64 * 3), ("dropped", C.c_uint64 * 3)] + [(k, C.c_uint64) for k in ("num_vars", "num_cons_padded", "num_vars_padded")]
+
+
+class CircomR1cs:
+    """a circom .r1cs file parsed onto the device (sbn_circom_r1cs_load): per matrix (row, remapped column, canonical value) in file order.  The handles
+    made from it (r1cs_from_circom, nizk_instance_from_circom, snark_encode_circom) keep nothing of it"""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    def info(self):
+        """-> dict of sbn_circom_info's fields (nnz and dropped as 3-tuples)"""
+        o = CircomInfo()
+        self.ctx._chk(lib().sbn_circom_r1cs_info(self.h, C.byref(o)), "sbn_circom_r1cs_info")
+        return {k: (tuple(int(x) for x in getattr(o, k)) if k in ("nnz", "dropped") else int(getattr(o, k))) for k, _ in CircomInfo._fields_}
+
+    def download(self, m):
+        """matrix m as to_sparse_matrices_padded(num_vars_padded) returns it -> (rows, cols, [32-byte values])"""
+        n = self.info()["nnz"][m] if 0 <= m <= 2 else 0
+        rows, cols, vals = (C.c_uint32 * max(n, 1))(), (C.c_uint32 * max(n, 1))(), (C.c_uint8 * (32 * max(n, 1)))()
+        self.ctx._chk(lib().sbn_circom_r1cs_download(self.ctx.h, self.h, m, rows, cols, vals), "sbn_circom_r1cs_download")
+        raw = bytes(vals)
+        return [int(rows[i]) for i in range(n)], [int(cols[i]) for i in range(n)], [raw[32 * i:32 * i + 32] for i in range(n)]
+
+    def free(self):
+        if self.h:
+            lib().sbn_circom_r1cs_free(self.ctx.h, self.h)
             self.h = None
 
 
@@ -1504,6 +1547,41 @@ class Context:
         self._chk(lib().sbn_nizk_verify(self.h, inst.h, _ptr(input_) if input_ else None, C.c_size_t(len(input_) // 32), gens.h, _ptr(proof), C.c_size_t(len(proof)), tr.h,
                                         C.byref(acc)), "sbn_nizk_verify")
         return bool(acc.value)
+
+    # ---- circom's .r1cs and .wtns files straight onto the device (r1cs_reader.rs, keyless_benchmark.rs:38-72)
+    def circom_r1cs_load(self, data):
+        """R1CS::from_reader + to_sparse_matrices_padded on the bytes of a .r1cs file (sbn_circom_r1cs_load) -> CircomR1cs; a refused file raises SbnError.
+        data: bytes, or a numpy uint8 array (passed where it lies)"""
+        h = C.c_void_p()
+        self._chk(lib().sbn_circom_r1cs_load(self.h, _ptr(data) if len(data) else None, C.c_size_t(len(data)), C.byref(h)), "sbn_circom_r1cs_load")
+        return CircomR1cs(self, h)
+
+    def r1cs_from_circom(self, cr):
+        """the R1cs sbn_r1cs_upload makes of the parsed circuit's triplets (sbn_r1cs_from_circom)"""
+        h = C.c_void_p()
+        self._chk(lib().sbn_r1cs_from_circom(self.h, cr.h, C.byref(h)), "sbn_r1cs_from_circom")
+        i = cr.info()
+        return R1cs(self, h, i["num_cons_padded"], i["num_vars_padded"])
+
+    def nizk_instance_from_circom(self, cr, digest=b""):
+        """Instance::new on the parsed circuit (sbn_nizk_instance_from_circom) -> NizkInst"""
+        h = C.c_void_p()
+        self._chk(lib().sbn_nizk_instance_from_circom(self.h, cr.h, _ptr(digest) if digest else None, C.c_size_t(len(digest)), C.byref(h)), "sbn_nizk_instance_from_circom")
+        i = cr.info()
+        return NizkInst(self, h, i["num_constraints"], i["num_vars"], i["num_pub_inputs"])
+
+    def snark_encode_circom(self, cr, gens):
+        """Instance::new + SNARK::encode on the parsed circuit (sbn_snark_encode_circom) -> SnarkKey"""
+        h = C.c_void_p()
+        self._chk(lib().sbn_snark_encode_circom(self.h, cr.h, gens.h, C.byref(h)), "sbn_snark_encode_circom")
+        return SnarkKey(self, h)
+
+    def circom_wtns_load(self, data, num_inputs):
+        """parse_wtns on the bytes of a .wtns file (sbn_circom_wtns_load) -> (vars Table, input bytes, the file's value count)"""
+        t, n = C.c_void_p(), C.c_size_t(0)
+        inp = (C.c_uint8 * (32 * max(num_inputs, 1)))()
+        self._chk(lib().sbn_circom_wtns_load(self.h, _ptr(data) if len(data) else None, C.c_size_t(len(data)), C.c_size_t(num_inputs), C.byref(t), inp, C.byref(n)), "sbn_circom_wtns_load")
+        return Table(self, t), bytes(inp)[:32 * num_inputs], n.value
 
     # ---- profiling
     def prof_enable(self, on=True):

@@ -40,6 +40,64 @@ static void dense_timestamps(sbn_ctx* c, const sbn_dense* h, int side, uint32_t*
   LAUNCH(c, "k_dense_rank", k_dense_rank, stream_grid(n), 256, kin, iin, n, cells, (const uint32_t*)start, dense_read_ts(h, side), dense_audit(h, side));
 }
 
+// the sort's share of the dense workspace for M = batch * N ops over `cells` cells
+struct DenseWs { size_t b_m, b_cnt, b_sum, b_start, bytes; };
+static DenseWs dense_ws_sizes(size_t M, size_t cells) {
+  const uint32_t ntiles = (uint32_t)((M + DENSE_TILE - 1) / DENSE_TILE);
+  const size_t nc = (size_t)DENSE_BINS * ntiles, nchunks = (nc + DENSE_SCAN_CHUNK - 1) / DENSE_SCAN_CHUNK;
+  DenseWs w;
+  w.b_m = r1cs_align(M * 4); w.b_cnt = r1cs_align(nc * 4); w.b_sum = r1cs_align(nchunks * 4); w.b_start = r1cs_align(cells * 4);
+  w.bytes = 4 * w.b_m + w.b_cnt + w.b_sum + w.b_start;
+  return w;
+}
+// sbn_dense_build behind its validation and its three copies: the triplets lie on the device already — rows_dev / cols_dev / vals_dev, matrix k's nnz[k]
+// entries from a.off[k] on, canonical values (ark-ff's limbs under SBN_SCALARS_MONT), every address below `cells` — and are read, not kept.  The first
+// ws_off bytes of the context's dense workspace are the caller's (the host entry point stages its copies there).  The caller holds the context's mutex;
+// the call returns behind the stream, so what the triplets lie in is free again
+static int dense_build_staged(sbn_ctx* c, const uint32_t* rows_dev, const uint32_t* cols_dev, const uint32_t* vals_dev, const DenseArgs& a, size_t batch, size_t N, size_t cells,
+                              size_t ws_off, uint32_t flags, sbn_dense** out) {
+  const size_t M = batch * N;
+  size_t ops_len = 1; while (ops_len < 5 * M) ops_len <<= 1;    // DensePolynomial::merge pads to the next power of two (hyrax.rs:237-251)
+  const size_t mem_len = 2 * cells;
+  sbn_dense* h = new sbn_dense();
+  h->batch = batch; h->N = N; h->cells = cells; h->log_n = r1cs_log2(N);
+  h->ops.owned = h->mem.owned = false;                          // a stray sbn_table_free must not recycle the handle's buffers
+  size_t got = 0;
+  hipError_t e = pool_get(c, ops_len * 32, &h->ops.d, &got);
+  if (e != hipSuccess) { (void)hipGetLastError(); h->ops.d = nullptr; dense_release(c, h); return fail(c, SBN_ENOMEM, "dense_build: comb_ops (%zu entries, %zu bytes): %s", ops_len, ops_len * 32, hipGetErrorString(e)); }
+  h->ops.len = ops_len; h->ops.cap = got / 32;
+  e = pool_get(c, mem_len * 32, &h->mem.d, &got);
+  if (e != hipSuccess) { (void)hipGetLastError(); h->mem.d = nullptr; dense_release(c, h); return fail(c, SBN_ENOMEM, "dense_build: comb_mem (%zu entries): %s", mem_len, hipGetErrorString(e)); }
+  h->mem.len = mem_len; h->mem.cap = got / 32;
+  e = hipMalloc(&h->u32s, (4 * M + 2 * cells) * 4);
+  if (e != hipSuccess) { (void)hipGetLastError(); h->u32s = nullptr; dense_release(c, h); return fail(c, SBN_ENOMEM, "dense_build: address and timestamp arrays (%zu bytes): %s", (4 * M + 2 * cells) * 4, hipGetErrorString(e)); }
+
+  // workspace behind the caller's part: two (key, index) buffers of the sort, its counts and chunk sums, the run starts
+  const DenseWs w = dense_ws_sizes(M, cells);
+  int rc = ensure(c, c->dense_ws, ws_off + w.bytes);
+  if (rc) { dense_release(c, h); return rc; }
+  uint8_t* p = (uint8_t*)c->dense_ws.p + ws_off;
+  uint32_t *key[2], *idx[2];
+  key[0] = (uint32_t*)p; p += w.b_m; key[1] = (uint32_t*)p; p += w.b_m; idx[0] = (uint32_t*)p; p += w.b_m; idx[1] = (uint32_t*)p; p += w.b_m;
+  uint32_t* counts = (uint32_t*)p; p += w.b_cnt;
+  uint32_t* sums = (uint32_t*)p; p += w.b_sum;
+  uint32_t* start = (uint32_t*)p;
+
+  LAUNCH(c, "k_dense_expand", k_dense_expand, stream_grid(M), 256, rows_dev, cols_dev, a, h->log_n, (uint32_t)M, dense_addr(h, 0), dense_addr(h, 1));
+  for (int side = 0; side < 2; side++) dense_timestamps(c, h, side, key, idx, counts, sums, start);
+  LAUNCH(c, "k_dense_tables", k_dense_tables, stream_grid(ops_len + mem_len), 256, (const uint32_t*)h->u32s, vals_dev, a, h->log_n, (uint32_t)batch,
+         (flags & SBN_SCALARS_MONT) ? 1 : 0, (const uint32_t*)dense_audit(h, 0), ops_len, mem_len, (uint32_t*)h->ops.d, (uint32_t*)h->mem.d);
+  const hipError_t ce = hipGetLastError();
+  const hipError_t se = hipStreamSynchronize(c->stream);        // the triplets and the staged copies are free again from here
+  if (c->prof) prof_drain(c);
+  if (ce != hipSuccess || se != hipSuccess) {
+    dense_release(c, h);
+    return fail(c, SBN_EHIP, "dense_build: %s", hipGetErrorString(ce != hipSuccess ? ce : se));
+  }
+  *out = h;
+  return SBN_OK;
+}
+
 extern "C" {
 
 void sbn_dense_free(sbn_ctx* c, sbn_dense* h) {
@@ -82,40 +140,18 @@ int sbn_dense_build(sbn_ctx* c, size_t num_vars_x, size_t num_vars_y, const uint
       if (!fr_canonical(vals[k] + 32 * e)) return fail(c, SBN_EINVAL, "dense_build: matrix %zu entry %zu: value >= r", k, e);
     }
   const size_t M = batch * N;
-  size_t ops_len = 1; while (ops_len < 5 * M) ops_len <<= 1;    // DensePolynomial::merge pads to the next power of two (hyrax.rs:237-251)
-  const size_t mem_len = 2 * cells;
 
   std::lock_guard<std::mutex> g(c->mu);
   hipSetDevice(c->device);
-  sbn_dense* h = new sbn_dense();
-  h->batch = batch; h->N = N; h->cells = cells; h->log_n = r1cs_log2(N);
-  h->ops.owned = h->mem.owned = false;                          // a stray sbn_table_free must not recycle the handle's buffers
-  size_t got = 0;
-  hipError_t e = pool_get(c, ops_len * 32, &h->ops.d, &got);
-  if (e != hipSuccess) { (void)hipGetLastError(); h->ops.d = nullptr; dense_release(c, h); return fail(c, SBN_ENOMEM, "dense_build: comb_ops (%zu entries, %zu bytes): %s", ops_len, ops_len * 32, hipGetErrorString(e)); }
-  h->ops.len = ops_len; h->ops.cap = got / 32;
-  e = pool_get(c, mem_len * 32, &h->mem.d, &got);
-  if (e != hipSuccess) { (void)hipGetLastError(); h->mem.d = nullptr; dense_release(c, h); return fail(c, SBN_ENOMEM, "dense_build: comb_mem (%zu entries): %s", mem_len, hipGetErrorString(e)); }
-  h->mem.len = mem_len; h->mem.cap = got / 32;
-  e = hipMalloc(&h->u32s, (4 * M + 2 * cells) * 4);
-  if (e != hipSuccess) { (void)hipGetLastError(); h->u32s = nullptr; dense_release(c, h); return fail(c, SBN_ENOMEM, "dense_build: address and timestamp arrays (%zu bytes): %s", (4 * M + 2 * cells) * 4, hipGetErrorString(e)); }
-
-  // workspace: the staged triplets, two (key, index) buffers of the sort, its counts and chunk sums, the run starts
-  const uint32_t ntiles = (uint32_t)((M + DENSE_TILE - 1) / DENSE_TILE);
-  const size_t nc = (size_t)DENSE_BINS * ntiles, nchunks = (nc + DENSE_SCAN_CHUNK - 1) / DENSE_SCAN_CHUNK;
-  const size_t b_idx = r1cs_align(std::max<size_t>(total, 1) * 4), b_val = r1cs_align(std::max<size_t>(total, 1) * 32), b_m = r1cs_align(M * 4);
-  const size_t b_cnt = r1cs_align(nc * 4), b_sum = r1cs_align(nchunks * 4), b_start = r1cs_align(cells * 4);
-  int rc = ensure(c, c->dense_ws, b_val + 2 * b_idx + 4 * b_m + b_cnt + b_sum + b_start);
-  if (rc) { dense_release(c, h); return rc; }
+  // workspace: the staged triplets, then what dense_build_staged takes behind them
+  const size_t b_idx = r1cs_align(std::max<size_t>(total, 1) * 4), b_val = r1cs_align(std::max<size_t>(total, 1) * 32);
+  const size_t staged = b_val + 2 * b_idx;
+  int rc = ensure(c, c->dense_ws, staged + dense_ws_sizes(M, cells).bytes);
+  if (rc) return rc;
   uint8_t* w = (uint8_t*)c->dense_ws.p;
   uint32_t* s_val = (uint32_t*)w; w += b_val;
   uint32_t* s_row = (uint32_t*)w; w += b_idx;
-  uint32_t* s_col = (uint32_t*)w; w += b_idx;
-  uint32_t *key[2], *idx[2];
-  key[0] = (uint32_t*)w; w += b_m; key[1] = (uint32_t*)w; w += b_m; idx[0] = (uint32_t*)w; w += b_m; idx[1] = (uint32_t*)w; w += b_m;
-  uint32_t* counts = (uint32_t*)w; w += b_cnt;
-  uint32_t* sums = (uint32_t*)w; w += b_sum;
-  uint32_t* start = (uint32_t*)w;
+  uint32_t* s_col = (uint32_t*)w;
 
   DenseArgs a; memset(&a, 0, sizeof a);
   hipError_t ce = hipSuccess;
@@ -129,21 +165,11 @@ int sbn_dense_build(sbn_ctx* c, size_t num_vars_x, size_t num_vars_y, const uint
     }
     off += nnz[k];
   }
-  if (ce == hipSuccess) {
-    LAUNCH(c, "k_dense_expand", k_dense_expand, stream_grid(M), 256, (const uint32_t*)s_row, (const uint32_t*)s_col, a, h->log_n, (uint32_t)M, dense_addr(h, 0), dense_addr(h, 1));
-    for (int side = 0; side < 2; side++) dense_timestamps(c, h, side, key, idx, counts, sums, start);
-    LAUNCH(c, "k_dense_tables", k_dense_tables, stream_grid(ops_len + mem_len), 256, (const uint32_t*)h->u32s, (const uint32_t*)s_val, a, h->log_n, (uint32_t)batch,
-           (flags & SBN_SCALARS_MONT) ? 1 : 0, (const uint32_t*)dense_audit(h, 0), ops_len, mem_len, (uint32_t*)h->ops.d, (uint32_t*)h->mem.d);
-    ce = hipGetLastError();
+  if (ce != hipSuccess) {
+    hipStreamSynchronize(c->stream);                            // the caller's arrays are free again from here
+    return fail(c, SBN_EHIP, "dense_build: %s", hipGetErrorString(ce));
   }
-  const hipError_t se = hipStreamSynchronize(c->stream);        // the caller's arrays and the staged copies are free again from here
-  if (c->prof) prof_drain(c);
-  if (ce != hipSuccess || se != hipSuccess) {
-    dense_release(c, h);
-    return fail(c, SBN_EHIP, "dense_build: %s", hipGetErrorString(ce != hipSuccess ? ce : se));
-  }
-  *out = h;
-  return SBN_OK;
+  return dense_build_staged(c, s_row, s_col, s_val, a, batch, N, cells, staged, flags, out);
 }
 
 }  // extern "C"

@@ -18,10 +18,9 @@ struct sbn_r1cs {
 static size_t r1cs_align(size_t b) { return (b + 255) & ~(size_t)255; }
 static uint32_t r1cs_log2(size_t n) { uint32_t l = 0; while (((size_t)1 << l) < n) l++; return l; }
 
-// host arrays of one compressed copy -> device (values converted to the table representation), then the merge-path partition
-static int r1cs_csr_upload(sbn_ctx* c, R1csCsr& m, const std::vector<uint32_t>& row_end, const std::vector<uint32_t>& idx, const std::vector<uint8_t>& val,
-                           uint32_t flags) {
-  m.nrows = (uint32_t)row_end.size(); m.nnz = (uint32_t)idx.size();
+// one compressed copy of `nrows` rows and `nnz` non-zeros: its device memory, nothing in it yet
+static int r1cs_csr_alloc(sbn_ctx* c, R1csCsr& m, size_t nrows, size_t nnz) {
+  m.nrows = (uint32_t)nrows; m.nnz = (uint32_t)nnz;
   m.nchunks = (uint32_t)(((uint64_t)m.nrows + m.nnz + R1CS_CHUNK - 1) / R1CS_CHUNK);
   const size_t b_re = r1cs_align((size_t)m.nrows * 4), b_sr = r1cs_align(((size_t)m.nchunks + 1) * 4), b_idx = r1cs_align((size_t)m.nnz * 4);
   const size_t b_val = r1cs_align((size_t)m.nnz * 32);
@@ -29,16 +28,28 @@ static int r1cs_csr_upload(sbn_ctx* c, R1csCsr& m, const std::vector<uint32_t>& 
   if (e != hipSuccess) { m.mem = nullptr; return fail(c, SBN_ENOMEM, "r1cs_upload: hipMalloc (%zu non-zeros): %s", (size_t)m.nnz, hipGetErrorString(e)); }
   uint8_t* p = (uint8_t*)m.mem;
   m.row_end = (uint32_t*)p; m.start_row = (uint32_t*)(p + b_re); m.idx = (uint32_t*)(p + b_re + b_sr); m.val = (uint32_t*)(p + b_re + b_sr + b_idx);
-  HIPCHK(c, hipMemcpyAsync(m.row_end, row_end.data(), (size_t)m.nrows * 4, hipMemcpyHostToDevice, c->stream));
+  return SBN_OK;
+}
+// behind row_end, idx and val (canonical, or ark-ff's limbs under SBN_SCALARS_MONT): the values into the table representation, then the merge-path partition
+static int r1cs_csr_finish(sbn_ctx* c, R1csCsr& m, uint32_t flags) {
   if (m.nnz) {
-    HIPCHK(c, hipMemcpyAsync(m.idx, idx.data(), (size_t)m.nnz * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(m.val, val.data(), (size_t)m.nnz * 32, hipMemcpyHostToDevice, c->stream));
     if (!(flags & SBN_SCALARS_MONT)) LAUNCH(c, "k_fr_to_mont", k_fr_to_mont, stream_grid(m.nnz), 256, (const uint32_t*)m.val, m.val, (size_t)m.nnz);
     else LAUNCH(c, "k_fr_to_mont", k_fr_from_ark, stream_grid(m.nnz), 256, (const uint32_t*)m.val, m.val, (size_t)m.nnz);
   }
   LAUNCH(c, "k_r1cs_partition", k_r1cs_partition, stream_grid((size_t)m.nchunks + 1), 256, (const uint32_t*)m.row_end, m.nrows, m.nnz, m.nchunks, m.start_row);
   LAUNCHCHK(c);
   return SBN_OK;
+}
+// host arrays of one compressed copy -> device (values converted to the table representation), then the merge-path partition
+static int r1cs_csr_upload(sbn_ctx* c, R1csCsr& m, const std::vector<uint32_t>& row_end, const std::vector<uint32_t>& idx, const std::vector<uint8_t>& val,
+                           uint32_t flags) {
+  int rc; if ((rc = r1cs_csr_alloc(c, m, row_end.size(), idx.size()))) return rc;
+  HIPCHK(c, hipMemcpyAsync(m.row_end, row_end.data(), (size_t)m.nrows * 4, hipMemcpyHostToDevice, c->stream));
+  if (m.nnz) {
+    HIPCHK(c, hipMemcpyAsync(m.idx, idx.data(), (size_t)m.nnz * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(m.val, val.data(), (size_t)m.nnz * 32, hipMemcpyHostToDevice, c->stream));
+  }
+  return r1cs_csr_finish(c, m, flags);
 }
 
 // y = M x into `out` (rows >= nrows dropped): merge-path pass, then fix-up passes until one lane is left.  Enqueue only.

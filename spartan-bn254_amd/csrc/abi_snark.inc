@@ -93,6 +93,7 @@ static int snark_convert(sbn_ctx* c, const char* pfx, const sbn_host::snark::Sha
   }
   return SBN_OK;
 }
+static int snark_encode_finish(sbn_ctx* c, sbn_snark_key* k, const sbn_host::snark::Shape& sh, const sbn_snark_gens* gens, sbn_snark_key** out);
 
 extern "C" {
 
@@ -132,6 +133,16 @@ int sbn_snark_encode(sbn_ctx* c, size_t num_cons, size_t num_vars, size_t num_in
   rc = sbn_r1cs_upload(c, sh.nc, sh.nv, rows, ncols, vals, nnz, flags, &k->inst);
   if (rc == SBN_OK) rc = sbn_dense_build(c, sh.nx, sh.ny, rows, ncols, vals, nnz, (size_t)sn::BATCH, flags, &k->dense);
   if (rc) { snark_key_release(c, k); return rc; }
+  return snark_encode_finish(c, k, sh, gens, out);
+}
+
+}  // extern "C"
+
+// SNARK::encode behind the two resident halves (k->inst, k->dense): the N >= 2 rule, the two commitments, the commitment's bytes.  Takes the key over:
+// *out <- k, or k is released.  Shared by sbn_snark_encode and sbn_snark_encode_circom (abi_circom.inc)
+static int snark_encode_finish(sbn_ctx* c, sbn_snark_key* k, const sbn_host::snark::Shape& sh, const sbn_snark_gens* gens, sbn_snark_key** out) {
+  namespace sn = sbn_host::snark;
+  int rc = SBN_OK;
   const size_t N = k->dense->N;
   if (N < 2) { snark_key_release(c, k); return fail(c, SBN_EINVAL, "snark encode: no matrix has more than one entry (N = %zu): the dot-product circuits cannot be split  [product_tree.rs:89 assert_eq]", N); }
   k->cm = sn::comm_of(sh, N);
@@ -164,6 +175,8 @@ int sbn_snark_encode(sbn_ctx* c, size_t num_cons, size_t num_vars, size_t num_in
   *out = k;
   return SBN_OK;
 }
+
+extern "C" {
 
 int sbn_snark_key_from_comm(sbn_ctx* c, const uint8_t* comm, size_t len, sbn_snark_key** out) {
   if (!c || !comm || !out) return SBN_EINVAL;

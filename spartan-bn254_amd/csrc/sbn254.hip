@@ -17,6 +17,7 @@
 //   SparseMatPolyEvalProof::verify, PolyEvalNetworkProof::verify, ProductLayerProof / HashLayerProof::verify  src/sparse_mlpoly_full.rs:1815-1845, :1581-1650, :1436-1520, :1048-1265 -> sbn_sparse_eval_verify
 //   KZGProof::verify, KZGBatchProof::batch_verify, Bn254::pairing  src/kzg.rs:196-217, :315-352 -> sbn_kzg_verify / _batched / sbn_pairing_products / sbn_g2_prepare
 //   NIZKGens::new, NIZK::prove, NIZK::verify            src/snark.rs:162-287 -> sbn_nizk_*
+//   R1CS::from_reader, to_sparse_matrices_padded, parse_wtns   src/r1cs_reader.rs:55-242, examples/keyless_benchmark.rs:38-72 -> sbn_circom_*
 //   the verifier's short sums of proof points (nizk/mod.rs:560-565, :389-394 as GroupElement::vartime_multiscalar_mul)          -> sbn_g1_small_sums
 // There is no CPU fallback in this file: every entry point needs the gfx950 device.
 #include "../../include/sbn254.h"
@@ -30,6 +31,7 @@
 #include "kzg_kernels.cuh"
 #include "r1cs_kernels.cuh"
 #include "dense_kernels.cuh"
+#include "circom_kernels.cuh"
 #include "transcript_kernels.cuh"
 #include "polyeval_kernels.cuh"
 #include "decompress_kernels.cuh"
@@ -45,6 +47,7 @@
 #include "proof_host.hpp"
 #include "sparse_verify_host.hpp"
 #include "snark_host.hpp"
+#include "circom_host.hpp"
 #include "pairing_host.hpp"
 
 #include <hip/hip_runtime.h>
@@ -92,6 +95,7 @@ using namespace sbn;
 #include "abi_sparse_verify.inc"
 #include "abi_snark.inc"
 #include "abi_nizk.inc"
+#include "abi_circom.inc"
 
 extern "C" {
 
