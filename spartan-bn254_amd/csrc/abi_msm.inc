@@ -312,12 +312,6 @@ int sbn_unipoly_eval(const uint8_t* coeffs, size_t n, const uint8_t r[32], uint8
 void sbn_factored_lens(size_t ell, size_t* left, size_t* right) { if (left) *left = ell / 2; if (right) *right = ell - ell / 2; }
 
 // ---- generators: MultiCommitGens::new (commitments.rs:31-62) ----
-static const uint64_t FR_MOD[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
-static bool fr_canonical(const uint8_t b[32]) {
-  uint64_t v[4]; memcpy(v, b, 32);
-  for (int i = 3; i >= 0; i--) { if (v[i] < FR_MOD[i]) return true; if (v[i] > FR_MOD[i]) return false; }
-  return false;
-}
 // GroupElement::from_uniform_bytes (group.rs:110-131): the scalar s with point = s*G
 static void uniform_bytes_scalar(const uint8_t ub[64], uint8_t s[32]) {
   sbn_host::sha3_256(ub, 64, s);

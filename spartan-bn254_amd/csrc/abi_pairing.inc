@@ -5,7 +5,8 @@
 //                                             e(C - y G + z pi, g2) * e(-pi, tau_g2) == 1
 //                                         which holds by bilinearity alone: no G2 point is multiplied, both are fixed per SRS.  The G1 sum is one
 //                                         sbn_g1_small_sums call (k_window_sums and the host fold), the product one k_pairing_products launch.
-// Included by sbn254.hip.
+// The byte-level point and scalar helpers (g1_xy_valid, g1_neg_bytes, fr_neg_bytes, fq_to_dev_mont) are verify_host.hpp.
+// Included by sbn254.hip; needs abi_small_sums.inc (sbn_g1_small_sums).
 
 static const size_t PAIR_CHECKS_MAX = (size_t)1 << 16;      // a grid of 2^16 waves, 19 MiB of descriptors and 24 MiB of GT bytes: sizes stay far from any overflow
 
@@ -14,22 +15,6 @@ struct sbn_g2_lines {
   void* d = nullptr;             // nlines x 128 B of line values, then nlines x u32 square_first
   size_t nlines = 0, bytes = 0;
 };
-
-static void fr_neg_bytes(const uint8_t in[32], uint8_t out[32]) {
-  sbn_host::fr::El x; memcpy(x.v, in, 32);
-  const sbn_host::fr::El z = sbn_host::fr::sub(sbn_host::fr::from_u64(0), x);
-  memcpy(out, z.v, 32);
-}
-// -P of a canonical affine point (the identity, 64 zero bytes, stays)
-static void g1_neg_bytes(const uint8_t in[64], uint8_t out[64]) {
-  memcpy(out, in, 64);
-  sbn_host::Fq y; memcpy(y.v, in + 32, 32);
-  if (sbn_host::is_zero(y)) return;
-  uint64_t br = 0, r[4];
-  for (int i = 0; i < 4; i++) { sbn_host::u128 d = (sbn_host::u128)sbn_host::QP[i] - y.v[i] - br; r[i] = (uint64_t)d; br = (uint64_t)(d >> 127); }
-  memcpy(out + 32, r, 32);
-}
-static bool g1_is_identity(const uint8_t xy[64]) { for (int k = 0; k < 64; k++) if (xy[k]) return false; return true; }
 
 // the shared end of the two KZG checks: L = sum_k s_k P_k (the caller's terms, then -y G and z pi are appended here), then the product
 static int kzg_check_run(sbn_ctx* c, const sbn_g2_lines* g2, const sbn_g2_lines* tau_g2, std::vector<uint8_t>& pts, std::vector<uint8_t>& scal,
@@ -124,11 +109,9 @@ int sbn_pairing_products(sbn_ctx* c, const uint8_t* p_xy, const sbn_g2_lines* co
   int rc;
   if ((rc = ensure_pin(c, bytes))) return rc;
   memcpy(c->pin, stage.data(), desc_bytes);
-  void* slab = nullptr; size_t slab_bytes = 0;
-  const hipError_t e = pool_get(c, bytes, &slab, &slab_bytes);
-  if (e != hipSuccess) return fail(c, SBN_ENOMEM, "hipMalloc pairing products: %s", hipGetErrorString(e));
-  struct Drop { sbn_ctx* c; void* p; size_t b; ~Drop() { hipStreamSynchronize(c->stream); pool_put(c, p, b); } } drop{c, slab, slab_bytes};
-  uint8_t* p0 = (uint8_t*)slab;
+  SlabLease slab(c);
+  if ((rc = slab.get(bytes, "pairing products"))) return rc;
+  uint8_t* p0 = (uint8_t*)slab.p;
   HIPCHK(c, hipMemcpyAsync(p0, c->pin, desc_bytes, hipMemcpyHostToDevice, c->stream));
   LAUNCH(c, "k_pairing_products", k_pairing_products, (unsigned)nchecks, 64, (const PairCheck*)p0,
          any ? (const uint32_t*)((const uint8_t*)any->d + any->nlines * PAIR_LINE_BYTES) : (const uint32_t*)nullptr, (uint32_t)(any ? any->nlines : 0),

@@ -12,24 +12,9 @@
 // folds the blind (bullet.rs:104).  The transcript stays on the host: a_vec = R goes in as n separate 32-byte messages (transcript.rs:46-50,
 // ~2 200 Keccak permutations at n = 8192), strictly sequential and BEHIND Cx and Cy in the byte stream, so what hides behind the first commit
 // is the host's own computation of R, not the absorption (DESIGN.md 4.11).
-// Included by sbn254.hip.
+// polyeval_host_eq, joint_reduce and OpeningShape are verify_host.hpp (the verifiers run them too); opening_point is abi_verify_common.inc.
+// Included by sbn254.hip; needs abi_proof_common.inc, abi_verify_common.inc and abi_bullet.inc.
 
-// EqPolynomial::evals (hyrax.rs:355-369) on the host, canonical bytes out: the values stay plain integers, the point is in Montgomery form
-// (mmul(s, r R) = s r), so a level costs one product per new pair
-static void polyeval_host_eq(const uint8_t* r, size_t m, std::vector<uint8_t>& out) {
-  using namespace sbn_host::fr;
-  const size_t N = (size_t)1 << m;
-  std::vector<El> e(N);
-  e[0] = from_u64(1);
-  size_t size = 1;
-  for (size_t j = 0; j < m; j++) {
-    const El rj = to_m(el_from(r + 32 * j));
-    for (size_t k = size; k-- > 0;) { const El s = e[k]; const El hi = mmul(s, rj); e[2 * k + 1] = hi; e[2 * k] = sub(s, hi); }
-    size *= 2;
-  }
-  out.resize(32 * N);
-  for (size_t i = 0; i < N; i++) memcpy(&out[32 * i], e[i].v, 32);
-}
 // the copy of the caller's R_size + 1 generators (+ h) that the commits run over, with its lookup table: built on the first opening, owned by `gens`
 static int polyeval_ext(sbn_ctx* c, const sbn_bases* gens, const sbn_bases** out) {
   return derived_set(gens, DERIVED_POLYEVAL, std::string(), [&](sbn_bases** ext) -> int {
@@ -43,7 +28,8 @@ static int polyeval_ext(sbn_ctx* c, const sbn_bases* gens, const sbn_bases** out
 static int polyeval_check(sbn_ctx* c, const sbn_bases* gens, const sbn_table* Z, const uint8_t* blinds, const uint8_t* r, size_t ell, const uint8_t* Zr,
                           const uint8_t* blind_Zr, const uint8_t* rnd) {
   if (ell == 0 || ell > 2 * (size_t)PE_SIDE_MAX) return fail(c, SBN_EINVAL, "polyeval: ell = %zu is outside 1 .. %d", ell, 2 * PE_SIDE_MAX);
-  const size_t ml = ell / 2, mr = ell - ml, L_size = (size_t)1 << ml, n = (size_t)1 << mr;
+  const OpeningShape sh = opening_shape(ell);
+  const size_t mr = sh.mr, L_size = sh.L_size, n = sh.n;
   if (Z->len != ((size_t)1 << ell)) return fail(c, SBN_EINVAL, "polyeval: the table has %zu entries, r has %zu variables  [hyrax.rs:77 assert_eq]", Z->len, ell);
   if (gens->n != n + 1 || !gens->has_h) return fail(c, SBN_EINVAL, "polyeval: the generator set has %zu points%s, the opening needs %zu + 1 with h  [nizk/mod.rs:412-415, :455]", gens->n, gens->has_h ? "" : " and no h", n);
   for (size_t j = 0; j < ell; j++) if (!fr_canonical(r + 32 * j)) return fail(c, SBN_EINVAL, "polyeval: r[%zu] is not canonical", j);
@@ -59,7 +45,8 @@ static int polyeval_prove_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_ta
                                  uint8_t out_Cx_xy[64], int* Cx_is_inf, uint8_t out_Cy_xy[64], int* Cy_is_inf) {
   using namespace sbn_host::fr;
   typedef std::chrono::steady_clock clk;
-  const size_t ml = ell / 2, mr = ell - ml, L_size = (size_t)1 << ml, n = (size_t)1 << mr, lg = mr;
+  const OpeningShape sh = opening_shape(ell);
+  const size_t ml = sh.ml, mr = sh.mr, L_size = sh.L_size, n = sh.n, lg = sh.lg;
   sbn_host::Script ts{t};
   int rc;
   sbn_bullet st; st.n = st.m = n; st.has_q = true; st.has_h = true; st.q_scaled = true; memset(&st.qs, 0, sizeof st.qs);
@@ -71,9 +58,9 @@ static int polyeval_prove_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_ta
   const size_t rows_per_slice = (L_size + nslices - 1) / nslices; nslices = (L_size + rows_per_slice - 1) / rows_per_slice;
   if (col_tiles > 0x7fffffff || nslices > 65535) return fail(c, SBN_EINVAL, "polyeval: bound grid too large");
   if ((rc = ensure(c, c->sc_partial, std::max<size_t>(4096, nslices * n * 32)))) return rc;
-  hipError_t e = pool_get(c, (5 * n + 2 * (n + 2) + 2) * 32, &st.slab, &st.slab_bytes);     // the bullet state's layout (bullet_begin_impl)
-  if (e != hipSuccess) return fail(c, SBN_ENOMEM, "hipMalloc polyeval state: %s", hipGetErrorString(e));
-  struct Drop { sbn_ctx* c; sbn_bullet* s; ~Drop() { hipStreamSynchronize(c->stream); pool_put(c, s->slab, s->slab_bytes); } } drop{c, &st};
+  SlabLease slab(c);
+  if ((rc = slab.get((5 * n + 2 * (n + 2) + 2) * 32, "polyeval state"))) return rc;     // the bullet state's layout (bullet_begin_impl)
+  st.slab = slab.p; st.slab_bytes = slab.bytes;
   uint8_t* p0 = (uint8_t*)st.slab; st.d_a = p0; st.d_b = p0 + 32 * n; st.d_s = p0 + 64 * n; st.d_a2 = p0 + 96 * n; st.d_b2 = p0 + 128 * n;
   st.d_w = p0 + 160 * n; st.d_dots = p0 + 160 * n + 64 * (n + 2);
   uint32_t* W0 = (uint32_t*)st.d_w; uint32_t* W1 = W0 + 8 * (n + 1); uint32_t* BL = W1 + 8 * (n + 1);
@@ -85,9 +72,7 @@ static int polyeval_prove_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_ta
 
   // ---- front: L, R, L*Z, <blinds, L>, the Cx / Cy rows; one two-row commit ----
   {
-    PolyEvalPoint pt; memset(&pt, 0, sizeof pt);
-    for (size_t j = 0; j < ml; j++) { const El x = to_dev_mont(el_from(r + 32 * j)); memcpy(pt.l[j], x.v, 32); }
-    for (size_t j = 0; j < mr; j++) { const El x = to_dev_mont(el_from(r + 32 * (ml + j))); memcpy(pt.r[j], x.v, 32); }
+    const PolyEvalPoint pt = opening_point(sh, r);
     if (blinds) {
       memcpy((uint8_t*)c->pin + 4096, blinds, L_size * 32);
       HIPCHK(c, hipMemcpyAsync(d_blinds, (uint8_t*)c->pin + 4096, L_size * 32, hipMemcpyHostToDevice, c->stream));
@@ -179,29 +164,6 @@ int sbn_polyeval_prove(sbn_ctx* c, const sbn_bases* gens, const sbn_table* Z, co
 }
 
 }  // extern "C"
-// the reduction both builds' joint openings start with (sparse_mlpoly_full.rs:384-397, :514-535): the evals under `label_evals`, lc challenges, the fold
-// of the evals from the last challenge down, the joint claim under `label_claim`.  rj: the lc challenges, then r; claim: canonical
-static void joint_reduce(const uint8_t* evals, size_t count, size_t lc, sbn_host::Label label_evals, sbn_host::Label label_chal, sbn_host::Label label_claim,
-                         const uint8_t* r, size_t ell_r, sbn_host::MerlinTranscript& t, std::vector<uint8_t>& rj, uint8_t claim[32]) {
-  using namespace sbn_host::fr;
-  const size_t ell = lc + ell_r;
-  sbn_host::Script ts{t};
-  ts.scalars(label_evals, evals, count);                           // sparse_mlpoly_full.rs:384
-  rj.assign(32 * ell, 0);
-  ts.challenges(label_chal, rj.data(), lc);                        // :387
-  if (ell_r) memcpy(&rj[32 * lc], r, 32 * ell_r);
-  std::vector<El> pe(count);
-  for (size_t i = 0; i < count; i++) pe[i] = el_from(evals + 32 * i);
-  size_t len = count;
-  for (size_t j = lc; j-- > 0;) {                                  // bound_poly_var_bot from the last challenge down (:389-391, hyrax.rs:206-214)
-    const El cj = to_m(el_from(&rj[32 * j]));
-    len /= 2;
-    for (size_t i = 0; i < len; i++) pe[i] = add(pe[2 * i], mmul(cj, sub(pe[2 * i + 1], pe[2 * i])));
-  }
-  memcpy(claim, pe[0].v, 32);
-  ts.scalar(label_claim, claim);                                   // :397
-}
-
 // the reduction and the opening on the transcript `t` (a copy of the caller's); count = 2^lc evals, canonical as r is; the caller holds the
 // context's mutex.  out_challenges: lc x 32 or NULL
 static int joint_opening_locked(sbn_ctx* c, const sbn_bases* gens, const sbn_table* Z, const uint8_t* evals, size_t count, size_t lc,

@@ -1,6 +1,7 @@
 // abi_proof_common.inc — what the one-call provers share on the host beside their transcript script (proof_host.hpp) and their derived generator
 // sets (abi_msm.inc: derived_set): a row commit whose points the host needs (rows_to_host_launch / _collect: the commit, the hand-over kernel, the
-// one wait, affine bytes) and the envelope of a prover that keeps its transcript on the host (prove_on_copy).  Included by sbn254.hip.
+// one wait, affine bytes) and the envelope of a prover that keeps its transcript on the host (prove_on_copy).  The verifiers' counterpart is
+// abi_verify_common.inc.  Included by sbn254.hip.
 
 // `nrows` rows of R canonical scalars (and their blinds, or null) as ONE commit over `ext`; the XYZZ sums and the `nextra` words at `extra` that
 // travel with them go to the host mailbox from word `slot_word` on, the flag to word `flag_word` — launches only; *seq is what

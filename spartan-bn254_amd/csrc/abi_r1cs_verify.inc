@@ -1,6 +1,7 @@
 // abi_r1cs_verify.inc — C ABI: R1CSProof::verify (r1csproof.rs:463-619) and ZKSumcheckInstanceProof::verify (sumcheck.rs:366-457) in ONE call each,
 // with DotProductProof::verify (nizk/mod.rs:368-400), KnowledgeProof / ProductProof / EqualityProof::verify (nizk/mod.rs:61-81, :243-283, :126-149)
-// and the Merlin transcript inside.  The opening of comm_vars is polyeval_verify_locked (abi_polyeval_verify.inc) on a handle made of the proof's bytes.
+// and the Merlin transcript inside.  The opening of comm_vars is polyeval_verify_locked (abi_polyeval_verify.inc) on a handle made of the proof's bytes
+// (bases_from_compressed_locked, abi_verify_common.inc).
 //
 // No fresh point is ever multiplied.  Every point of a check is a point of the proof or a generator, every coefficient a scalar the host derives
 // from the transcript — c * Cy_i = (c w0) P_{i-1} + (c w1) comm_eval_i, and so on down to the proof's own points — so every check is a sum of
@@ -9,7 +10,9 @@
 // two equality proofs) is one such sum and one host wait: the kernel writes it to the hand-over area itself, the host brings it to affine form.
 // Every equation, moved to one side, waits for the call's last launch, which answers "the sum is the identity" for all of them as packed
 // bits.  Negated coefficients are r - x on the host; no scalar multiplication and no point addition runs on the CPU.
-// Included by sbn254.hip.
+// The envelope (verify_on_copy), the hand-over area (vbox_ensure) and the device state's lease (SlabLease) are abi_verify_common.inc and ctx.hpp,
+// g1_compressed_normalise and g1_xy_valid verify_host.hpp.
+// Included by sbn254.hip; needs abi_verify_common.inc and abi_polyeval_verify.inc.
 
 struct VSum {
   uint32_t n = 0; uint32_t idx[SEL_TERMS_MAX]; sbn_host::fr::El s[SEL_TERMS_MAX];
@@ -23,17 +26,14 @@ static inline size_t rv_pin_bytes(size_t np, size_t max_eq) { return RV_PIN_DESC
 
 // the device state of one call: the proof's points (compressed, canonical, flags, table layout), descriptors, sums, verdict bits, the table
 struct VerifyRun {
-  sbn_ctx* c; void* slab = nullptr; size_t slab_bytes = 0;
+  sbn_ctx* c; SlabLease slab;
   size_t np = 0, ntab = 0, max_eq = 0;
   uint32_t *d_comp = nullptr, *d_canon = nullptr, *d_mont = nullptr, *d_claim = nullptr, *d_desc = nullptr, *d_out = nullptr, *d_bits = nullptr, *d_table = nullptr;
   uint8_t* d_ok = nullptr;
   uint32_t xy_idx = 0; uint8_t xy[64];               // the one proof point the host needs in affine form, and its bytes once the first sum is back
   bool first = true, reject = false;                 // reject: a point of the proof does not decompress
   std::vector<VSum> eqs;
-  explicit VerifyRun(sbn_ctx* c_) : c(c_) {}
-  VerifyRun(const VerifyRun&) = delete;
-  VerifyRun& operator=(const VerifyRun&) = delete;
-  ~VerifyRun() { if (slab) { hipStreamSynchronize(c->stream); pool_put(c, slab, slab_bytes); } }
+  explicit VerifyRun(sbn_ctx* c_) : c(c_), slab(c_) {}
 };
 
 // the proof's np compressed points (identity normalised) to the device, ONE decompress launch, ONE table launch over them and the generators in
@@ -52,9 +52,8 @@ static int rv_begin(VerifyRun& V, const uint8_t* comp, size_t np, Pow2Src src, c
   const size_t o_comp = 0, o_canon = up(32 * np), o_ok = o_canon + 64 * np, o_mont = up(o_ok + 4 * ok_words), o_claim = up(o_mont + 64 * np), o_desc = o_claim + 256,
                o_out = up(o_desc + 4 * (size_t)SEL_DESC_WORDS * max_eq), o_bits = up(o_out + 128 * max_eq), o_table = up(o_bits + 4 * ((max_eq + 31) / 32)),
                total = o_table + 128 * (size_t)POW2_BITS * ntab;
-  hipError_t e = pool_get(c, total, &V.slab, &V.slab_bytes);
-  if (e != hipSuccess) { V.slab = nullptr; return fail(c, SBN_ENOMEM, "hipMalloc r1cs verify state: %s", hipGetErrorString(e)); }
-  uint8_t* p0 = (uint8_t*)V.slab;
+  if ((rc = V.slab.get(total, "r1cs verify state"))) return rc;
+  uint8_t* p0 = (uint8_t*)V.slab.p;
   V.d_comp = (uint32_t*)(p0 + o_comp); V.d_canon = (uint32_t*)(p0 + o_canon); V.d_ok = p0 + o_ok; V.d_mont = (uint32_t*)(p0 + o_mont); V.d_claim = (uint32_t*)(p0 + o_claim);
   V.d_desc = (uint32_t*)(p0 + o_desc); V.d_out = (uint32_t*)(p0 + o_out); V.d_bits = (uint32_t*)(p0 + o_bits); V.d_table = (uint32_t*)(p0 + o_table);
   uint8_t* pin = (uint8_t*)c->pin + RV_PIN_DESC + rv_desc_bytes(max_eq);      // (behind the descriptors, which the first sum stages while these copies may be in flight)
@@ -193,12 +192,6 @@ static int zk_verify_rounds(VerifyRun& V, sbn_host::Script& ts, const uint8_t* c
   return SBN_OK;
 }
 
-// a compressed point as the reference's deserialisation and serialisation leave it: the identity in the form sbn_g1_compress writes
-static inline void rv_normalise(const uint8_t in[32], uint8_t out[32]) {
-  memcpy(out, in, 32);
-  if (out[31] & 0x40) { memset(out, 0, 32); out[31] = 0x40; }
-}
-
 // EqualityProof::verify (nizk/mod.rs:126-149): C1 is a sum of table points, C2 and alpha are points of the proof
 static int rv_equality(VerifyRun& V, sbn_host::Script& ts, const VSum& C1, uint32_t iC2, const uint8_t* c2_comp, uint32_t iAlpha, const uint8_t* alpha_comp, const uint8_t* z, uint32_t iH1) {
   using namespace sbn_host::fr;
@@ -229,7 +222,7 @@ static int zk_sumcheck_verify_locked(sbn_ctx* c, const sbn_bases* g1, const sbn_
   int rc;
   if ((rc = ensure_pin(c, rv_pin_bytes(np, max_eq)))) return rc;
   std::vector<uint8_t> comp(32 * np);
-  for (size_t i = 0; i < rounds; i++) for (int k = 0; k < 4; k++) rv_normalise(proof + stride * i + 32 * k, comp.data() + 32 * (4 * i + k));
+  for (size_t i = 0; i < rounds; i++) for (int k = 0; k < 4; k++) g1_compressed_normalise(proof + stride * i + 32 * k, comp.data() + 32 * (4 * i + k));
   VerifyRun V(c);
   Pow2Src src; memset(&src, 0, sizeof src);
   src.n[1] = 1; src.p[2] = (const uint32_t*)g1->d_pts; src.n[2] = 2; src.p[3] = (const uint32_t*)gn->d_pts; src.n[3] = (uint32_t)N + 1;
@@ -279,13 +272,13 @@ static int r1cs_verify_locked(sbn_ctx* c, const R1csProofShape& s, const uint8_t
     if (rc == SBN_EINVAL && bad != SIZE_MAX) return SBN_OK;        // a row commitment does not decompress
     if (rc) return rc;
   }
-  struct DropBases { sbn_ctx* c; sbn_bases* b; ~DropBases() { sbn_bases_free(c, b); } } drop{c, comm};
+  struct FreeBases { sbn_ctx* c; sbn_bases* b; ~FreeBases() { sbn_bases_free(c, b); } } drop{c, comm};
 
   // the table's points: phase 1's rounds, phase 2's rounds, then the eleven others; the generators behind them
   const uint32_t b1 = 0, b2 = 4 * (uint32_t)s.nx, iAz = 4 * (uint32_t)nr, iBz = iAz + 1, iCz = iAz + 2, iPr = iAz + 3, iKa = iAz + 4, iPa = iAz + 5, iPb = iAz + 6, iPd = iAz + 7,
                  iE1 = iAz + 8, iE2 = iAz + 9, iCv = iAz + 10;
   std::vector<uint8_t> comp(32 * np);
-  auto put = [&](uint32_t idx, const uint8_t* b) { rv_normalise(b, comp.data() + 32 * (size_t)idx); };
+  auto put = [&](uint32_t idx, const uint8_t* b) { g1_compressed_normalise(b, comp.data() + 32 * (size_t)idx); };
   for (size_t i = 0; i < s.nx; i++) for (uint32_t k = 0; k < 4; k++) put(b1 + 4 * (uint32_t)i + k, o_sc1 + 320 * i + 32 * k);
   for (size_t i = 0; i < s.ny; i++) for (uint32_t k = 0; k < 4; k++) put(b2 + 4 * (uint32_t)i + k, o_sc2 + 288 * i + 32 * k);
   for (uint32_t k = 0; k < 4; k++) put(iAz + k, o_claims + 32 * k);
@@ -309,7 +302,7 @@ static int r1cs_verify_locked(sbn_ctx* c, const R1csProofShape& s, const uint8_t
   ts.protocol("R1CS proof");                                        // r1csproof.rs:478
   ts.scalars("input", input, num_inputs);
   ts.message("poly_commitment", "poly_commitment_begin", 21);
-  for (size_t i = 0; i < s.L; i++) { uint8_t b[32]; rv_normalise(o_comm + 32 * i, b); ts.point("poly_commitment_share", b); }
+  for (size_t i = 0; i < s.L; i++) { uint8_t b[32]; g1_compressed_normalise(o_comm + 32 * i, b); ts.point("poly_commitment_share", b); }
   ts.message("poly_commitment", "poly_commitment_end", 19);
   std::vector<uint8_t> tau(32 * s.nx);
   ts.challenges("challenge_tau", tau.data(), s.nx);

@@ -1,6 +1,5 @@
 // abi_tables.inc — C ABI: device-resident tables, sumcheck rounds, openings, derefs gather, network pieces (include/sbn254.h, B3 + 8f).
 // ---- tables + sumcheck rounds ----
-static inline sbn_host::fr::El el_from(const uint8_t b[32]) { sbn_host::fr::El e; memcpy(e.v, b, 32); return e; }
 static inline ScScalar scs_from(const sbn_host::fr::El& e) { ScScalar s; memcpy(s.v, e.v, 32); return s; }
 // the three constants of a hash layer on the host (a lone GPU lane took 11 us for them, once per call): g R, g^2 R^2 (one Montgomery product with
 // the plain integer ts gives ts g^2 R), (r - tau) R — canonical, passed as kernel arguments

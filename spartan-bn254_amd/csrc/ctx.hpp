@@ -54,8 +54,8 @@ struct sbn_ctx {
   uint32_t* d_bad = nullptr;                 // device word: scalars >= r met by the kernels that read the caller's input (input_check_*)
   uint32_t* h_bad = nullptr;                 // its pinned host copy
   uint32_t* mbox = nullptr; uint32_t mbox_seq = 0;   // coherent pinned mailbox of the single-launch sumcheck rounds (results + per-instance flags)
-  uint32_t* vbox = nullptr;                  // coherent pinned hand-over area of the opening check (abi_polyeval_verify.inc): staged sums, flags, the sequence word
-  uint32_t* sbox = nullptr; size_t sbox_words = 0;   // coherent pinned hand-over area of the window sums (abi_small_sums.inc): one flag per block, then the sums
+  uint32_t* vbox = nullptr;                  // coherent pinned hand-over area of the opening check (abi_verify_common.inc): staged sums, flags, the sequence word
+  uint32_t* sbox = nullptr; size_t sbox_words = 0;   // coherent pinned hand-over area of the window sums (abi_verify_common.inc): one flag per block, then the sums
   std::vector<std::pair<void*, size_t>> pool; size_t pool_bytes = 0;   // cached table buffers (see pool_get)
   uint64_t last_job[4] = {0, 0, 0, 0};      // window bits, windows, (digit, point) slots, buckets of the most recent bucket job
   uint64_t last_acc[6] = {0, 0, 0, 0, 0, 0};   // SEG, LPB, L, chunks, combine launches, quad combine of the most recent bucket job (sbn_prof_last_acc)
@@ -171,6 +171,21 @@ struct TableScope {
   sbn_table* give(sbn_table* t) { held.erase(std::find(held.begin(), held.end(), t)); return t; }     // to the caller: no longer the scope's
   void give_all() { held.clear(); }
   int done() { ok = true; return SBN_OK; }
+};
+
+// The pooled device state of one call (pool_get).  It goes back to the pool when the call ends, on any path, behind a wait for the stream: nothing
+// of the call stays queued on a buffer the next call may be handed.  `what` names the state in the out-of-memory message
+struct SlabLease {
+  sbn_ctx* c; void* p = nullptr; size_t bytes = 0;
+  explicit SlabLease(sbn_ctx* c_) : c(c_) {}
+  SlabLease(const SlabLease&) = delete;
+  SlabLease& operator=(const SlabLease&) = delete;
+  ~SlabLease() { if (p) { hipStreamSynchronize(c->stream); pool_put(c, p, bytes); } }
+  int get(size_t want, const char* what) {
+    const hipError_t e = pool_get(c, want, &p, &bytes);
+    if (e != hipSuccess) { p = nullptr; return fail(c, SBN_ENOMEM, "hipMalloc %s: %s", what, hipGetErrorString(e)); }
+    return SBN_OK;
+  }
 };
 
 static int ensure(sbn_ctx* c, DevBuf& b, size_t bytes) {

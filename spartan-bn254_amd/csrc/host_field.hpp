@@ -203,6 +203,13 @@ static inline El mul(const El& a, const El& b) {
   return acc;
 }
 static inline El from_u64(uint64_t x) { El r = {{x, 0, 0, 0}}; return r; }
+static inline El el_from(const uint8_t b[32]) { El e; memcpy(e.v, b, 32); return e; }
+// Scalar::from_bytes (scalar.rs:87-95) takes these 32 little-endian bytes: the value is below r
+static inline bool fr_canonical(const uint8_t b[32]) {
+  uint64_t v[4]; memcpy(v, b, 32);
+  for (int i = 3; i >= 0; i--) { if (v[i] < P[i]) return true; if (v[i] > P[i]) return false; }
+  return false;
+}
 static inline El inv_small(uint64_t k) {           // 1/k for k in {2, 6}: (r*m + 1)/k with the m that makes it divisible
   // r = 1 mod 2 and r = 1 mod 6 (r - 1 is divisible by 2^28 * 3), so (r*(k-1) + 1) / k is an integer < r and k times it is 1 mod r
   u128 carry = 1; uint64_t t[5];

@@ -215,14 +215,12 @@ static int bases_glv_table(sbn_ctx* c, const sbn_bases* b, const uint32_t** out)
   return SBN_OK;
 }
 
-// MSM over device-resident canonical scalars and Montgomery affine bases -> canonical affine bytes on the host
-// (b: the generator set d_bases belongs to, or null for points staged by the call — only a set keeps a GLV table)
-static int msm_device(sbn_ctx* c, const uint32_t* d_scal, const uint32_t* d_bases, size_t n, uint8_t out_xy[64], int* out_is_inf, const sbn_bases* b = nullptr) {
-  if (n == 0) { memset(out_xy, 0, 64); if (out_is_inf) *out_is_inf = 1; return SBN_OK; }
-  if (n > 0x7fffffffull) return fail(c, SBN_EINVAL, "msm: n=%zu exceeds 2^31-1", n);
+// The ONE plan of a single MSM of n terms (1 .. 2^31-1: the callers' check) over device-resident canonical scalars and Montgomery affine bases
+// (b: the generator set d_bases belongs to, or null for points staged by the call — only a set keeps a GLV table): the window shape, the
+// BucketJob and the GLV switch, with the table and the half-scalar buffer the GLV path allocates.  No launch of the job itself
+static int msm_single_plan(sbn_ctx* c, const MsmOverrides& o, const uint32_t* d_scal, const uint32_t* d_bases, size_t n, const sbn_bases* b, BucketJob* out) {
   BucketJob J; memset(&J, 0, sizeof J);
   J.mode = MODE_SINGLE;
-  const MsmOverrides o = msm_overrides_read();
   {
     int cm = 1; while ((1 << cm) < c->sort_rs_max) cm++;
     const bool s2 = sort2_applies(c, MODE_SINGLE, n, S2_C_MIN);
@@ -230,9 +228,8 @@ static int msm_device(sbn_ctx* c, const uint32_t* d_scal, const uint32_t* d_base
   }
   J.P = (size_t)J.s.W; J.threads = n; J.points = d_bases;
   J.da.scalars = d_scal; J.da.n = n; J.da.estride = n; J.da.bad = c->d_bad;
-  const bool glv = glv_applies(c, o, b, n, J.s);
-  int rc;
-  if (glv) {
+  if (glv_applies(c, o, b, n, J.s)) {
+    int rc;
     const uint32_t* tab;
     if ((rc = bases_glv_table(c, b, &tab))) return rc;
     if ((rc = ensure(c, c->glv_scal, 2 * n * 16))) return rc;
@@ -240,20 +237,50 @@ static int msm_device(sbn_ctx* c, const uint32_t* d_scal, const uint32_t* d_base
     J.da.scalars = (const uint32_t*)c->glv_scal.p; J.da.n = 2 * n; J.da.estride = 2 * n;
     J.glv = true; J.glv_gap = b->n + (b->has_h ? 1 : 0) - n;
   }
-  if ((rc = ensure_pin(c, std::max<size_t>(4096, J.P * 128)))) return rc;
-  if ((rc = input_check_begin(c))) return rc;
-  if (glv) LAUNCH(c, "k_glv_split", k_glv_split, (unsigned)((n + 255) / 256), 256, d_scal, n, (uint32_t*)c->glv_scal.p, c->d_bad);
-  if ((rc = run_bucket_job(c, J, o))) return rc;
+  *out = J;
+  return SBN_OK;
+}
+// the planned job, launches only: the J.s.W window sums (XYZZ) stay in c->wsum.  k_glv_split counts scalars >= r into c->d_bad
+static int msm_single_run(sbn_ctx* c, const MsmOverrides& o, const BucketJob& J, const uint32_t* d_scal, size_t n) {
+  if (J.glv) LAUNCH(c, "k_glv_split", k_glv_split, (unsigned)((n + 255) / 256), 256, d_scal, n, (uint32_t*)c->glv_scal.p, c->d_bad);
+  return run_bucket_job(c, J, o);
+}
+// plan and run, for a caller that hands the window sums over itself (the verifiers: abi_verify_common.inc); *shape: what fold_windows needs
+static int msm_single_launch(sbn_ctx* c, const uint32_t* d_scal, const uint32_t* d_bases, size_t n, const sbn_bases* b, MsmShape* shape) {
+  if (n == 0 || n > 0x7fffffffull) return fail(c, SBN_EINVAL, "msm: n=%zu is outside 1 .. 2^31-1", n);
+  const MsmOverrides o = msm_overrides_read();
+  BucketJob J;
+  int rc;
+  if ((rc = msm_single_plan(c, o, d_scal, d_bases, n, b, &J))) return rc;
+  if ((rc = msm_single_run(c, o, J, d_scal, n))) return rc;
+  *shape = J.s;
+  return SBN_OK;
+}
+// sum_w 2^(c w) S_w over W window sums as the device left them: the 254-doubling serial chain, on the host.  The one fold of every bucket job's
+// and every k_window_sums launch's sums
+static sbn_host::Pt fold_windows(const sbn_host::Pt* S, int W, int c) {
+  std::vector<sbn_host::Pt> T((size_t)W);
+  for (int w = 0; w < W; w++) T[(size_t)w] = sbn_host::pt_from_device(S[w]);
+  return sbn_host::combine_windows(T.data(), W, c);
+}
+
+// MSM over device-resident canonical scalars and Montgomery affine bases -> canonical affine bytes on the host (b: as msm_single_plan takes it)
+static int msm_device(sbn_ctx* c, const uint32_t* d_scal, const uint32_t* d_bases, size_t n, uint8_t out_xy[64], int* out_is_inf, const sbn_bases* b = nullptr) {
+  if (n == 0) { memset(out_xy, 0, 64); if (out_is_inf) *out_is_inf = 1; return SBN_OK; }
+  if (n > 0x7fffffffull) return fail(c, SBN_EINVAL, "msm: n=%zu exceeds 2^31-1", n);
+  const MsmOverrides o = msm_overrides_read();
+  BucketJob J;
+  int rc;
+  if ((rc = msm_single_plan(c, o, d_scal, d_bases, n, b, &J))) return rc;
+  if ((rc = ensure_pin(c, std::max<size_t>(4096, J.P * 128)))) return rc;      // sized from the shape the plan ends up with
+  if ((rc = input_check_begin(c))) return rc;                                   // ahead of k_glv_split, which counts into c->d_bad
+  if ((rc = msm_single_run(c, o, J, d_scal, n))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->pin, c->wsum.p, J.P * 128, hipMemcpyDeviceToHost, c->stream));
   if ((rc = input_check_fetch(c))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->prof) prof_drain(c);
   if ((rc = input_check_end(c))) return rc;
-  // sum_w 2^(c w) S_w: the 254-doubling serial chain, on the host
-  std::vector<sbn_host::Pt> S((size_t)J.s.W);
-  for (int w = 0; w < J.s.W; w++) S[(size_t)w] = sbn_host::pt_from_device(((const sbn_host::Pt*)c->pin)[w]);
-  sbn_host::Pt total = sbn_host::combine_windows(S.data(), J.s.W, J.s.c);
-  sbn_host::to_affine_bytes(total, out_xy, out_is_inf);
+  sbn_host::to_affine_bytes(fold_windows((const sbn_host::Pt*)c->pin, J.s.W, J.s.c), out_xy, out_is_inf);
   return SBN_OK;
 }
 

@@ -45,6 +45,7 @@
 #include "host_keccak.hpp"
 #include "host_strobe.hpp"
 #include "proof_host.hpp"
+#include "verify_host.hpp"
 #include "sparse_verify_host.hpp"
 #include "snark_host.hpp"
 #include "circom_host.hpp"
@@ -68,6 +69,11 @@
 #include <vector>
 
 using namespace sbn;
+// the host vocabulary of host_field.hpp and verify_host.hpp that the abi_*.inc files call by its short names
+using sbn_host::fr::el_from; using sbn_host::fr::fr_canonical;
+using sbn_host::g1_xy_valid; using sbn_host::g1_compressed_normalise; using sbn_host::g1_is_identity; using sbn_host::g1_neg_bytes; using sbn_host::fr_neg_bytes;
+using sbn_host::fq_to_dev_mont; using sbn_host::OpeningShape; using sbn_host::opening_shape; using sbn_host::polyeval_host_eq; using sbn_host::joint_reduce;
+using sbn_host::polyeval_verify_script; using sbn_host::polyeval_verify_scalars; using sbn_host::PolyevalFinal;
 
 #include "ctx.hpp"
 #include "msm_host.hpp"
@@ -78,6 +84,7 @@ using namespace sbn;
 #include "abi_sumcheck.inc"
 #include "abi_product_proof.inc"
 #include "abi_proof_common.inc"
+#include "abi_verify_common.inc"
 #include "abi_bullet.inc"
 #include "abi_polyeval.inc"
 #include "abi_polyeval_verify.inc"
