@@ -157,60 +157,7 @@ __global__ void __launch_bounds__(64) k_pp_unscale(uint32_t* __restrict__ fin, c
 // blocks per dot-product circuit of k_pp_dotp over tables of `len` entries; the partial sums need SC_PACK_MAX * pp_dotp_grid(len) * 32 bytes of c->sc_partial
 static inline size_t pp_dotp_grid(size_t len) { return std::min<size_t>(std::max<size_t>(1, (len + 255) / 256), 1024); }
 
-// One boundary's transcript work from the phase (pos, pos_begin, cur_flags): the records k_tr_layer_step executes.
-//   close (n_close > 0): append_scalar("claim_prod_left" / "claim_prod_right") per circuit, ("claim_dotp_left" / "_right" / "_weight") per
-//   dot-product circuit (product_tree.rs:352-365; append_scalar = append_message of the 32 canonical bytes, transcript.rs:28-32), then
-//   challenge_scalar("challenge_r_layer"); open: n_open x challenge_scalar("rand_coeffs_next_layer") (challenge_vector, transcript.rs:69-73).
-// The appended values are the closing layer's final claims in the order of sbn_sumcheck_finish: data index = table index.
-static int transcript_plan_boundary(uint8_t pos, uint8_t pos_begin, uint8_t cur_flags, size_t n_close, size_t n_dotp_close, size_t n_open, std::vector<uint8_t>& recs, uint8_t end[3]) {
-  using S = sbn_host::StrobeT<sbn_host::StrobePlan>;
-  sbn_host::MerlinTranscriptT<sbn_host::StrobePlan> p;
-  memset(p.s.st, 0, sizeof p.s.st);
-  p.s.pos = pos; p.s.pos_begin = pos_begin; p.s.cur_flags = cur_flags;
-  std::vector<uint8_t> masks; p.s.perm.blocks = &masks;
-  struct Put { size_t lin; size_t table; };
-  std::vector<Put> puts; std::vector<size_t> chal;
-  const uint8_t zero[32] = {0}; const uint8_t n32[4] = {32, 0, 0, 0};
-  auto append = [&](const char* label, size_t table) {
-    p.s.meta_ad((const uint8_t*)label, strlen(label), false); p.s.meta_ad(n32, 4, true);
-    p.s.begin_op(S::FLAG_A, false);                                   // ad's header; the 32 bytes follow from here
-    puts.push_back({masks.size() / 200 * (size_t)S::RATE + p.s.pos, table});
-    p.s.absorb(zero, 32);
-  };
-  auto challenge = [&](const char* label) {
-    uint8_t out[64];
-    p.challenge_bytes((const uint8_t*)label, strlen(label), out, 64);
-    chal.push_back(masks.size() / 200);                               // blocks completed when the 64 bytes are read
-    return p.s.pos == 64 && masks.size() >= 200;
-  };
-  bool ok = true;
-  if (n_close) {
-    for (size_t i = 0; i < n_close; i++) { append("claim_prod_left", i); append("claim_prod_right", n_close + i); }
-    const size_t o = 2 * n_close + 1;
-    for (size_t k = 0; k < n_dotp_close; k++) { append("claim_dotp_left", o + k); append("claim_dotp_right", o + n_dotp_close + k); append("claim_dotp_weight", o + 2 * n_dotp_close + k); }
-    ok = challenge("challenge_r_layer") && ok;
-  }
-  for (size_t i = 0; i < n_open; i++) ok = challenge("rand_coeffs_next_layer") && ok;
-  const size_t nblk = masks.size() / 200;
-  for (size_t k = 0; k < chal.size(); k++) if (chal[k] == 0 || chal[k] > nblk || (k && chal[k] <= chal[k - 1])) ok = false;   // one challenge per block at most, each behind a permutation of this step
-  if (!ok || chal.empty() || chal.back() != nblk) return SBN_EINVAL;
-  recs.assign(nblk * (size_t)TR_REC_BYTES, 0);
-  for (size_t b = 0; b < nblk; b++) {
-    uint8_t* rec = recs.data() + b * TR_REC_BYTES;
-    memcpy(rec, masks.data() + 200 * b, 200);
-    memset(rec + TR_REC_SRC, 0xff, 336);
-  }
-  for (size_t b : chal) recs[(b - 1) * TR_REC_BYTES + TR_REC_FLAGS] = 1;
-  for (const Put& q : puts)
-    for (size_t o = 0; o < 32; o++) {
-      const size_t lin = q.lin + o, b = lin / S::RATE, at = lin % S::RATE;
-      if (b >= nblk) return SBN_EINVAL;
-      const uint16_t idx = (uint16_t)(32 * q.table + o);
-      memcpy(recs.data() + b * TR_REC_BYTES + TR_REC_SRC + 2 * at, &idx, 2);
-    }
-  end[0] = p.s.pos; end[1] = p.s.pos_begin; end[2] = p.s.cur_flags;
-  return SBN_OK;
-}
+#include "transcript_plan.hpp"      // transcript_plan_boundary: the records k_tr_layer_step executes, one boundary's transcript work
 
 // the job itself; the caller holds the mutex and has checked the arguments.  dotp_partials_present: the caller has just run k_pp_dotp over these
 // dot-product circuits with this job's grid (dotp_grid) into c->sc_partial and nothing has written there since: the pass is not repeated.  force_plain: every layer in PLAIN mode (the rerun behind a zero

@@ -1,24 +1,8 @@
-// abi_transcript.inc — C ABI: a Merlin v1.0 transcript (merlin::Transcript as src/transcript.rs uses it) on the host, and the
-// plan of a sumcheck round's transcript work that the device step executes (transcript_kernels.cuh).  No context, no device.
+// abi_transcript.inc — C ABI: a Merlin v1.0 transcript (merlin::Transcript as src/transcript.rs uses it) on the host.  The plan of a
+// sumcheck round's transcript work that the device step executes (transcript_kernels.cuh) is transcript_plan.hpp's.  No context, no device.
+#include "transcript_plan.hpp"      // transcript_plan_round
 
 struct sbn_transcript { sbn_host::MerlinTranscript t; };
-
-// One sumcheck round's seven transcript operations (unipoly.rs:117-122 + challenge_scalar("challenge_nextround")) from the phase
-// (pos, pos_begin): the XOR mask of every block the round completes (200 bytes each; labels, lengths, operation headers, padding),
-// coefficient bytes left zero.  The round ends behind the PRF's 64 bytes: pos = 64, pos_begin = 0, cur_flags = I|A|C.
-static void transcript_plan_round(uint8_t pos, uint8_t pos_begin, uint8_t cur_flags, std::vector<uint8_t>& masks, uint8_t end[3]) {
-  sbn_host::MerlinTranscriptT<sbn_host::StrobePlan> p;
-  memset(p.s.st, 0, sizeof p.s.st);
-  p.s.pos = pos; p.s.pos_begin = pos_begin; p.s.cur_flags = cur_flags;
-  masks.clear(); p.s.perm.blocks = &masks;
-  const uint8_t zero[32] = {0};
-  uint8_t out[64];
-  p.append_message((const uint8_t*)"poly", 4, (const uint8_t*)"UniPoly_begin", 13);
-  for (int k = 0; k < 4; k++) p.append_message((const uint8_t*)"coeff", 5, zero, 32);
-  p.append_message((const uint8_t*)"poly", 4, (const uint8_t*)"UniPoly_end", 11);
-  p.challenge_bytes((const uint8_t*)"challenge_nextround", 19, out, 64);
-  end[0] = p.s.pos; end[1] = p.s.pos_begin; end[2] = p.s.cur_flags;
-}
 
 extern "C" {
 

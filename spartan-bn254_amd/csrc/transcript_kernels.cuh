@@ -6,7 +6,7 @@
 //   * Keccak-f[1600] runs with ONE 64-bit state lane per SIMD lane (25 of 64 active): theta's column parities, pi and chi's row
 //     neighbours are wave shuffles (ds_bpermute through __shfl, nine 64-bit exchanges per round in three dependent steps), rho a per-lane rotate count.
 //   * STROBE's bookkeeping (operation headers, lengths, labels, the run_f padding bytes, where the blocks end) depends on the
-//     phase `pos` alone, never on a value, so the host plans it with its own Strobe code (host_strobe.hpp, StrobePlan) as
+//     phase `pos` alone, never on a value, so the host plans it with its own Strobe code (transcript_plan.hpp over host_strobe.hpp's StrobePlan) as
 //     one 200-byte XOR mask per block; the step XORs mask and coefficient bytes into the state, eight bytes per lane, at
 //     whatever phase the round starts.  A round is two blocks (three when the first round starts at pos >= 78).
 //   * field work is laid out so that independent products share one instruction stream: different lanes, same fe_mul.
@@ -14,13 +14,9 @@
 #pragma once
 #include "fp.cuh"
 #include "sumcheck_kernels.cuh"
+#include "transcript_plan.hpp"      // TR_RATE, TR_COEFF_*, TR_REC_*: the layout the host plans and the steps execute
 
 namespace sbn {
-
-constexpr int TR_RATE = 166;                 // STROBE-128
-constexpr int TR_ROUND_STREAM = 255;         // bytes one sumcheck round absorbs ahead of the PRF's permutation
-constexpr int TR_COEFF_FIRST = 38;           // offset of the first coefficient's 32 bytes in that stream: 25 ("poly" / "UniPoly_begin") + 13
-constexpr int TR_COEFF_STRIDE = 45;          // 2 + 5 + 4 + 2 + 32 per "coeff" message
 
 struct TrConst { uint32_t rho[25]; uint32_t rc[24][2]; };
 __host__ __device__ constexpr TrConst tr_make_const() {
@@ -197,12 +193,10 @@ __global__ void __launch_bounds__(64) k_tr_sumcheck_step(TrStepArgs A) {
 // folds claims_to_verify[i] = l_i + r_layer (r_i - l_i) (:370-372), then opens the next layer: n challenge_scalar("rand_coeffs_next_layer")
 // and the joint claim sum_i claims_to_verify[i] c_i (:317-321).  One wavefront does "close" and/or "open" in ONE launch.  No appended value
 // depends on a challenge of the same step, so the step runs the whole sponge first and does the field work behind it.
-// The host plans every block as one record (abi_product_proof.inc, transcript_plan_boundary): the XOR mask (labels, lengths, headers,
+// The host plans every block as one record (transcript_plan.hpp, transcript_plan_boundary): the XOR mask (labels, lengths, headers,
 // padding), a flag "a 64-byte challenge is read behind this block's permutation", and for each of the 166 rate bytes the index of the
 // data byte XORed there (the closing layer's final claims, canonical, 32 bytes each) or 0xffff.  Keccak-f and the lane layout are
 // k_tr_sumcheck_step's.
-constexpr int TR_REC_BYTES = 544;            // 200 mask, 8 flags, 168 x 2 byte sources
-constexpr int TR_REC_FLAGS = 200, TR_REC_SRC = 208;
 constexpr int TR_LAYER_DATA_MAX = 80;        // scalars staged for the appends (SC_FINAL_MAX: one per table of the largest sumcheck)
 constexpr int TR_LAYER_CHAL_MAX = SC_PACK_MAX + 1;
 struct TrLayerArgs {

@@ -8,21 +8,11 @@ import product_proof_model as pm
 import pyref
 import transcript_model as tm
 from conftest import fr_bytes
+from transcript_phase_lib import _against_model, _ints
 
 pytestmark = pytest.mark.gpu
 R = pyref.R
 SBN_EINVAL = -1          # include/sbn254.h
-
-
-def _ints(b):
-    return [int.from_bytes(b[32 * i:32 * i + 32], "little") for i in range(len(b) // 32)]
-
-
-def _upload_circuits(ctx, inputs):
-    """inputs: per circuit a list of ints (2^L) -> layers[i][j] (Tables: the input, then sbn_product_circuit_many's layers down to two entries), all tables made"""
-    ins = [ctx.table_upload(fr_bytes(v)) for v in inputs]
-    pcs = ctx.product_circuit_many(ins)
-    return [[ins[i]] + pcs[i][:-1] for i in range(len(ins))], [t for pc in pcs for t in pc] + ins
 
 
 def _dotp_claims(ctx, dtabs):
@@ -75,43 +65,6 @@ def _loop(ctx, sbn, layers, dotps, tr, dotp_claims):
     for t in tops:
         t[0].free(); t[1].free()
     return polys, claims + dclaims, fr_bytes(rand), fr_bytes(claims_to_verify)
-
-
-def _case_inputs(n_circ, n_dotp, L, seed, kind="uniform"):
-    N, h = 1 << L, 1 << (L - 1)
-    vals = pyref.prng_scalars(n_circ * N + 3 * n_dotp * h, seed)
-    if kind == "zero_entries":
-        vals = [0 if i % 5 == 0 else v for i, v in enumerate(vals)]
-    elif kind == "zero_product":
-        vals[3] = 0
-    elif kind == "ones":
-        vals = [1] * len(vals)
-    ins = [vals[i * N:(i + 1) * N] for i in range(n_circ)]
-    o = n_circ * N
-    dots = [tuple(vals[o + (3 * k + t) * h:o + (3 * k + t + 1) * h] for t in range(3)) for k in range(n_dotp)]
-    return ins, dots
-
-
-def _against_model(ctx, sbn, n_circ, n_dotp, L, seed, kind="uniform"):
-    ins, dots = _case_inputs(n_circ, n_dotp, L, seed, kind)
-    layers, owned = _upload_circuits(ctx, ins)
-    dtabs = [tuple(ctx.table_upload(fr_bytes(t)) for t in d) for d in dots]
-    try:
-        tr = sbn.Transcript(b"product proof test"); m = tm.Transcript(b"product proof test")
-        got = ctx.product_proof_prove(layers, dtabs, tr)
-        circuits = [pm.product_circuit(v) for v in ins]
-        want = pm.prove(m, circuits, dots)
-        flat = pm.proof_to_flat(want)
-        for name, g, w in zip(("out_polys", "out_claims", "out_rand", "out_claims_final"), got, flat):
-            assert g == w, (name, n_circ, n_dotp, L, kind)
-        assert tr.state() == m.state(), (n_circ, n_dotp, L, kind)
-        ok, _, _ = pm.verify(tm.Transcript(b"product proof test"), pm.proof_from_flat(*got, n_circ, n_dotp, L),
-                             [pm.circuit_evaluate(c) for c in circuits], [pm.dotp_evaluate(d) for d in dots], L)
-        assert ok
-        tr.free()
-    finally:
-        for t in owned + [t for d in dtabs for t in d]:
-            t.free()
 
 
 @pytest.mark.parametrize("n_circ", [1, 2, 4, 12, 16])
