@@ -959,6 +959,40 @@ int sbn_nizk_instance_from_circom(sbn_ctx* ctx, const sbn_circom_r1cs* f, const 
 int sbn_snark_encode_circom(sbn_ctx* ctx, const sbn_circom_r1cs* f, const sbn_snark_gens* gens, sbn_snark_key** out);
 int sbn_circom_wtns_load(sbn_ctx* ctx, const uint8_t* file, size_t len, size_t num_inputs, sbn_table** vars, uint8_t* input, size_t* num_witness);
 
+/* ---- the KZG SRS as a file buffer: KZGSrs::load_from_file / save_to_file / load_or_generate (kzg.rs:66-115), and a consistency check ----
+ * The file is what #[derive(CanonicalSerialize)] writes for KZGSrs { powers_g1, tau_g2, g2 } in compressed mode (ark-serialize 0.5):
+ *     n (u64 little-endian) | n x 32 B powers, each as sbn_g1_compress writes it | tau_g2 64 B | g2 64 B | anything (ignored)
+ * A compressed G2 point is x.c0 then x.c1 (32 B each, little-endian canonical), bit 7 of byte 63 = "y is the larger of y and -y" (Fq2 ordered by c1
+ * first, c0 on a tie), bit 6 = identity.
+ *
+ * sbn_kzg_srs_load: bytes in, resident handles out.  *out_srs is the handle sbn_kzg_srs_upload makes (no h, no duplicate map); *out_g2 and *out_tau_g2
+ *   are what sbn_g2_prepare makes of the file's g2 and tau_g2 (both NULL for a prover that never verifies); out_g2_xy (or NULL) receives g2 | tau_g2 as
+ *   128-byte canonical points.  The powers go up in chunks of SBN_SRS_CHUNK points (read when the context is created) through pinned staging, the copy
+ *   of one chunk beside the square roots of the one before; nothing but the Montgomery affine point is written per point.
+ *   Refused with SBN_EINVAL and the reason in sbn_last_error; no handle is left and the stream is drained.  The reference's own refusals: a file shorter
+ *   than its length field says, a power with x >= q, with x^3 + 3 not a square or with both flag bits set, a G2 coordinate >= q, both flag bits, a G2 x
+ *   with no y on the twist, a G2 point outside the r-torsion.  Beyond the reference: n = 0, an identity among the powers, an identity g2 or tau_g2 (no
+ *   SRS has them and every consumer divides by them, in effect).  For a power, *bad_index is the smallest refused index of the whole file and the text
+ *   names it; otherwise *bad_index is SIZE_MAX.
+ *   SBN_SRS_CHECK in flags runs sbn_kzg_srs_check on what was loaded, with a rho drawn from the OS; an inconsistent file is refused like a bad point.
+ *   Without it the file is loaded as the reference loads it: arkworks checks no relation between the points either.
+ * sbn_kzg_srs_check: *consistent <- 1 exactly when P_0 = (1, 2) — the G sbn_kzg_verify hard-wires — and e(P_{i+1}, g2) = e(P_i, tau_g2) for all
+ *   i < n - 1, the relations batched by the powers of rho: T = sum_i rho^i P_i (one MSM over the handle), A = T - P_0, B = rho T - rho^n P_{n-1},
+ *   e(A, g2) e(-B, tau_g2) == 1 (one pairing product).  A false accept has probability at most n / r over rho (Schwartz-Zippel), so the caller draws rho
+ *   AFTER the file is fixed.  rho = 0 or rho >= r: SBN_EINVAL.  For n = 1 the check is the P_0 test alone.
+ * sbn_kzg_srs_save: the bytes of save_to_file.  out = NULL is the size query: *out_len <- 8 + 32 n + 128.  cap below that: SBN_EINVAL, nothing written.
+ *   g2_xy, tau_g2_xy: 128-byte points as sbn_g2_prepare takes them (SBN_POINTS_MONT: ark-ff limbs), refused with SBN_EINVAL where it refuses them.
+ *   An all-zero point of the handle is written as the identity (31 zero bytes, 0x40).
+ * sbn_kzg_srs_g2_from_tau: host only.  g2 = arkworks' generator of G2, tau_g2 = [tau] g2, as canonical bytes: with sbn_kzg_srs_from_tau and the save,
+ *   the "generate" half of load_or_generate for a caller who supplies tau.  tau = 0 or tau >= r: SBN_EINVAL. */
+#define SBN_SRS_CHECK 1u
+int sbn_kzg_srs_load(sbn_ctx* ctx, const uint8_t* bytes, size_t len, uint32_t flags, sbn_bases** out_srs, sbn_g2_lines** out_g2, sbn_g2_lines** out_tau_g2,
+                     uint8_t out_g2_xy[256], size_t* bad_index);
+int sbn_kzg_srs_check(sbn_ctx* ctx, const sbn_bases* srs, const sbn_g2_lines* g2, const sbn_g2_lines* tau_g2, const uint8_t rho[32], int* consistent);
+int sbn_kzg_srs_save(sbn_ctx* ctx, const sbn_bases* srs, const uint8_t g2_xy[128], const uint8_t tau_g2_xy[128], uint32_t flags, uint8_t* out, size_t cap,
+                     size_t* out_len);
+int sbn_kzg_srs_g2_from_tau(const uint8_t tau[32], uint8_t out_g2_xy[128], uint8_t out_tau_g2_xy[128]);
+
 /* ---- per-kernel timing (HIP events on the context's stream), for bench.py's roofline line ---- */
 int sbn_prof_enable(sbn_ctx* ctx, int on);
 int sbn_prof_reset(sbn_ctx* ctx);

@@ -72,6 +72,7 @@ pub struct sbn_circom_info {
 pub const SBN_OK: c_int = 0;
 pub const SBN_SCALARS_MONT: u32 = 1;
 pub const SBN_POINTS_MONT: u32 = 2;
+pub const SBN_SRS_CHECK: u32 = 1;
 
 /// MSMs below this many terms stay on arkworks: the Σ-protocol steps commit 1–5 scalars at a time (`nizk/mod.rs`,
 /// `sumcheck.rs:539-634`) and a device call is a ~20 µs round trip + a ~0.3 ms latency-bound bucket pass.
@@ -267,6 +268,10 @@ extern "C" {
     pub fn sbn_nizk_instance_from_circom(ctx: *mut sbn_ctx, f: *const sbn_circom_r1cs, digest: *const u8, digest_len: usize, out: *mut *mut sbn_nizk_inst) -> c_int;
     pub fn sbn_snark_encode_circom(ctx: *mut sbn_ctx, f: *const sbn_circom_r1cs, gens: *const sbn_snark_gens, out: *mut *mut sbn_snark_key) -> c_int;
     pub fn sbn_circom_wtns_load(ctx: *mut sbn_ctx, file: *const u8, len: usize, num_inputs: usize, vars: *mut *mut sbn_table, input: *mut u8, num_witness: *mut usize) -> c_int;
+    pub fn sbn_kzg_srs_load(ctx: *mut sbn_ctx, bytes: *const u8, len: usize, flags: u32, out_srs: *mut *mut sbn_bases, out_g2: *mut *mut sbn_g2_lines, out_tau_g2: *mut *mut sbn_g2_lines, out_g2_xy: *mut u8, bad_index: *mut usize) -> c_int;
+    pub fn sbn_kzg_srs_check(ctx: *mut sbn_ctx, srs: *const sbn_bases, g2: *const sbn_g2_lines, tau_g2: *const sbn_g2_lines, rho: *const u8, consistent: *mut c_int) -> c_int;
+    pub fn sbn_kzg_srs_save(ctx: *mut sbn_ctx, srs: *const sbn_bases, g2_xy: *const u8, tau_g2_xy: *const u8, flags: u32, out: *mut u8, cap: usize, out_len: *mut usize) -> c_int;
+    pub fn sbn_kzg_srs_g2_from_tau(tau: *const u8, out_g2_xy: *mut u8, out_tau_g2_xy: *mut u8) -> c_int;
     pub fn sbn_prof_enable(ctx: *mut sbn_ctx, on: c_int) -> c_int;
     pub fn sbn_prof_reset(ctx: *mut sbn_ctx) -> c_int;
     pub fn sbn_prof_count(ctx: *mut sbn_ctx) -> c_int;
@@ -991,6 +996,34 @@ impl KzgSrs {
     }
     pub fn len(&self) -> usize { unsafe { sbn_bases_len(self.0) } }
     pub fn is_empty(&self) -> bool { self.len() == 0 }
+    /// KZGSrs::load_from_file (kzg.rs:79-88) on the file's bytes: the powers are decompressed on the device, the two G2 points on the host.
+    /// -> (the SRS, the prepared g2, the prepared tau_g2).  A refusal is the library's text: it names the reason and, for a power, its index.
+    /// `check_consistency`: also run the consistency check (SBN_SRS_CHECK), which arkworks' deserialisation does not.
+    pub fn load(bytes: &[u8], check_consistency: bool) -> Result<(KzgSrs, G2Lines, G2Lines), String> {
+        let (mut b, mut g2, mut tau_g2) = (null_mut(), null_mut(), null_mut());
+        let mut bad: usize = usize::MAX;
+        let flags = if check_consistency { SBN_SRS_CHECK } else { 0 };
+        let rc = unsafe { sbn_kzg_srs_load(ctx(), bytes.as_ptr(), bytes.len(), flags, &mut b, &mut g2, &mut tau_g2, null_mut(), &mut bad) };
+        if rc != SBN_OK {
+            return Err(unsafe { std::ffi::CStr::from_ptr(sbn_last_error(ctx())) }.to_string_lossy().into_owned());
+        }
+        Ok((KzgSrs(b), G2Lines(g2), G2Lines(tau_g2)))
+    }
+    /// KZGSrs::save_to_file (kzg.rs:66-77) as bytes; `g2_xy`, `tau_g2_xy`: G2Affine's in-memory x.c0, x.c1, y.c0, y.c1 (ark-ff Montgomery limbs)
+    pub fn save(&self, g2_xy: &[u8; 128], tau_g2_xy: &[u8; 128]) -> Vec<u8> {
+        let mut len: usize = 0;
+        check(unsafe { sbn_kzg_srs_save(ctx(), self.0, null(), null(), 0, null_mut(), 0, &mut len) });
+        let mut out = vec![0u8; len];
+        check(unsafe { sbn_kzg_srs_save(ctx(), self.0, g2_xy.as_ptr(), tau_g2_xy.as_ptr(), SBN_POINTS_MONT, out.as_mut_ptr(), out.len(), &mut len) });
+        out.truncate(len);
+        out
+    }
+    /// are the points the powers of one tau that matches tau_g2?  `rho`: drawn by the caller AFTER the file is fixed (non-zero)
+    pub fn check(&self, g2: &G2Lines, tau_g2: &G2Lines, rho: &Scalar) -> bool {
+        let mut consistent: c_int = 0;
+        check(unsafe { sbn_kzg_srs_check(ctx(), self.0, g2.0, tau_g2.0, rho.to_bytes().as_ptr(), &mut consistent) });
+        consistent != 0
+    }
 }
 /// KZGPolyCommitment::commit (kzg.rs:386-395) and KZGCommitment::commit (kzg.rs:132-147): the first min(n, srs len) coefficients
 pub fn kzg_commit(coeffs: &Table, n: usize, srs: &KzgSrs) -> GroupElement {

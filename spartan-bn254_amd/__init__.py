@@ -5,8 +5,8 @@ Rust shim would.  It contains no arithmetic and no fallback: if
 gfx950 device is missing, loading / context creation raises.
 """
 from .binding import (  # noqa: F401
-    Context, Group, Bases, Table, Dense, DerefsKey, SnarkGens, SnarkKey, NizkInst, CircomR1cs, SbnError, SbnUnsat, SBN_EUNSAT, SBN_SNARK_CHECK_SAT, lib, lib_path, build_library,
+    Context, Group, Bases, Table, Dense, DerefsKey, SnarkGens, SnarkKey, NizkInst, CircomR1cs, SbnError, SbnUnsat, SBN_EUNSAT, SBN_SNARK_CHECK_SAT, SBN_SRS_CHECK, kzg_srs_g2_from_tau, lib, lib_path, build_library,
     SBN_SCALARS_MONT, SBN_POINTS_MONT, g1_compress, g1_sum, Transcript, fr_from_wide, unipoly_from_evals, unipoly_eval, factored_lens, r1cs_proof_sizes, sparse_eval_sizes, sparse_eval_kzg_sizes, EXPORTED_SYMBOLS,
 )
 
-__version__ = "0.13.0"   # 13th extension of the C ABI's surface: sbn_sparse_eval_prove_kzg, sbn_derefs_key_*
+__version__ = "0.14.0"   # 14th extension of the C ABI's surface: sbn_kzg_srs_load, _check, _save, _g2_from_tau

@@ -36,9 +36,11 @@ EXPORTED_SYMBOLS = [
     "sbn_nizk_gens_new", "sbn_nizk_instance_new", "sbn_nizk_instance_free", "sbn_nizk_instance_r1cs", "sbn_nizk_sizes", "sbn_nizk_is_sat", "sbn_nizk_prove", "sbn_nizk_verify",
     "sbn_circom_r1cs_load", "sbn_circom_r1cs_info", "sbn_circom_r1cs_download", "sbn_circom_r1cs_free", "sbn_r1cs_from_circom", "sbn_nizk_instance_from_circom",
     "sbn_snark_encode_circom", "sbn_circom_wtns_load",
+    "sbn_kzg_srs_load", "sbn_kzg_srs_check", "sbn_kzg_srs_save", "sbn_kzg_srs_g2_from_tau",
 ]
 SBN_EUNSAT = -5
 SBN_SNARK_CHECK_SAT = 1
+SBN_SRS_CHECK = 1
 
 
 class SbnError(RuntimeError):
@@ -161,6 +163,10 @@ def lib():
         L.sbn_nizk_instance_from_circom.argtypes = [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]
         L.sbn_snark_encode_circom.argtypes = [C.c_void_p] * 4
         L.sbn_circom_wtns_load.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t] + [C.c_void_p] * 3
+        L.sbn_kzg_srs_load.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32] + [C.c_void_p] * 5
+        L.sbn_kzg_srs_check.argtypes = [C.c_void_p] * 6
+        L.sbn_kzg_srs_save.argtypes = [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sbn_kzg_srs_g2_from_tau.argtypes = [C.c_void_p] * 3
         _LIB = L
     return _LIB
 
@@ -243,6 +249,15 @@ def g1_compress(xy):
     if rc:
         raise SbnError(f"sbn_g1_compress rc={rc}")
     return bytes(out)
+
+
+def kzg_srs_g2_from_tau(tau):
+    """sbn_kzg_srs_g2_from_tau (host only) -> (g2_xy, tau_g2_xy): arkworks' G2 generator and [tau] of it, 128 canonical bytes each"""
+    g2 = (C.c_uint8 * 128)(); tg2 = (C.c_uint8 * 128)()
+    rc = lib().sbn_kzg_srs_g2_from_tau(_ptr(tau), g2, tg2)
+    if rc:
+        raise SbnError(f"sbn_kzg_srs_g2_from_tau rc={rc}: tau must be canonical and non-zero")
+    return bytes(g2), bytes(tg2)
 
 
 def g1_sum(xy):
@@ -1298,6 +1313,39 @@ class Context:
         hb = C.c_void_p()
         self._chk(lib().sbn_kzg_srs_from_tau(self.h, _ptr(tau), C.c_size_t(n), C.byref(hb)), "sbn_kzg_srs_from_tau")
         return Bases(self, hb)
+
+    def kzg_srs_load(self, data, flags=0, want_lines=True):
+        """sbn_kzg_srs_load on the bytes of an SRS file -> (Bases, G2Lines of g2 or None, G2Lines of tau_g2 or None, g2_xy, tau_g2_xy).  A refusal
+        raises SbnError with the index of the refused power in `.bad_index` (None where the refusal is not a power's)"""
+        hb, hg, ht = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        xy = (C.c_uint8 * 256)(); bad = C.c_size_t(0)
+        rc = lib().sbn_kzg_srs_load(self.h, _ptr(data) if len(data) else None, C.c_size_t(len(data)), C.c_uint32(flags), C.byref(hb),
+                                    C.byref(hg) if want_lines else None, C.byref(ht) if want_lines else None, xy, C.byref(bad))
+        if rc:
+            err = SbnError(f"sbn_kzg_srs_load: rc={rc}: {lib().sbn_last_error(self.h).decode()}")
+            err.bad_index = bad.value if bad.value != C.c_size_t(-1).value else None
+            err.handles = (hb.value, hg.value, ht.value)
+            raise err
+        raw = bytes(xy)
+        return Bases(self, hb), (G2Lines(self, hg) if want_lines else None), (G2Lines(self, ht) if want_lines else None), raw[:128], raw[128:]
+
+    def kzg_srs_check(self, srs, g2, tau_g2, rho):
+        """sbn_kzg_srs_check -> True when the handle's points are the powers of one tau that matches tau_g2 (batched by the powers of rho)"""
+        ok = C.c_int(0)
+        self._chk(lib().sbn_kzg_srs_check(self.h, srs.h, g2.h, tau_g2.h, _ptr(rho), C.byref(ok)), "sbn_kzg_srs_check")
+        return bool(ok.value)
+
+    def kzg_srs_save_size(self, srs):
+        n = C.c_size_t(0)
+        self._chk(lib().sbn_kzg_srs_save(self.h, srs.h, None, None, C.c_uint32(0), None, C.c_size_t(0), C.byref(n)), "sbn_kzg_srs_save")
+        return n.value
+
+    def kzg_srs_save(self, srs, g2_xy, tau_g2_xy, flags=0, out=None):
+        """sbn_kzg_srs_save -> the file's bytes.  `out`: a writable buffer (bytearray or numpy uint8) to fill instead; its length is the cap"""
+        buf = bytearray(self.kzg_srs_save_size(srs)) if out is None else out
+        n = C.c_size_t(0)
+        self._chk(lib().sbn_kzg_srs_save(self.h, srs.h, _ptr(g2_xy), _ptr(tau_g2_xy), C.c_uint32(flags), _ptr(buf), C.c_size_t(len(buf)), C.byref(n)), "sbn_kzg_srs_save")
+        return bytes(buf[:n.value]) if out is None else n.value
 
     def kzg_commit(self, srs, t, n=None):
         out = (C.c_uint8 * 64)(); inf = C.c_int()

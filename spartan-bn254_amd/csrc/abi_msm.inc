@@ -30,6 +30,7 @@ int sbn_ctx_create(int device, sbn_ctx** out) {
   c->sort2_ok = sort2_set_lds();
   if (const char* e2 = getenv("SBN_SORT2_MIN")) c->sort2_min = (size_t)strtoull(e2, nullptr, 0);
   if (const char* eg = getenv("SBN_MSM_GLV")) { const int v = atoi(eg); if (v == 0 || v == 1) c->msm_glv = v; }
+  if (const char* es = getenv("SBN_SRS_CHUNK")) { const long long v = atoll(es); if (v >= 1 && v <= (1ll << 26)) c->srs_chunk = (size_t)v; }   // tests: force many small chunks
   *out = c;
   return SBN_OK;
 }
@@ -43,6 +44,7 @@ void sbn_ctx_destroy(sbn_ctx* c) {
   for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
   for (auto& b : c->pool) hipFree(b.first);
   if (c->pin) hipHostFree(c->pin);
+  for (void* p : c->srs_pin) if (p) hipHostFree(p);
   if (c->d_bad) hipFree(c->d_bad);
   if (c->h_bad) hipHostFree(c->h_bad);
   if (c->mbox) hipHostFree(c->mbox);

@@ -44,6 +44,8 @@ struct sbn_ctx {
   DevBuf glv_scal;                           // GLV half-scalars of a single MSM (glv_kernels.cuh): 2n x 16 B
   DevBuf kzg_ws;                             // KZG division levels, evals and batched-opening arguments (abi_kzg.inc)
   DevBuf r1cs_ws;                            // R1CS SpMV carries and block sums (abi_r1cs.inc)
+  size_t srs_chunk = (size_t)1 << 18;        // points a chunk of sbn_kzg_srs_load / _save (SBN_SRS_CHUNK, read when the context is created)
+  void* srs_pin[2] = {nullptr, nullptr}; size_t srs_pin_cap = 0;   // their two pinned staging buffers (abi_kzg_srs.inc); the device side is zstage
   DevBuf dense_ws;                           // staged triplets and sort buffers of sbn_dense_build (abi_dense.inc)
   int msm_glv = -1;                          // single MSMs over the GLV endomorphism: -1 automatic (msm_host.hpp: glv_applies), 0 never, 1 wherever it can run (SBN_MSM_GLV)
   bool sort2_ok = false;      // dynamic LDS of its level-1 scatter granted

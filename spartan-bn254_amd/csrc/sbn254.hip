@@ -18,6 +18,7 @@
 //   KZGProof::verify, KZGBatchProof::batch_verify, Bn254::pairing  src/kzg.rs:196-217, :315-352 -> sbn_kzg_verify / _batched / sbn_pairing_products / sbn_g2_prepare
 //   NIZKGens::new, NIZK::prove, NIZK::verify            src/snark.rs:162-287 -> sbn_nizk_*
 //   R1CS::from_reader, to_sparse_matrices_padded, parse_wtns   src/r1cs_reader.rs:55-242, examples/keyless_benchmark.rs:38-72 -> sbn_circom_*
+//   KZGSrs::load_from_file, save_to_file, load_or_generate  src/kzg.rs:66-115 -> sbn_kzg_srs_load / _save / _check / _g2_from_tau
 //   the verifier's short sums of proof points (nizk/mod.rs:560-565, :389-394 as GroupElement::vartime_multiscalar_mul)          -> sbn_g1_small_sums
 // There is no CPU fallback in this file: every entry point needs the gfx950 device.
 #include "../../include/sbn254.h"
@@ -42,6 +43,7 @@
 #include "sparse_eval_kernels.cuh"
 #include "derefs_key_kernels.cuh"
 #include "pairing_kernels.cuh"
+#include "srs_kernels.cuh"
 #include "host_keccak.hpp"
 #include "host_strobe.hpp"
 #include "proof_host.hpp"
@@ -50,6 +52,7 @@
 #include "snark_host.hpp"
 #include "circom_host.hpp"
 #include "pairing_host.hpp"
+#include "srs_host.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -103,6 +106,7 @@ using sbn_host::polyeval_verify_script; using sbn_host::polyeval_verify_scalars;
 #include "abi_snark.inc"
 #include "abi_nizk.inc"
 #include "abi_circom.inc"
+#include "abi_kzg_srs.inc"
 
 extern "C" {
 
