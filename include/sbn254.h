@@ -959,6 +959,61 @@ int sbn_nizk_instance_from_circom(sbn_ctx* ctx, const sbn_circom_r1cs* f, const 
 int sbn_snark_encode_circom(sbn_ctx* ctx, const sbn_circom_r1cs* f, const sbn_snark_gens* gens, sbn_snark_key** out);
 int sbn_circom_wtns_load(sbn_ctx* ctx, const uint8_t* file, size_t len, size_t num_inputs, sbn_table** vars, uint8_t* input, size_t* num_witness);
 
+/* ---- a circuit digest computed on the device: the bytes sbn_nizk_instance_from_circom takes, for a caller who has no Rust side to ask ----
+ * THIS IS THE LIBRARY'S OWN DIGEST.  It is not the reference's R1CSShape::get_digest (zlib over bincode, r1cs.rs:97-101), which is not reproduced here:
+ * a NIZK proof made under one digest does not verify under the other.  Prover and verifier must both take this one, or both the reference's.
+ * It is defined over what sbn_circom_r1cs_download returns — kept entries in file order, remapped columns, canonical values — and not over the
+ * file's bytes, so the order of the file's sections and its dropped (>= r) entries do not change it:
+ *     leaf(m, j) = SHAKE256("sbn254/r1cs-digest/leaf/v1" | u8 m | u64le j | u32le k | k x (u32le row | u32le col | val[32]))[0..32]
+ *                  entries 128 j .. 128 j + k - 1 of matrix m,  k = min(128, nnz[m] - 128 j);  no leaf for nnz[m] = 0
+ *     root       = SHAKE256("sbn254/r1cs-digest/root/v1" | u64le num_constraints | num_variables | num_pub_inputs | num_cons_padded | num_vars_padded
+ *                           | for m = 0, 1, 2: u64le nnz[m] | the leaves of m in order)[0..32]
+ * with the five shape fields as sbn_circom_r1cs_info gives them.  A row, a column, a value, a shape field, the matrix an entry sits in and the order
+ * of two entries all change it.
+ * Work: ONE launch of k_circom_digest_leaves, a lane a leaf (Keccak-f[1600] on 25 lanes in registers, the leaf's 5 KiB read as dwords where the handle
+ * holds them), the leaves (32 B per 128 entries) brought back behind ONE host wait, and one SHAKE256 over them on the host (DESIGN 4.25 has the times).
+ * SBN_EINVAL: a NULL pointer.  A circuit without entries has a digest (the root over the shape and three zero counts) and launches nothing. */
+int sbn_circom_r1cs_digest(sbn_ctx* ctx, const sbn_circom_r1cs* f, uint8_t out[32]);
+
+/* ---- the prover's randomness: RandomTape (random.rs) and the draw plans that fill `rnd` for every one-call prover above.  Host only: no context,
+ *      no device.  A tape is a Merlin transcript of its own; a tape started from the same `init` gives the draws the reference's tape gives, so a Rust
+ *      caller and a C caller with one seed make one proof.  A Rust caller may equally keep its own tape and pass its draws as before. ----
+ * sbn_random_tape_new: RandomTape::new (random.rs:15-23): Transcript::new(name), append_scalar(b"init_randomness", init).  The reference's names are
+ *   b"snark_proof" (snark.rs:438) and b"proof" (snark.rs:210).  init: 32 canonical bytes (>= r: SBN_EINVAL), or NULL: 64 bytes from getrandom(2) reduced
+ *   mod r as a challenge is (sbn_fr_from_wide), which stands in for Scalar::random(&mut OsRng); a failure of getrandom is SBN_EOS with errno's text.
+ *   A fixed init makes a proof reproducible and its blinds predictable: it is for tests and for a caller that derives it from its own entropy.
+ * sbn_random_tape_scalars: random_scalar / random_vector (:25-31): n x challenge_scalar(label) (transcript.rs:56-71), n x 32 canonical bytes.  n = 0 and
+ *   an empty label (NULL with length 0) are legal.
+ * sbn_random_tape_free: wipes the state before it is released.  No call prints, logs or keeps init or a draw; error texts never hold one.
+ * sbn_random_tape_last_error: why the last call on this tape was refused; with NULL, why this thread's last sbn_random_tape_new was.
+ *
+ * Draw plans.  Each fills `out` exactly as the matching prove call documents its rnd, with the reference's labels in the reference's order, and
+ * advances the tape by those draws.  out_scalars is the caller's count and must equal the plan's, which is the one the matching *_sizes call gives;
+ * a refusal (SBN_EINVAL: a NULL pointer, a shape the *_sizes call refuses, another count) draws nothing and leaves the tape as it was.
+ *   sbn_zk_sumcheck_draw_rnd   num_rounds (n + 4), n = 4 (r1cs) or 3 (quad): blinds_poly[num_rounds], blinds_evals[num_rounds] (sumcheck.rs:483-484,
+ *                              :673-674), then per round d_vec[n], r_delta, r_beta (nizk/mod.rs:326-328)
+ *   sbn_polyeval_draw_rnd      3 + 2 lg, lg = the right half of sbn_factored_lens(ell): d, r_delta, r_beta, blinds_vec (nizk/mod.rs:458-464).  Two things
+ *                              are the reference's and are kept: r_beta is drawn under the label b"r_delta" (:460), and blinds_vec_1[lg] is drawn whole,
+ *                              then blinds_vec_2[lg], while rnd stores them as (v1[i], v2[i]) pairs
+ *   sbn_r1cs_proof_draw_rnd    sbn_r1cs_proof_sizes' count: poly_blinds[L] (r1csproof.rs:225), phase 1, Az_blind, Bz_blind, Cz_blind, prod_Az_Bz_blind
+ *                              (:318-321), t1, t2 (nizk/mod.rs:44-45), b1 .. b5 (:181-185), r (:108), phase 2, blind_eval (r1csproof.rs:410), the opening, r
+ *   sbn_sparse_eval_draw_rnd   sbn_sparse_eval_sizes' / _kzg_sizes' count (kzg = 0 / 1): the openings of derefs (Hyrax build only), ops, mem
+ *   sbn_snark_draw_rnd         sbn_snark_sizes' count: the R1CS proof's draws, then the sparse proof's, from ONE tape (name b"snark_proof")
+ *   sbn_nizk_draw_rnd          sbn_nizk_sizes' count: the R1CS proof's draws (name b"proof") */
+#define SBN_EOS (-6)               /* the operating system refused a request (getrandom) */
+typedef struct sbn_random_tape sbn_random_tape;
+int sbn_random_tape_new(const uint8_t* name, size_t name_len, const uint8_t* init /* 32 bytes, or NULL */, sbn_random_tape** out);
+int sbn_random_tape_scalars(sbn_random_tape* tape, const uint8_t* label, size_t label_len, size_t n, uint8_t* out);
+void sbn_random_tape_free(sbn_random_tape* tape);
+const char* sbn_random_tape_last_error(const sbn_random_tape* tape);
+int sbn_zk_sumcheck_draw_rnd(size_t num_rounds, size_t n, sbn_random_tape* tape, uint8_t* out, size_t out_scalars);
+int sbn_polyeval_draw_rnd(size_t ell, sbn_random_tape* tape, uint8_t* out, size_t out_scalars);
+int sbn_r1cs_proof_draw_rnd(size_t num_cons, size_t num_vars, sbn_random_tape* tape, uint8_t* out, size_t out_scalars);
+int sbn_sparse_eval_draw_rnd(size_t num_vars_x, size_t num_vars_y, size_t num_ops /* N */, size_t batch, int kzg, sbn_random_tape* tape, uint8_t* out,
+                             size_t out_scalars);
+int sbn_snark_draw_rnd(const sbn_snark_key* key, int kzg, sbn_random_tape* tape, uint8_t* out, size_t out_scalars);
+int sbn_nizk_draw_rnd(const sbn_nizk_inst* inst, sbn_random_tape* tape, uint8_t* out, size_t out_scalars);
+
 /* ---- the KZG SRS as a file buffer: KZGSrs::load_from_file / save_to_file / load_or_generate (kzg.rs:66-115), and a consistency check ----
  * The file is what #[derive(CanonicalSerialize)] writes for KZGSrs { powers_g1, tau_g2, g2 } in compressed mode (ark-serialize 0.5):
  *     n (u64 little-endian) | n x 32 B powers, each as sbn_g1_compress writes it | tau_g2 64 B | g2 64 B | anything (ignored)

@@ -61,6 +61,7 @@ use crate::unipoly::{CompressedUniPoly, UniPoly};
 #[repr(C)] pub struct sbn_snark_key { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_nizk_inst { _p: [u8; 0] }
 #[repr(C)] pub struct sbn_circom_r1cs { _p: [u8; 0] }
+#[repr(C)] pub struct sbn_random_tape { _p: [u8; 0] }
 /// what `sbn_circom_r1cs_info` fills: the file's header fields, the kept and dropped entries per matrix, the shape `Instance::new` gives
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct sbn_circom_info {
@@ -268,6 +269,17 @@ extern "C" {
     pub fn sbn_nizk_instance_from_circom(ctx: *mut sbn_ctx, f: *const sbn_circom_r1cs, digest: *const u8, digest_len: usize, out: *mut *mut sbn_nizk_inst) -> c_int;
     pub fn sbn_snark_encode_circom(ctx: *mut sbn_ctx, f: *const sbn_circom_r1cs, gens: *const sbn_snark_gens, out: *mut *mut sbn_snark_key) -> c_int;
     pub fn sbn_circom_wtns_load(ctx: *mut sbn_ctx, file: *const u8, len: usize, num_inputs: usize, vars: *mut *mut sbn_table, input: *mut u8, num_witness: *mut usize) -> c_int;
+    pub fn sbn_circom_r1cs_digest(ctx: *mut sbn_ctx, f: *const sbn_circom_r1cs, out: *mut u8) -> c_int;
+    pub fn sbn_random_tape_new(name: *const u8, name_len: usize, init: *const u8, out: *mut *mut sbn_random_tape) -> c_int;
+    pub fn sbn_random_tape_scalars(tape: *mut sbn_random_tape, label: *const u8, label_len: usize, n: usize, out: *mut u8) -> c_int;
+    pub fn sbn_random_tape_free(tape: *mut sbn_random_tape);
+    pub fn sbn_random_tape_last_error(tape: *const sbn_random_tape) -> *const c_char;
+    pub fn sbn_zk_sumcheck_draw_rnd(num_rounds: usize, n: usize, tape: *mut sbn_random_tape, out: *mut u8, out_scalars: usize) -> c_int;
+    pub fn sbn_polyeval_draw_rnd(ell: usize, tape: *mut sbn_random_tape, out: *mut u8, out_scalars: usize) -> c_int;
+    pub fn sbn_r1cs_proof_draw_rnd(num_cons: usize, num_vars: usize, tape: *mut sbn_random_tape, out: *mut u8, out_scalars: usize) -> c_int;
+    pub fn sbn_sparse_eval_draw_rnd(num_vars_x: usize, num_vars_y: usize, num_ops: usize, batch: usize, kzg: c_int, tape: *mut sbn_random_tape, out: *mut u8, out_scalars: usize) -> c_int;
+    pub fn sbn_snark_draw_rnd(key: *const sbn_snark_key, kzg: c_int, tape: *mut sbn_random_tape, out: *mut u8, out_scalars: usize) -> c_int;
+    pub fn sbn_nizk_draw_rnd(inst: *const sbn_nizk_inst, tape: *mut sbn_random_tape, out: *mut u8, out_scalars: usize) -> c_int;
     pub fn sbn_kzg_srs_load(ctx: *mut sbn_ctx, bytes: *const u8, len: usize, flags: u32, out_srs: *mut *mut sbn_bases, out_g2: *mut *mut sbn_g2_lines, out_tau_g2: *mut *mut sbn_g2_lines, out_g2_xy: *mut u8, bad_index: *mut usize) -> c_int;
     pub fn sbn_kzg_srs_check(ctx: *mut sbn_ctx, srs: *const sbn_bases, g2: *const sbn_g2_lines, tau_g2: *const sbn_g2_lines, rho: *const u8, consistent: *mut c_int) -> c_int;
     pub fn sbn_kzg_srs_save(ctx: *mut sbn_ctx, srs: *const sbn_bases, g2_xy: *const u8, tau_g2_xy: *const u8, flags: u32, out: *mut u8, cap: usize, out_len: *mut usize) -> c_int;

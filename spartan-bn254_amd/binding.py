@@ -37,6 +37,8 @@ EXPORTED_SYMBOLS = [
     "sbn_circom_r1cs_load", "sbn_circom_r1cs_info", "sbn_circom_r1cs_download", "sbn_circom_r1cs_free", "sbn_r1cs_from_circom", "sbn_nizk_instance_from_circom",
     "sbn_snark_encode_circom", "sbn_circom_wtns_load",
     "sbn_kzg_srs_load", "sbn_kzg_srs_check", "sbn_kzg_srs_save", "sbn_kzg_srs_g2_from_tau",
+    "sbn_circom_r1cs_digest", "sbn_random_tape_new", "sbn_random_tape_scalars", "sbn_random_tape_free", "sbn_random_tape_last_error",
+    "sbn_zk_sumcheck_draw_rnd", "sbn_polyeval_draw_rnd", "sbn_r1cs_proof_draw_rnd", "sbn_sparse_eval_draw_rnd", "sbn_snark_draw_rnd", "sbn_nizk_draw_rnd",
 ]
 SBN_EUNSAT = -5
 SBN_SNARK_CHECK_SAT = 1
@@ -167,6 +169,17 @@ def lib():
         L.sbn_kzg_srs_check.argtypes = [C.c_void_p] * 6
         L.sbn_kzg_srs_save.argtypes = [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
         L.sbn_kzg_srs_g2_from_tau.argtypes = [C.c_void_p] * 3
+        L.sbn_circom_r1cs_digest.argtypes = [C.c_void_p] * 3
+        L.sbn_random_tape_new.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.sbn_random_tape_scalars.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        L.sbn_random_tape_free.restype = None; L.sbn_random_tape_free.argtypes = [C.c_void_p]
+        L.sbn_random_tape_last_error.restype = C.c_char_p; L.sbn_random_tape_last_error.argtypes = [C.c_void_p]
+        L.sbn_zk_sumcheck_draw_rnd.argtypes = [C.c_size_t] * 2 + [C.c_void_p] * 2 + [C.c_size_t]
+        L.sbn_polyeval_draw_rnd.argtypes = [C.c_size_t] + [C.c_void_p] * 2 + [C.c_size_t]
+        L.sbn_r1cs_proof_draw_rnd.argtypes = [C.c_size_t] * 2 + [C.c_void_p] * 2 + [C.c_size_t]
+        L.sbn_sparse_eval_draw_rnd.argtypes = [C.c_size_t] * 4 + [C.c_int] + [C.c_void_p] * 2 + [C.c_size_t]
+        L.sbn_snark_draw_rnd.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 2 + [C.c_size_t]
+        L.sbn_nizk_draw_rnd.argtypes = [C.c_void_p] * 3 + [C.c_size_t]
         _LIB = L
     return _LIB
 
@@ -258,6 +271,65 @@ def kzg_srs_g2_from_tau(tau):
     if rc:
         raise SbnError(f"sbn_kzg_srs_g2_from_tau rc={rc}: tau must be canonical and non-zero")
     return bytes(g2), bytes(tg2)
+
+
+class RandomTape:
+    """RandomTape (random.rs) behind the C ABI, host only: no Context.  name: b"snark_proof" for snark_prove, b"proof" for nizk_prove (snark.rs:438, :210).
+    init: 32 canonical bytes — a tape started from the same init gives the draws the reference's tape gives; a fixed init is for tests — or None:
+    the library takes it from the operating system.  Every draw_* fills rnd exactly as the matching prove call takes it and advances the tape"""
+
+    def __init__(self, name, init=None):
+        self.h = C.c_void_p()
+        rc = lib().sbn_random_tape_new(_ptr(name) if name else None, C.c_size_t(len(name)), _ptr(init), C.byref(self.h))
+        if rc:
+            self.h = None
+            raise SbnError(f"sbn_random_tape_new rc={rc}: {lib().sbn_random_tape_last_error(None).decode()}")
+
+    def _chk(self, rc, what):
+        if rc:
+            raise SbnError(f"{what} rc={rc}: {lib().sbn_random_tape_last_error(self.h).decode()}")
+
+    def scalars(self, label, n=1):
+        """random_scalar / random_vector: n x challenge_scalar(label) -> n x 32 canonical bytes"""
+        out = (C.c_uint8 * (32 * max(n, 1)))()
+        self._chk(lib().sbn_random_tape_scalars(self.h, _ptr(label) if label else None, C.c_size_t(len(label)), C.c_size_t(n), out), "sbn_random_tape_scalars")
+        return bytes(out)[:32 * n]
+
+    def _plan(self, fn, what, args, count):
+        out = (C.c_uint8 * (32 * max(count, 1)))()
+        self._chk(fn(*args, self.h, out, C.c_size_t(count)), what)
+        return bytes(out)[:32 * count]
+
+    def draw_zk_sumcheck(self, num_rounds, n):
+        return self._plan(lib().sbn_zk_sumcheck_draw_rnd, "sbn_zk_sumcheck_draw_rnd", (C.c_size_t(num_rounds), C.c_size_t(n)), num_rounds * (n + 4))
+
+    def draw_polyeval(self, ell):
+        return self._plan(lib().sbn_polyeval_draw_rnd, "sbn_polyeval_draw_rnd", (C.c_size_t(ell),), 3 + 2 * factored_lens(ell)[1])
+
+    def draw_r1cs_proof(self, num_cons, num_vars):
+        n = C.c_size_t(0)
+        if lib().sbn_r1cs_proof_sizes(C.c_size_t(num_cons), C.c_size_t(num_vars), C.byref(n), None):
+            raise SbnError(f"sbn_r1cs_proof_sizes refuses {num_cons} x {num_vars}")
+        return self._plan(lib().sbn_r1cs_proof_draw_rnd, "sbn_r1cs_proof_draw_rnd", (C.c_size_t(num_cons), C.c_size_t(num_vars)), n.value)
+
+    def draw_sparse_eval(self, nx, ny, num_ops, batch, kzg=False):
+        n = C.c_size_t(0)
+        if (lib().sbn_sparse_eval_kzg_sizes if kzg else lib().sbn_sparse_eval_sizes)(C.c_size_t(nx), C.c_size_t(ny), C.c_size_t(num_ops), C.c_size_t(batch), C.byref(n), None):
+            raise SbnError(f"sbn_sparse_eval_sizes refuses ({nx}, {ny}, {num_ops}, {batch})")
+        return self._plan(lib().sbn_sparse_eval_draw_rnd, "sbn_sparse_eval_draw_rnd", (C.c_size_t(nx), C.c_size_t(ny), C.c_size_t(num_ops), C.c_size_t(batch), int(kzg)), n.value)
+
+    def draw_snark(self, key, kzg=False):
+        """the rnd of Context.snark_prove / snark_prove_kzg on this SnarkKey"""
+        return self._plan(lib().sbn_snark_draw_rnd, "sbn_snark_draw_rnd", (key.h, int(kzg)), key.sizes(kzg)[0])
+
+    def draw_nizk(self, inst):
+        """the rnd of Context.nizk_prove on this NizkInst"""
+        return self._plan(lib().sbn_nizk_draw_rnd, "sbn_nizk_draw_rnd", (inst.h,), inst.sizes()[0])
+
+    def free(self):
+        if self.h:
+            lib().sbn_random_tape_free(self.h)
+            self.h = None
 
 
 def g1_sum(xy):
@@ -659,6 +731,12 @@ class CircomR1cs:
         self.ctx._chk(lib().sbn_circom_r1cs_download(self.ctx.h, self.h, m, rows, cols, vals), "sbn_circom_r1cs_download")
         raw = bytes(vals)
         return [int(rows[i]) for i in range(n)], [int(cols[i]) for i in range(n)], [raw[32 * i:32 * i + 32] for i in range(n)]
+
+    def digest(self):
+        """the library's own circuit digest (sbn_circom_r1cs_digest; NOT the reference's get_digest): 32 bytes for nizk_instance_from_circom"""
+        out = (C.c_uint8 * 32)()
+        self.ctx._chk(lib().sbn_circom_r1cs_digest(self.ctx.h, self.h, out), "sbn_circom_r1cs_digest")
+        return bytes(out)
 
     def free(self):
         if self.h:
@@ -1630,6 +1708,10 @@ class Context:
         inp = (C.c_uint8 * (32 * max(num_inputs, 1)))()
         self._chk(lib().sbn_circom_wtns_load(self.h, _ptr(data) if len(data) else None, C.c_size_t(len(data)), C.c_size_t(num_inputs), C.byref(t), inp, C.byref(n)), "sbn_circom_wtns_load")
         return Table(self, t), bytes(inp)[:32 * num_inputs], n.value
+
+    def circom_r1cs_digest(self, cr):
+        """the library's own circuit digest of a parsed circuit, leaves hashed on the device (sbn_circom_r1cs_digest) -> 32 bytes"""
+        return cr.digest()
 
     # ---- profiling
     def prof_enable(self, on=True):

@@ -9,6 +9,8 @@
 //                 (column, position), k_circom_ends, k_circom_gather; then the tail both routes share (r1cs_csr_finish)
 //   encode        sbn_snark_encode from sbn_r1cs_upload on, with r1cs_from_staged and dense_build_staged on the staged arrays
 //   wtns          the value section in one copy, k_circom_wtns: the test against r and the vars table
+//   digest        the library's own circuit digest (circom_host.hpp: the definition): k_circom_digest_leaves, one lane a leaf of 128 staged entries, the
+//                 leaves brought back behind ONE host wait, the root one SHAKE256 over them on the host
 // A handle made from a sbn_circom_r1cs copies what it keeps: the parsed circuit may be freed right after.  Included by sbn254.hip behind abi_nizk.inc.
 
 struct sbn_circom_r1cs {
@@ -213,6 +215,44 @@ int sbn_circom_r1cs_download(sbn_ctx* c, const sbn_circom_r1cs* f, int m, uint32
   HIPCHK(c, hipMemcpyAsync(cols, f->cols + o, n * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(vals, f->vals + 8 * o, n * 32, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SBN_OK;
+}
+
+int sbn_circom_r1cs_digest(sbn_ctx* c, const sbn_circom_r1cs* f, uint8_t out[32]) {
+  if (!c || !f || !out) return SBN_EINVAL;
+  namespace cf = sbn_host::circom;
+  CircomDigestArgs a; memset(&a, 0, sizeof a);
+  {
+    uint8_t head[28]; memset(head, 0, sizeof head);                             // the zero byte in front, the domain string, a zero byte where m goes
+    static_assert(sizeof cf::DIGEST_LEAF_DOMAIN - 1 == 26, "the leaf header is 39 bytes: k_circom_digest_leaves' word stream depends on it");
+    memcpy(head + 1, cf::DIGEST_LEAF_DOMAIN, 26);
+    memcpy(a.head, head, 28);
+  }
+  size_t first[3], leaves = 0;
+  for (int m = 0; m < 3; m++) {
+    // what the kernel's two guards rest on: a lane that met one would leave its 32 bytes unwritten, and the root would hash what lay there before
+    if (f->off[m] + f->nnz[m] > f->total || f->total > UINT32_MAX) return fail(c, SBN_EINVAL, "circom digest: matrix %d holds entries %zu .. %zu of %zu", m, f->off[m], f->off[m] + f->nnz[m], f->total);
+    first[m] = leaves; leaves += cf::digest_leaves(f->nnz[m]);
+    a.off[m] = (uint32_t)f->off[m]; a.nnz[m] = (uint32_t)f->nnz[m]; a.leaf_first[m] = (uint32_t)first[m];
+  }
+  a.leaves = (uint32_t)leaves;
+  std::vector<uint8_t> h(32 * std::max<size_t>(leaves, 1));
+  if (leaves) {
+    std::lock_guard<std::mutex> g(c->mu);
+    hipSetDevice(c->device);
+    int rc;
+    if ((rc = ensure(c, c->dense_ws, 32 * leaves))) return rc;
+    LAUNCH(c, "k_circom_digest_leaves", k_circom_digest_leaves, (unsigned)((leaves + 63) / 64), 64, (const uint32_t*)f->rows, (const uint32_t*)f->cols, (const uint32_t*)f->vals,
+           f->total, a, (uint64_t*)c->dense_ws.p);
+    LAUNCHCHK(c);
+    HIPCHK(c, hipMemcpyAsync(h.data(), c->dense_ws.p, 32 * leaves, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                                 // the one wait
+    if (c->prof) prof_drain(c);
+  }
+  const uint64_t shape[5] = {f->scan.n_cons, f->scan.n_wires, f->scan.n_pub, f->sh.nc, f->sh.nv};
+  const uint64_t nnz[3] = {f->nnz[0], f->nnz[1], f->nnz[2]};
+  const uint8_t* const lv[3] = {h.data() + 32 * first[0], h.data() + 32 * first[1], h.data() + 32 * first[2]};
+  cf::digest_root(shape, nnz, lv, out);
   return SBN_OK;
 }
 

@@ -19,6 +19,7 @@
 // size that is no multiple of 32.  (A value >= r, which the example replaces by its low 64 bits, is refused by sbn_circom_wtns_load on the device.)
 // tests/circom_host_check.cpp builds this header alone, under ASan + UBSan.
 #pragma once
+#include "host_keccak.hpp"
 #include "snark_host.hpp"
 #include <vector>
 
@@ -33,6 +34,7 @@ static inline const char* why(int e) {
   return (e >= 0 && e < (int)(sizeof W / sizeof W[0])) ? W[e] : "?";
 }
 
+static inline void put_u32(uint8_t* p, uint32_t x) { p[0] = (uint8_t)x; p[1] = (uint8_t)(x >> 8); p[2] = (uint8_t)(x >> 16); p[3] = (uint8_t)(x >> 24); }
 static inline uint32_t get_u32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 // [off, off + n) lies inside a buffer of len bytes
 static inline bool fits(size_t off, uint64_t n, size_t len) { return off <= len && n <= (uint64_t)(len - off); }
@@ -135,6 +137,50 @@ static inline int wtns_scan(const uint8_t* p, size_t len, WtnsSpan* w) {
 // the raw shape a circuit file gives Instance::new (r1cs_reader.rs:255-257, keyless_benchmark.rs:96-100 with snark.rs:74-90's padding)
 static inline bool shape_of(const R1csScan& s, snark::Shape* sh) {
   return snark::shape_make((size_t)s.n_cons, (size_t)(s.n_wires - 1 - s.n_pub), (size_t)s.n_pub, sh);
+}
+
+// ---- the circuit digest: THE LIBRARY'S OWN.  It is not the reference's R1CSShape::get_digest (zlib over bincode, r1cs.rs:97-101), which is not
+//      reproduced here: a proof made under one digest does not verify under the other.  It binds a NIZK proof to its circuit for a caller who has no
+//      Rust side to ask.  Defined over what sbn_circom_r1cs_download returns — kept entries in file order, remapped columns, canonical values — and
+//      not over file bytes, so section order and dropped (>= r) entries do not change it:
+//        leaf(m, j) = SHAKE256("sbn254/r1cs-digest/leaf/v1" | u8 m | u64le j | u32le k | k x (u32le row | u32le col | val[32]))[0..32]
+//                     entries 128 j .. 128 j + k - 1 of matrix m, k = min(128, nnz[m] - 128 j); no leaf for nnz[m] = 0
+//        root       = SHAKE256("sbn254/r1cs-digest/root/v1" | u64le num_constraints | num_variables | num_pub_inputs | num_cons_padded | num_vars_padded
+//                              | for m = 0, 1, 2: u64le nnz[m] | the leaves of m in order)[0..32]
+//      The leaves are device work (circom_kernels.cuh: k_circom_digest_leaves); digest_leaf below is the same function on the host, for the checks
+//      (tests/circuit_digest_check.cpp builds the three functions alone, under ASan + UBSan) ----
+static const char DIGEST_LEAF_DOMAIN[] = "sbn254/r1cs-digest/leaf/v1";      // 26 bytes: with u8 m, u64 j and u32 k a header of 39
+static const char DIGEST_ROOT_DOMAIN[] = "sbn254/r1cs-digest/root/v1";
+static const size_t DIGEST_LEAF_ENTRIES = 128;
+static inline size_t digest_leaves(uint64_t nnz) { return (size_t)((nnz + DIGEST_LEAF_ENTRIES - 1) / DIGEST_LEAF_ENTRIES); }
+
+// rows, cols, vals: the k entries of the leaf
+static inline void digest_leaf(uint8_t m, uint64_t j, uint32_t k, const uint32_t* rows, const uint32_t* cols, const uint8_t* vals, uint8_t out[32]) {
+  Keccak h(136, 0x1f);
+  uint8_t b[8];
+  h.absorb((const uint8_t*)DIGEST_LEAF_DOMAIN, sizeof DIGEST_LEAF_DOMAIN - 1);
+  h.absorb(&m, 1);
+  snark::put_u64(b, j); h.absorb(b, 8);
+  put_u32(b, k); h.absorb(b, 4);
+  for (uint32_t e = 0; e < k; e++) {
+    put_u32(b, rows[e]); put_u32(b + 4, cols[e]);
+    h.absorb(b, 8);
+    h.absorb(vals + 32 * (size_t)e, 32);
+  }
+  h.squeeze(out, 32);
+}
+
+// shape: num_constraints, num_variables, num_pub_inputs, num_cons_padded, num_vars_padded; leaves[m]: digest_leaves(nnz[m]) x 32 bytes
+static inline void digest_root(const uint64_t shape[5], const uint64_t nnz[3], const uint8_t* const leaves[3], uint8_t out[32]) {
+  Keccak h(136, 0x1f);
+  uint8_t b[8];
+  h.absorb((const uint8_t*)DIGEST_ROOT_DOMAIN, sizeof DIGEST_ROOT_DOMAIN - 1);
+  for (int i = 0; i < 5; i++) { snark::put_u64(b, shape[i]); h.absorb(b, 8); }
+  for (int m = 0; m < 3; m++) {
+    snark::put_u64(b, nnz[m]); h.absorb(b, 8);
+    h.absorb(leaves[m], 32 * digest_leaves(nnz[m]));
+  }
+  h.squeeze(out, 32);
 }
 
 }  // namespace circom

@@ -139,4 +139,108 @@ __global__ void __launch_bounds__(256) k_circom_wtns(const uint32_t* __restrict_
   }
 }
 
+// ---- the circuit digest's leaves (circom_host.hpp: the definition): leaf(m, j) = SHAKE256(header | k x (u32le row | u32le col | val[32]))[0..32] over
+// entries 128 j .. 128 j + k - 1 of matrix m.  One lane a leaf, one wave a block: a leaf is 38 dependent permutations and nothing of it is shared, so
+// the lanes of a wave walk their leaves block by block in step.
+// The message is read as dwords.  The header has 39 bytes, so one zero byte is put in front of it: in the stream V = 0 | header | entries the header
+// fills words 0 .. 9 and entry e words 10 + 10 e .. (row, col, eight value words: exactly what rows / cols / vals hold), and message word n is
+// (V[n] >> 8) | (V[n + 1] << 24).  A block of the rate (136 B = 34 words) is therefore 35 loads whose REGISTER index is fixed and whose ADDRESS moves:
+// the state and the block stay in registers under static indices (no scratch), and the position inside the entry is address arithmetic.  A lane's
+// loads walk its own 5 KiB, 4 B a time: each line is fetched once and re-read from L1 / L2 (64 lanes x 128 B live a wave); against the ~8 k ALU
+// instructions of one permutation the 35 loads a block are a few per cent of the time (DESIGN 4.25 has the measured figure).
+struct CircomDigestArgs {
+  uint32_t head[7];                          // V[0 .. 6] of a leaf: the zero byte, the 26 bytes of the domain string, a zero byte where m goes
+  uint32_t off[3], nnz[3];                   // where matrix m's entries start in rows / cols / vals, and how many there are
+  uint32_t leaf_first[3], leaves;            // the leaves of matrix m are leaf_first[m] .. ; leaves: all of them
+};
+static const int DIGEST_LEAF = 128;          // entries a leaf
+static const int DIGEST_RATE_WORDS = 34;     // SHAKE256: 136 bytes
+
+// Keccak-f[1600] (FIPS 202 3.2-3.4) on 25 lanes in registers; rho and pi folded into one table of fixed rotations, chi row by row
+__device__ __forceinline__ uint64_t keccak_rol(uint64_t x, int n) { return n ? (x << n) | (x >> (64 - n)) : x; }
+__device__ __forceinline__ void keccak_f1600(uint64_t (&a)[25]) {
+  static constexpr uint64_t RC[24] = {
+    0x0000000000000001ull, 0x0000000000008082ull, 0x800000000000808aull, 0x8000000080008000ull, 0x000000000000808bull, 0x0000000080000001ull,
+    0x8000000080008081ull, 0x8000000000008009ull, 0x000000000000008aull, 0x0000000000000088ull, 0x0000000080008009ull, 0x000000008000000aull,
+    0x000000008000808bull, 0x800000000000008bull, 0x8000000000008089ull, 0x8000000000008003ull, 0x8000000000008002ull, 0x8000000000000080ull,
+    0x000000000000800aull, 0x800000008000000aull, 0x8000000080008081ull, 0x8000000000008080ull, 0x0000000080000001ull, 0x8000000080008008ull};
+  // rho offset of lane x + 5 y
+  constexpr int RHO[25] = {0, 1, 62, 28, 27, 36, 44, 6, 55, 20, 3, 10, 43, 25, 39, 41, 45, 15, 21, 8, 18, 2, 61, 56, 14};
+#pragma unroll 1
+  for (int r = 0; r < 24; r++) {
+    uint64_t C[5], B[25];
+#pragma unroll
+    for (int x = 0; x < 5; x++) C[x] = a[x] ^ a[x + 5] ^ a[x + 10] ^ a[x + 15] ^ a[x + 20];
+#pragma unroll
+    for (int x = 0; x < 5; x++) {
+      const uint64_t D = C[(x + 4) % 5] ^ keccak_rol(C[(x + 1) % 5], 1);
+#pragma unroll
+      for (int y = 0; y < 5; y++) a[x + 5 * y] ^= D;
+    }
+#pragma unroll
+    for (int x = 0; x < 5; x++)
+#pragma unroll
+      for (int y = 0; y < 5; y++) B[y + 5 * ((2 * x + 3 * y) % 5)] = keccak_rol(a[x + 5 * y], RHO[x + 5 * y]);      // pi after rho
+#pragma unroll
+    for (int y = 0; y < 5; y++)
+#pragma unroll
+      for (int x = 0; x < 5; x++) a[x + 5 * y] = B[x + 5 * y] ^ (~B[(x + 1) % 5 + 5 * y] & B[(x + 2) % 5 + 5 * y]);
+    a[0] ^= RC[r];
+  }
+}
+
+__global__ void __launch_bounds__(64) k_circom_digest_leaves(const uint32_t* __restrict__ rows, const uint32_t* __restrict__ cols, const uint32_t* __restrict__ vals,
+                                                             size_t total, CircomDigestArgs A, uint64_t* __restrict__ out) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= A.leaves) return;
+  const uint32_t m = (g >= A.leaf_first[1] ? 1u : 0u) + (g >= A.leaf_first[2] ? 1u : 0u);
+  const uint32_t first = m == 0 ? A.leaf_first[0] : (m == 1 ? A.leaf_first[1] : A.leaf_first[2]);
+  const uint32_t nnz = m == 0 ? A.nnz[0] : (m == 1 ? A.nnz[1] : A.nnz[2]);
+  const uint32_t off = m == 0 ? A.off[0] : (m == 1 ? A.off[1] : A.off[2]);
+  const uint32_t j = g - first;
+  // this guard and the one on e0 + k keep every read inside the arrays; sbn_circom_r1cs_digest checks off[m] + nnz[m] <= total before the launch and
+  // derives the leaf counts from the same nnz, so neither fires and every lane below `leaves` writes its 32 bytes
+  if ((uint64_t)j * DIGEST_LEAF >= nnz) return;
+  const uint32_t k = min((uint32_t)DIGEST_LEAF, nnz - j * DIGEST_LEAF);
+  const size_t e0 = (size_t)off + (size_t)j * DIGEST_LEAF;           // the leaf's first entry; e0 + k <= off + nnz <= total
+  if (e0 + k > total) return;
+  const uint32_t vwords = 10u + 10u * k;                             // the words of V that exist; behind them the stream is zero
+  const uint32_t len = 39u + 40u * k;                                // the message's bytes
+  const uint32_t nblocks = len / 136u + 1u;                          // pad10*1 always adds at least one byte
+  const uint32_t pad_word = len >> 2, pad_val = 0x1fu << (8u * (len & 3u));
+  uint32_t head[10];
+#pragma unroll
+  for (int i = 0; i < 7; i++) head[i] = A.head[i];
+  head[6] |= m << 24; head[7] = j; head[8] = 0u; head[9] = k;        // u8 m | u64le j | u32le k
+  uint64_t a[25];
+#pragma unroll
+  for (int i = 0; i < 25; i++) a[i] = 0;
+  for (uint32_t b = 0; b < nblocks; b++) {
+    const uint32_t w0 = b * DIGEST_RATE_WORDS;                       // the block's first message word
+    uint32_t v[DIGEST_RATE_WORDS + 1];
+#pragma unroll
+    for (int i = 0; i <= DIGEST_RATE_WORDS; i++) {
+      const uint32_t n = w0 + i;
+      uint32_t x = 0;
+      if (i < 10 && b == 0) x = head[i];
+      else if (n < vwords) {
+        const uint32_t t = n - 10u, e = t / 10u, f = t - 10u * e;
+        x = f == 0 ? rows[e0 + e] : (f == 1 ? cols[e0 + e] : vals[8 * (e0 + e) + (f - 2u)]);
+      }
+      v[i] = x;
+    }
+#pragma unroll
+    for (int i = 0; i < DIGEST_RATE_WORDS; i += 2) {
+      uint32_t lo = (v[i] >> 8) | (v[i + 1] << 24), hi = (v[i + 1] >> 8) | (v[i + 2] << 24);
+      if (w0 + i == pad_word) lo ^= pad_val;
+      if (w0 + i + 1 == pad_word) hi ^= pad_val;
+      if (i == DIGEST_RATE_WORDS - 2 && b == nblocks - 1) hi ^= 0x80000000u;      // the last bit of pad10*1, in the last byte of the rate
+      a[i >> 1] ^= (uint64_t)lo | ((uint64_t)hi << 32);
+    }
+    keccak_f1600(a);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) out[4 * (size_t)g + i] = a[i];
+}
+
 }  // namespace sbn

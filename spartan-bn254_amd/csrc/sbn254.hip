@@ -53,6 +53,7 @@
 #include "circom_host.hpp"
 #include "pairing_host.hpp"
 #include "srs_host.hpp"
+#include "random_tape_host.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -107,6 +108,7 @@ using sbn_host::polyeval_verify_script; using sbn_host::polyeval_verify_scalars;
 #include "abi_nizk.inc"
 #include "abi_circom.inc"
 #include "abi_kzg_srs.inc"
+#include "abi_random_tape.inc"
 
 extern "C" {
 
