@@ -1048,6 +1048,32 @@ int sbn_kzg_srs_save(sbn_ctx* ctx, const sbn_bases* srs, const uint8_t g2_xy[128
                      size_t* out_len);
 int sbn_kzg_srs_g2_from_tau(const uint8_t tau[32], uint8_t out_g2_xy[128], uint8_t out_tau_g2_xy[128]);
 
+/* ---- a powers-of-tau ceremony file (.ptau, what circom users hold) as the KZG SRS: an SRS whose tau nobody knows ----
+ * The format, all integers little-endian (written from a description; NOT compared with a file snarkjs wrote):
+ *     "ptau" | u32 version = 1 | u32 nSections | nSections x ( u32 id | u64 size | size bytes )
+ *     section 1 (44 B)   u32 n8 = 32 | n8 bytes q = BN254's base prime | u32 power (1 .. 28) | u32 ceremonyPower
+ *     section 2 (tauG1)  2^(power+1) - 1 points of 64 B: x | y;  point i = [tau^i] G1
+ *     section 3 (tauG2)  2^power points of 128 B: x.c0 | x.c1 | y.c0 | y.c1;  point i = [tau^i] G2; only points 0 and 1 are read
+ *   A coordinate is 32 bytes of v 2^256 mod q: the limbs SBN_POINTS_MONT means.  A point of all zero bytes is the identity.  Sections come in any order;
+ *   ids other than 1, 2, 3 are skipped (a real file has 4 .. 7, a prepared one 12 .. 15); a second section 1, 2 or 3 is refused; the sizes of sections
+ *   1, 2 and 3 must be exactly the values above.
+ * sbn_ptau_scan: host only, no context.  Walks the section table, every offset and size checked against len without overflow, and reads section 1; no
+ *   point is touched.  off_g1 / off_g2 are the byte offsets of the first point of sections 2 / 3 in `bytes`.  SBN_EINVAL: a NULL pointer, or a file the
+ *   load below would refuse before it reads a point.
+ * sbn_kzg_srs_load_ptau: the first n powers (n = 0: all n_g1 of them; n > n_g1: SBN_EINVAL) and tauG2[0], tauG2[1] -> the three handles and out_g2_xy of
+ *   sbn_kzg_srs_load, with its outputs and refusal conventions: the reason in sbn_last_error, *bad_index the smallest refused index of the first n powers or
+ *   SIZE_MAX, no handle left, the stream drained.  For one tau and n the handle is byte for byte the one sbn_kzg_srs_from_tau and sbn_kzg_srs_load make.
+ *   Read: the header, the section table, section 1, the first 64 n bytes of section 2 and the first 256 bytes of section 3 — a caller who has mapped a
+ *   32 GiB file pays for that prefix only (the whole of `len` must still cover every section the table names).
+ *   Every point is validated on the device (k_ptau_points, the chunks and staging of sbn_kzg_srs_load): both residues < q, not the all-zero point,
+ *   y^2 = x^3 + 3; each coordinate changes Montgomery form with one field product; no square root.  The two G2 points are taken out of Montgomery form on
+ *   the host and go through every refusal of sbn_g2_prepare (>= q, the identity, off the twist, outside the r-torsion).
+ *   SBN_SRS_CHECK in flags runs sbn_kzg_srs_check on what was loaded, exactly as in sbn_kzg_srs_load.  The ceremony's contribution chain is not verified. */
+typedef struct { uint32_t power, ceremony_power; uint64_t n_g1, n_g2, off_g1, off_g2; } sbn_ptau_info;
+int sbn_ptau_scan(const uint8_t* bytes, size_t len, sbn_ptau_info* out);
+int sbn_kzg_srs_load_ptau(sbn_ctx* ctx, const uint8_t* bytes, size_t len, size_t n, uint32_t flags, sbn_bases** out_srs, sbn_g2_lines** out_g2,
+                          sbn_g2_lines** out_tau_g2, uint8_t out_g2_xy[256], size_t* bad_index);
+
 /* ---- per-kernel timing (HIP events on the context's stream), for bench.py's roofline line ---- */
 int sbn_prof_enable(sbn_ctx* ctx, int on);
 int sbn_prof_reset(sbn_ctx* ctx);

@@ -69,6 +69,12 @@ pub struct sbn_circom_info {
     pub nnz: [u64; 3], pub dropped: [u64; 3],
     pub num_vars: u64, pub num_cons_padded: u64, pub num_vars_padded: u64,
 }
+/// what `sbn_ptau_scan` fills: the header section of a powers-of-tau file, the point counts and the byte offsets of sections 2 and 3
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct sbn_ptau_info {
+    pub power: u32, pub ceremony_power: u32,
+    pub n_g1: u64, pub n_g2: u64, pub off_g1: u64, pub off_g2: u64,
+}
 
 pub const SBN_OK: c_int = 0;
 pub const SBN_SCALARS_MONT: u32 = 1;
@@ -284,6 +290,8 @@ extern "C" {
     pub fn sbn_kzg_srs_check(ctx: *mut sbn_ctx, srs: *const sbn_bases, g2: *const sbn_g2_lines, tau_g2: *const sbn_g2_lines, rho: *const u8, consistent: *mut c_int) -> c_int;
     pub fn sbn_kzg_srs_save(ctx: *mut sbn_ctx, srs: *const sbn_bases, g2_xy: *const u8, tau_g2_xy: *const u8, flags: u32, out: *mut u8, cap: usize, out_len: *mut usize) -> c_int;
     pub fn sbn_kzg_srs_g2_from_tau(tau: *const u8, out_g2_xy: *mut u8, out_tau_g2_xy: *mut u8) -> c_int;
+    pub fn sbn_ptau_scan(bytes: *const u8, len: usize, out: *mut sbn_ptau_info) -> c_int;
+    pub fn sbn_kzg_srs_load_ptau(ctx: *mut sbn_ctx, bytes: *const u8, len: usize, n: usize, flags: u32, out_srs: *mut *mut sbn_bases, out_g2: *mut *mut sbn_g2_lines, out_tau_g2: *mut *mut sbn_g2_lines, out_g2_xy: *mut u8, bad_index: *mut usize) -> c_int;
     pub fn sbn_prof_enable(ctx: *mut sbn_ctx, on: c_int) -> c_int;
     pub fn sbn_prof_reset(ctx: *mut sbn_ctx) -> c_int;
     pub fn sbn_prof_count(ctx: *mut sbn_ctx) -> c_int;
@@ -1020,6 +1028,24 @@ impl KzgSrs {
             return Err(unsafe { std::ffi::CStr::from_ptr(sbn_last_error(ctx())) }.to_string_lossy().into_owned());
         }
         Ok((KzgSrs(b), G2Lines(g2), G2Lines(tau_g2)))
+    }
+    /// A powers-of-tau ceremony file (.ptau) as the SRS: the first `n` powers (0: all of them) of its tauG1 section and tauG2[0], tauG2[1].  `bytes`
+    /// may be a memory map of the whole file: only the section table, 64 n bytes of section 2 and 256 bytes of section 3 are read.  Every point is
+    /// validated on the device; a refusal is the library's text, as in `load`.
+    pub fn load_ptau(bytes: &[u8], n: usize, check_consistency: bool) -> Result<(KzgSrs, G2Lines, G2Lines), String> {
+        let (mut b, mut g2, mut tau_g2) = (null_mut(), null_mut(), null_mut());
+        let mut bad: usize = usize::MAX;
+        let flags = if check_consistency { SBN_SRS_CHECK } else { 0 };
+        let rc = unsafe { sbn_kzg_srs_load_ptau(ctx(), bytes.as_ptr(), bytes.len(), n, flags, &mut b, &mut g2, &mut tau_g2, null_mut(), &mut bad) };
+        if rc != SBN_OK {
+            return Err(unsafe { std::ffi::CStr::from_ptr(sbn_last_error(ctx())) }.to_string_lossy().into_owned());
+        }
+        Ok((KzgSrs(b), G2Lines(g2), G2Lines(tau_g2)))
+    }
+    /// the header of a .ptau file (host only): None for a file `load_ptau` would refuse before it reads a point
+    pub fn ptau_info(bytes: &[u8]) -> Option<sbn_ptau_info> {
+        let mut info = sbn_ptau_info::default();
+        if unsafe { sbn_ptau_scan(bytes.as_ptr(), bytes.len(), &mut info) } == SBN_OK { Some(info) } else { None }
     }
     /// KZGSrs::save_to_file (kzg.rs:66-77) as bytes; `g2_xy`, `tau_g2_xy`: G2Affine's in-memory x.c0, x.c1, y.c0, y.c1 (ark-ff Montgomery limbs)
     pub fn save(&self, g2_xy: &[u8; 128], tau_g2_xy: &[u8; 128]) -> Vec<u8> {

@@ -5,7 +5,7 @@ Rust shim would.  It contains no arithmetic and no fallback: if
 gfx950 device is missing, loading / context creation raises.
 """
 from .binding import (  # noqa: F401
-    Context, Group, Bases, Table, Dense, DerefsKey, SnarkGens, SnarkKey, NizkInst, CircomR1cs, SbnError, SbnUnsat, SBN_EUNSAT, SBN_SNARK_CHECK_SAT, SBN_SRS_CHECK, kzg_srs_g2_from_tau, lib, lib_path, build_library,
+    Context, Group, Bases, Table, Dense, DerefsKey, SnarkGens, SnarkKey, NizkInst, CircomR1cs, SbnError, SbnUnsat, SBN_EUNSAT, SBN_SNARK_CHECK_SAT, SBN_SRS_CHECK, kzg_srs_g2_from_tau, ptau_scan, PtauInfo, lib, lib_path, build_library,
     SBN_SCALARS_MONT, SBN_POINTS_MONT, g1_compress, g1_sum, Transcript, fr_from_wide, unipoly_from_evals, unipoly_eval, factored_lens, r1cs_proof_sizes, sparse_eval_sizes, sparse_eval_kzg_sizes, EXPORTED_SYMBOLS,
     RandomTape,
 )

@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = [
     "sbn_nizk_gens_new", "sbn_nizk_instance_new", "sbn_nizk_instance_free", "sbn_nizk_instance_r1cs", "sbn_nizk_sizes", "sbn_nizk_is_sat", "sbn_nizk_prove", "sbn_nizk_verify",
     "sbn_circom_r1cs_load", "sbn_circom_r1cs_info", "sbn_circom_r1cs_download", "sbn_circom_r1cs_free", "sbn_r1cs_from_circom", "sbn_nizk_instance_from_circom",
     "sbn_snark_encode_circom", "sbn_circom_wtns_load",
-    "sbn_kzg_srs_load", "sbn_kzg_srs_check", "sbn_kzg_srs_save", "sbn_kzg_srs_g2_from_tau",
+    "sbn_kzg_srs_load", "sbn_kzg_srs_check", "sbn_kzg_srs_save", "sbn_kzg_srs_g2_from_tau", "sbn_ptau_scan", "sbn_kzg_srs_load_ptau",
     "sbn_circom_r1cs_digest", "sbn_random_tape_new", "sbn_random_tape_scalars", "sbn_random_tape_free", "sbn_random_tape_last_error",
     "sbn_zk_sumcheck_draw_rnd", "sbn_polyeval_draw_rnd", "sbn_r1cs_proof_draw_rnd", "sbn_sparse_eval_draw_rnd", "sbn_snark_draw_rnd", "sbn_nizk_draw_rnd",
 ]
@@ -169,6 +169,8 @@ def lib():
         L.sbn_kzg_srs_check.argtypes = [C.c_void_p] * 6
         L.sbn_kzg_srs_save.argtypes = [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
         L.sbn_kzg_srs_g2_from_tau.argtypes = [C.c_void_p] * 3
+        L.sbn_ptau_scan.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sbn_kzg_srs_load_ptau.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32] + [C.c_void_p] * 5
         L.sbn_circom_r1cs_digest.argtypes = [C.c_void_p] * 3
         L.sbn_random_tape_new.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.sbn_random_tape_scalars.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
@@ -271,6 +273,20 @@ def kzg_srs_g2_from_tau(tau):
     if rc:
         raise SbnError(f"sbn_kzg_srs_g2_from_tau rc={rc}: tau must be canonical and non-zero")
     return bytes(g2), bytes(tg2)
+
+
+class PtauInfo(C.Structure):
+    """sbn_ptau_info: what sbn_ptau_scan reads from a .ptau file's section table and header section"""
+    _fields_ = [("power", C.c_uint32), ("ceremony_power", C.c_uint32), ("n_g1", C.c_uint64), ("n_g2", C.c_uint64), ("off_g1", C.c_uint64), ("off_g2", C.c_uint64)]
+
+
+def ptau_scan(data):
+    """sbn_ptau_scan (host only) -> PtauInfo; SbnError for a file the load would refuse before it reads a point"""
+    info = PtauInfo()
+    rc = lib().sbn_ptau_scan(_ptr(data) if len(data) else None, C.c_size_t(len(data)), C.byref(info))
+    if rc:
+        raise SbnError(f"sbn_ptau_scan rc={rc}: not a .ptau file this library loads")
+    return info
 
 
 class RandomTape:
@@ -1401,6 +1417,20 @@ class Context:
                                     C.byref(hg) if want_lines else None, C.byref(ht) if want_lines else None, xy, C.byref(bad))
         if rc:
             err = SbnError(f"sbn_kzg_srs_load: rc={rc}: {lib().sbn_last_error(self.h).decode()}")
+            err.bad_index = bad.value if bad.value != C.c_size_t(-1).value else None
+            err.handles = (hb.value, hg.value, ht.value)
+            raise err
+        raw = bytes(xy)
+        return Bases(self, hb), (G2Lines(self, hg) if want_lines else None), (G2Lines(self, ht) if want_lines else None), raw[:128], raw[128:]
+
+    def kzg_srs_load_ptau(self, data, n=0, flags=0, want_lines=True):
+        """sbn_kzg_srs_load_ptau on the bytes of a .ptau file: the first n powers (0: all) -> what kzg_srs_load returns, with its SbnError on a refusal"""
+        hb, hg, ht = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        xy = (C.c_uint8 * 256)(); bad = C.c_size_t(0)
+        rc = lib().sbn_kzg_srs_load_ptau(self.h, _ptr(data) if len(data) else None, C.c_size_t(len(data)), C.c_size_t(n), C.c_uint32(flags), C.byref(hb),
+                                         C.byref(hg) if want_lines else None, C.byref(ht) if want_lines else None, xy, C.byref(bad))
+        if rc:
+            err = SbnError(f"sbn_kzg_srs_load_ptau: rc={rc}: {lib().sbn_last_error(self.h).decode()}")
             err.bad_index = bad.value if bad.value != C.c_size_t(-1).value else None
             err.handles = (hb.value, hg.value, ht.value)
             raise err

@@ -4,14 +4,17 @@
 //                             k + 1 beside k_srs_decompress of chunk k, and land in the handle's layout with nothing else written per point.
 //   sbn_kzg_srs_check         are the powers the powers of ONE tau that matches tau_g2?  One MSM over the handle, two short sums, one pairing product.
 //   sbn_kzg_srs_save          the other direction: k_srs_compress in the same chunks, the two G2 points compressed on the host.
+//   sbn_ptau_scan             host only: the section table and the header section of a powers-of-tau ceremony file (ptau_host.hpp)
+//   sbn_kzg_srs_load_ptau     the bytes of a .ptau file -> the same three handles: the first n points of section 2 through the SAME chunk loop with 64-byte
+//                             points and k_ptau_points (no square root), points 0 and 1 of section 3 converted on the host
 //   sbn_kzg_srs_g2_from_tau   host only: g2 and [tau] g2 for a caller who supplies tau (with sbn_kzg_srs_from_tau: the "generate" half of load_or_generate).
 // Included by sbn254.hip; needs abi_kzg.inc (kzg_pow2_table), abi_small_sums.inc and abi_pairing.inc.
 
 // The chunk is sbn_ctx::srs_chunk points (2^18 = 8 MiB of file bytes unless SBN_SRS_CHUNK says otherwise; DESIGN, "the SRS from a file").
 
-// two pinned staging buffers and two device buffers of `chunk` compressed points each
-static int srs_staging(sbn_ctx* c, size_t chunk) {
-  const size_t bytes = chunk * 32;
+// two pinned staging buffers and two device buffers of `chunk` points of `width` file bytes each (32: a compressed power; 64: a point of a .ptau file)
+static int srs_staging(sbn_ctx* c, size_t chunk, size_t width = 32) {
+  const size_t bytes = chunk * width;
   int rc;
   for (int k = 0; k < 2; k++) if ((rc = ensure(c, c->zstage[k], bytes + 64))) return rc;
   if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
@@ -36,11 +39,13 @@ static const char* srs_g1_reason(const uint8_t p[32]) {
 static unsigned long long* srs_bad_dev(sbn_ctx* c) { return (unsigned long long*)(c->d_bad + 2); }
 static volatile unsigned long long* srs_bad_host(sbn_ctx* c, int k) { return (volatile unsigned long long*)(c->h_bad + 2 + 2 * k); }
 
-// the n compressed powers at `in` into b->d_pts (n >= 1; the context's mutex is held).  *bad <- the smallest refused index, or SIZE_MAX.
-static int srs_decompress_chunks(sbn_ctx* c, const uint8_t* in, size_t n, uint32_t* d_pts, size_t* bad) {
+// the n points at `in` into b->d_pts (n >= 1; the context's mutex is held).  *bad <- the smallest refused index, or SIZE_MAX.  The ONE chunk loop of both
+// loads: `width` is the file's bytes per point and picks the kernel, 32 = k_srs_decompress (a compressed power), 64 = k_ptau_points (x | y in ark-ff's
+// Montgomery limbs); a chunk is srs_chunk points whatever its width.
+static int srs_load_chunks(sbn_ctx* c, const uint8_t* in, size_t n, size_t width, uint32_t* d_pts, size_t* bad) {
   const size_t chunk = std::min(c->srs_chunk, n), nchunks = (n + chunk - 1) / chunk;
   int rc;
-  if ((rc = srs_staging(c, chunk))) return rc;
+  if ((rc = srs_staging(c, chunk, width))) return rc;
   HIPCHK(c, hipMemsetAsync(srs_bad_dev(c), 0xff, 8, c->stream));
   hipEvent_t copied[2], done[2];
   for (int k = 0; k < 2; k++) { copied[k] = evt_get(c); done[k] = evt_get(c); }
@@ -51,12 +56,13 @@ static int srs_decompress_chunks(sbn_ctx* c, const uint8_t* in, size_t n, uint32
     const size_t first = i * chunk, cnt = std::min(chunk, n - first);
     // chunk i - 2 has left both staging buffers, and its copy of the refusal word has landed: the one host read a chunk
     if (i >= 2) { e = hipEventSynchronize(done[k]); if (e != hipSuccess) break; if (*srs_bad_host(c, k) != ~0ull) { stop = true; break; } }
-    memcpy(c->srs_pin[k], in + 32 * first, 32 * cnt);
-    e = hipMemcpyAsync(c->zstage[k].p, c->srs_pin[k], 32 * cnt, hipMemcpyHostToDevice, c->copy_stream);
+    memcpy(c->srs_pin[k], in + width * first, width * cnt);
+    e = hipMemcpyAsync(c->zstage[k].p, c->srs_pin[k], width * cnt, hipMemcpyHostToDevice, c->copy_stream);
     if (e == hipSuccess) e = hipEventRecord(copied[k], c->copy_stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, copied[k], 0);
     if (e != hipSuccess) break;
-    LAUNCH(c, "k_srs_decompress", k_srs_decompress, (unsigned)((cnt + 63) / 64), 64, (const uint32_t*)c->zstage[k].p, cnt, first, d_pts, srs_bad_dev(c));
+    if (width == 32) LAUNCH(c, "k_srs_decompress", k_srs_decompress, (unsigned)((cnt + 63) / 64), 64, (const uint32_t*)c->zstage[k].p, cnt, first, d_pts, srs_bad_dev(c));
+    else LAUNCH(c, "k_ptau_points", k_ptau_points, (unsigned)((cnt + 63) / 64), 64, (const uint32_t*)c->zstage[k].p, cnt, first, d_pts, srs_bad_dev(c));
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync((void*)srs_bad_host(c, k), srs_bad_dev(c), 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipEventRecord(done[k], c->stream);
@@ -121,6 +127,55 @@ static bool srs_draw_rho(uint8_t rho[32]) {
   bool zero = true; for (int k = 0; k < 32; k++) if (rho[k]) zero = false;
   if (zero) rho[0] = 1;
   return true;
+}
+
+// why the device refused point i of a .ptau file, from its 64 bytes
+static const char* ptau_g1_reason(const uint8_t p[64]) {
+  uint64_t x[4], y[4]; memcpy(x, p, 32); memcpy(y, p + 32, 32);
+  if (sbn_host::geq_p(x) || sbn_host::geq_p(y)) return "a coordinate is not canonical (>= q)";
+  bool zero = true; for (int k = 0; k < 64; k++) if (p[k]) zero = false;
+  if (zero) return "the identity is no power of tau";
+  return "the point is not on the curve (y^2 != x^3 + 3)";
+}
+
+// What sbn_kzg_srs_load and sbn_kzg_srs_load_ptau share behind their parsers: n points of `width` file bytes at `in` into a fresh handle (srs_load_chunks), the
+// two G2 handles from g2s (g2 | tau_g2, canonical bytes), the check under SBN_SRS_CHECK, and the refusal conventions.  `what` opens every error text.
+static int srs_load_points(sbn_ctx* c, const char* what, const uint8_t* in, size_t n, size_t width, const uint8_t g2s[256], uint32_t flags, sbn_bases** out_srs,
+                           sbn_g2_lines** out_g2, sbn_g2_lines** out_tau_g2, uint8_t out_g2_xy[256], size_t* bad_index) {
+  sbn_bases* b = nullptr;
+  int rc;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    hipSetDevice(c->device);
+    b = new sbn_bases(); b->n = n; b->has_h = false;
+    const hipError_t he = hipMalloc(&b->d_pts, n * 64);
+    if (he != hipSuccess) { delete b; return fail(c, SBN_ENOMEM, "hipMalloc SRS (%zu points): %s", n, hipGetErrorString(he)); }
+    size_t bad = SIZE_MAX;
+    rc = srs_load_chunks(c, in, n, width, (uint32_t*)b->d_pts, &bad);
+    if (rc == SBN_OK && bad != SIZE_MAX) {
+      if (bad_index) *bad_index = bad;
+      rc = fail(c, SBN_EINVAL, "%s: power %zu: %s", what, bad, width == 32 ? srs_g1_reason(in + 32 * bad) : ptau_g1_reason(in + 64 * bad));
+    }
+    if (rc) { sbn_bases_free(c, b); return rc; }
+  }
+  sbn_g2_lines *l_g2 = nullptr, *l_tau = nullptr;
+  const bool want_lines = out_g2 != nullptr || (flags & SBN_SRS_CHECK);
+  if (want_lines) {
+    rc = sbn_g2_prepare(c, g2s, 0, &l_g2);
+    if (rc == SBN_OK) rc = sbn_g2_prepare(c, g2s + 128, 0, &l_tau);
+  }
+  if (rc == SBN_OK && (flags & SBN_SRS_CHECK)) {
+    uint8_t rho[32]; int ok = 0;
+    if (!srs_draw_rho(rho)) rc = fail(c, SBN_EHIP, "%s: no randomness from the OS for the consistency check", what);
+    else if ((rc = sbn_kzg_srs_check(c, b, l_g2, l_tau, rho, &ok)) == SBN_OK && !ok)
+      rc = fail(c, SBN_EINVAL, "%s: the powers are not the powers of one tau that matches tau_g2 (sbn_kzg_srs_check)", what);
+  }
+  if (rc || !out_g2) { sbn_g2_lines_free(c, l_g2); sbn_g2_lines_free(c, l_tau); l_g2 = l_tau = nullptr; }
+  if (rc) { std::lock_guard<std::mutex> g(c->mu); sbn_bases_free(c, b); return rc; }
+  *out_srs = b;
+  if (out_g2) { *out_g2 = l_g2; *out_tau_g2 = l_tau; }
+  if (out_g2_xy) memcpy(out_g2_xy, g2s, 256);
+  return SBN_OK;
 }
 
 extern "C" {
@@ -195,41 +250,38 @@ int sbn_kzg_srs_load(sbn_ctx* c, const uint8_t* bytes, size_t len, uint32_t flag
   uint8_t g2s[256];                                                             // g2 | tau_g2
   if ((e = sr::g2_decompress(bytes + s.tau_g2_off, g2s + 128))) return fail(c, SBN_EINVAL, "srs load: tau_g2: %s", sr::err_text(e));
   if ((e = sr::g2_decompress(bytes + s.g2_off, g2s))) return fail(c, SBN_EINVAL, "srs load: g2: %s", sr::err_text(e));
-  const size_t n = (size_t)s.n;
-  sbn_bases* b = nullptr;
-  int rc;
-  {
-    std::lock_guard<std::mutex> g(c->mu);
-    hipSetDevice(c->device);
-    b = new sbn_bases(); b->n = n; b->has_h = false;
-    const hipError_t he = hipMalloc(&b->d_pts, n * 64);
-    if (he != hipSuccess) { delete b; return fail(c, SBN_ENOMEM, "hipMalloc SRS (%zu points): %s", n, hipGetErrorString(he)); }
-    size_t bad = SIZE_MAX;
-    rc = srs_decompress_chunks(c, bytes + s.powers_off, n, (uint32_t*)b->d_pts, &bad);
-    if (rc == SBN_OK && bad != SIZE_MAX) {
-      if (bad_index) *bad_index = bad;
-      rc = fail(c, SBN_EINVAL, "srs load: power %zu: %s", bad, srs_g1_reason(bytes + s.powers_off + 32 * bad));
-    }
-    if (rc) { sbn_bases_free(c, b); return rc; }
-  }
-  sbn_g2_lines *l_g2 = nullptr, *l_tau = nullptr;
-  const bool want_lines = out_g2 != nullptr || (flags & SBN_SRS_CHECK);
-  if (want_lines) {
-    rc = sbn_g2_prepare(c, g2s, 0, &l_g2);
-    if (rc == SBN_OK) rc = sbn_g2_prepare(c, g2s + 128, 0, &l_tau);
-  }
-  if (rc == SBN_OK && (flags & SBN_SRS_CHECK)) {
-    uint8_t rho[32]; int ok = 0;
-    if (!srs_draw_rho(rho)) rc = fail(c, SBN_EHIP, "srs load: no randomness from the OS for the consistency check");
-    else if ((rc = sbn_kzg_srs_check(c, b, l_g2, l_tau, rho, &ok)) == SBN_OK && !ok)
-      rc = fail(c, SBN_EINVAL, "srs load: the powers are not the powers of one tau that matches tau_g2 (sbn_kzg_srs_check)");
-  }
-  if (rc || !out_g2) { sbn_g2_lines_free(c, l_g2); sbn_g2_lines_free(c, l_tau); l_g2 = l_tau = nullptr; }
-  if (rc) { std::lock_guard<std::mutex> g(c->mu); sbn_bases_free(c, b); return rc; }
-  *out_srs = b;
-  if (out_g2) { *out_g2 = l_g2; *out_tau_g2 = l_tau; }
-  if (out_g2_xy) memcpy(out_g2_xy, g2s, 256);
+  return srs_load_points(c, "srs load", bytes + s.powers_off, (size_t)s.n, 32, g2s, flags, out_srs, out_g2, out_tau_g2, out_g2_xy, bad_index);
+}
+
+int sbn_ptau_scan(const uint8_t* bytes, size_t len, sbn_ptau_info* out) {
+  namespace pt = sbn_host::ptau;
+  if ((!bytes && len) || !out) return SBN_EINVAL;
+  pt::Scan s;
+  if (pt::scan(bytes, len, &s)) return SBN_EINVAL;
+  out->power = s.power; out->ceremony_power = s.ceremony_power; out->n_g1 = s.n_g1; out->n_g2 = s.n_g2; out->off_g1 = s.off_g1; out->off_g2 = s.off_g2;
   return SBN_OK;
+}
+
+int sbn_kzg_srs_load_ptau(sbn_ctx* c, const uint8_t* bytes, size_t len, size_t n, uint32_t flags, sbn_bases** out_srs, sbn_g2_lines** out_g2,
+                          sbn_g2_lines** out_tau_g2, uint8_t out_g2_xy[256], size_t* bad_index) {
+  namespace pt = sbn_host::ptau;
+  if (!c) return SBN_EINVAL;
+  if (out_srs) *out_srs = nullptr;
+  if (out_g2) *out_g2 = nullptr;
+  if (out_tau_g2) *out_tau_g2 = nullptr;
+  if (bad_index) *bad_index = SIZE_MAX;
+  if (!out_srs || (!bytes && len)) return fail(c, SBN_EINVAL, "ptau load: a null pointer");
+  if (flags & ~SBN_SRS_CHECK) return fail(c, SBN_EINVAL, "ptau load: unknown flags 0x%x", flags);
+  if ((out_g2 == nullptr) != (out_tau_g2 == nullptr)) return fail(c, SBN_EINVAL, "ptau load: the two G2 handles come together or not at all");
+  pt::Scan s;
+  int e = pt::scan(bytes, len, &s);
+  if (e) return fail(c, SBN_EINVAL, "ptau load: %s", pt::err_text(e));
+  if (n > s.n_g1) return fail(c, SBN_EINVAL, "ptau load: n=%zu, the file holds %llu powers", n, (unsigned long long)s.n_g1);
+  if (n == 0) n = (size_t)s.n_g1;
+  uint8_t g2s[256];                                                             // g2 | tau_g2: points 0 and 1 of section 3
+  if ((e = pt::g2_convert(bytes + s.off_g2 + 128, g2s + 128))) return fail(c, SBN_EINVAL, "ptau load: tau_g2: %s", pt::err_text(e));
+  if ((e = pt::g2_convert(bytes + s.off_g2, g2s))) return fail(c, SBN_EINVAL, "ptau load: g2: %s", pt::err_text(e));
+  return srs_load_points(c, "ptau load", bytes + s.off_g1, n, 64, g2s, flags, out_srs, out_g2, out_tau_g2, out_g2_xy, bad_index);
 }
 
 int sbn_kzg_srs_save(sbn_ctx* c, const sbn_bases* srs, const uint8_t g2_xy[128], const uint8_t tau_g2_xy[128], uint32_t flags, uint8_t* out, size_t cap, size_t* out_len) {

@@ -19,6 +19,7 @@
 //   NIZKGens::new, NIZK::prove, NIZK::verify            src/snark.rs:162-287 -> sbn_nizk_*
 //   R1CS::from_reader, to_sparse_matrices_padded, parse_wtns   src/r1cs_reader.rs:55-242, examples/keyless_benchmark.rs:38-72 -> sbn_circom_*
 //   KZGSrs::load_from_file, save_to_file, load_or_generate  src/kzg.rs:66-115 -> sbn_kzg_srs_load / _save / _check / _g2_from_tau
+//   (no twin in the reference) a powers-of-tau ceremony file as that SRS                   -> sbn_ptau_scan / sbn_kzg_srs_load_ptau
 //   the verifier's short sums of proof points (nizk/mod.rs:560-565, :389-394 as GroupElement::vartime_multiscalar_mul)          -> sbn_g1_small_sums
 // There is no CPU fallback in this file: every entry point needs the gfx950 device.
 #include "../../include/sbn254.h"
@@ -44,6 +45,7 @@
 #include "derefs_key_kernels.cuh"
 #include "pairing_kernels.cuh"
 #include "srs_kernels.cuh"
+#include "ptau_kernels.cuh"
 #include "host_keccak.hpp"
 #include "host_strobe.hpp"
 #include "proof_host.hpp"
@@ -53,6 +55,7 @@
 #include "circom_host.hpp"
 #include "pairing_host.hpp"
 #include "srs_host.hpp"
+#include "ptau_host.hpp"
 #include "random_tape_host.hpp"
 
 #include <hip/hip_runtime.h>

@@ -6,11 +6,15 @@
 //   sbn_spartan prove  --mode snark|nizk C.r1cs W.wtns -o P.sbnp [--srs F] [--check-sat] [--label L] [--tape-init HEX]
 //   sbn_spartan verify --mode snark C.comm P.sbnp [--srs F] [--label L]
 //   sbn_spartan verify --mode nizk  C.r1cs P.sbnp [--label L]
+//   sbn_spartan info   F.ptau                                   the sbn_ptau_info fields of a powers-of-tau ceremony file (host only)
+//   sbn_spartan srs    F.ptau -o F.srs [--n N] [--check]        the first N powers (default: all) as the reference's SRS file (sbn_kzg_srs_save)
 //
 // prove: both files are loaded onto the device, then gens, then encode (snark) or the NIZK instance under the DEVICE digest (sbn_circom_r1cs_digest: the
 // library's own, not the reference's get_digest), then tape -> draw plan -> one prove call; the proof file (standalone_host.hpp) holds the raw shape, the
 // inputs and the proof, so verify takes inputs and shape from it.  The transcript label defaults to "keyless_snark" (keyless_benchmark.rs:166).
-// --srs: the KZG build, through sbn_kzg_srs_load, sbn_derefs_key_build and the _kzg calls.
+// --srs: the KZG build, through sbn_kzg_srs_load, sbn_derefs_key_build and the _kzg calls.  A file that begins with "ptau" is a ceremony file: it is
+// mapped, not read, and goes through sbn_kzg_srs_load_ptau, which takes the prefix the circuit needs (npo2(2 batch) N powers for encode and prove, known
+// once the circuit is encoded; one power for verify, which needs the two G2 points only).
 // --tape-init HEX (64 hex digits, a canonical scalar, little-endian) fixes the prover's randomness.  IT EXISTS FOR TESTS: a proof made with a known init has
 // known blinds and hides nothing.  Without it the tape is seeded from the operating system.
 // Exit status: 0 done or accepted; 1 proof refused; 2 usage, file or library error (sbn_last_error on stderr); 3 the witness does not satisfy the circuit
@@ -22,6 +26,10 @@
 #include <cstdlib>
 #include <string>
 #include <vector>
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 namespace sa = sbn_standalone;
 
@@ -79,6 +87,33 @@ void write_file(const std::string& path, const std::vector<uint8_t>& data) {
   const bool ok = fwrite(data.data(), 1, data.size(), f) == data.size();
   if (fclose(f) || !ok) die(2, "cannot write " + path);
 }
+struct Mapped {                                     // a file mapped read-only: a 32 GiB ceremony file costs the pages that are touched
+  const uint8_t* p = nullptr; size_t len = 0;
+  explicit Mapped(const std::string& path) {
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) die(2, "cannot open " + path);
+    struct stat st;
+    if (fstat(fd, &st) || st.st_size < 0) { close(fd); die(2, "cannot read " + path); }
+    len = (size_t)st.st_size;
+    if (len) {
+      void* m = mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0);
+      if (m == MAP_FAILED) { close(fd); die(2, "cannot map " + path); }
+      p = (const uint8_t*)m;
+    }
+    close(fd);
+  }
+  ~Mapped() { if (p) munmap((void*)p, len); }
+  Mapped(const Mapped&) = delete;
+  Mapped& operator=(const Mapped&) = delete;
+};
+bool is_ptau(const std::string& path) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) die(2, "cannot open " + path);
+  char m[4] = {0, 0, 0, 0};
+  const size_t got = fread(m, 1, 4, f);
+  fclose(f);
+  return got == 4 && !memcmp(m, "ptau", 4);
+}
 std::string hex(const uint8_t* p, size_t n) { std::string s; char b[3]; for (size_t i = 0; i < n; i++) { snprintf(b, sizeof b, "%02x", p[i]); s += b; } return s; }
 
 struct Stages {                                     // per-stage wall times, printed in the order they ran
@@ -94,7 +129,8 @@ struct Stages {                                     // per-stage wall times, pri
 
 struct Args {
   std::string cmd, mode, out, srs, label = "keyless_snark", tape_init;
-  bool check_sat = false;
+  bool check_sat = false, check_srs = false;
+  size_t n = 0;
   std::vector<std::string> files;
 };
 const char USAGE[] =
@@ -102,7 +138,9 @@ const char USAGE[] =
     "       sbn_spartan encode C.r1cs -o C.comm [--srs F]\n"
     "       sbn_spartan prove --mode snark|nizk C.r1cs W.wtns -o P.sbnp [--srs F] [--check-sat] [--label L] [--tape-init HEX (tests only)]\n"
     "       sbn_spartan verify --mode snark C.comm P.sbnp [--srs F] [--label L]\n"
-    "       sbn_spartan verify --mode nizk C.r1cs P.sbnp [--label L]\n";
+    "       sbn_spartan verify --mode nizk C.r1cs P.sbnp [--label L]\n"
+    "       sbn_spartan info F.ptau\n"
+    "       sbn_spartan srs F.ptau -o F.srs [--n N] [--check]\n";
 
 Args parse(int argc, char** argv) {
   Args a;
@@ -117,13 +155,19 @@ Args parse(int argc, char** argv) {
     else if (s == "--label") a.label = value();
     else if (s == "--tape-init") a.tape_init = value();
     else if (s == "--check-sat") a.check_sat = true;
+    else if (s == "--check") a.check_srs = true;
+    else if (s == "--n") {
+      const std::string v = value();
+      if (v.empty() || v.size() > 18 || v.find_first_not_of("0123456789") != std::string::npos) die(2, "--n takes a count\n" + std::string(USAGE));
+      a.n = (size_t)std::stoull(v);
+    }
     else if (s.size() > 1 && s[0] == '-') die(2, "unknown option " + s + "\n" + USAGE);
     else a.files.push_back(s);
   }
-  const size_t nfiles = a.cmd == "info" || a.cmd == "encode" ? 1 : 2;
-  if ((a.cmd != "info" && a.cmd != "encode" && a.cmd != "prove" && a.cmd != "verify") || a.files.size() != nfiles) die(2, USAGE);
+  const size_t nfiles = a.cmd == "info" || a.cmd == "encode" || a.cmd == "srs" ? 1 : 2;
+  if ((a.cmd != "info" && a.cmd != "encode" && a.cmd != "prove" && a.cmd != "verify" && a.cmd != "srs") || a.files.size() != nfiles) die(2, USAGE);
   if ((a.cmd == "prove" || a.cmd == "verify") && a.mode != "snark" && a.mode != "nizk") die(2, std::string("--mode snark|nizk is needed\n") + USAGE);
-  if ((a.cmd == "encode" || a.cmd == "prove") && a.out.empty()) die(2, std::string("-o is needed\n") + USAGE);
+  if ((a.cmd == "encode" || a.cmd == "prove" || a.cmd == "srs") && a.out.empty()) die(2, std::string("-o is needed\n") + USAGE);
   if (a.mode == "nizk" && !a.srs.empty()) die(2, "--srs is the KZG build of snark mode: nizk mode has no commitment to open");
   return a;
 }
@@ -143,6 +187,19 @@ void load_srs(Handles& h, const std::string& path, bool want_g2) {
   const std::vector<uint8_t> bytes = read_file(path);
   size_t bad = 0;
   check(h, sbn_kzg_srs_load(h.ctx, bytes.data(), bytes.size(), 0, &h.srs, want_g2 ? &h.g2 : nullptr, want_g2 ? &h.tau_g2 : nullptr, nullptr, &bad), "sbn_kzg_srs_load");
+}
+// the first n powers (0: all) of a ceremony file; g2_xy (or NULL) receives g2 | tau_g2
+void load_ptau(Handles& h, const std::string& path, size_t n, uint32_t flags, bool want_g2, uint8_t* g2_xy = nullptr) {
+  const Mapped m(path);
+  size_t bad = 0;
+  check(h, sbn_kzg_srs_load_ptau(h.ctx, m.p, m.len, n, flags, &h.srs, want_g2 ? &h.g2 : nullptr, want_g2 ? &h.tau_g2 : nullptr, g2_xy, &bad), "sbn_kzg_srs_load_ptau");
+}
+// the powers the KZG build of this circuit touches: the derefs polynomial's padded length npo2(2 batch) N (sbn_sparse_eval_prove_kzg opens over one fewer)
+size_t srs_powers_needed(const sbn_snark_key* key) {
+  const sbn_dense* d = sbn_snark_key_dense(key);
+  size_t k = 1;
+  while (k < 2 * sbn_dense_batch(d)) k <<= 1;
+  return k * sbn_dense_num_ops(d);
 }
 
 void new_transcript(Handles& h, const std::string& label) {
@@ -178,7 +235,32 @@ void print_spans(int mode, uint64_t nc_padded, uint64_t nv_padded, size_t proof_
   printf("proof %-16s bytes %zu\n", "total", proof_bytes);
 }
 
+int run_ptau_info(const Args& a) {
+  const Mapped m(a.files[0]);
+  sbn_ptau_info i;
+  if (sbn_ptau_scan(m.p, m.len, &i)) die(2, a.files[0] + " is not a .ptau file this library loads (sbn_ptau_scan)");
+  printf("power %u\nceremonyPower %u\nn_g1 %llu\nn_g2 %llu\noff_g1 %llu\noff_g2 %llu\n", i.power, i.ceremony_power, (unsigned long long)i.n_g1, (unsigned long long)i.n_g2,
+         (unsigned long long)i.off_g1, (unsigned long long)i.off_g2);
+  return 0;
+}
+
+int run_srs(const Args& a) {
+  Handles h; open_ctx(h);
+  Stages st;
+  uint8_t g2_xy[256];
+  load_ptau(h, a.files[0], a.n, a.check_srs ? SBN_SRS_CHECK : 0, false, g2_xy); st.mark(a.check_srs ? "load_ptau+check" : "load_ptau");
+  size_t len = 0;
+  check(h, sbn_kzg_srs_save(h.ctx, h.srs, nullptr, nullptr, 0, nullptr, 0, &len), "sbn_kzg_srs_save");
+  std::vector<uint8_t> out(len);
+  check(h, sbn_kzg_srs_save(h.ctx, h.srs, g2_xy, g2_xy + 128, 0, out.data(), out.size(), &len), "sbn_kzg_srs_save"); st.mark("save");
+  write_file(a.out, out); st.mark("write");
+  st.print();
+  printf("powers %zu\nsrs bytes %zu\n", sbn_bases_len(h.srs), len);
+  return 0;
+}
+
 int run_info(const Args& a) {
+  if (is_ptau(a.files[0])) return run_ptau_info(a);
   Handles h; open_ctx(h);
   const sbn_circom_info info = load_circuit(h, a.files[0]);
   uint8_t d[32];
@@ -191,9 +273,11 @@ int run_encode(const Args& a) {
   Handles h; open_ctx(h);
   Stages st;
   const sbn_circom_info info = load_circuit(h, a.files[0]); st.mark("load_r1cs");
-  if (!a.srs.empty()) { load_srs(h, a.srs, false); st.mark("load_srs"); }
+  const bool ptau = !a.srs.empty() && is_ptau(a.srs);
+  if (!a.srs.empty() && !ptau) { load_srs(h, a.srs, false); st.mark("load_srs"); }
   check(h, sbn_snark_gens_new(h.ctx, (size_t)info.num_constraints, (size_t)info.num_vars, (size_t)info.num_pub_inputs, max_nnz(info), &h.gens), "sbn_snark_gens_new"); st.mark("gens");
   check(h, sbn_snark_encode_circom(h.ctx, h.circ, h.gens, &h.key), "sbn_snark_encode_circom"); st.mark("encode");
+  if (ptau) { load_ptau(h, a.srs, srs_powers_needed(h.key), 0, false); st.mark("load_srs"); }
   if (h.srs) { check(h, sbn_derefs_key_build(h.ctx, sbn_snark_key_dense(h.key), h.srs, &h.dkey), "sbn_derefs_key_build"); st.mark("derefs_key"); }
   size_t n = 0;
   check(h, sbn_snark_key_comm(h.key, nullptr, 0, &n), "sbn_snark_key_comm");
@@ -229,7 +313,8 @@ int run_prove(const Args& a) {
     if (nwit != info.num_variables) die(2, "the witness holds " + std::to_string(nwit) + " values, the circuit has " + std::to_string(info.num_variables) + " wires");
   }
   st.mark("load_wtns");
-  if (kzg) { load_srs(h, a.srs, false); st.mark("load_srs"); }
+  const bool ptau = kzg && is_ptau(a.srs);
+  if (kzg && !ptau) { load_srs(h, a.srs, false); st.mark("load_srs"); }
   size_t n_rnd = 0, n_proof = 0;
   if (nizk) {
     check(h, sbn_nizk_gens_new(h.ctx, nc, nv, ni, &h.gens), "sbn_nizk_gens_new"); st.mark("gens");
@@ -240,6 +325,7 @@ int run_prove(const Args& a) {
   } else {
     check(h, sbn_snark_gens_new(h.ctx, nc, nv, ni, (size_t)pf.num_nz_entries, &h.gens), "sbn_snark_gens_new"); st.mark("gens");
     check(h, sbn_snark_encode_circom(h.ctx, h.circ, h.gens, &h.key), "sbn_snark_encode_circom"); st.mark("encode");
+    if (ptau) { load_ptau(h, a.srs, srs_powers_needed(h.key), 0, false); st.mark("load_srs"); }
     if (kzg) { check(h, sbn_derefs_key_build(h.ctx, sbn_snark_key_dense(h.key), h.srs, &h.dkey), "sbn_derefs_key_build"); st.mark("derefs_key"); }
     check(h, sbn_snark_sizes(h.key, kzg, &n_rnd, &n_proof), "sbn_snark_sizes");
   }
@@ -297,7 +383,7 @@ int run_verify(const Args& a) {
   } else {
     const std::vector<uint8_t> comm = read_file(a.files[0]);
     check(h, sbn_snark_key_from_comm(h.ctx, comm.data(), comm.size(), &h.key), "sbn_snark_key_from_comm"); st.mark("load_comm");
-    if (kzg) { load_srs(h, a.srs, true); st.mark("load_srs"); }
+    if (kzg) { if (is_ptau(a.srs)) load_ptau(h, a.srs, 1, 0, true); else load_srs(h, a.srs, true); st.mark("load_srs"); }
     check(h, sbn_snark_gens_new(h.ctx, (size_t)pf.num_cons, (size_t)pf.num_vars, ni, (size_t)pf.num_nz_entries, &h.gens), "sbn_snark_gens_new"); st.mark("gens");
     size_t n_rnd = 0, n_proof = 0;
     check(h, sbn_snark_sizes(h.key, kzg, &n_rnd, &n_proof), "sbn_snark_sizes");
@@ -319,6 +405,7 @@ int main(int argc, char** argv) {
     if (a.cmd == "info") return run_info(a);
     if (a.cmd == "encode") return run_encode(a);
     if (a.cmd == "prove") return run_prove(a);
+    if (a.cmd == "srs") return run_srs(a);
     return run_verify(a);
   } catch (const Fail& f) {
     fprintf(stderr, "sbn_spartan: %s\n", f.text.c_str());

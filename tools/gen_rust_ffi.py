@@ -8,7 +8,7 @@ import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OPAQUE = ["sbn_ctx", "sbn_bases", "sbn_table", "sbn_sumcheck", "sbn_bullet", "sbn_group", "sbn_group_bases", "sbn_r1cs", "sbn_dense", "sbn_derefs_key", "sbn_transcript", "sbn_g2_lines", "sbn_snark_gens", "sbn_snark_key", "sbn_nizk_inst", "sbn_circom_r1cs", "sbn_circom_info", "sbn_random_tape"]
+OPAQUE = ["sbn_ctx", "sbn_bases", "sbn_table", "sbn_sumcheck", "sbn_bullet", "sbn_group", "sbn_group_bases", "sbn_r1cs", "sbn_dense", "sbn_derefs_key", "sbn_transcript", "sbn_g2_lines", "sbn_snark_gens", "sbn_snark_key", "sbn_nizk_inst", "sbn_circom_r1cs", "sbn_circom_info", "sbn_random_tape", "sbn_ptau_info"]
 SCALAR = {"int": "c_int", "size_t": "usize", "uint32_t": "u32", "uint64_t": "u64", "uint8_t": "u8", "double": "f64", "char": "c_char", "void": "c_void"}
 
 
