@@ -109,7 +109,8 @@ int sbn_msm_bases_dev(sbn_ctx* ctx, const sbn_bases* b, const void* scalars_dev,
  *   sbn_commit_rows with L = 1.
  * DensePolynomial::commit -> commit_inner (hyrax.rs:253-267, 283-308): C[i] = commit(Z[i*R..(i+1)*R], blinds[i]),
  *   Z row-major L x R, R == sbn_bases_len(b), blinds NULL = all zero (random_tape == None, hyrax.rs:301-305).
- * out_xy: L x 64 B canonical affine; out_inf: L flags or NULL. */
+ * out_xy: L x 64 B canonical affine; out_inf: L flags or NULL.  flags: SBN_SCALARS_MONT only; any other bit is SBN_EINVAL
+ *   (also through sbn_group_commit_rows / sbn_group_commit_rows_dev). */
 int sbn_commit_rows(sbn_ctx* ctx, const sbn_bases* b, const uint8_t* Z, const uint8_t* blinds, size_t L, size_t R,
                     uint32_t flags, uint8_t* out_xy, uint8_t* out_inf);
 int sbn_commit_rows_dev(sbn_ctx* ctx, const sbn_bases* b, const void* Z_dev, const void* blinds_dev, size_t L, size_t R,

@@ -147,7 +147,10 @@ int sbn_msm(sbn_ctx* c, const uint8_t* scalars, const uint8_t* points, size_t n,
   return msm_device(c, ds, (const uint32_t*)c->stage_pts.p, n, out_xy, out_is_inf);
 }
 
-int sbn_commit_rows_dev(sbn_ctx* c, const sbn_bases* b, const void* Z_dev, const void* blinds_dev, size_t L, size_t R, uint32_t flags, uint8_t* out_xy, uint8_t* out_inf) {
+}  // extern "C"
+// flags: SBN_SCALARS_MONT, or the private SBN_SCALARS_INTERNAL (sbn_commit_table: Z and the blinds are this library's table values).  The
+// exported entry point below admits the public bit only.
+static int commit_rows_dev_impl(sbn_ctx* c, const sbn_bases* b, const void* Z_dev, const void* blinds_dev, size_t L, size_t R, uint32_t flags, uint8_t* out_xy, uint8_t* out_inf) {
   if (!c || !b || (!out_xy && L) || (!Z_dev && L * R)) return SBN_EINVAL;
   if (R != b->n) return fail(c, SBN_EINVAL, "commit: gens_n.n (%zu) != row length (%zu)  [commitments.rs:146 assert_eq]", b->n, R);
   if (blinds_dev && !b->has_h) return fail(c, SBN_EINVAL, "commit: blinds given but the table has no h");
@@ -176,6 +179,11 @@ int sbn_commit_rows_dev(sbn_ctx* c, const sbn_bases* b, const void* Z_dev, const
   }
   return commit_rows_device(c, b, dZ, dB, L, R, out_xy, out_inf);
 }
+extern "C" {
+int sbn_commit_rows_dev(sbn_ctx* c, const sbn_bases* b, const void* Z_dev, const void* blinds_dev, size_t L, size_t R, uint32_t flags, uint8_t* out_xy, uint8_t* out_inf) {
+  if (c && (flags & ~SBN_SCALARS_MONT)) return fail(c, SBN_EINVAL, "commit: unknown flags %#x", flags);
+  return commit_rows_dev_impl(c, b, Z_dev, blinds_dev, L, R, flags, out_xy, out_inf);
+}
 // Host-pointer variant.  A large matrix is cut into row chunks: while chunk i is being committed, chunk i+1 crosses PCIe
 // into the other of two staging buffers (copy stream), so the 1 GiB of a keyless derefs commitment costs about
 // max(transfer, compute) instead of their sum.  Rows are independent (hyrax.rs:259-261), so chunking cannot change results.
@@ -184,6 +192,7 @@ int sbn_commit_rows_dev(sbn_ctx* c, const sbn_bases* b, const void* Z_dev, const
 // commits every N-th row of a larger matrix: sbn_group_commit_rows)
 static int commit_rows_host(sbn_ctx* c, const sbn_bases* b, const uint8_t* Z, size_t row_stride, const uint8_t* blinds, size_t L, size_t R, uint32_t flags, uint8_t* out_xy, uint8_t* out_inf) {
   if (!c || !b || (!out_xy && L) || (!Z && L * R)) return SBN_EINVAL;
+  if (flags & ~SBN_SCALARS_MONT) return fail(c, SBN_EINVAL, "commit: unknown flags %#x", flags);
   if (R != b->n) return fail(c, SBN_EINVAL, "commit: gens_n.n (%zu) != row length (%zu)  [commitments.rs:146 assert_eq]", b->n, R);
   if (blinds && !b->has_h) return fail(c, SBN_EINVAL, "commit: blinds given but the table has no h");
   if (L == 0) return SBN_OK;

@@ -680,7 +680,7 @@ int sbn_commit_table(sbn_ctx* c, const sbn_bases* b, const sbn_table* t, const u
     std::lock_guard<std::mutex> g(c->mu); hipSetDevice(c->device);
     LAUNCH(c, "k_fr_to_mont", k_fr_to_mont, stream_grid(L), 256, (const uint32_t*)dB, (uint32_t*)dB, L);
   }
-  rc = sbn_commit_rows_dev(c, b, t->d, dB, L, R, SBN_SCALARS_INTERNAL, out_xy, out_inf);
+  rc = commit_rows_dev_impl(c, b, t->d, dB, L, R, SBN_SCALARS_INTERNAL, out_xy, out_inf);
   if (dB) sbn_dev_free(c, dB);
   return rc;
 }

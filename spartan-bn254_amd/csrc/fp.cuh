@@ -374,6 +374,15 @@ template <class M> __device__ __forceinline__ Fe<M> cols_reduce(Cols s) {
 }
 
 // the value into (-0.1p, 1.1p) (for |a| < 13p), normalised: a Montgomery product with one
+// Second line of the contract, for the long sums that call it (the equal-base merge, msm_kernels.cuh): |a| < 448p, normalised, gives
+// a normalised value in (-0.76p, 1.76p), inside fe_canon_small's (-p, 2p): fe_canon, fe_store, fe_is_zero and fe_from_mont(fe_reduce(a))
+// stay exact on it.  Why: the result is (a ONE + m p) / 2^261 with 0 <= m < 2^261, so a e <= result < a e + p where
+// e = ONE29 / 2^261 = 0.2848 p / 169.2848 p < 1 / 594 (both fields): |a| < K p lands in (-K p / 594, p + K p / 594), K = 13 -> (-0.022p, 1.022p),
+// K = 448 -> (-0.755p, 1.755p), and (-p, 2p) would hold up to K = 594.  What stops earlier is the signed column bound of fe_mul against
+// ONE29, 9 |a_k| max_j ONE29[j] + 9 * 2^58 < 2^63: |a_k| <= 1.33 * 2^30 (Fr; 1.39 * 2^30 on Fq).  Limbs 0..7 of a normalised value are below
+// 2^29 and its top limb is at most K (P29[8] + 1) + 1 in magnitude, which meets that limit up to K = 451 (Fr; 473 on Fq).  A value that is
+// not normalised is in the domain when its limbs meet the same limit.  tests/fe_model.py states both lines (pre_reduce); the merge's
+// sums reach 320 r (tests/merge_model.py).
 template <class M> __device__ __forceinline__ Fe<M> fe_reduce(const Fe<M>& a) { return fe_mul<M>(a, fe_one<M>()); }
 
 // x in (-p, 2p), normalised  ->  the representative in [0, p), normalised
@@ -391,7 +400,7 @@ template <class M> __device__ __forceinline__ Fe<M> fe_canon_small(Fe<M> x) {
   for (int k = 0; k < NL; k++) x.v[k] = (x.v[k] & keep) | (y.v[k] & ~keep);
   return x;
 }
-// any lazy value (|a| < 13p, limbs within fe_mul's operand limits) -> the representative in [0, p), normalised
+// any lazy value (|a| < 13p, limbs within fe_mul's operand limits; or the wider |a| < 448p of fe_reduce's second line) -> the representative in [0, p), normalised
 template <class M> __device__ __forceinline__ Fe<M> fe_canon(const Fe<M>& a) { return fe_canon_small<M>(fe_reduce<M>(a)); }
 
 template <class M> __device__ __forceinline__ bool fe_is_zero(const Fe<M>& a) { return fe_is_zero_limbs(fe_canon<M>(a)); }      // modulo p

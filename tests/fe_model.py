@@ -382,8 +382,20 @@ def pre_subb(F, K, J, a, b):
     return all(0 <= i32(x) <= J * MASK for x in b[:NL - 1]) and 0 <= to_int(b) < (K - Fraction(1, 1000)) * F.p
 
 
-def pre_reduce(F, a):
-    return abs(to_int(a)) < 13 * F.p and pre_mul(a, F.ONE29)
+REDUCE_TIGHT, REDUCE_WIDE = 13, 448
+
+
+def pre_reduce(F, a, wide=False):
+    """fe_reduce / fe_canon / fe_store / fe_is_zero, both lines of fp.cuh's contract.
+    tight: |a| < 13 p -> (-0.1p, 1.1p).  wide: |a| < 448 p -> (-0.76p, 1.76p), still inside fe_canon_small's (-p, 2p).
+    Either way the limbs must fit fe_mul's signed columns against ONE29 (a normalised value below 451 p does)."""
+    return abs(to_int(a)) < (REDUCE_WIDE if wide else REDUCE_TIGHT) * F.p and pre_mul(a, F.ONE29)
+
+
+def reduce_interval(F, a):
+    """the interval fe_reduce(a) must land in, from the arithmetic alone: (a ONE + m p) / 2^261 with 0 <= m < 2^261"""
+    lo = Fraction(to_int(a) * to_int(F.ONE29), RMONT)
+    return lo, lo + F.p
 
 
 def pre_canon_small(F, x):

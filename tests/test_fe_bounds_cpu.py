@@ -209,6 +209,59 @@ def test_reduce_and_mul_ranges(F):
         assert 0 <= fm.to_int(r) < Fraction(fm.to_int(sq) ** 2, fm.RMONT) + p
 
 
+def wide_edges(F, rng):
+    """values at the top of fe_reduce's wide domain (|a| < 448 p) and at the sums the equal-base merge feeds it (160, 320 r)"""
+    p, K = F.p, fm.REDUCE_WIDE
+    xs = [K * p - 1, K * p - (1 << 200), K * p - p // 3, (K - 1) * p, (K - 1) * p + 1, 320 * p - 1, 320 * p, 160 * p + 1, 13 * p, 13 * p + 1]
+    xs += [rng.randrange(13 * p, K * p) for _ in range(40)]
+    return xs + [-x for x in xs]
+
+
+@pytest.mark.parametrize("F", [fm.FQ, fm.FR], ids=["Fq", "Fr"])
+def test_reduce_wide_contract_derivation(F):
+    """the second line of fe_reduce's contract, from the arithmetic: e = ONE29 / 2^261 < 1 / 594 bounds the output, the signed
+    column bound of fe_mul against ONE29 bounds the top limb; 448 p satisfies both with room, and covers the merge's 320 r"""
+    p, K = F.p, fm.REDUCE_WIDE
+    e = Fraction(fm.to_int(F.ONE29), fm.RMONT)
+    assert Fraction(1, 595) < e < Fraction(1, 594)
+    assert K * p * e < Fraction(76, 100) * p and fm.REDUCE_TIGHT * p * e < Fraction(1, 10) * p      # (-0.76p, 1.76p) and (-0.1p, 1.1p)
+    assert 594 * p * e < p < 595 * p * e                                                             # (-p, 2p) itself would hold up to 594 p
+    amax = ((1 << 63) - 9 * (1 << 58) - 1) // (9 * max(F.ONE29))                                     # 9 |a_k| max ONE29 + 9 2^58 < 2^63
+    assert amax >= 1 << 30                                                                          # limbs 0..7 of any fe_add_lazy of two normalised values
+    kmax = (amax - 1) // (F.P8 + 1)                                                                 # |top limb| <= K (P8 + 1) + 1
+    assert K <= kmax and kmax == {"FqP": 473, "FrP": 451}[F.name]
+    assert fm.pre_mul([fm.MASK] * 8 + [K * (F.P8 + 1) + 1], F.ONE29) and not fm.pre_mul([fm.MASK] * 8 + [amax + 1], F.ONE29)
+    assert K * 10 >= 320 * 14                                                                       # 40 % above the largest sum of the merge
+
+
+@pytest.mark.parametrize("F", [fm.FQ, fm.FR], ids=["Fq", "Fr"])
+def test_reduce_canon_is_zero_wide_domain(F):
+    """|a| < 448 p, normalised or not, both signs: fe_reduce lands in [a e, a e + p), inside (-0.76p, 1.76p); fe_canon and
+    fe_is_zero are exact"""
+    p = F.p
+    rng = random.Random(29)
+    n = 0
+    for x in wide_edges(F, rng):
+        for v in (fm.from_int(x), fm.unnormalised(x, rng)):
+            assert fm.pre_reduce(F, v, wide=True) and not fm.pre_reduce(F, v)
+            r = fm.fe_reduce(F, v)
+            lo, hi = fm.reduce_interval(F, v)
+            assert fm.is_normalised(r) and lo <= fm.to_int(r) < hi and inside(r, -0.76, 1.76, p) and (fm.to_int(r) - x) % p == 0
+            assert fm.pre_canon_small(F, r)
+            assert fm.fe_canon(F, v) == fm.from_int(x % p), x
+            assert fm.fe_is_zero(F, v) == (x % p == 0)
+            n += 1
+    for k in (14, 160, 320, 400, fm.REDUCE_WIDE - 1):                  # every k p is zero, its neighbours are not
+        for s in (1, -1):
+            for v in (fm.from_int(s * k * p), fm.unnormalised(s * k * p, rng)):
+                assert fm.pre_reduce(F, v, wide=True) and fm.fe_is_zero(F, v) and fm.fe_canon(F, v) == [0] * 9
+            assert not fm.fe_is_zero(F, fm.from_int(s * k * p + 1)) and not fm.fe_is_zero(F, fm.unnormalised(s * k * p - 1, rng))
+    assert n >= 200
+    # outside the domain the model says so: the value bound first, the column bound before (-p, 2p) is lost
+    assert not fm.pre_reduce(F, fm.from_int(fm.REDUCE_WIDE * p), wide=True)
+    assert not fm.pre_mul(fm.from_int(512 * p), F.ONE29)
+
+
 @pytest.mark.parametrize("F", [fm.FQ, fm.FR], ids=["Fq", "Fr"])
 def test_cols_at_capacity(F):
     """6 products, a carry pass, 6 more, one reduction, every limb at 2^29 - 1; and the lazy two-product form at its limits"""

@@ -77,6 +77,14 @@ def rand_int(rng, lo, hi):
     return rng.randrange(int(lo), int(hi))
 
 
+def wide_edges(F, rng):
+    """the top of fe_reduce's wide domain and the sums the equal-base merge feeds it, both signs"""
+    p, K = F.p, fm.REDUCE_WIDE
+    xs = [K * p - 1, K * p - (1 << 200), K * p - p // 3, (K - 1) * p, (K - 1) * p + 1, 320 * p - 1, 320 * p, 160 * p + 1, 13 * p, 13 * p + 1]
+    xs += [rand_int(rng, 13 * p, K * p) for _ in range(64)]
+    return xs + [-x for x in xs]
+
+
 def field_cases(F, op, rng):
     """(inputs, model output, check) per case: adversarial first, then random"""
     p, P8 = F.p, F.P8
@@ -106,6 +114,8 @@ def field_cases(F, op, rng):
         else:
             C += [[fm.from_int(x)] for x in edge] + ([[fm.unnormalised(x, rng)] for x in edge] if op != "sqr" else [])
             C += [[fm.from_int(rand_int(rng, -13 * p, 13 * p))] for _ in range(nr)]
+            if op != "sqr":                                 # the wide line of fe_reduce's contract: |a| < 448 p (the equal-base merge's sums)
+                C += [[v] for x in wide_edges(F, rng) for v in (fm.from_int(x), fm.unnormalised(x, rng))]
     elif op in ("mulu", "squ"):
         top = [fm.MASK * 2] * 8 + [2 * P8 + 1]              # a sum of two normalised values, limbs at their maximum
         if op == "mulu":
@@ -125,6 +135,11 @@ def field_cases(F, op, rng):
         for k in range(-8 if op == "maybe_zero" else -12, 9 if op == "maybe_zero" else 13):
             C += [[fm.from_int(k * p)]] + [[fm.unnormalised(k * p, rng)] for _ in range(4)]
         C += [[fm.from_int(rand_int(rng, -8 * p, 8 * p))] for _ in range(nr)]
+        if op == "is_zero":                                 # up to the top of the wide domain: k p and its neighbours, both signs
+            for k in (14, 160, 320, 400, fm.REDUCE_WIDE - 1):
+                for x in (k * p, -k * p, k * p + 1, -k * p - 1, k * p - 1):
+                    C += [[fm.from_int(x)], [fm.unnormalised(x, rng)]]
+            C += [[v] for x in wide_edges(F, rng) for v in (fm.from_int(x), fm.unnormalised(x, rng))]
     elif op == "eq":
         for _ in range(nr):
             x = rand_int(rng, 0, p)
@@ -218,15 +233,21 @@ def model_field(F, op, ins):
         ok = fm.is_normalised(r) and 0 <= fm.to_int(r) < Fraction(x * y, fm.RMONT) + p and (fm.to_int(r) - x * y * rinv) % p == 0
         return r, ok, None
     if op in ("reduce", "canon"):
-        assert fm.pre_reduce(F, a)
+        tight = fm.pre_reduce(F, a)
+        assert tight or fm.pre_reduce(F, a, wide=True)
         r = fm.fe_reduce(F, a) if op == "reduce" else fm.fe_canon(F, a)
-        ok = (below(r, 1.1, p, -0.1) if op == "reduce" else fm.to_int(r) == fm.to_int(a) % p) and fm.is_normalised(r)
-        return r, ok and (fm.to_int(r) - fm.to_int(a)) % p == 0, (op, r, 1.1) if op == "reduce" else None
+        if tight:
+            ok = (below(r, 1.1, p, -0.1) if op == "reduce" else fm.to_int(r) == fm.to_int(a) % p) and fm.is_normalised(r)
+            return r, ok and (fm.to_int(r) - fm.to_int(a)) % p == 0, (op, r, 1.1) if op == "reduce" else None
+        lo, hi = fm.reduce_interval(F, a)
+        ok = (lo <= fm.to_int(r) < hi and below(r, 1.76, p, -0.76) if op == "reduce" else fm.to_int(r) == fm.to_int(a) % p) and fm.is_normalised(r)
+        return r, ok and (fm.to_int(r) - fm.to_int(a)) % p == 0, (op + " wide", r, 1.76) if op == "reduce" else None
     if op == "canon_small":
         assert fm.pre_canon_small(F, a)
         r = fm.fe_canon_small(F, a); return r, r == fm.from_int(fm.to_int(a) % p), None
     if op in ("is_zero", "maybe_zero", "eq"):
         if op == "is_zero":
+            assert fm.pre_reduce(F, a, wide=True)
             v = fm.fe_is_zero(F, a); ok = v == (fm.to_int(a) % p == 0)
         elif op == "eq":
             v = fm.fe_eq(F, a, ins[1]); ok = v == ((fm.to_int(a) - fm.to_int(ins[1])) % p == 0)
